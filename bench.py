@@ -19,11 +19,7 @@ import os
 import sys
 import time
 
-# before the HIP runtime initialises (see poseidon_amd/__init__.py): enough hardware queues for the chain, the weight-gradient stream
-# AND an RCCL communicator's streams — with the default 4 the step loses its stream overlap as soon as a process group exists
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
-import torch  # noqa: E402
+import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -47,8 +43,11 @@ def parse():
     ap.add_argument("--channels", type=int, default=4)
     ap.add_argument("--compute", default="fp16", choices=["fp16", "bf16", "fp32", "bf16x3"])
     ap.add_argument("--no-parity", action="store_true", help="skip the in-process parity check against the golden fixture")
-    ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one hipGraph per step")
-    ap.add_argument("--graph", action="store_true", help="force hipGraph replay (default: time both in the warm-up, keep the faster)")
+    ap.add_argument("--no-graph", action="store_true", help="eager launches of the recorded step (the default; overrides --graph)")
+    ap.add_argument("--graph", action="store_true",
+                    help="time hipGraph replay of the step instead of eager launches (slower on MI355X: 32.9 vs 18.3 ms for the default "
+                         "workload: the two-stream fork / join is serialised; a process capturing the two-stream step under a 2-hardware-queue "
+                         "runtime has died with no error)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short runs of BASELINE.json's configs 2, 4 and 5 that the default single-GPU headline run appends (`other_configs`)")
@@ -68,9 +67,15 @@ def parse():
                          "auto: time both in the warm-up, keep the faster; none: no exchange (diagnostic: what the process group costs)")
     ap.add_argument("--launch-dump", default=None, help="write every launch of the replayed steps (entry point, integer arguments, "
                                                         "stream, start/end in ms since the step's first launch) to this JSON file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0) to DIR/<name>.npy: the prediction, the "
+                         "loss, per-parameter gradient norms and a fixed, seeded sample of the gradients (float32 / float64, <= 64 MB in all)")
     ap.add_argument("--_cpu-worker", dest="cpu_worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--_emu", dest="emu", action="store_true", help=argparse.SUPPRESS)      # tests/test_bench_flow_cpu.py (see _enter_emulation)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def usable_cores(cap=32):
@@ -390,6 +395,38 @@ def launch_table(engine, run_step, nsteps=3, dump=None):
     return table, worst
 
 
+DUMP_BUDGET = 64 << 20      # bytes: every file --dump-outputs writes, together
+
+
+def dump_outputs(out_dir, model, pred, loss):
+    """--dump-outputs: what a caller of the timed step holds after its last call — the prediction, the loss and the parameter gradients —
+    as .npy files, so that two builds can be compared output for output (the inputs and weights are seeded: identical with the same
+    arguments).  The prediction is written whole while it fits in half of DUMP_BUDGET (`output.npy`, float32), else as a seeded sample of
+    its elements (`output_sample.npy`).  The gradients, taken in named_parameters() order: one L2 norm per parameter (`grad_norms.npy`,
+    float64) and their concatenation, whole while it fits in a quarter of the budget (`grads.npy`), else a seeded sample (`grads_sample.npy`).
+    The sample positions depend only on the seed and the element count, so two runs of one configuration sample the same elements."""
+    import numpy as np
+
+    def fit(flat, k, seed):
+        if flat.numel() <= k:
+            return flat, ""
+        idx = torch.randint(0, flat.numel(), (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+        return flat[idx.to(flat.device)], "_sample"
+
+    grads = [p.grad.detach().float().reshape(-1) for _, p in model.named_parameters() if p.grad is not None]
+    out, tag = fit(pred.detach().float().reshape(-1), DUMP_BUDGET // 2 // 4, 1)
+    files = {"output" + tag: out.reshape(pred.shape) if not tag else out,
+             "loss": torch.tensor([float(loss)], dtype=torch.float64),
+             "grad_norms": torch.stack([g.double().norm() for g in grads])}
+    gs, tag = fit(torch.cat(grads), DUMP_BUDGET // 4 // 4, 2)
+    files["grads" + tag] = gs
+    arrays = {k: v.cpu().numpy() for k, v in files.items()}
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_BUDGET
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 DEV = "cuda"     # "cpu" only under the hidden --_emu switch: the CPU-emulated kernels of tests/hipemu over gloo, for the control-flow test
 
 
@@ -552,6 +589,7 @@ def main():
         out = model(**kw)
         out.loss.backward()
         loss_buf.copy_(out.loss.detach())
+        return out.output.detach()
 
     # warm-up (eager): builds the arena, runs the device self test, fills allocator pools, records the step tape
     for i in range(4):   # (call 1 of a step signature runs the ops, call 2 records the step tape, later calls replay it)
@@ -562,11 +600,11 @@ def main():
             overlapped.attach()   # the engine exists now: from here on the backward launches the range all-reduces itself
     _sync()
 
-    graph = None
-    if not a.no_graph and exchange[0] != "overlap":
+    graph = graph_pred = None
+    if a.graph and not a.no_graph and exchange[0] != "overlap":
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            compute_step()
+            graph_pred = compute_step()       # (the recorded step's prediction: every replay rewrites it)
         _sync()
 
     use_graph = [graph is not None]
@@ -574,10 +612,12 @@ def main():
     def step():
         if use_graph[0]:
             graph.replay()
+            pred = graph_pred
         else:
-            compute_step()
+            pred = compute_step()
         if exchange[0] == "after":
             after.allreduce()
+        return pred
 
     def probe(flag, n=3):
         use_graph[0] = flag
@@ -590,18 +630,10 @@ def main():
         _sync()
         return (time.perf_counter() - t) / n, t_enq / n
 
-    # hipGraph replay removes the CPU launch cost but (ROCm 7.2) serialises most of the side-stream overlap; eager launches
-    # overlap the weight-gradient stream with the main chain.  Which wins depends on the host CPU: measure both, keep one.
+    # hipGraph replay removes the CPU launch cost but (ROCm 7.2) serialises most of the side-stream overlap; eager launches overlap the
+    # weight-gradient stream with the main chain and won every measured run (rounds 3-6: 18.3-19.8 vs 32.9-34.5 ms), so they are the
+    # default and the graph is timed only on request (--graph)
     mode_info = {}
-    if graph is not None and not a.graph:
-        tg, _ = probe(True)
-        te, te_enq = probe(False)
-        if dist:
-            tt2 = torch.tensor([tg, te], device=DEV, dtype=torch.float64)
-            dist.all_reduce(tt2, op=dist.ReduceOp.MAX)
-            tg, te = float(tt2[0]), float(tt2[1])
-        use_graph[0] = tg <= te
-        mode_info = {"probe_graph_ms": tg * 1e3, "probe_eager_ms": te * 1e3, "eager_cpu_enqueue_ms": te_enq * 1e3}
     if dist is not None and a.dp == "auto" and exchange[0] is not None:
         # gradient exchange: one chunked all-reduce after the step vs range all-reduces launched from inside the backward
         ug = use_graph[0]
@@ -630,7 +662,7 @@ def main():
     _sync()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        pred = step()
     _sync()
     if dist:
         dist.barrier()
@@ -640,6 +672,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
     ms = dt / a.steps * 1e3
+    if a.dump_outputs and rank == 0:      # before anything below steps the model again
+        dump_outputs(a.dump_outputs, model, pred, loss_buf)
     # exposed communication = timed step - the same step with the gradient exchange switched off (same process, same mode)
     exposed = None
     if dist is not None and exchange[0] is not None:

@@ -56,15 +56,30 @@ def build_cached(sanitize: str = "", kind: str = "bf16") -> str:
                        [os.path.join(HERE, "hip", "hip_runtime.h"), os.path.abspath(__file__)]):
         h.update(open(path, "rb").read())
     h.update(sanitize.encode())
+    import shutil
+    import tempfile
     gen = os.path.join(HERE, "_build", h.hexdigest()[:16])
     out = os.path.join(gen, kind)
     lib = os.path.join(out, "libscot_emu.so")
     if os.path.exists(lib):
         return lib
     if not os.path.isdir(gen):
-        import shutil
-        shutil.rmtree(os.path.join(HERE, "_build"), ignore_errors=True)   # one generation only
-    return build(out, sanitize=sanitize, defines=("SCOT_OPERAND_FP16",) if kind == "f16" else ())
+        for old in glob.glob(os.path.join(HERE, "_build", "*")):      # one generation only
+            if old != gen:
+                shutil.rmtree(old, ignore_errors=True)
+    os.makedirs(gen, exist_ok=True)
+    # processes that find no build (pytest-xdist workers on a fresh checkout) each build in a private directory and rename it into
+    # place: the first rename wins, nobody compiles or loads files another process is still writing
+    tmp = tempfile.mkdtemp(prefix=f".{kind}-", dir=gen)
+    try:
+        build(tmp, sanitize=sanitize, defines=("SCOT_OPERAND_FP16",) if kind == "f16" else ())
+        try:
+            os.rename(tmp, out)
+        except OSError:
+            pass        # another process got there first
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    return lib
 
 
 if __name__ == "__main__":

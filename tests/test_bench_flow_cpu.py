@@ -73,6 +73,27 @@ def test_one_rank_group_and_bare_flow(tmp_path):
     assert d["n_gpus"] == 1 and d["config"]["grad_exchange"] in ("overlap", "after")
 
 
+@pytest.mark.timeout(1200)
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the prediction, loss and gradients of the last timed step as float32 / float64 .npy files within 64 MB, and the
+    same arrays again from a second run with the same arguments (seeded weights and inputs)."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"dump{k}"
+        d = _run(1, ["--dp", "after", "--steps", "3", "--dump-outputs", str(out)], tmp_path)
+        assert d["steps"] == 3
+        runs.append({f.stem: np.load(f) for f in out.glob("*.npy")})
+    a, b = runs
+    assert set(a) == {"output", "loss", "grad_norms", "grads"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["output"].shape == (2, 4, 32, 32) and np.isfinite(a["output"]).all() and np.abs(a["output"]).max() > 0
+    assert abs(float(a["loss"][0]) - d["config"]["loss"]) <= 1e-6 * abs(d["config"]["loss"])    # (later steps see the same inputs)
+    assert (a["grad_norms"] > 0).any() and np.isclose(np.sqrt((a["grad_norms"] ** 2).sum()), np.linalg.norm(a["grads"].astype(np.float64)))
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-6, atol=0, err_msg=k)
+
+
 def test_group_size_must_match_gpus(tmp_path):
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--_emu", "--gpus", "4"], env=env, capture_output=True, text=True, timeout=300)

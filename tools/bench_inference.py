@@ -3,7 +3,6 @@ usage: python tools/bench_inference.py [batch]"""
 import os
 import sys
 import time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from poseidon_amd.config import preset

@@ -6,7 +6,6 @@ import socket
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 

@@ -2,7 +2,6 @@
 stream (priority 0 = torch's lowest) against the same step issued on a priority -1 stream (the side stream stays at 0); rounds 1 / 4 tried stream
 priorities before the queue-sharing bug of streams.py was found, hence the re-check."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from poseidon_amd.config import preset

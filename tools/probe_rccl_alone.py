@@ -6,7 +6,6 @@ fork / join measurement of every stream pair at each phase.  usage: python tools
 import os
 import socket
 import sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch.distributed as dist

@@ -1,6 +1,5 @@
 """Six models in a row, same size: which ones run slow in the un-synchronised training loop, and what about them differs?"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from poseidon_amd.config import preset

@@ -4,7 +4,6 @@ Poseidon-B, 2 x batch 32 against 1 x batch 64 (fwd + bwd, fp16 build).  usage: p
 import os
 import sys
 import time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from poseidon_amd.config import preset

@@ -5,7 +5,6 @@ Prints the two loss trajectories, their largest relative gap, the fp16 run's ove
 final weights.   usage: python tools/train_fp16_vs_fp32.py [steps=60] [batches=6] [model=B]"""
 import os
 import sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
