@@ -49,8 +49,7 @@ def stage_groups(cfg, stage_prefix: str) -> List[str]:
 def backward_order_groups(cfg, skips_on_side: bool = True) -> List[str]:
     """Group keys in the order the backward announces them final: name prefixes, and for a stage announced in halves (stage_split)
     `<stage>blocks[s:]` (blocks s.. and the stage's other parameters) then `<stage>blocks[:s]`.  The ConvNeXt skip blocks' backward runs
-    on the side stream beside the encoder stages (engine.skip_side), so their range is announced after the encoder's (before it with
-    SCOT_SKIP_SIDE=0 / no side stream)."""
+    on the side stream beside the encoder stages, so their range is announced after the encoder's (before it with no side stream)."""
     nl = len(cfg.depths)
     g = ["patch_recovery."]
     for k in reversed(range(nl)):

@@ -18,7 +18,7 @@ from __future__ import annotations
 import math
 import os
 import weakref
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -38,22 +38,14 @@ def cpb_coords_table(ws: int) -> torch.Tensor:
     return tab.reshape(-1, 2).contiguous()
 
 
-# Policy switches of the engine.  Every entry's losing setting has a committed measurement (profiles/HISTORY.md, profiles/round2..6), so none of
-# them is an environment knob any more (round 6: 26 -> 5 `os.environ` reads in this file, one of them the generic SCOT_ENGINE_OPTIONS of the A/B scripts); tests and tools/ A/B scripts that still want the
-# other setting patch this dict (or pass `options=` to ScOTEngine) before the engine is built.
+# Policy switches of the engine that are still decided per configuration: each has a committed measurement of both settings
+# (profiles/HISTORY.md, profiles/round2..6) and a test that compares them, or is real configuration.  Tests and tools/ A/B scripts that
+# want the other setting patch this dict (or pass `options=` to ScOTEngine) before the engine is built; SCOT_ENGINE_OPTIONS="a=0,b=1"
+# does the same for the A/B scripts.  Settled switches of earlier rounds are plain code now.
 ENGINE_OPTIONS = dict(
-    tape_c=True,              # recorded steps are replayed inside the library (scot_tape_replay), not by a Python loop over the calls
-    tape_inference=True,      # inference forwards are recorded / replayed too (rollouts: hundreds of forwards of one signature)
-    skip_side=True,           # ConvNeXt skip blocks on the second stream, beside the deep stages' chain
-    group_wgrads=True,        # a layer's weight gradients as one grouped launch
-    cln_partial=True,         # small-row-count norm backward through per-workgroup partial sums
     lean_tail=True,           # fused layer tail without 4C-wide tensors in HBM (round 3: -0.25 ms)
     recycle=True,             # rows that die inside a layer come from a pool (stores land on lines the previous layer left in L2 / MALL)
-    attn_x3=True,             # bf16x3 mode: split products inside the 16x16-window attention kernels too
-    trunk_bf16=False,         # patch embed / merge / unmerge / recovery on 16-bit operands (costs ~1e-3 of output error each)
-    trunk_x3=True,            # fp16 mode: the trunk on the split 16-bit MFMA (fp32 operands, 3 products)
     fused_mlp=True,           # csrc/mlp_fused.hip at C = 96 / 192 (round 2: 23.7 vs 24.9 ms)
-    fused_tail=True,          # projection half + MLP half of a layer's tail in one launch per direction
     fused_min_rows=4096,      # ... from this many token rows on: a tail workgroup owns 64 / 128 rows, so 2048 rows are 32 workgroups on 256 CUs
                               # (round 6, profiles/round6/fused_min_rows_ab.txt: Poseidon-T batch 32 6.18 -> 5.72 ms, Poseidon-B batch 8 10.42 -> 9.41 ms;
                               #  16384 loses again: 5.85 — at 8192 rows the fused tail still wins)
@@ -61,14 +53,25 @@ ENGINE_OPTIONS = dict(
     fused_bwd48=False,        # ... and the backward tail (the round-2 form: gelu'(u) stored, du stored, no qkv prologue; the lean form and
                               # scot_wgrad_mlp need C % 32 == 0): built and tested, measured NEUTRAL on Poseidon-T batch 32 (the weight-gradient
                               # stream paces that backward: 3.56 ms either way) — profiles/round6/tail48_ab.txt
-    fused_next_qkv=(48, 96, 192),   # widths at which the forward tail also produces the next layer's q/k/v projection
-    fused_qkv_dgrad=(96,),      # widths at which the backward tail applies the previous layer's qkv data gradient as a prologue (192 spills)
-    dgrad_wt=True,            # transposed 16-bit weight copies: data gradients as NT products (stages 2/3: 1.7-2.2x)
     grad_scale="auto",        # fp16 mode: initial power-of-two gradient scale ("auto" = from the loss normalisation; a number; "1" = off)
     ls_rescale=True,          # fp16 mode: ConvNeXt skip branches run their backward under an extra power of two (layer scale ~1e-6)
-    lazy_grads=True,          # first writers of the ScOTLayers' weight gradients store (round 6: 18.58 -> 18.24 ms)
-    attn_rep=16,              # replicas of the attention backward's atomically accumulated table / logit-scale gradients
 )
+
+# widths at which a fused forward tail also produces the next layer's q/k/v projection
+FUSED_NEXT_QKV = (48, 96, 192)
+# widths at which a fused backward tail applies the previous layer's qkv data gradient as a prologue (the C = 192 variant spills and
+# costs more than the GEMM it replaces: 125 vs 87 + 20 us)
+FUSED_QKV_DGRAD = (96,)
+# replicas of the attention backward's atomically accumulated table / logit-scale gradients (window w -> replica w % ATTN_REP)
+ATTN_REP = 16
+
+
+class TailPlan(NamedTuple):
+    """How one ScOTLayer's tail (out-projection + norm + residual, MLP + norm + residual) runs, per direction.
+    fwd: "tail" (one scot_block_tail_fwd launch) | "proj" (scot_proj_cln_fwd, then the MLP layer by layer) | "layers".
+    bwd: "lean" (scot_block_tail_bwd without 4C-wide tensors; its forward stores none either) | "tail" | "proj" | "layers"."""
+    fwd: str
+    bwd: str
 
 
 class _Token:
@@ -81,11 +84,11 @@ class ScOTEngine:
         if compute not in ("fp16", "bf16", "fp32", "bf16x3"):
             raise ValueError("compute must be 'fp16', 'bf16', 'fp32' or 'bf16x3'")
         opt = dict(ENGINE_OPTIONS, **(options or {}))
-        for kv in filter(None, os.environ.get("SCOT_ENGINE_OPTIONS", "").split(",")):      # A/B runs only (tools/gpu_ab.sh): "lazy_grads=0,attn_rep=8"
+        for kv in filter(None, os.environ.get("SCOT_ENGINE_OPTIONS", "").split(",")):      # A/B runs only (tools/ab_options.sh): "lean_tail=0,fused_min_rows=0"
             k, _, v = kv.partition("=")
             cur = ENGINE_OPTIONS.get(k.strip())
             opt[k.strip()] = (v.strip() not in ("0", "false", "False")) if isinstance(cur, bool) else \
-                (int(v) if isinstance(cur, int) else (tuple(int(c) for c in v.split("+") if c) if isinstance(cur, tuple) else v.strip()))
+                (int(v) if isinstance(cur, int) else v.strip())
         if set(opt) != set(ENGINE_OPTIONS):
             raise ValueError(f"unknown engine option(s): {sorted(set(opt) - set(ENGINE_OPTIONS))}")
         self.options = opt
@@ -103,10 +106,8 @@ class ScOTEngine:
         self.stochastic = False
         self.launch_timer = None    # bench.py: list that collects per-launch HIP-event timings of replayed steps
         self.tape_max = max(1, int(os.environ.get("SCOT_TAPE_MAX", "2")))
-        # ... and replayed from C: one scot_tape_replay call per run of launches instead of one ctypes call per launch (option tape_c=False: the
-        # Python loop over the recorded calls)
-        self.tape_c = opt["tape_c"] and __import__("platform").machine() in ("x86_64", "AMD64")     # (scot_tape_replay is System V x86-64 only)
-        self.tape_inference = opt["tape_inference"]      # inference forwards are recorded / replayed too
+        # ... and replayed from C: one scot_tape_replay call per run of launches instead of one ctypes call per launch
+        self.tape_c = __import__("platform").machine() in ("x86_64", "AMD64")     # (scot_tape_replay is System V x86-64 only)
         self._rec = None
         self._rec_keep = None
         self._taped = {}
@@ -118,11 +119,8 @@ class ScOTEngine:
         self._events = []                                               # events of the current step (a recorded step keeps its own alive)
         # ConvNeXt skip blocks off the critical path: a skip's blocks only feed the decoder stage that consumes the skip (forward)
         # / the encoder stage that produced it (backward), so they run on the side stream beside the deep stages' latency-bound
-        # chain instead of in front of it (option skip_side=False: in line)
-        self.skip_side = opt["skip_side"]
-        self.group_wgrads = opt["group_wgrads"]
+        # chain instead of in front of it
         self.grad_fill_event = None       # ScOT.zero_grad(overlap=True): recorded behind the gradient arena's fill on the side stream
-        self.cln_partial = opt["cln_partial"]     # small-row-count LN backward through partial sums
         # the fused layer tail WITHOUT 4C-wide tensors in HBM (round 3): the forward stores neither gelu(u) nor gelu'(u) and keeps the
         # pre-norm rows as 16-bit, the backward recomputes gelu'(u) and does not store du, scot_wgrad_mlp recomputes both for the
         # fc1 / fc2 weight gradients, the norms' parameter gradients go through per-workgroup partial rows instead of atomics
@@ -141,26 +139,20 @@ class ScOTEngine:
         # bf16x3: activations and weights stay fp32 in HBM; the GEMMs split them into hi + lo bf16 while staging into LDS and
         # run three bf16 MFMAs per K-step (≈ fp32 accuracy at the bf16 MFMA rate); so do the 16x16-window attention kernels
         self.compute = {"fp16": ops.BF16, "bf16": ops.BF16, "fp32": ops.F32, "bf16x3": ops.X3}[compute]
-        # attention kernels' arithmetic: bf16x3 also splits inside the 16x16-window kernels (option attn_x3=False: exact fp32 MFMA)
-        self.acm = ops.BF16 if half else (ops.X3 if (compute == "bf16x3" and opt["attn_x3"]) else ops.F32)
+        # attention kernels' arithmetic: bf16x3 also splits inside the 16x16-window kernels
+        self.acm = ops.BF16 if half else (ops.X3 if compute == "bf16x3" else ops.F32)
         self.adt = ops.HALF[self.lib_kind] if half else torch.float32
         self.device = arena.data.device
         # The "trunk" (patch embed, merge, unmerge, recovery: < 2 % of the FLOPs) is the only path every output pixel's
         # signal must traverse; each bf16 GEMM on it adds ~1e-3 of relative error that nothing downstream averages out.
-        # It therefore always runs on the exact fp32 MFMA with fp32 operands (option trunk_bf16 restores 16-bit operands).
-        trunk32 = self.compute == ops.BF16 and not opt["trunk_bf16"]
-        self.tcm = ops.F32 if (trunk32 or self.compute != ops.BF16) else ops.BF16
-        # ... on the SPLIT 16-bit MFMA in the fp16 mode (fp32 operands, hi + lo bfloat16 halves, three MFMAs: 2^-17 operand error, 1/5 of
-        # the exact fp32 MFMA's time; ops.gemm routes it to the bfloat16 build, whose halves keep fp32's range under the gradient scale).
-        # option trunk_x3=False: exact fp32 MFMA
-        if compute == "fp16" and self.tcm == ops.F32 and opt["trunk_x3"]:
-            self.tcm = ops.X3
+        # It therefore always has fp32 operands and runs on the exact fp32 MFMA, or on the SPLIT 16-bit MFMA in the fp16 mode (hi + lo
+        # bfloat16 halves, three MFMAs: 2^-17 operand error, 1/5 of the exact fp32 MFMA's time; ops.gemm routes it to the bfloat16 build,
+        # whose halves keep fp32's range under the gradient scale).
+        self.tcm = ops.X3 if compute == "fp16" else ops.F32
         # (tried in round 2: the trunk on the split 16-bit MFMA instead of the exact fp32 MFMA — 0.19 ms faster, same forward
         # parity, but the fp32 trunk gradients under the fp16 build's gradient scale exceed binary16's range in the split: NaN)
-        self.tadt = torch.float32 if self.tcm != ops.BF16 else self.adt
         self.grid, self.enc, self.dec = stage_plan(cfg)
         self.drop_rates = drop_path_rates(cfg)      # per-layer stochastic-depth rate (0 for the training recipe, train.py:262)
-        self.precision_probe = None                 # tools/probes: set of layer pieces run in fp32 during an inference forward
         self.drop_path_masks = None                 # tests: {(layer prefix, branch 0|1): [B] scale} instead of random draws
         self.cond = bool(cfg.use_conditioning)
         self._coords: Dict[int, torch.Tensor] = {}
@@ -176,23 +168,19 @@ class ScOTEngine:
         self._keep = []
         # csrc/mlp_fused.hip (validated and measured on MI355X in round 2: 23.7 vs 24.9 ms/step): fc1 → GELU → fc2 → cond-LN →
         # residual in one launch (and its backward chain, and the projection + LN pair) for the C = 96 / 192 stages of the 16-bit
-        # modes; option fused_mlp=False restores the layer-by-layer launches
+        # modes; option fused_mlp=False restores the layer-by-layer launches.  tail_plan decides per layer which of them run.
         self.fused_mlp = opt["fused_mlp"] and half
-        self.fused_tail = opt["fused_tail"]     # MLP-half + projection-half backward in one launch
         self.fused_min_rows = int(opt["fused_min_rows"])
-        # ... forward: the next layer's q/k/v projection as epilogue (channel widths).  Backward: the previous layer's qkv dgrad as
-        # prologue — at C = 96 only: the C = 192 prologue variant spills and costs more than the GEMM it replaces (125 vs 87 + 20 us)
-        self.fused_next_qkv = set(opt["fused_next_qkv"])
-        self.fused_qkv_dgrad = set(opt["fused_qkv_dgrad"])
+        self._plans: Dict[tuple, TailPlan] = {}
         # bf16 mode: GEMM operands must already be bf16 in HBM (gemm_fast streams raw 16-byte chunks into LDS), so the
         # weights get a bf16 shadow arena that is re-cast from the fp32 master at the start of EVERY forward (one pass,
         # inside the timed step), and every producer of a GEMM operand also writes a bf16 copy.
         self.shadow = torch.empty(arena.size, dtype=self.adt, device=self.device) if self.compute == ops.BF16 else None
         # ... and a second copy holding every weight MATRIX transposed (same offsets): the data gradients dX = dY · W then run as the
         # forward's NT product on W^T instead of the strided-operand NN product (stages 2/3: 1.7–2.2x slower for the same shape).
-        # Filled by one launch per training forward, on the side stream (scot_transpose_cast).  option dgrad_wt=False: NN products.
+        # Filled by one launch per training forward, on the side stream (scot_transpose_cast).
         self.shadow_t, self._wt_names, self._wt_desc, self._wt_tiles = None, {}, None, 0
-        if self.shadow is not None and opt["dgrad_wt"]:
+        if self.shadow is not None:
             self._plan_transposed_weights()
         # fp16 operands have 5 exponent bits: the backward runs on gradients multiplied by a power of two chosen from the loss
         # normalisation (d loss / d prediction = O(1 / number of output elements); see _grad_scale) and the gradient arena is
@@ -221,7 +209,6 @@ class ScOTEngine:
         if self.scale_grads and opt["ls_rescale"]:
             self._plan_layer_scale_rescale()
         self._wviews: Dict[str, torch.Tensor] = {}
-        self._lean_cache: Dict[tuple, bool] = {}
         # 16-bit weight copies are refreshed only when the fp32 master changed: `weights_version()` (set by ScOT: in-place edits of
         # the parameters / the arena and the fused optimizer's steps all move it) is compared with the version the copies were made
         # from.  None (an engine built by hand): refresh at every forward.  The fused AdamW writes the copies itself.
@@ -229,7 +216,7 @@ class ScOTEngine:
         self._shadow_v = self._shadow_t_v = object()
         self._copies_maintained = False      # True once an optimizer (FusedAdamW) writes the 16-bit copies itself
         self._build_cpb_plan()
-        if self.compute == ops.BF16 and arena.grad is not None and opt["lazy_grads"]:
+        if self.compute == ops.BF16 and arena.grad is not None:
             self._plan_grad_partition()
 
     def _build_cpb_plan(self):
@@ -262,12 +249,11 @@ class ScOTEngine:
         self.cpb_max_ws = max(wss)
         self.cpb_tables = torch.empty(tab_off, device=self.device)
         self.cpb_z = torch.empty(z_off, device=self.device)
-        # the attention backward accumulates dtable / dlogit_scale with atomics: R replicas (window w -> replica w % R) keep the
-        # same-address chains short; replica 0 of the tables is what the bias-MLP backward reads after the per-stage fold
-        self.attn_rep = R = max(1, int(self.options["attn_rep"]))
+        # the attention backward accumulates dtable / dlogit_scale with atomics: ATTN_REP replicas keep the same-address chains short;
+        # replica 0 of the tables is what the bias-MLP backward reads after the per-stage fold
         self.cpb_tab_total, self.cpb_ls_total = tab_off, sum(b.heads for b in blocks)
-        self.cpb_dtables = torch.zeros(R * tab_off, device=self.device)
-        self.cpb_dls = torch.zeros(R * self.cpb_ls_total, device=self.device) if R > 1 else None
+        self.cpb_dtables = torch.zeros(ATTN_REP * tab_off, device=self.device)
+        self.cpb_dls = torch.zeros(ATTN_REP * self.cpb_ls_total, device=self.device)
         self.cpb_ls_off, cur = {}, 0
         for b in blocks:
             self.cpb_ls_off[b.prefix] = cur
@@ -368,10 +354,9 @@ class ScOTEngine:
             first, n = self.cpb_index[blocks[0].prefix], len(blocks)
             mw, mh = max(b.window_shift()[0] for b in blocks), max(b.heads for b in blocks)
             def run():
-                if self.attn_rep > 1:
-                    td, sd, tmax, smax = self._replica_desc(blocks)
-                    ops.replica_reduce(self.cpb_dtables, 1, self.attn_rep, self.cpb_tab_total, td, 1, tmax, self.cpb_dtables)
-                    ops.replica_reduce(self.cpb_dls, 0, self.attn_rep, self.cpb_ls_total, sd, n, smax, self.arena.grad)
+                td, sd, tmax, smax = self._replica_desc(blocks)
+                ops.replica_reduce(self.cpb_dtables, 1, ATTN_REP, self.cpb_tab_total, td, 1, tmax, self.cpb_dtables)
+                ops.replica_reduce(self.cpb_dls, 0, ATTN_REP, self.cpb_ls_total, sd, n, smax, self.arena.grad)
                 ops.cpb_bwd_batched(self.arena.data, self.cpb_desc, first, n, mw, mh, self.cpb_coords, self.cpb_z, self.cpb_dtables,
                                     self.arena.grad)
             self.off_critical_path(run)
@@ -462,10 +447,10 @@ class ScOTEngine:
     def transpose_weights(self):
         ops.transpose_cast(self.arena.data, self.shadow_t, self._wt_desc, len(self._wt_names), self._wt_tiles)
 
-    def WT(self, name, w=None):
-        """W(name)^T as a GEMM operand ([in, out], contiguous), or None when no transposed copy is kept (`w`: the operand the caller
-        is about to use — a transposed copy only stands in for the 16-bit weight copy, never for the fp32 master)."""
-        if self.shadow_t is None or name not in self._wt_names or (w is not None and w.dtype != self.adt):
+    def WT(self, name):
+        """W(name)^T as a GEMM operand ([in, out], contiguous), or None when no transposed copy is kept (fp32 operands, or a matrix
+        _plan_transposed_weights leaves out)."""
+        if self.shadow_t is None or name not in self._wt_names:
             return None
         v = self._wtviews.get(name)
         if v is None:
@@ -473,15 +458,6 @@ class ScOTEngine:
             v = self.shadow_t[off:off + r * c].view(c, r)
             self._wtviews[name] = v
         return v
-
-    def TW(self, name):
-        """Trunk weight operand (fp32 master when the trunk computes in fp32)."""
-        return self.arena.view(name) if self.tcm != ops.BF16 else self.W(name)
-
-    def to_tadt(self, x):
-        if self.tadt == torch.float32:
-            return x
-        return self.to_adt(x)
 
     def to_adt(self, x):
         """Copy of fp32 `x` in the GEMM operand dtype (identity in fp32 mode)."""
@@ -652,7 +628,7 @@ class ScOTEngine:
         gw_w, gw_b, _, _ = self._norm_params(prefix)
         g = self._norm_grads(prefix)
         t = time if self.cond else None
-        nf = ops.cln_bwd_partial_floats(rows, rows_per_sample, C, self.cond) if self.cln_partial else 0
+        nf = ops.cln_bwd_partial_floats(rows, rows_per_sample, C, self.cond)
         if nf and self._norm_grads_contiguous(prefix, C):
             # the deep stages' norms (1024 / 4096 rows): dx on the chain with every row's loads in flight at once, the cross-block
             # sums of the parameter gradients through a small partial matrix finished on the weight-gradient stream
@@ -666,22 +642,39 @@ class ScOTEngine:
                     sample_scale=sample_scale)
         return dx
 
-    def _lean_ok(self, pre, rows, rows_per_sample, C, hid) -> bool:
-        """may this ScOTLayer's tail run in the form that keeps no 4C-wide tensor (see `lean_tail`)?  Needs the fused tail in both
-        directions, the transposed 16-bit copy of W2, and the gradient arena's contiguous [W1 | b1 | W2 | b2] and norm layouts."""
-        key = (pre, rows, rows_per_sample)
-        ok = self._lean_cache.get(key)
-        if ok is None:
-            w2 = pre + ".output.dense.weight"
-            ok = (C != 48 and self.use_fused("mlp_bwd", C, rows) and self.use_fused("proj_bwd", C, rows) and self.use_fused("mlp_fwd", C, rows) and self.use_fused("proj_fwd", C, rows)
-                  and self.fused_tail and hid == 4 * C and hid % 128 == 0 and rows_per_sample % 64 == 0
-                  and self.WT(w2, self.W(w2)) is not None and ops.tail_workgroups(rows, rows_per_sample, C) > 0)
-            if ok:
-                gs = [self.arena.gview(pre + n) for n in (".intermediate.dense.weight", ".intermediate.dense.bias", ".output.dense.weight", ".output.dense.bias")]
-                ok = all(b.data_ptr() == a.data_ptr() + 4 * a.numel() for a, b in zip(gs, gs[1:]))
-                ok = ok and self._norm_grads_contiguous(pre + ".layernorm_before", C) and self._norm_grads_contiguous(pre + ".layernorm_after", C)
-            self._lean_cache[key] = ok
-        return ok
+    def tail_plan(self, blk: BlockGeom, B: int, train: bool) -> TailPlan:
+        """How this ScOTLayer's tail runs in each direction, made once per (layer, batch, train) — the prefix fixes the width, the hidden
+        width, the geometry and the tensor layouts.  The forward keeps it in the layer's record and layer_bwd follows it.
+        csrc/mlp_fused.hip covers C = 96 / 192 in the 16-bit modes (each half, or the whole tail) and C = 48 as the whole tail only; a
+        tail workgroup owns 64 (128) rows, so below `fused_min_rows` rows the launch leaves most CUs idle and the layer-by-layer GEMMs
+        (hundreds of 64 x 64 tiles) win.  The backward kernels need whole 64-row tiles per sample."""
+        key = (blk.prefix, B, train)
+        plan = self._plans.get(key)
+        if plan is None:
+            C, (H, W) = blk.dim, blk.res
+            L, hid = H * W, int(self.cfg.mlp_ratio * C)
+            fused = self.fused_mlp and B * L >= self.fused_min_rows
+            if fused and C == 48 and hid == 192:        # (one 192-wide hidden chunk)
+                fwd = "tail" if self.options["fused_fwd48"] else "layers"
+                bwd = "tail" if self.options["fused_bwd48"] and L % 64 == 0 else "layers"
+            elif fused and C in (96, 192):
+                fwd = "tail" if hid % 128 == 0 else "proj"
+                bwd = fwd if L % 64 == 0 else "layers"
+                if bwd == "tail" and train and self.lean_tail and self._lean_layout_ok(blk.prefix, C, hid):
+                    bwd = "lean"
+            else:
+                fwd = bwd = "layers"
+            plan = self._plans[key] = TailPlan(fwd, bwd)
+        return plan
+
+    def _lean_layout_ok(self, pre, C, hid) -> bool:
+        """what the lean tail needs beyond the fused tail: hid = 4C, the transposed 16-bit copy of W2 (scot_wgrad_mlp), and the gradient
+        arena's contiguous [W1 | b1 | W2 | b2] and norm layouts"""
+        if hid != 4 * C or self.WT(pre + ".output.dense.weight") is None:
+            return False
+        gs = [self.arena.gview(pre + n) for n in (".intermediate.dense.weight", ".intermediate.dense.bias", ".output.dense.weight", ".output.dense.bias")]
+        return (all(b.data_ptr() == a.data_ptr() + 4 * a.numel() for a, b in zip(gs, gs[1:]))
+                and self._norm_grads_contiguous(pre + ".layernorm_before", C) and self._norm_grads_contiguous(pre + ".layernorm_after", C))
 
     def _norm_grads_contiguous(self, prefix, C) -> bool:
         """the norm's parameter gradients back to back in the gradient arena (what scot_cln_bwd_finish adds its column sums into)"""
@@ -816,20 +809,9 @@ class ScOTEngine:
         self.flush_side()
         return g
 
-    def use_fused(self, part: str, C: int, rows: Optional[int] = None) -> bool:
-        """csrc/mlp_fused.hip covers C = 96 / 192 in the 16-bit modes; a tail workgroup owns 64 (128) rows, so below `fused_min_rows` rows the
-        launch leaves most CUs idle and the layer-by-layer GEMMs (hundreds of 64 x 64 tiles) win"""
-        if C == 48:     # the whole tail as ONE launch per direction (there are no stand-alone C = 48 halves)
-            return (self.fused_mlp and self.fused_tail and self.options["fused_fwd48" if part.endswith("_fwd") else "fused_bwd48"]
-                    and (rows is None or rows >= self.fused_min_rows))
-        return self.fused_mlp and C in (96, 192) and (rows is None or rows >= self.fused_min_rows)
-
-    def wgrad(self, cm, dy, x, gw, b_gelu=False, dbias=None):
-        """dW += dy^T x (+ dbias): queued until the next flush_side(), where the queued problems that share a compute mode and
-        a token count — the four Linear layers of a ScOTLayer — go out as ONE grouped launch (ops.wgrad_group)."""
-        if b_gelu or not self.group_wgrads:
-            self.off_critical_path(lambda: ops.linear_wgrad(cm, dy, x, gw, b_gelu=b_gelu, dbias=dbias), dy, x)
-            return
+    def wgrad(self, cm, dy, x, gw, dbias=None):
+        """dW += dy^T x (+ dbias), or the store grad_mode(gw) asks for: queued until the next flush_side(), where the queued problems
+        that share a compute mode and a token count — the four Linear layers of a ScOTLayer — go out as ONE grouped launch (ops.wgrad_group)."""
         self._wgq.append((cm, dy, x, gw, dbias))
 
     def _drain_wgrads(self):
@@ -869,9 +851,9 @@ class ScOTEngine:
             ops.linear_wgrad(cm, dy, x, tmp, dbias=db)
             ops.axpy_dev(gw.view(-1), tmp.view(-1), self.grad_unscale())
 
-    def linear_bwd_params(self, wname, bname, dy, x, b_gelu=False):
+    def linear_bwd_params(self, wname, bname, dy, x):
         """dW += dy^T x and db += Σ dy in ONE wgrad launch (the bias sum rides on the dY tiles already in LDS)."""
-        self.wgrad(self.compute, dy, x, self.G(wname), b_gelu=b_gelu, dbias=self.G(bname) if bname is not None else None)
+        self.wgrad(self.compute, dy, x, self.G(wname), dbias=self.G(bname) if bname is not None else None)
 
     # ------------------------------------------------------------------------------------------ ScOTLayer
     def mark(self, label):
@@ -886,7 +868,7 @@ class ScOTEngine:
         called within a stage); needs the unpadded window geometry (the projection input is then exactly the previous output rows)."""
         H, W = blk.res
         ws, _ = blk.window_shift()
-        return H % ws == 0 and W % ws == 0 and blk.dim in self.fused_next_qkv and not self.precision_probe
+        return H % ws == 0 and W % ws == 0 and blk.dim in FUSED_NEXT_QKV
 
     def layer_fwd(self, blk: BlockGeom, x, x16, B, time, train, qkv_pre=None, next_blk=None, want_attn=False, idx=0):
         """reference ScOTLayer.forward (model.py:500-581) + Swinv2Attention/Intermediate/Output (HF:389-561).  qkv_pre: this layer's
@@ -918,9 +900,6 @@ class ScOTEngine:
             xp = x16
         wqkv = self.Wspan(a + "qkv_weight", 3 * C * C).view(3 * C, C)
         bqkv = self.arena.span(a + "qkv_bias", 3 * C) if cfg.qkv_bias else None
-        ex = self.precision_probe if (self.precision_probe and not train and not padded) else None
-        if ex:   # tools/probes/bf16_error_sources.py: selected pieces of an inference forward in fp32 (never on the product path)
-            return self._layer_fwd_probe(blk, x, x16, B, time, ex) + (None,)
         if qkv_pre is not None:
             assert not padded
             qkv = qkv_pre
@@ -948,16 +927,11 @@ class ScOTEngine:
         dp1 = self.drop_path_scale(pre, B, 0) if self.stochastic else None
         dp2 = self.drop_path_scale(pre, B, 1) if self.stochastic else None
         hid = int(cfg.mlp_ratio * C)
-        proj_f = self.use_fused("proj_fwd", C, B * L)
-        mlp_f = self.use_fused("mlp_fwd", C, B * L) and (hid % 128 == 0 if C != 48 else hid == 192)
-        if C == 48 and not (proj_f and mlp_f):
-            proj_f = mlp_f = False           # C = 48 exists as the whole tail only
-        done_tail = False
-        lean_used = False
+        plan = self.tail_plan(blk, B, train)
         qkv_next = None
-        if proj_f and mlp_f and self.fused_tail:
+        if plan.fwd == "tail":
             # projection + norm + residual, then MLP + norm + residual, for the same rows in one launch
-            lean = train and self.lean_tail and self._lean_ok(pre, B * L, L, C, hid)
+            lean = plan.bwd == "lean"
             zdt = self.adt if lean else torch.float32        # pre-norm rows: only the norm backward's x-hat reads them
             proj = self.new(B * L, C, dtype=zdt) if train else None
             st1 = (self.new(B * L), self.new(B * L)) if train else (None, None)
@@ -974,52 +948,30 @@ class ScOTEngine:
                 qkv_next = nxt16("qkvn", B * L, 3 * C, dtype=self.adt)
                 nq = (self.Wspan(na + "qkv_weight", 3 * C * C).view(3 * C, C),
                       self.arena.span(na + "qkv_bias", 3 * C) if cfg.qkv_bias else None, qkv_next)
-            done_tail = ops.block_tail_fwd(
-                (attn_c, self.W(pre + ".attention.output.dense.weight"), self.P(pre + ".attention.output.dense.bias"), x, h, h16, proj,
-                 st1[0], st1[1], n1[0], n1[1], n1[2], n1[3], dp1),
-                (self.W(pre + ".intermediate.dense.weight"), self.P(pre + ".intermediate.dense.bias"), self.W(pre + ".output.dense.weight"),
-                 self.P(pre + ".output.dense.bias"), out, out16, u, gp, y2, st2[0], st2[1], n2[0], n2[1], n2[2], n2[3], dp2),
-                time if self.cond else None, B * L, L, C, hid, cfg.layer_norm_eps, *nq, z16=lean)
-            lean_used = lean
-            if not done_tail:
-                if lean:
-                    raise RuntimeError("scot_block_tail_fwd rejected a shape the engine selected it for")
-                qkv_next = None
-                if C == 48:
-                    proj_f = mlp_f = False   # layer by layer
-        if done_tail:
-            pass
-        elif proj_f:
-            proj = self.new(B * L, C) if train else None
-            st1 = (self.new(B * L), self.new(B * L)) if train else (None, None)
-            h, h16 = dead("h", B * L, C), tmp("h16", B * L, C, dtype=self.adt)
-            gw_w, gw_b, bw_w, bw_b = self._norm_params(pre + ".layernorm_before")
-            if not ops.proj_cln_fwd(attn_c, self.W(pre + ".attention.output.dense.weight"), self.P(pre + ".attention.output.dense.bias"),
-                                    x, h, h16, proj, st1[0], st1[1], time if self.cond else None, gw_w, gw_b, bw_w, bw_b, dp1, B * L, L,
-                                    C, cfg.layer_norm_eps):
-                raise RuntimeError("scot_proj_cln_fwd rejected a shape the engine selected it for")
+            if not ops.block_tail_fwd(
+                    (attn_c, self.W(pre + ".attention.output.dense.weight"), self.P(pre + ".attention.output.dense.bias"), x, h, h16, proj,
+                     st1[0], st1[1], n1[0], n1[1], n1[2], n1[3], dp1),
+                    (self.W(pre + ".intermediate.dense.weight"), self.P(pre + ".intermediate.dense.bias"), self.W(pre + ".output.dense.weight"),
+                     self.P(pre + ".output.dense.bias"), out, out16, u, gp, y2, st2[0], st2[1], n2[0], n2[1], n2[2], n2[3], dp2),
+                    time if self.cond else None, B * L, L, C, hid, cfg.layer_norm_eps, *nq, z16=lean):
+                raise RuntimeError("scot_block_tail_fwd rejected a shape the engine selected it for")
         else:
-            proj = tmp("proj", B * L, C)
-            ops.linear_fwd(cm, attn_c, self.W(pre + ".attention.output.dense.weight"), proj,
-                           bias=self.P(pre + ".attention.output.dense.bias"))
-            h, h16, st1 = self.norm_fwd(pre + ".layernorm_before", proj, x, L, C, cfg.layer_norm_eps, time, need_stats=train,
-                                        copy=True, sample_scale=dp1, out=dead("h", B * L, C), out16=tmp("h16", B * L, C, dtype=self.adt))
-        if done_tail:
-            pass
-        elif mlp_f:
-            u = self.new(B * L, hid, dtype=self.adt) if train else None
-            gp = self.new(B * L, hid, dtype=self.adt) if train else None
-            y2 = self.new(B * L, C) if train else None
-            st2 = (self.new(B * L), self.new(B * L)) if train else (None, None)
-            out, out16 = nxt("out", B * L, C), nxt16("out16", B * L, C, dtype=self.adt)
-            gw_w, gw_b, bw_w, bw_b = self._norm_params(pre + ".layernorm_after")
-            if not ops.mlp_block_fwd(h16, h, self.W(pre + ".intermediate.dense.weight"), self.P(pre + ".intermediate.dense.bias"),
-                                     self.W(pre + ".output.dense.weight"), self.P(pre + ".output.dense.bias"), out, out16, u, gp, y2,
-                                     st2[0], st2[1], time if self.cond else None, gw_w, gw_b, bw_w, bw_b, dp2, B * L, L, C, hid,
-                                     cfg.layer_norm_eps):
-                raise RuntimeError("scot_mlp_block_fwd rejected a shape the engine selected it for")
-        else:
-            # fc1 epilogue emits a = gelu(u) AND gp = gelu'(u) (one erf, fp32 registers); u itself is never stored
+            if plan.fwd == "proj":
+                proj = self.new(B * L, C) if train else None
+                st1 = (self.new(B * L), self.new(B * L)) if train else (None, None)
+                h, h16 = dead("h", B * L, C), tmp("h16", B * L, C, dtype=self.adt)
+                gw_w, gw_b, bw_w, bw_b = self._norm_params(pre + ".layernorm_before")
+                if not ops.proj_cln_fwd(attn_c, self.W(pre + ".attention.output.dense.weight"), self.P(pre + ".attention.output.dense.bias"),
+                                        x, h, h16, proj, st1[0], st1[1], time if self.cond else None, gw_w, gw_b, bw_w, bw_b, dp1, B * L, L,
+                                        C, cfg.layer_norm_eps):
+                    raise RuntimeError("scot_proj_cln_fwd rejected a shape the engine selected it for")
+            else:
+                proj = tmp("proj", B * L, C)
+                ops.linear_fwd(cm, attn_c, self.W(pre + ".attention.output.dense.weight"), proj,
+                               bias=self.P(pre + ".attention.output.dense.bias"))
+                h, h16, st1 = self.norm_fwd(pre + ".layernorm_before", proj, x, L, C, cfg.layer_norm_eps, time, need_stats=train,
+                                            copy=True, sample_scale=dp1, out=dead("h", B * L, C), out16=tmp("h16", B * L, C, dtype=self.adt))
+            # the MLP layer by layer: the fc1 epilogue emits a = gelu(u) AND gp = gelu'(u) (one erf, fp32 registers); u itself is never stored
             u = tmp("u", B * L, hid, dtype=self.adt)
             gp = self.new(B * L, hid, dtype=self.adt) if train else None
             ops.linear_fwd(cm, h16, self.W(pre + ".intermediate.dense.weight"), u, bias=self.P(pre + ".intermediate.dense.bias"),
@@ -1031,77 +983,13 @@ class ScOTEngine:
         rec = None
         if train:
             rec = dict(blk=blk, xp=xp, qkv=qkv, attn_p=attn, table=table, lse=lse, attn_c=attn_c, proj=proj, st1=st1, h16=h16, u=u, gp=gp,
-                       y2=y2, st2=st2, geom=(H, W, Hp, Wp, ws, shift, padded), dp=(dp1, dp2), lean=bool(done_tail and lean_used))
+                       y2=y2, st2=st2, geom=(H, W, Hp, Wp, ws, shift, padded), dp=(dp1, dp2), plan=plan, lean=plan.bwd == "lean")
         return out, out16, rec, qkv_next
 
     def dgrad_into(self, cm, dy, w, g, wt=None):
         """g += dy·w, in place (every reader of g launched so far is on the same stream)"""
         ops.linear_dgrad(cm, dy, w, g, accumulate=True, wt=wt)
         return g
-
-    def _layer_fwd_probe(self, blk, x, x16, B, time, ex):
-        """Inference forward of one ScOTLayer with chosen pieces in fp32 (ex: set of 'qkv', 'attn', 'proj', 'mlp'): measures
-        where the bf16 mode's error comes from.  Not used by any product path."""
-        cfg, cm = self.cfg, self.compute
-        H, W = blk.res
-        C, heads, pre = blk.dim, blk.heads, blk.prefix
-        ws, shift = blk.window_shift()
-        L = H * W
-        a = pre + ".attention.self."
-        f32 = torch.float32
-        bqkv = self.arena.span(a + "qkv_bias", 3 * C) if cfg.qkv_bias else None
-        qdt = f32 if ("attn" in ex or "qkv" in ex) else self.adt
-        qkv = self.new(B * L, 3 * C, dtype=qdt)
-        if "qkv" in ex:
-            ops.linear_fwd(ops.F32, x, self.arena.span(a + "qkv_weight", 3 * C * C).view(3 * C, C), qkv, bias=bqkv)
-        else:
-            ops.linear_fwd(cm, x16, self.Wspan(a + "qkv_weight", 3 * C * C).view(3 * C, C), qkv, bias=bqkv)
-        table = self.cpb_table(pre)
-        nW = (H // ws) * (W // ws)
-        lse = self.new(B * nW, heads, ws * ws)
-        if "attn" in ex:
-            if qkv.dtype != f32:
-                q2 = self.new(B * L, 3 * C)
-                ops.cast(qkv, q2)
-                qkv = q2
-            attn = self.new(B * L, C)
-            ops.window_attn_fwd(ops.F32, qkv, attn, lse, table, self.P(a + "logit_scale"), B, H, W, C, heads, ws, shift)
-        else:
-            if qkv.dtype != self.adt:
-                q2 = self.new(B * L, 3 * C, dtype=self.adt)
-                ops.cast(qkv, q2)
-                qkv = q2
-            attn = self.new(B * L, C, dtype=self.adt)
-            ops.window_attn_fwd(cm, qkv, attn, lse, table, self.P(a + "logit_scale"), B, H, W, C, heads, ws, shift)
-        proj = self.new(B * L, C)
-        if "proj" in ex:
-            if attn.dtype != f32:
-                a2 = self.new(B * L, C)
-                ops.cast(attn, a2)
-                attn = a2
-            ops.linear_fwd(ops.F32, attn, self.arena.view(pre + ".attention.output.dense.weight"), proj,
-                           bias=self.P(pre + ".attention.output.dense.bias"))
-        else:
-            if attn.dtype != self.adt:
-                a2 = self.new(B * L, C, dtype=self.adt)
-                ops.cast(attn, a2)
-                attn = a2
-            ops.linear_fwd(cm, attn, self.W(pre + ".attention.output.dense.weight"), proj, bias=self.P(pre + ".attention.output.dense.bias"))
-        h, h16, _ = self.norm_fwd(pre + ".layernorm_before", proj, x, L, C, cfg.layer_norm_eps, time, need_stats=False, copy=True)
-        hid = int(cfg.mlp_ratio * C)
-        y2 = self.new(B * L, C)
-        if "mlp" in ex:
-            u = self.new(B * L, hid)
-            ops.linear_fwd(ops.F32, h, self.arena.view(pre + ".intermediate.dense.weight"), u, bias=self.P(pre + ".intermediate.dense.bias"),
-                           gelu_deriv_out=u)
-            ops.linear_fwd(ops.F32, u, self.arena.view(pre + ".output.dense.weight"), y2, bias=self.P(pre + ".output.dense.bias"))
-        else:
-            u = self.new(B * L, hid, dtype=self.adt)
-            ops.linear_fwd(cm, h16, self.W(pre + ".intermediate.dense.weight"), u, bias=self.P(pre + ".intermediate.dense.bias"),
-                           gelu_deriv_out=u)
-            ops.linear_fwd(cm, u, self.W(pre + ".output.dense.weight"), y2, bias=self.P(pre + ".output.dense.bias"))
-        out, out16, _ = self.norm_fwd(pre + ".layernorm_after", y2, h, L, C, cfg.layer_norm_eps, time, need_stats=False, copy=True)
-        return out, out16, None
 
     def layer_bwd(self, rec, g, B, time, pend=None, defer_qkv_dgrad=False):
         """g: fp32 [B*L, C] gradient wrt the layer output; returns (gradient wrt the layer input — the same buffer —,
@@ -1115,24 +1003,16 @@ class ScOTEngine:
         a = pre + ".attention.self."
         L, Lp = H * W, Hp * Wp
         hid = int(cfg.mlp_ratio * C)
-        mlp_f = self.use_fused("mlp_bwd", C, B * L) and (hid % 128 == 0 if C != 48 else hid == 192) and L % 64 == 0
-        proj_f = self.use_fused("proj_bwd", C, B * L) and L % 64 == 0
-        if C == 48 and not (mlp_f and proj_f and rec.get("gp") is not None):
-            mlp_f = proj_f = False           # C = 48 exists as the whole tail only
-        tail_f = mlp_f and proj_f and self.fused_tail
-        can_prologue = tail_f and C in self.fused_qkv_dgrad and not padded
+        plan: TailPlan = rec["plan"]
+        can_prologue = plan.bwd in ("lean", "tail") and C in FUSED_QKV_DGRAD and not padded
         if pend is not None and not can_prologue:
             g = self.dgrad_into(cm, pend[0], pend[1], g, wt=pend[2])
             pend = None
         d_attn = self.pool("d_attn", B * L, C, dtype=adt)      # read by this layer's attention backward (same stream) and by nothing else
-        done_tail = False
-        lean = bool(rec.get("lean"))
-        if lean:
+        if plan.bwd == "lean":
             # the tail without 4C-wide tensors: gelu'(u) recomputed from h16, du never stored, the norms' parameter gradients as
             # per-workgroup partial rows; on the weight-gradient stream: the partial rows' column sums, the fc1 / fc2 gradients with
             # gelu(u) / du recomputed (scot_wgrad_mlp), the out-projection's (and, below, the qkv projection's) through the grouped GEMM
-            if not tail_f:
-                raise RuntimeError("the forward kept no gelu(u) / gelu'(u) for this layer, but the backward's fused tail is switched off")
             d_y2, d_proj = self.new(B * L, C, dtype=adt), self.new(B * L, C, dtype=adt)
             n2, n1 = self._norm_params(pre + ".layernorm_after"), self._norm_params(pre + ".layernorm_before")
             g2, g1 = self._norm_grads(pre + ".layernorm_after"), self._norm_grads(pre + ".layernorm_before")
@@ -1150,9 +1030,8 @@ class ScOTEngine:
                     h16=rec["h16"], b1=b1, z16=True, partial2=part2, partial1=part1):
                 raise RuntimeError("scot_block_tail_bwd rejected a shape the engine selected it for")
             pend = None
-            done_tail = True
             first2, first1 = next(t for t in g2 if t is not None), next(t for t in g1 if t is not None)
-            h16r, w2t = rec["h16"], self.WT(w2n, self.W(w2n))
+            h16r, w2t = rec["h16"], self.WT(w2n)
             gW1, gb1, gW2, gb2 = self.G(w1n), self.G(pre + ".intermediate.dense.bias"), self.G(w2n), self.G(pre + ".output.dense.bias")
 
             self._finq += [(part2, nwg, ncol, first2), (part1, nwg, ncol, first1)]
@@ -1166,47 +1045,25 @@ class ScOTEngine:
                     raise RuntimeError("scot_wgrad_mlp rejected a shape the engine selected it for")
             self.off_critical_path(side, h16r, d_y2)
             self.linear_bwd_params(pre + ".attention.output.dense.weight", pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
-        elif tail_f:
+        elif plan.bwd == "tail":
             # both halves of the block tail in one launch: the residual-stream gradient between them stays in registers
             d_y2, d_u, d_proj = self.new(B * L, C, dtype=adt), self.new(B * L, hid, dtype=adt), self.new(B * L, C, dtype=adt)
             n2, g2 = self._norm_params(pre + ".layernorm_after"), self._norm_grads(pre + ".layernorm_after")
             n1, g1 = self._norm_params(pre + ".layernorm_before"), self._norm_grads(pre + ".layernorm_before")
-            gout = g
-            done_tail = ops.block_tail_bwd(
-                g, gout,
-                (rec["y2"], rec["st2"][0], rec["st2"][1], n2[0], n2[1], rec["dp"][1], rec["gp"], self.W(pre + ".intermediate.dense.weight"),
-                 self.W(pre + ".output.dense.weight"), d_y2, d_u, g2[0], g2[1], g2[2], g2[3]),
-                (rec["proj"], rec["st1"][0], rec["st1"][1], n1[0], n1[1], rec["dp"][0], self.W(pre + ".attention.output.dense.weight"),
-                 d_proj, d_attn, g1[0], g1[1], g1[2], g1[3]),
-                time if self.cond else None, B * L, L, C, hid, dqkv=pend[0] if pend else None, wqkv=pend[1] if pend else None)
-            if not done_tail and pend is not None:
-                g = self.dgrad_into(cm, pend[0], pend[1], g, wt=pend[2])
+            if not ops.block_tail_bwd(
+                    g, g,
+                    (rec["y2"], rec["st2"][0], rec["st2"][1], n2[0], n2[1], rec["dp"][1], rec["gp"], self.W(pre + ".intermediate.dense.weight"),
+                     self.W(pre + ".output.dense.weight"), d_y2, d_u, g2[0], g2[1], g2[2], g2[3]),
+                    (rec["proj"], rec["st1"][0], rec["st1"][1], n1[0], n1[1], rec["dp"][0], self.W(pre + ".attention.output.dense.weight"),
+                     d_proj, d_attn, g1[0], g1[1], g1[2], g1[3]),
+                    time if self.cond else None, B * L, L, C, hid, dqkv=pend[0] if pend else None, wqkv=pend[1] if pend else None):
+                raise RuntimeError("scot_block_tail_bwd rejected a shape the engine selected it for")
             pend = None
-            if not done_tail and C == 48:
-                mlp_f = proj_f = False       # layer by layer
-            if done_tail:
-                g = gout
-                self.linear_bwd_params(pre + ".output.dense.weight", pre + ".output.dense.bias", d_y2, rec["u"])
-                self.linear_bwd_params(pre + ".intermediate.dense.weight", pre + ".intermediate.dense.bias", d_u, rec["h16"])
-                self.linear_bwd_params(pre + ".attention.output.dense.weight", pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
-        if done_tail:
-            pass
-        elif mlp_f:
-            # the whole dependent chain of the MLP half in one launch; the two weight gradients follow on the side stream
-            d_y2 = self.new(B * L, C, dtype=adt)
-            d_u = self.new(B * L, hid, dtype=adt)
-            gw_w, gw_b, _, _ = self._norm_params(pre + ".layernorm_after")
-            gg = self._norm_grads(pre + ".layernorm_after")
-            g2 = g
-            if not ops.mlp_block_bwd(g, g2, rec["y2"], rec["st2"][0], rec["st2"][1], time if self.cond else None, gw_w, gw_b,
-                                     rec["dp"][1], rec["gp"], self.W(pre + ".intermediate.dense.weight"),
-                                     self.W(pre + ".output.dense.weight"), d_y2, d_u, gg[0], gg[1], gg[2], gg[3], B * L, L, C, hid):
-                raise RuntimeError("scot_mlp_block_bwd rejected a shape the engine selected it for")
-            g = g2
             self.linear_bwd_params(pre + ".output.dense.weight", pre + ".output.dense.bias", d_y2, rec["u"])
             self.linear_bwd_params(pre + ".intermediate.dense.weight", pre + ".intermediate.dense.bias", d_u, rec["h16"])
+            self.linear_bwd_params(pre + ".attention.output.dense.weight", pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
         else:
-            # out = h + CLN_after(y2)
+            # the MLP layer by layer — out = h + CLN_after(y2)
             d_y2 = self.norm_bwd(pre + ".layernorm_after", g, rec["y2"], rec["st2"], L, C, time, adt, sample_scale=rec["dp"][1])
             # y2 = gelu(u) W2^T + b2
             self.linear_bwd_params(pre + ".output.dense.weight", pre + ".output.dense.bias", d_y2, rec["u"])   # rec["u"] = gelu(u)
@@ -1216,23 +1073,21 @@ class ScOTEngine:
             # u = h W1^T + b1
             self.linear_bwd_params(pre + ".intermediate.dense.weight", pre + ".intermediate.dense.bias", d_u, rec["h16"])
             g = self.dgrad_into(cm, d_u, self.W(pre + ".intermediate.dense.weight"), g, wt=self.WT(pre + ".intermediate.dense.weight"))
-        # h = x + CLN_before(proj)
-        if done_tail:
-            pass
-        elif proj_f:
-            d_proj = self.new(B * L, C, dtype=adt)
-            gw_w, gw_b, _, _ = self._norm_params(pre + ".layernorm_before")
-            gg = self._norm_grads(pre + ".layernorm_before")
-            if not ops.proj_cln_bwd(g, rec["proj"], rec["st1"][0], rec["st1"][1], time if self.cond else None, gw_w, gw_b, rec["dp"][0],
-                                    self.W(pre + ".attention.output.dense.weight"), d_proj, d_attn, gg[0], gg[1], gg[2], gg[3], B * L,
-                                    L, C):
-                raise RuntimeError("scot_proj_cln_bwd rejected a shape the engine selected it for")
-            self.linear_bwd_params(pre + ".attention.output.dense.weight", pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
-        else:
-            d_proj = self.norm_bwd(pre + ".layernorm_before", g, rec["proj"], rec["st1"], L, C, time, adt, sample_scale=rec["dp"][0])
-            self.linear_bwd_params(pre + ".attention.output.dense.weight", pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
-            ops.linear_dgrad(cm, d_proj, self.W(pre + ".attention.output.dense.weight"), d_attn,
-                             wt=self.WT(pre + ".attention.output.dense.weight"))
+            # h = x + CLN_before(proj)
+            if plan.bwd == "proj":
+                d_proj = self.new(B * L, C, dtype=adt)
+                gw_w, gw_b, _, _ = self._norm_params(pre + ".layernorm_before")
+                gg = self._norm_grads(pre + ".layernorm_before")
+                if not ops.proj_cln_bwd(g, rec["proj"], rec["st1"][0], rec["st1"][1], time if self.cond else None, gw_w, gw_b, rec["dp"][0],
+                                        self.W(pre + ".attention.output.dense.weight"), d_proj, d_attn, gg[0], gg[1], gg[2], gg[3], B * L,
+                                        L, C):
+                    raise RuntimeError("scot_proj_cln_bwd rejected a shape the engine selected it for")
+                self.linear_bwd_params(pre + ".attention.output.dense.weight", pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
+            else:
+                d_proj = self.norm_bwd(pre + ".layernorm_before", g, rec["proj"], rec["st1"], L, C, time, adt, sample_scale=rec["dp"][0])
+                self.linear_bwd_params(pre + ".attention.output.dense.weight", pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
+                ops.linear_dgrad(cm, d_proj, self.W(pre + ".attention.output.dense.weight"), d_attn,
+                                 wt=self.WT(pre + ".attention.output.dense.weight"))
         if padded:
             d_attn_p = self.pool("d_attn_p", B * Lp, C, dtype=adt)
             ops.copy2d(d_attn, d_attn_p, B, H, W, Hp, Wp, C)
@@ -1240,14 +1095,10 @@ class ScOTEngine:
             d_attn_p = d_attn
         d_qkv = self.new(B * Lp, 3 * C, dtype=adt)
         d_table = self.cpb_table(pre, grad=True)   # zeroed once per backward; its MLP backward is batched per stage
-        if self.attn_rep > 1:
-            lo = self.cpb_ls_off[pre]
-            ops.window_attn_bwd_rep(self.acm, rec["qkv"], rec["attn_p"], d_attn_p, rec["lse"], rec["table"], self.P(a + "logit_scale"), d_qkv,
-                                    d_table, self.cpb_dls[lo:lo + heads], B, Hp, Wp, C, heads, ws, shift, self.attn_rep, self.cpb_tab_total,
-                                    self.cpb_ls_total)
-        else:
-            ops.window_attn_bwd(self.acm, rec["qkv"], rec["attn_p"], d_attn_p, rec["lse"], rec["table"], self.P(a + "logit_scale"), d_qkv,
-                                d_table, self.G(a + "logit_scale"), B, Hp, Wp, C, heads, ws, shift)
+        lo = self.cpb_ls_off[pre]
+        ops.window_attn_bwd_rep(self.acm, rec["qkv"], rec["attn_p"], d_attn_p, rec["lse"], rec["table"], self.P(a + "logit_scale"), d_qkv,
+                                d_table, self.cpb_dls[lo:lo + heads], B, Hp, Wp, C, heads, ws, shift, ATTN_REP, self.cpb_tab_total,
+                                self.cpb_ls_total)
         wqkv = self.Wspan(a + "qkv_weight", 3 * C * C).view(3 * C, C)
         gwqkv = self.arena.span(a + "qkv_weight", 3 * C * C, grad=True).view(3 * C, C)
         self.wgrad(cm, d_qkv, rec["xp"], gwqkv, dbias=self.arena.span(a + "qkv_bias", 3 * C, grad=True) if cfg.qkv_bias else None)
@@ -1274,10 +1125,10 @@ class ScOTEngine:
         H, W = st.res
         C = st.dim
         H2, W2 = (H + 1) // 2, (W + 1) // 2
-        cat = self.new(B * H2 * W2, 4 * C, dtype=self.tadt)
+        cat = self.new(B * H2 * W2, 4 * C)
         ops.space_to_depth(x, stage_in, cat, B, H, W, C, 0)
         r = self.new(B * H2 * W2, 2 * C)
-        ops.linear_fwd(self.tcm, cat, self.TW(st.prefix + ".downsample.reduction.weight"), r)
+        ops.linear_fwd(self.tcm, cat, self.P(st.prefix + ".downsample.reduction.weight"), r)
         out, out16, stats = self.norm_fwd(st.prefix + ".downsample.norm", r, None, H2 * W2, 2 * C, 1e-5, time, need_stats=train, copy=True)
         return out, out16, (dict(cat=cat, r=r, stats=stats) if train else None)
 
@@ -1285,47 +1136,42 @@ class ScOTEngine:
         H, W = st.res
         C = st.dim
         H2, W2 = (H + 1) // 2, (W + 1) // 2
-        d_r = self.norm_bwd(st.prefix + ".downsample.norm", g, rec["r"], rec["stats"], H2 * W2, 2 * C, time, self.tadt)
+        d_r = self.norm_bwd(st.prefix + ".downsample.norm", g, rec["r"], rec["stats"], H2 * W2, 2 * C, time, torch.float32)
         self.wgrad(self.tcm, d_r, rec["cat"], self.G(st.prefix + ".downsample.reduction.weight"))
         d_cat = self.new(B * H2 * W2, 4 * C)
-        ops.linear_dgrad(self.tcm, d_r, self.TW(st.prefix + ".downsample.reduction.weight"), d_cat,
-                         wt=self.WT(st.prefix + ".downsample.reduction.weight", self.TW(st.prefix + ".downsample.reduction.weight")))
+        ops.linear_dgrad(self.tcm, d_r, self.P(st.prefix + ".downsample.reduction.weight"), d_cat)
         d_sum = self.new(B * H * W, C)
         ops.depth_to_space(d_cat, d_sum, B, H, W, H2, W2, C, 0)
         return d_sum
 
-    def unmerge_fwd(self, st: StageGeom, x, x16, B, time, train):
+    def unmerge_fwd(self, st: StageGeom, x, B, time, train):
         """reference ScOTPatchUnmerging (model.py:737-760)."""
         h, w = st.res
         oh, ow = st.out_res
         C = st.dim
-        xin = x if self.tadt == torch.float32 else x16
-        up = self.new(B * h * w, 2 * C, dtype=self.tadt)
-        ops.linear_fwd(self.tcm, xin, self.TW(st.prefix + ".upsample.upsample.weight"), up)
-        sh = self.new(B * oh * ow, C // 2, dtype=self.tadt)
+        up = self.new(B * h * w, 2 * C)
+        ops.linear_fwd(self.tcm, x, self.P(st.prefix + ".upsample.upsample.weight"), up)
+        sh = self.new(B * oh * ow, C // 2)
         ops.depth_to_space(up, sh, B, oh, ow, h, w, C // 2, 1)
-        n, _, stats = self.norm_fwd(st.prefix + ".upsample.norm", sh, None, oh * ow, C // 2, 1e-5, time, out_dtype=self.tadt,
+        n, _, stats = self.norm_fwd(st.prefix + ".upsample.norm", sh, None, oh * ow, C // 2, 1e-5, time,
                                     need_stats=train)
         out = self.new(B * oh * ow, C // 2)
-        ops.linear_fwd(self.tcm, n, self.TW(st.prefix + ".upsample.mixup.weight"), out)
-        return out, self.to_adt(out), (dict(x=xin, sh=sh, stats=stats, n=n) if train else None)
+        ops.linear_fwd(self.tcm, n, self.P(st.prefix + ".upsample.mixup.weight"), out)
+        return out, self.to_adt(out), (dict(x=x, sh=sh, stats=stats, n=n) if train else None)
 
     def unmerge_bwd(self, st: StageGeom, rec, g, B, time):
         h, w = st.res
         oh, ow = st.out_res
         C = st.dim
-        g16 = self.to_tadt(g)
-        self.wgrad(self.tcm, g16, rec["n"], self.G(st.prefix + ".upsample.mixup.weight"))
-        d_n = self.new(B * oh * ow, C // 2, dtype=self.tadt)
-        ops.linear_dgrad(self.tcm, g16, self.TW(st.prefix + ".upsample.mixup.weight"), d_n,
-                         wt=self.WT(st.prefix + ".upsample.mixup.weight", self.TW(st.prefix + ".upsample.mixup.weight")))
-        d_sh = self.norm_bwd(st.prefix + ".upsample.norm", d_n, rec["sh"], rec["stats"], oh * ow, C // 2, time, self.tadt)
-        d_up = self.new(B * h * w, 2 * C, dtype=self.tadt)
+        self.wgrad(self.tcm, g, rec["n"], self.G(st.prefix + ".upsample.mixup.weight"))
+        d_n = self.new(B * oh * ow, C // 2)
+        ops.linear_dgrad(self.tcm, g, self.P(st.prefix + ".upsample.mixup.weight"), d_n)
+        d_sh = self.norm_bwd(st.prefix + ".upsample.norm", d_n, rec["sh"], rec["stats"], oh * ow, C // 2, time, torch.float32)
+        d_up = self.new(B * h * w, 2 * C)
         ops.space_to_depth(d_sh, None, d_up, B, oh, ow, C // 2, 1)
         self.wgrad(self.tcm, d_up, rec["x"], self.G(st.prefix + ".upsample.upsample.weight"))
         gx = self.new(B * h * w, C)
-        ops.linear_dgrad(self.tcm, d_up, self.TW(st.prefix + ".upsample.upsample.weight"), gx,
-                         wt=self.WT(st.prefix + ".upsample.upsample.weight", self.TW(st.prefix + ".upsample.upsample.weight")))
+        ops.linear_dgrad(self.tcm, d_up, self.P(st.prefix + ".upsample.upsample.weight"), gx)
         return gx
 
     # ------------------------------------------------------------------------------------------ ConvNeXt skip block
@@ -1463,7 +1309,7 @@ class ScOTEngine:
         self.stochastic = bool(train if stochastic is None else stochastic)
         self._events.clear()          # (the previous step's: a destroyed event's pending work completes regardless)
         if (not self.tape_mode or (train and labels is None) or self.stage_timing or self.collect_attn or self._capturing()
-                or (not train and (self.stochastic or not self.tape_inference))):
+                or (not train and self.stochastic)):
             return self._forward(pixel_values, time, labels, pixel_mask, train)
         # (inference forwards are taped too — an autoregressive rollout is hundreds of forwards of one signature, and issued through the
         # Python op wrappers a forward is host-bound: 400 launches at ~10 us each against ~5.5 ms of GPU time)
@@ -1657,10 +1503,10 @@ class ScOTEngine:
         else:
             cpb_all()
         # embeddings (model.py:295-366)
-        cols = self.new(B * L0, Cin * p * p, dtype=self.tadt)
+        cols = self.new(B * L0, Cin * p * p)
         ops.patchify(pixel_values, cols, B, Cin, H, W, p)
         e = self.new(B * L0, C0)
-        wemb = self.TW("embeddings.patch_embeddings.projection.weight").view(C0, Cin * p * p)
+        wemb = self.P("embeddings.patch_embeddings.projection.weight").view(C0, Cin * p * p)
         ops.linear_fwd(self.tcm, cols, wemb, e, bias=self.P("embeddings.patch_embeddings.projection.bias"))
         x, x16, est = self.norm_fwd("embeddings.norm", e, None, L0, C0, 1e-5, time, need_stats=train, copy=True)
         tokmask = None
@@ -1681,7 +1527,7 @@ class ScOTEngine:
         # encoder (model.py:816-861)
         skips: List[torch.Tensor] = []
         skip_ev = []
-        side_skips = self.skip_side and self.use_side and not self.stage_timing
+        side_skips = self.use_side and not self.stage_timing
 
         def skip_blocks(i, st, s_in):
             """ConvNeXt blocks on skip i (model.py:1388-1393) → (processed skip, per-block records)"""
@@ -1740,7 +1586,7 @@ class ScOTEngine:
             hidden_dec.append(x)
             urec = None
             if st.resample:
-                x, x16, urec = self.unmerge_fwd(st, x, x16, B, time, train)
+                x, x16, urec = self.unmerge_fwd(st, x, B, time, train)
             if train:
                 tape["dec"].append((recs, urec))
 
@@ -1748,9 +1594,8 @@ class ScOTEngine:
         self.mark("fwd head")
         Cout = cfg.num_out_channels
         rc = self.new(B * L0, Cout * p * p)
-        xr = x if self.tadt == torch.float32 else x16
-        wrec = self.TW("patch_recovery.projection.weight").view(C0, Cout * p * p)
-        ops.gemm(ops.NN, self.tcm, B * L0, Cout * p * p, C0, xr, C0, wrec, Cout * p * p, rc, Cout * p * p)
+        wrec = self.P("patch_recovery.projection.weight").view(C0, Cout * p * p)
+        ops.gemm(ops.NN, self.tcm, B * L0, Cout * p * p, C0, x, C0, wrec, Cout * p * p, rc, Cout * p * p)
         img = self.new(B, Cout, H, W)
         ops.unpatchify(rc, self.P("patch_recovery.projection.bias"), img, B, Cout, H, W, gh, gw, p)
         pred = self.new(B, Cout, H, W)
@@ -1776,7 +1621,7 @@ class ScOTEngine:
             loss = self.new(1)
             ops.loss_finish(sums, meta["counts"], meta["G"], meta["normalized"], loss)
         if train:
-            tape["head"] = dict(x=xr, img=img, pred=pred, labels=labels, mask=mask_u8, mask_full=mask_full, sums=sums, meta=meta,
+            tape["head"] = dict(x=x, img=img, pred=pred, labels=labels, mask=mask_u8, mask_full=mask_full, sums=sums, meta=meta,
                                 shape=(B, Cout, H, W))
             tape["hidden"] = (hidden_dec, hidden_enc)
         self.last_hidden = (hidden_dec, hidden_enc)
@@ -1821,8 +1666,7 @@ class ScOTEngine:
                 torch.cuda.current_stream().wait_event(ev)
         self.tdo_dynamic(fill_done)
         self.h_zero(self.cpb_dtables)
-        if self.cpb_dls is not None:
-            self.h_zero(self.cpb_dls)
+        self.h_zero(self.cpb_dls)
         self.mark("bwd head")
         _, Cout, H, W = hd["shape"]
         p = cfg.patch_size
@@ -1865,9 +1709,9 @@ class ScOTEngine:
         d_img = self.new(B, Cout, H, W)
         ops.conv5(g_pred, self.P("patch_recovery.mixup.weight"), d_img, B, Cout, H, W, transpose=True)
         self.off_critical_path(lambda: ops.nchw_channel_sum(d_img, self.G("patch_recovery.projection.bias"), B, Cout, H * W), d_img)
-        d_rc = self.new(B * L0, Cout * p * p, dtype=self.tadt)
+        d_rc = self.new(B * L0, Cout * p * p)
         ops.patchify(d_img, d_rc, B, Cout, H, W, p)
-        wrec = self.TW("patch_recovery.projection.weight").view(C0, Cout * p * p)
+        wrec = self.P("patch_recovery.projection.weight").view(C0, Cout * p * p)
         self.off_critical_path(lambda: ops.gemm(ops.TN, self.tcm, C0, Cout * p * p, B * L0, hd["x"], C0, d_rc, Cout * p * p,
                                                 self.G("patch_recovery.projection.weight").view(C0, Cout * p * p), Cout * p * p,
                                                 accumulate=True), hd["x"], d_rc)
@@ -1940,7 +1784,7 @@ class ScOTEngine:
         nl = len(self.dec)
         g_skips: List[Optional[torch.Tensor]] = [None] * nl  # gradient wrt the (ConvNeXt-processed) skips
         skip_ev = [None] * nl
-        side_skips = self.skip_side and self.use_side and not self.stage_timing
+        side_skips = self.use_side and not self.stage_timing
 
         def skip_bwd(i, gi):
             """backward of the ConvNeXt blocks on skip i: gradient wrt the encoder stage's output (in place on gi)"""
@@ -2001,7 +1845,7 @@ class ScOTEngine:
             ops.batch_sum(g, self.G("embeddings.position_embeddings").view(-1), B, L0 * C0)
         if emb.get("tokmask") is not None:
             ops.mask_tokens_bwd(g, emb["tokmask"], self.G("embeddings.mask_token").view(-1), B * L0, C0)
-        d_e = self.norm_bwd("embeddings.norm", g, emb["e"], emb["stats"], L0, C0, time, self.tadt)
+        d_e = self.norm_bwd("embeddings.norm", g, emb["e"], emb["stats"], L0, C0, time, torch.float32)
         self.wgrad(self.tcm, d_e, emb["cols"], self.G("embeddings.patch_embeddings.projection.weight").view(C0, Cin * p * p),
                    dbias=self.G("embeddings.patch_embeddings.projection.bias"))
         if scaled and self.on_grads_final is None and not self.use_side:
