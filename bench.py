@@ -1,14 +1,17 @@
 #!/usr/bin/env python
 """bench.py — PDE-grid samples/s (forward + backward, loss included, optimizer excluded) of the scOT hot path.
 
-  python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py --gpus N --steps K --warmup W [--full]          (N>1: launched by torch.distributed.run, one rank per GPU)
 
 Workload (BASELINE.json metric / configs[2]): Poseidon-B, per-GPU batch 64, 128x128x4 synthetic CE-RP-shaped grids
 (N(0,1) channels, all active, groups [0,1,3,4]), 16-bit MFMA compute with fp32 accumulation, weak scaling (per-device batch
 fixed, as reference train.py:281).  Default --compute fp16: the fastest mode whose ScOT.forward output stays within the north
-star's 1e-3 rel-L2 of the real reference on trained-like parameters — checked IN THIS PROCESS against the committed golden
+star's 1e-3 rel-L2 of the real reference on trained-like parameters — with --full, checked IN THIS PROCESS against the committed golden
 fixture before anything is timed (config.parity); bf16 operands (--compute bf16) do not meet it (6e-3).  A "step" = zero the gradient arena + ScOT.forward (incl. grouped relative-L1 loss) + backward into the
 arena (+ mean all-reduce of the arena for N>1).  Inputs are resident in HBM before the timed region.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  --full adds everything else: the parity and
+batch-consistency checks, the per-launch table behind `roofline`'s kernel families, the forward / backward split, the weight-refresh
+time, the exposed and GPU time of the gradient exchange (N>1), BASELINE.json's other configurations and the CPU baseline.
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -42,15 +45,19 @@ def parse():
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--channels", type=int, default=4)
     ap.add_argument("--compute", default="fp16", choices=["fp16", "bf16", "fp32", "bf16x3"])
-    ap.add_argument("--no-parity", action="store_true", help="skip the in-process parity check against the golden fixture")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the parity and consistency checks, the per-launch table and "
+                         "per-kernel roofline, the phase split, the weight-refresh and gradient-exchange timings, the other configurations "
+                         "and the CPU baseline (the --no-* switches below leave parts of it out)")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the in-process parity check against the golden fixture")
     ap.add_argument("--no-graph", action="store_true", help="eager launches of the recorded step (the default; overrides --graph)")
     ap.add_argument("--graph", action="store_true",
                     help="time hipGraph replay of the step instead of eager launches (slower on MI355X: 32.9 vs 18.3 ms for the default "
                          "workload: the two-stream fork / join is serialised; a process capturing the two-stream step under a 2-hardware-queue "
                          "runtime has died with no error)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (`cpu_baseline`)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short runs of BASELINE.json's configs 2, 4 and 5 that the default single-GPU headline run appends (`other_configs`)")
+                    help="--full: skip the short runs of BASELINE.json's configs 2, 4 and 5 that it appends to the single-GPU headline run (`other_configs`)")
     ap.add_argument("--rccl-channels", type=int, default=0,
                     help="N>1: cap RCCL at this many channels (NCCL_MAX_NCHANNELS, set before the process group exists): every channel is a "
                          "workgroup the collectives take from a backward that is throughput-bound on both of its streams; 0 = RCCL's choice")
@@ -65,8 +72,8 @@ def parse():
                     help="N>1: all-reduce each gradient range from inside the backward as soon as it is final (RCCL on a side "
                          "stream, eager launches), or one chunked all-reduce after the step (works with hipGraph replay); "
                          "auto: time both in the warm-up, keep the faster; none: no exchange (diagnostic: what the process group costs)")
-    ap.add_argument("--launch-dump", default=None, help="write every launch of the replayed steps (entry point, integer arguments, "
-                                                        "stream, start/end in ms since the step's first launch) to this JSON file")
+    ap.add_argument("--launch-dump", default=None, help="--full: write every launch of the per-launch-timed steps (entry point, integer "
+                                                        "arguments, stream, start/end in ms since the step's first launch) to this JSON file")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (rank 0) to DIR/<name>.npy: the prediction, the "
                          "loss, per-parameter gradient norms and a fixed, seeded sample of the gradients (float32 / float64, <= 64 MB in all)")
@@ -75,6 +82,8 @@ def parse():
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.launch_dump and not a.full:
+        ap.error("--launch-dump needs --full (the per-launch table is one of its runs)")
     return a
 
 
@@ -542,7 +551,7 @@ def main():
                          skip_connections=[1, 0], window_size=4, mlp_ratio=4.0, qkv_bias=True, drop_path_rate=0.0, p=1,
                          channel_slice_list_normalized_loss=[0, 1, ch - 1, ch], use_conditioning=True)
     parity = None
-    if rank == 0 and not a.no_parity:
+    if rank == 0 and a.full and not a.no_parity:
         parity = parity_check(a.model, a.compute, a.size, ch)
         if parity.get("fixture") and not parity["meets_bound"]:
             print(f"bench.py: --compute {a.compute} is at {parity['output_rel_l2']:.2e} from the reference fixture (bound "
@@ -566,7 +575,7 @@ def main():
     # gradients, direct-to-LDS / four-register-set GEMMs and the XCD-local attention grid are only selected at the large row counts):
     # samples are independent, so prediction[i] of the batch must equal the prediction of sample i alone, up to accumulation order.
     consistency = None
-    if rank == 0 and not a.no_parity:
+    if rank == 0 and a.full and not a.no_parity:
         full = model(**kw).output.detach().clone()       # (grad mode on: the training forward, the one that is timed)
         worst = 0.0
         for i in sorted({0, B // 3, B - 1}):
@@ -676,7 +685,7 @@ def main():
         dump_outputs(a.dump_outputs, model, pred, loss_buf)
     # exposed communication = timed step - the same step with the gradient exchange switched off (same process, same mode)
     exposed = None
-    if dist is not None and exchange[0] is not None:
+    if a.full and dist is not None and exchange[0] is not None:
         mode = exchange[0]
         if mode == "overlap":
             overlapped.detach()
@@ -693,7 +702,7 @@ def main():
             for _ in range(3):
                 probe(False, n=1)
     comm = None
-    if dist is not None and exchange[0] is not None:   # GPU time of the gradient exchange alone (pack + collective + unpack), outside the timed region
+    if a.full and dist is not None and exchange[0] is not None:   # GPU time of the gradient exchange alone (pack + collective + unpack), outside the timed region
         if exchange[0] == "overlap":
             overlapped.timing = []
             for _ in range(3):
@@ -715,7 +724,7 @@ def main():
     # a loop around a foreign optimizer pays this pass at the top of every forward.  Reported, not included in `value`.
     refresh_ms = None
     eng = model._engine
-    if eng.shadow is not None:
+    if a.full and eng.shadow is not None:
         from poseidon_amd import ops as _ops
         prev = _ops.use(eng.lib_kind)
         try:
@@ -734,7 +743,7 @@ def main():
     # forward / backward split of the step on the GPU's clock: three events on the main stream around the two halves of a few extra
     # steps (the backward's last act is the main stream's wait for the weight-gradient stream, so its end covers both streams)
     phase = None
-    if not use_graph[0]:
+    if a.full and not use_graph[0]:
         ev = [[_event() for _ in range(3)] for _ in range(5)]
         for e in ev:
             model.zero_grad(overlap=True)
@@ -749,15 +758,16 @@ def main():
         phase = {"forward_ms": sorted(e[0].elapsed_time(e[1]) for e in ev)[2], "backward_ms": sorted(e[1].elapsed_time(e[2]) for e in ev)[2]}
     table = worst = None
     table_err = None
-    try:   # every rank steps (under DP a step contains collectives); rank 0 reports
-        if a.emu:
-            raise RuntimeError("per-launch HIP-event timing needs the GPU")
-        eager = use_graph[0]
-        use_graph[0] = False
-        table, worst = launch_table(model._engine, step, dump=a.launch_dump if rank == 0 else None)
-        use_graph[0] = eager
-    except Exception as e:  # pragma: no cover
-        table_err = repr(e)
+    if a.full:
+        try:   # every rank steps (under DP a step contains collectives); rank 0 reports
+            if a.emu:
+                raise RuntimeError("per-launch HIP-event timing needs the GPU")
+            eager = use_graph[0]
+            use_graph[0] = False
+            table, worst = launch_table(model._engine, step, dump=a.launch_dump if rank == 0 else None)
+            use_graph[0] = eager
+        except Exception as e:  # pragma: no cover
+            table_err = repr(e)
     total_samples = B * world * a.steps
     value = total_samples / dt
 
@@ -769,65 +779,68 @@ def main():
                      "scope": "whole step, algorithmic FLOPs 3(B*F+P) per GPU (SURVEY.md 8d)"}
         roof = dict(step_roof, traffic=None)
         launches = None
-        try:
-            # the dominant kernel family of the committed rocprof summary (profiles/round2: the grouped weight-gradient GEMMs),
-            # timed live inside real steps (launch_table above)
-            if table is None:
-                raise RuntimeError(table_err)
-            launches = {"launches_per_step": sum(v["launches_per_step"] for v in table.values()),
-                        "kernel_ms_per_step": sum(v["ms_per_step"] for v in table.values()),
-                        "main_stream_ms_per_step": launch_table.main_stream_ms_per_step,
-                        "wgrad_instances": launch_table.wgrad_instances,
-                        "top": {k: {kk: round(vv, 3) for kk, vv in v.items()} for k, v in list(table.items())[:10]}}
-            # the GEMM family with the most in-step time is the one the roofline is quoted on (round 3: gemm_fast_kernel<NT>, the
-            # forward Linear layers and — on the transposed weight copies — the data gradients of the deep stages)
-            gemm_fams = {k: v for k, v in table.items() if v["gflop_per_step"] > 0}
-            if gemm_fams:
-                name, wg = max(gemm_fams.items(), key=lambda kv: kv[1]["ms_per_step"])
-                tf = wg["gflop_per_step"] / wg["ms_per_step"]      # GFLOP / ms = TFLOP/s
-                traffic, traffic_src, tj = None, None, {}
-                for rnd in ("round6", "round5", "round4", "round3", "round2"):   # HBM bytes per launch (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes)
-                    tpath = os.path.join(ROOT, "profiles", rnd, "pmc_traffic.json")
-                    if os.path.exists(tpath):
-                        tj = json.load(open(tpath))
-                        traffic_src = f"profiles/{rnd}/pmc_traffic.json"
-                        traffic = (tj.get("bytes_per_launch") or {}).get(name.split(" ")[0] + (" " + name.split(" ")[1] if name.startswith("gemm") else ""))
-                        if traffic is None and name.startswith("wgrad_group"):
-                            traffic = tj.get("wgrad_bytes_per_launch")
-                        break
-                # every family under its two roofs: algorithmic FLOPs against the dense MFMA peak, HBM bytes (PMC passes of the newest
-                # committed profile) against the 6.3 TB/s a streaming copy reaches on this part
-                fams = {}
-                tb = (tj.get("bytes_per_launch") or {}) if traffic_src else {}
-                for k, v in table.items():
-                    short = k.split(" ")[0] + (" " + k.split(" ")[1] if k.startswith("gemm") else "")
-                    e = {"ms_per_step": round(v["ms_per_step"], 3), "launches_per_step": v["launches_per_step"]}
-                    if v["gflop_per_step"] > 0:
-                        e["tflops"] = round(v["gflop_per_step"] / v["ms_per_step"], 1)
-                        e["frac_mfma"] = round(v["gflop_per_step"] / v["ms_per_step"] / peak, 4)
-                    if short in tb:
-                        gb = tb[short] * v["launches_per_step"] / 1e9
-                        e["hbm_gb_per_step"] = round(gb, 2)
-                        e["frac_hbm"] = round(gb / v["ms_per_step"] / 6.3, 4)         # GB / ms = TB/s
-                    if "frac_mfma" in e or "frac_hbm" in e:
-                        e["nearer_roof"] = "hbm" if e.get("frac_hbm", 0) > e.get("frac_mfma", 0) else "mfma"
-                    if v["ms_per_step"] >= 0.05:
-                        fams[k] = e
-                roof = {"bound": "mfma", "achieved": tf, "peak": peak, "unit": "TFLOP/s", "frac": tf / peak, "traffic": traffic,
-                        "families": fams, "traffic_source": traffic_src,
-                        "kernel": name + ": in-step durations (HIP events on the launching stream around every call of the replayed step)",
-                        "us_per_launch": wg["ms_per_step"] / wg["launches_per_step"] * 1e3,
-                        "launches_per_step": wg["launches_per_step"], "algorithmic_gflop_per_step": wg["gflop_per_step"],
-                        "gemm_families": {k: {"tflops": round(v["gflop_per_step"] / v["ms_per_step"], 1), "frac": round(v["gflop_per_step"] / v["ms_per_step"] / peak, 4),
-                                              "ms_per_step": round(v["ms_per_step"], 3), "launches_per_step": v["launches_per_step"]}
-                                          for k, v in gemm_fams.items()},
-                        "worst_wgrad_instance": worst, "whole_step": step_roof}
-        except Exception as e:  # pragma: no cover
-            roof = dict(step_roof, traffic=None, error=repr(e))
-        weight_refresh = {"ms": refresh_ms, "included_in_value": False,
-                          "ms_per_step_incl": (ms + refresh_ms) if refresh_ms is not None else None,
-                          "note": "16-bit + transposed operand copies of the weights, needed once per optimizer step: written by "
-                                  "FusedAdamW.step (outside forward + backward), or by the next forward after a foreign optimizer"}
+        if a.full:      # the per-kernel roofline needs the per-launch table
+            try:
+                # the dominant kernel family of the committed rocprof summary (profiles/round2: the grouped weight-gradient GEMMs),
+                # timed live inside real steps (launch_table above)
+                if table is None:
+                    raise RuntimeError(table_err)
+                launches = {"launches_per_step": sum(v["launches_per_step"] for v in table.values()),
+                            "kernel_ms_per_step": sum(v["ms_per_step"] for v in table.values()),
+                            "main_stream_ms_per_step": launch_table.main_stream_ms_per_step,
+                            "wgrad_instances": launch_table.wgrad_instances,
+                            "top": {k: {kk: round(vv, 3) for kk, vv in v.items()} for k, v in list(table.items())[:10]}}
+                # the GEMM family with the most in-step time is the one the roofline is quoted on (round 3: gemm_fast_kernel<NT>, the
+                # forward Linear layers and — on the transposed weight copies — the data gradients of the deep stages)
+                gemm_fams = {k: v for k, v in table.items() if v["gflop_per_step"] > 0}
+                if gemm_fams:
+                    name, wg = max(gemm_fams.items(), key=lambda kv: kv[1]["ms_per_step"])
+                    tf = wg["gflop_per_step"] / wg["ms_per_step"]      # GFLOP / ms = TFLOP/s
+                    traffic, traffic_src, tj = None, None, {}
+                    for rnd in ("round6", "round5", "round4", "round3", "round2"):   # HBM bytes per launch (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes)
+                        tpath = os.path.join(ROOT, "profiles", rnd, "pmc_traffic.json")
+                        if os.path.exists(tpath):
+                            tj = json.load(open(tpath))
+                            traffic_src = f"profiles/{rnd}/pmc_traffic.json"
+                            traffic = (tj.get("bytes_per_launch") or {}).get(name.split(" ")[0] + (" " + name.split(" ")[1] if name.startswith("gemm") else ""))
+                            if traffic is None and name.startswith("wgrad_group"):
+                                traffic = tj.get("wgrad_bytes_per_launch")
+                            break
+                    # every family under its two roofs: algorithmic FLOPs against the dense MFMA peak, HBM bytes (PMC passes of the newest
+                    # committed profile) against the 6.3 TB/s a streaming copy reaches on this part
+                    fams = {}
+                    tb = (tj.get("bytes_per_launch") or {}) if traffic_src else {}
+                    for k, v in table.items():
+                        short = k.split(" ")[0] + (" " + k.split(" ")[1] if k.startswith("gemm") else "")
+                        e = {"ms_per_step": round(v["ms_per_step"], 3), "launches_per_step": v["launches_per_step"]}
+                        if v["gflop_per_step"] > 0:
+                            e["tflops"] = round(v["gflop_per_step"] / v["ms_per_step"], 1)
+                            e["frac_mfma"] = round(v["gflop_per_step"] / v["ms_per_step"] / peak, 4)
+                        if short in tb:
+                            gb = tb[short] * v["launches_per_step"] / 1e9
+                            e["hbm_gb_per_step"] = round(gb, 2)
+                            e["frac_hbm"] = round(gb / v["ms_per_step"] / 6.3, 4)         # GB / ms = TB/s
+                        if "frac_mfma" in e or "frac_hbm" in e:
+                            e["nearer_roof"] = "hbm" if e.get("frac_hbm", 0) > e.get("frac_mfma", 0) else "mfma"
+                        if v["ms_per_step"] >= 0.05:
+                            fams[k] = e
+                    roof = {"bound": "mfma", "achieved": tf, "peak": peak, "unit": "TFLOP/s", "frac": tf / peak, "traffic": traffic,
+                            "families": fams, "traffic_source": traffic_src,
+                            "kernel": name + ": in-step durations (HIP events on the launching stream around every call of the replayed step)",
+                            "us_per_launch": wg["ms_per_step"] / wg["launches_per_step"] * 1e3,
+                            "launches_per_step": wg["launches_per_step"], "algorithmic_gflop_per_step": wg["gflop_per_step"],
+                            "gemm_families": {k: {"tflops": round(v["gflop_per_step"] / v["ms_per_step"], 1), "frac": round(v["gflop_per_step"] / v["ms_per_step"] / peak, 4),
+                                                  "ms_per_step": round(v["ms_per_step"], 3), "launches_per_step": v["launches_per_step"]}
+                                              for k, v in gemm_fams.items()},
+                            "worst_wgrad_instance": worst, "whole_step": step_roof}
+            except Exception as e:  # pragma: no cover
+                roof = dict(step_roof, traffic=None, error=repr(e))
+        weight_refresh = None
+        if a.full:
+            weight_refresh = {"ms": refresh_ms, "included_in_value": False,
+                              "ms_per_step_incl": (ms + refresh_ms) if refresh_ms is not None else None,
+                              "note": "16-bit + transposed operand copies of the weights, needed once per optimizer step: written by "
+                                      "FusedAdamW.step (outside forward + backward), or by the next forward after a foreign optimizer"}
         # whole-step HBM traffic of the newest committed PMC passes against the 8 TB/s peak and SURVEY 8(d)'s ideal fused traffic
         hbm = None
         for rnd in ("round6", "round5", "round4", "round3"):
@@ -873,7 +886,7 @@ def main():
                "parity": parity, "phases": phase, "weight_refresh": weight_refresh, "grad_overflow": overflow,
                "grad_comm_ms_per_step": comm, "grad_exchange_exposed": exposed, "rccl": rccl,
                "config": {"workload": f"Poseidon-{a.model} fwd+bwd, {a.size}x{a.size}x{ch} grids, per-GPU batch {B}",
-                          "global_batch": B * world, "parallelism": f"dp{world}", "graph": bool(use_graph[0]), **mode_info,
+                          "global_batch": B * world, "parallelism": f"dp{world}", "graph": bool(use_graph[0]), "full": a.full, **mode_info,
                           "grad_wire": a.wire if dist is not None else None, "grad_exchange": exchange[0],
                           "grad_collective": a.dp_collective if dist is not None else None, "grad_backend": a.dp_backend if dist is not None else None, "grad_comm_ms_per_step": comm,
                           "loss": float(loss_buf),
@@ -881,12 +894,12 @@ def main():
                           "in_step_launches": launches},
                "roofline": roof}
         headline = (a.model, B, a.size, ch) == ("B", 64, 128, 4)
-        if world == 1 and dist is None and headline and not a.no_other_configs:
+        if a.full and world == 1 and dist is None and headline and not a.no_other_configs:
             # the other BASELINE.json configurations, timed by this same process (the driver's line then referees all five)
             model._engine.reset_tapes()
             torch.cuda.empty_cache()
             res["other_configs"] = [other_config(*c, a.compute) for c in OTHER_CONFIGS]
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(a.model, a.size, ch, a.cpu_seconds)
             except Exception as e:  # pragma: no cover

@@ -54,7 +54,8 @@ def _run(world, extra, tmp_path, timeout=900):
 @pytest.mark.timeout(1500)
 @pytest.mark.parametrize("dp", ["auto", "overlap"])      # ("after" is the other arm of the auto probe)
 def test_two_rank_bench_flow(tmp_path, dp):
-    d = _run(2, ["--dp", dp], tmp_path)
+    d = _run(2, ["--dp", dp, "--full"], tmp_path)
+    assert d["config"]["full"] is True
     assert d["emulated"] and d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak"
     assert d["config"]["global_batch"] == 4 and d["config"]["parallelism"] == "dp2"
     assert d["value"] > 0 and d["ms_per_step"] > 0 and abs(d["value"] - 4 / (d["ms_per_step"] / 1e3)) < 1e-6 * d["value"]
@@ -68,9 +69,16 @@ def test_two_rank_bench_flow(tmp_path, dp):
 
 @pytest.mark.timeout(900)
 def test_one_rank_group_and_bare_flow(tmp_path):
-    """torchrun with one rank (the collective path with a group of one) and the bare single-process call"""
+    """torchrun with one rank (the collective path with a group of one) and the bare single-process call; without --full the line carries
+    the headline and the timed steps' own figures only: none of the sections that take runs of their own"""
     d = _run(1, ["--dp", "auto"], tmp_path)
     assert d["n_gpus"] == 1 and d["config"]["grad_exchange"] in ("overlap", "after")
+    assert "probe_dp_after_ms" in d["config"] and "probe_dp_overlap_ms" in d["config"]     # (the --dp auto choice is part of the set-up)
+    assert d["config"]["full"] is False and d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["grad_exchange_exposed"] is None and d["grad_comm_ms_per_step"] is None and d["phases"] is None
+    assert d["parity"] is None and d["weight_refresh"] is None and d["config"]["in_step_launches"] is None
+    assert d["roofline"]["bound"] == "mfma" and "families" not in d["roofline"] and "error" not in d["roofline"]
+    assert "other_configs" not in d and "cpu_baseline" not in d
 
 
 @pytest.mark.timeout(1200)
@@ -92,6 +100,12 @@ def test_dump_outputs_writes_the_last_timed_step(tmp_path):
     assert (a["grad_norms"] > 0).any() and np.isclose(np.sqrt((a["grad_norms"] ** 2).sum()), np.linalg.norm(a["grads"].astype(np.float64)))
     for k in a:
         np.testing.assert_allclose(a[k], b[k], rtol=1e-6, atol=0, err_msg=k)
+
+
+def test_launch_dump_needs_full(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--_emu", "--launch-dump", str(tmp_path / "l.json")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--launch-dump needs --full" in r.stderr and not (tmp_path / "l.json").exists()
 
 
 def test_group_size_must_match_gpus(tmp_path):

@@ -6,7 +6,7 @@ out=gpurun_out/r5ev; mkdir -p $out
 if [ "${1:-}" = tests ]; then
   timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 | tee $out/pytest_gpu.txt
 fi
-timeout 400 python bench.py --launch-dump $out/launches.json 2>$out/bench.err | tail -1 > $out/bench_default.json
+timeout 400 python bench.py --full --launch-dump $out/launches.json 2>$out/bench.err | tail -1 > $out/bench_default.json
 python tools/launch_summary.py $out/launches.json 80 > $out/launch_summary.txt 2>&1
 rm -f $out/launches.json
 python -c "import json;d=json.load(open('$out/bench_default.json'));print(d['value'], d['ms_per_step'], d['parity'], d['roofline']['frac'], d['roofline']['kernel'][:40], d['roofline']['whole_step']['frac'], d['roofline'].get('hbm'), d.get('cpu_baseline'))" | tee $out/summary.txt
@@ -34,14 +34,14 @@ done
 cd $R
 python tools/make_pmc_traffic.py $out/pmc_FETCH_SIZE.txt $out/pmc_WRITE_SIZE.txt $out/pmc_FETCH_SIZE_total.txt $out/pmc_WRITE_SIZE_total.txt > $out/pmc_traffic.json 2>$out/pmc_traffic.err
 # process-group overhead: the same bench under a 1-rank RCCL group (exposed exchange, RCCL's own log parsed into the line)
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --no-cpu-baseline --no-parity 2>$out/torchrun1.err | tail -1 > $out/bench_torchrun1.json
-timeout 300 python bench.py --no-cpu-baseline --no-parity 2>/dev/null | tail -1 > $out/bench_bare.json
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --full --no-cpu-baseline --no-parity 2>$out/torchrun1.err | tail -1 > $out/bench_torchrun1.json
+timeout 300 python bench.py --full --no-cpu-baseline --no-parity 2>/dev/null | tail -1 > $out/bench_bare.json
 # the non-headline configurations (parity cases, builder-reported speeds), each with the 128 x 128-tile GEMMs off as well
 i=0
 for args in "--model T --batch 32" "--model B --batch 32 --size 256" "--model L --batch 128 --channels 5" "--model B --compute bf16"; do
   i=$((i+1))
-  timeout 400 python bench.py $args --no-cpu-baseline --steps 10 2>/dev/null | tail -1 > $out/bench_other_$i.json
-  SCOT_GEMM_WIDE=0 timeout 400 python bench.py $args --no-cpu-baseline --no-parity --steps 10 2>/dev/null | tail -1 > $out/bench_other_${i}_wide0.json
+  timeout 400 python bench.py $args --full --no-cpu-baseline --steps 10 2>/dev/null | tail -1 > $out/bench_other_$i.json
+  SCOT_GEMM_WIDE=0 timeout 400 python bench.py $args --full --no-cpu-baseline --no-parity --steps 10 2>/dev/null | tail -1 > $out/bench_other_${i}_wide0.json
 done
 python tools/bench_inference.py 64 2>&1 | grep inference > $out/inference.txt
 true

@@ -6,7 +6,7 @@ out=gpurun_out/r6ev; mkdir -p $out
 if [ "${1:-}" = tests ]; then
   timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 | tee $out/pytest_gpu.txt
 fi
-timeout 400 python bench.py --launch-dump $out/launches.json 2>$out/bench.err | tail -1 > $out/bench_default.json
+timeout 400 python bench.py --full --launch-dump $out/launches.json 2>$out/bench.err | tail -1 > $out/bench_default.json
 python tools/launch_summary.py $out/launches.json 80 > $out/launch_summary.txt 2>&1
 rm -f $out/launches.json
 python -c "import json;d=json.load(open('$out/bench_default.json'));print(d['value'], d['ms_per_step'], d['parity'], d['roofline']['frac'], d['roofline']['kernel'][:40], d['roofline']['whole_step']['frac'], d['roofline'].get('hbm'), d.get('cpu_baseline'))" | tee $out/summary.txt
@@ -35,11 +35,11 @@ done
 cd $R
 python tools/make_pmc_traffic.py $out/pmc_FETCH_SIZE.txt $out/pmc_WRITE_SIZE.txt $out/pmc_FETCH_SIZE_total.txt $out/pmc_WRITE_SIZE_total.txt > $out/pmc_traffic.json 2>$out/pmc_traffic.err
 # process-group overhead: the same bench under a 1-rank RCCL group (exposed exchange, RCCL's own log parsed into the line)
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --no-cpu-baseline --no-parity --no-other-configs 2>$out/torchrun1.err | tail -1 > $out/bench_torchrun1.json
-timeout 300 python bench.py --no-cpu-baseline --no-parity --no-other-configs 2>/dev/null | tail -1 > $out/bench_bare.json
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 1 --rccl-channels 16 --no-cpu-baseline --no-parity --no-other-configs 2>/dev/null | tail -1 > $out/bench_torchrun1_ch16.json
-# the non-headline configurations are part of the default line (`other_configs`); here: the bfloat16 build and the 128 x 128-tile GEMMs switched off
-timeout 400 python bench.py --compute bf16 --no-cpu-baseline --no-other-configs --steps 10 2>/dev/null | tail -1 > $out/bench_bf16.json
-SCOT_GEMM_WIDE=0 timeout 400 python bench.py --model L --batch 128 --channels 5 --no-cpu-baseline --no-parity --steps 10 2>/dev/null | tail -1 > $out/bench_L_wide0.json
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --full --no-cpu-baseline --no-parity --no-other-configs 2>$out/torchrun1.err | tail -1 > $out/bench_torchrun1.json
+timeout 300 python bench.py --full --no-cpu-baseline --no-parity --no-other-configs 2>/dev/null | tail -1 > $out/bench_bare.json
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 1 --rccl-channels 16 --full --no-cpu-baseline --no-parity --no-other-configs 2>/dev/null | tail -1 > $out/bench_torchrun1_ch16.json
+# the non-headline configurations are part of the --full line (`other_configs`); here: the bfloat16 build and the 128 x 128-tile GEMMs switched off
+timeout 400 python bench.py --compute bf16 --full --no-cpu-baseline --no-other-configs --steps 10 2>/dev/null | tail -1 > $out/bench_bf16.json
+SCOT_GEMM_WIDE=0 timeout 400 python bench.py --model L --batch 128 --channels 5 --full --no-cpu-baseline --no-parity --steps 10 2>/dev/null | tail -1 > $out/bench_L_wide0.json
 python tools/bench_inference.py 64 2>&1 | grep inference > $out/inference.txt
 true

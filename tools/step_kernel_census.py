@@ -1,7 +1,7 @@
 """Kernel census of the TIMED steps of a rocprofv3 kernel_trace.csv: dispatches per step by kernel name, counted inside real step windows
 (from one forward's first kernel to the next one's) instead of dividing the whole trace by a step count — bench.py's process also runs
-warm-up, parity, per-launch-timed and phase-timed steps, whose helper dispatches (event-pair replays, clones of outputs) would otherwise
-be charged to the timed step.
+warm-up steps (and with --full parity, per-launch-timed and phase-timed ones), whose helper dispatches (event-pair replays, clones of
+outputs) would otherwise be charged to the timed step.
 usage: python tools/step_kernel_census.py <kernel_trace.csv> [marker=cpb_fwd_batched] [pattern=rocclr|Fill|elementwise]"""
 import csv
 import re

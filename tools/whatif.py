@@ -28,7 +28,7 @@ def main():
             raise SystemExit(f"no op wrapper named {n}")
         ret = True if n in ("wgrad_mlp", "wgrad_group", "block_tail_fwd", "block_tail_bwd") else None
         setattr(ops, n, lambda *a, _r=ret, **k: _r)
-    sys.argv = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), "--no-parity", "--no-cpu-baseline",
+    sys.argv = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), "--full", "--no-parity", "--no-cpu-baseline",
                 "--steps", "10", "--warmup", "3"] + sys.argv[2:]
     runpy.run_path(sys.argv[0], run_name="__main__")
 
