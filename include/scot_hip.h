@@ -47,7 +47,7 @@ int scot_scale_inplace_dev(float* x, size_t n, const float* scale_dev, int* nonf
 int scot_segments_scale(float* x, const long long* chunks, int nchunks, const float* scale_dev, int* nonfinite, scot_stream_t stream);
 /* Local power-of-two rescale of a gradient branch behind a tiny per-channel scale (ConvNeXt layer scale, model.py:191-195,212-213)
  * in the binary16 build — all factors stay on the device:
- *   scot_pow2_rescale: out2[0] = c = 2^k (k >= 0) with max|v|·c in (1/2, 1], out2[1] = 1/c;
+ *   scot_pow2_rescale: out2[0] = c = 2^k (0 <= k <= 40: a branch is never scaled down) with max|v|·c in [1/2, 1), out2[1] = 1/c;
  *   scot_colscale_dev: out[r,c] = g[r,c] * gamma[c] * mul[0]  (out: fp32 or the 16-bit operand format; C % 8 == 0);
  *   scot_axpy_dev:     dst += alpha[0] * src  (fp32; clear_src: src = 0 afterwards). */
 int scot_pow2_rescale(const float* v, int n, float* out2, scot_stream_t stream);
@@ -122,8 +122,9 @@ int scot_gemm(int layout, int compute, int M, int N, int K,
               const void* resid, int res_dt, int ldres,
               int accumulate, float* colsum_out, void* workspace, size_t ws_bytes, int aux_mul, void* C2,
               scot_stream_t stream);
-/* colsum_out (optional, fp32, +=): NT/NN: column sums of the stored result; TN: Σ_k A[k][m] — i.e. the bias gradient
- * when A = dY, taken from the dY tile already staged in LDS.
+/* colsum_out (optional, fp32, +=): NT/NN: column sums of the result — of the stored values for an fp32 C; for a 16-bit C the tiled
+ * kernels (csrc/gemm_fast.hip) sum the fp32 values before the store rounds them, the generic kernel (csrc/gemm.hip) what it stored;
+ * TN: Σ_k A[k][m] — i.e. the bias gradient when A = dY, taken from the dY tile already staged in LDS.
  * workspace (optional, 32-byte aligned device scratch owned by the caller): TN splits K over workgroups and writes
  * partial tiles there, reduced by one extra pass; without it TN falls back to fp32 atomics.
  * C2 (optional, NT/NN): the epilogue stores gelu(v) to C and gelu'(v) to C2 (same dtype/ld; C2 == C: gelu(v) only, the

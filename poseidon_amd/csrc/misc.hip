@@ -1365,7 +1365,7 @@ extern "C" int scot_operand_format() {
 // ------------------------------------------------------------------ local power-of-two rescale of a gradient branch (fp16 build)
 // A branch that ends in a tiny per-channel scale (ConvNeXt layer scale, 1e-6 at initialisation: model.py:191-195, 212-213) receives
 // gradients ~2^-20 below the rest of the network; under the backward's one global scale they flush to zero in binary16.  The branch's
-// backward therefore runs on (g ⊙ γ)·c with c = the power of two that brings max|γ| into (1/2, 1], its parameter gradients
+// backward therefore runs on (g ⊙ γ)·c with c = the power of two that brings max|γ| into [1/2, 1), its parameter gradients
 // accumulate in a scratch copy of their arena range, and `scot_axpy_dev` adds scratch / c into the arena (and d_input / c into the
 // residual-stream gradient).  c lives on the DEVICE (computed from γ every step): no host round trip, nothing step-dependent in the
 // recorded launches.

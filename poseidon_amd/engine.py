@@ -1197,7 +1197,7 @@ class ScOTEngine:
         ls = self._ls.get(pre) if C % 8 == 0 else None
         d_y2 = self.new(B * L, C, dtype=self.adt)
         if ls is not None:
-            # binary16 operands: the branch's gradients are (g ⊙ γ)·c with c = 2^k bringing max|γ| into (1/2, 1]; its parameter
+            # binary16 operands: the branch's gradients are (g ⊙ γ)·c with c = 2^k bringing max|γ| into [1/2, 1); its parameter
             # gradients go to the block's scratch range and are handed to the arena divided by c at the end (all on the device)
             ops.pow2_rescale(self.P(pre + ".weight"), ls["cs"])
             ops.colscale_dev(g, self.P(pre + ".weight"), ls["cs"][0:1], d_y2, B * L, C)

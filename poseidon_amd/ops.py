@@ -520,7 +520,7 @@ def gather_pairs(data, it, src, a, b, pv, lab, T, nsrc, H, W, transpose):
 
 
 def pow2_rescale(v, out2):
-    """out2[0] = c = 2^k >= 1 with max|v|·c in (1/2, 1], out2[1] = 1/c (device-side; see csrc/misc.hip)."""
+    """out2[0] = c = 2^k >= 1 with max|v|·c in [1/2, 1), out2[1] = 1/c (device-side; see csrc/misc.hip)."""
     _lib.check(L().scot_pow2_rescale(ptr(v), v.numel(), ptr(out2), stream()), "scot_pow2_rescale")
 
 

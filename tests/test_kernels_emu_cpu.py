@@ -568,3 +568,107 @@ def test_step_tape_program_is_the_recorded_call_sequence(emu):
     assert marks == ["host step"]
     for a, r in zip(got, ref):
         assert torch.equal(a, r)
+
+
+# ---- tests/test_kernels_guarded_gpu.py on the emulated kernels: every operand and result inside poisoned guard bands, per-element bounds,
+# bit-identity with the unguarded launch — small ragged shapes, so that a stray access of the kernel SOURCES is seen before a GPU is used
+@pytest.fixture()
+def guarded_bodies(gpu_test_bodies):
+    import test_kernels_guarded_gpu as GG
+    return GG
+
+
+@pytest.mark.parametrize("compute,layout,mixed,M,N,K,pad", [
+    (ops.F32, ops.NT, False, 70, 40, 24, 8), (ops.F32, ops.TN, False, 40, 24, 70, 0), (ops.BF16, ops.NT, False, 130, 72, 40, 8),
+    (ops.BF16, ops.NN, False, 130, 72, 40, 0), (ops.BF16, ops.TN, False, 72, 40, 136, 8), (ops.BF16, ops.NT, True, 65, 34, 24, 3),
+    (ops.BF16, ops.NN, True, 65, 34, 24, 0), (ops.BF16, ops.NT, False, 257, 130, 72, 3), (ops.BF16, ops.NT, False, 192, 96, 96, 16)])
+def test_guarded_gemm_layouts(guarded_bodies, compute, layout, mixed, M, N, K, pad):
+    guarded_bodies.gemm_layouts_guarded(compute, layout, mixed, M, N, K, pad)
+
+
+@pytest.mark.parametrize("compute,M,N,K,pad", [(ops.BF16, 136, 72, 40, 8), (ops.F32, 70, 40, 24, 0)])
+def test_guarded_gemm_epilogues(guarded_bodies, compute, M, N, K, pad):
+    guarded_bodies.gemm_epilogues_guarded(compute, M, N, K, pad)
+
+
+@pytest.mark.parametrize("kind,M,N,K,variant,pad", [("bf16", 256, 128, 128, 0, 8), ("bf16", 128, 256, 128, 1, 0), ("f16", 128, 128, 192, 2, 8)])
+def test_guarded_gemm_wide_tiles(guarded_bodies, kind, M, N, K, variant, pad):
+    guarded_bodies.gemm_wide_tiles_guarded(kind, M, N, K, variant, pad)
+
+
+def test_guarded_gemm_split_k_bf16x3_nan_and_range(guarded_bodies):
+    guarded_bodies.gemm_split_k_atomic_guarded("bf16", 96, 136, 640, 3, 8)
+    guarded_bodies.gemm_bf16x3_guarded(ops.NT, 130, 72, 40, 8)
+    guarded_bodies.gemm_bf16x3_guarded(ops.TN, 40, 72, 136, 0)
+    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NT, True, 65, 34, 24)
+    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NT, False, 136, 64, 40)
+    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NN, False, 136, 64, 40)
+    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NT, False, 128, 128, 64, wide=(2, 0))
+    guarded_bodies.gemm_operands_near_binary16_maximum(65, 40, 72)
+
+
+@pytest.mark.parametrize("kind,K,dims,forced,scaled", [
+    ("bf16", 512, [(40, 72), (72, 40), (48, 48)], -1, False), ("f16", 512, [(40, 72), (72, 40), (48, 48)], -1, True),
+    ("bf16", 2048, [(96, 384), (384, 96), (96, 96), (288, 96)], -1, True), ("bf16", 256, [(128, 256), (256, 128), (128, 128)], 1, True),
+    ("bf16", 256, [(128, 256), (256, 128), (128, 128)], 1 | (2 << 4), False), ("bf16", 1000, [(40, 160), (160, 40), (40, 40), (120, 40)], -1, False)])
+def test_guarded_wgrad_group(guarded_bodies, kind, K, dims, forced, scaled):
+    guarded_bodies.wgrad_group_guarded(kind, K, dims, forced, scaled)
+
+
+@pytest.mark.parametrize("kind,M,C,mode", [("bf16", 200, 96, ops.GRAD_STORE_SCALED), ("f16", 72, 192, ops.GRAD_ADD)])
+def test_guarded_wgrad_mlp(guarded_bodies, kind, M, C, mode):
+    guarded_bodies.wgrad_mlp_guarded(kind, M, C, mode)
+
+
+@pytest.mark.parametrize("kind,compute,case", [("bf16", ops.BF16, (1, 32, 32, 32, 1, 16, 8)), ("f16", ops.BF16, (1, 16, 16, 32, 2, 16, 0)),
+                                               ("bf16", ops.BF16, (2, 8, 8, 32, 2, 4, 2)), ("bf16", ops.F32, (1, 14, 14, 16, 1, 7, 3)),
+                                               ("bf16", ops.X3, (1, 16, 16, 16, 1, 16, 0))], ids=lambda v: str(v).replace(" ", ""))
+def test_guarded_window_attention(guarded_bodies, kind, compute, case):
+    guarded_bodies.window_attention_guarded(kind, compute, case)
+
+
+@pytest.mark.parametrize("kind,compute,case", [("bf16", ops.BF16, (2, 8, 8, 32, 2, 4, 2)), ("f16", ops.BF16, (1, 16, 16, 32, 2, 16, 0)),
+                                               ("bf16", ops.F32, (1, 14, 14, 16, 1, 7, 3))], ids=lambda v: str(v).replace(" ", ""))
+def test_guarded_window_attention_zero_token(guarded_bodies, kind, compute, case):
+    guarded_bodies.window_attention_zero_token(kind, compute, case)
+
+
+@pytest.mark.parametrize("cond,xdt,B,L,C,const", [(True, torch.float32, 2, 40, 96, False), (False, torch.bfloat16, 2, 64, 192, False),
+                                                  (True, torch.float32, 3, 9, 20, True), (True, torch.bfloat16, 3, 16, 768, True),
+                                                  (False, torch.float32, 2, 6, 384, False)])
+def test_guarded_cln(guarded_bodies, cond, xdt, B, L, C, const):
+    guarded_bodies.cln_guarded(cond, xdt, B, L, C, constant_row=const)
+
+
+@pytest.mark.parametrize("kind,C,B,L,train,cond,next_qkv,lean", [("bf16", 48, 1, 72, True, True, True, False), ("f16", 48, 2, 64, False, False, False, False),
+                                                                 ("bf16", 96, 1, 72, True, True, True, False), ("bf16", 96, 1, 72, True, False, False, True),
+                                                                 ("bf16", 192, 1, 72, True, True, True, True), ("f16", 192, 1, 64, False, True, True, False)])
+def test_guarded_block_tail_fwd(guarded_bodies, kind, C, B, L, train, cond, next_qkv, lean):
+    guarded_bodies.block_tail_fwd_guarded(kind, C, B, L, train, cond, next_qkv, lean)
+
+
+@pytest.mark.parametrize("kind,C,B,L,cond,form", [("bf16", 48, 1, 64, True, "stored"), ("bf16", 96, 1, 72, True, "stored"), ("bf16", 96, 3, 64, False, "prologue"),
+                                                  ("bf16", 96, 1, 72, True, "lean"), ("f16", 192, 1, 64, False, "lean"), ("bf16", 192, 1, 72, True, "prologue")])
+def test_guarded_block_tail_bwd(guarded_bodies, kind, C, B, L, cond, form):
+    guarded_bodies.block_tail_bwd_guarded(kind, C, B, L, cond, form)
+
+
+@pytest.mark.parametrize("kind", ["bf16", "f16"])
+def test_guarded_small_ops(guarded_bodies, kind):
+    prev = ops.use(kind)
+    try:
+        guarded_bodies.flat_ops_guarded(1000 * 4 + 3)
+        guarded_bodies.flat_ops_guarded(8192)
+        guarded_bodies.column_ops_guarded(37, 24)
+        guarded_bodies.column_ops_guarded(128, 96)
+        guarded_bodies.gather_guarded(12, 12, True)
+        guarded_bodies.gather_guarded(9, 13, False)
+        guarded_bodies.data_movement_guarded()
+    finally:
+        ops.use(prev)
+
+
+@pytest.mark.parametrize("C,B,L,train,cond", [(96, 1, 72, True, True), (192, 1, 72, False, False)])
+def test_guarded_fused_halves(guarded_bodies, C, B, L, train, cond):
+    guarded_bodies.fused_halves_fwd_guarded(C, B, L, train, cond)
+    guarded_bodies.fused_halves_bwd_guarded(C, B, 64, cond)

@@ -169,17 +169,22 @@ def test_gemm_epilogues(compute):
 
 
 # ----------------------------------------------------------------------------------------------- attention
-def _attn_ref(qkv, table, logit_scale, B, Hp, Wp, C, heads, ws, shift):
-    """fp64 torch restatement on [B, Hp*Wp, 3C] with roll/partition (HF:389-455, ref model.py:522-559)."""
+def _attn_ref(qkv, table, logit_scale, B, Hp, Wp, C, heads, ws, shift, hook=None, reverse=False):
+    """fp64 torch restatement on [B, Hp*Wp, 3C] with roll/partition (HF:389-455, ref model.py:522-559).
+    hook(name, tensor) -> tensor (optional) is called on the normalised q and k ("qk"), the logits ("s"), the probabilities ("p") and the
+    result ("out"): the points where the kernels round (tests/test_kernels_guarded_gpu.py builds its rounding model from them);
+    reverse: the three contractions are summed in the opposite order (only differs in finite precision)."""
+    hk = hook if hook is not None else (lambda name, t: t)
+    fl = (lambda t, dim: t.flip(dim)) if reverse else (lambda t, dim: t)
     N, d = ws * ws, C // heads
     x = qkv.view(B, Hp, Wp, 3 * C)
     if shift:
         x = torch.roll(x, (-shift, -shift), (1, 2))
     xw = x.view(B, Hp // ws, ws, Wp // ws, ws, 3 * C).permute(0, 1, 3, 2, 4, 5).reshape(-1, N, 3 * C)
     q, k, v = [t.reshape(-1, N, heads, d).transpose(1, 2) for t in xw.split(C, dim=-1)]
-    qn = q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)
-    kn = k / k.norm(dim=-1, keepdim=True).clamp_min(1e-12)
-    s = qn @ kn.transpose(-1, -2) * torch.exp(torch.clamp(logit_scale, max=math.log(100.0))).view(1, heads, 1, 1)
+    qn = hk("qk", q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12))
+    kn = hk("qk", k / k.norm(dim=-1, keepdim=True).clamp_min(1e-12))
+    s = fl(qn, -1) @ fl(kn, -1).transpose(-1, -2) * torch.exp(torch.clamp(logit_scale, max=math.log(100.0))).view(1, heads, 1, 1)
     yy = torch.arange(ws, device=qkv.device).repeat_interleave(ws)
     xx = torch.arange(ws, device=qkv.device).repeat(ws)
     idx = (yy.view(-1, 1) - yy.view(1, -1) + ws - 1) * (2 * ws - 1) + (xx.view(-1, 1) - xx.view(1, -1) + ws - 1)
@@ -192,11 +197,11 @@ def _attn_ref(qkv, table, logit_scale, B, Hp, Wp, C, heads, ws, shift):
         m = (rid.unsqueeze(1) != rid.unsqueeze(2)).to(s.dtype) * (-200.0)
         nW = m.shape[0]
         s = (s.view(B, nW, heads, N, N) + m.view(1, nW, 1, N, N)).view(-1, heads, N, N)
-    o = (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(-1, ws, ws, C)
+    o = (fl(hk("p", torch.softmax(hk("s", s), -1)), -1) @ fl(v, -2)).transpose(1, 2).reshape(-1, ws, ws, C)
     o = o.view(B, Hp // ws, Wp // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, Hp, Wp, C)
     if shift:
         o = torch.roll(o, (shift, shift), (1, 2))
-    return o.reshape(B, Hp * Wp, C)
+    return hk("out", o.reshape(B, Hp * Wp, C))
 
 
 ATTN_CASES = [  # B, Hp, Wp, C, heads, ws, shift

@@ -1,0 +1,1686 @@
+"""The hot-path kernels inside poisoned guard bands, judged per element (tests/kernel_checks.py).
+
+Every operand and every result of a case is a view inside a larger allocation whose surroundings hold NaN of one fixed bit pattern
+(`kernel_checks.guarded`); the kernel is launched once on those views and once on plain tensors with the same contents.  Then
+  (a) every band, row gap and padding is intact bit for bit            — no store outside the extent the call was given;
+  (b) every result is finite                                          — no load outside it reached an MFMA or a sum (0 * NaN = NaN);
+  (c) the LOCAL bound of the family holds: `gemm_excess <= 1` for products (no stored tolerance: the componentwise bound of an
+      fp32-accumulated inner product plus one rounding), a per-row comparison against a rounding model for attention and the conditional
+      layer norm, an exact or single-rounding compare for data movement;
+  (d) the result is BIT-IDENTICAL to the plain launch wherever the entry point is deterministic — an answer that depends on what lies
+      beside the operands is wrong even when both answers are within tolerance.  Results the header documents as order-dependent (fp32
+      atomics: TN products, K slices, colsum_out, bias gradients, attention's dbias_table / dlogit_scale, the norms' parameter gradients)
+      take the tolerance of their existing test in test_kernels_gpu.py instead.
+References, shape lists and tolerances come from test_kernels_gpu (imported as G; G.DEV is read at call time, so the CPU emulation's patch
+of that name reaches every allocation here).  The bodies take their shapes as arguments: tests/test_kernels_emu_cpu.py calls them with
+small ragged shapes on the emulated kernels."""
+import math
+
+import pytest
+import torch
+
+import kernel_checks as kc
+import test_kernels_gpu as G
+from poseidon_amd import ops
+
+pytestmark = pytest.mark.gpu
+
+F32 = torch.float32
+U_MFMA16 = 2.0 ** -23      # per-add roundoff assumed for the 16-bit MFMAs' internal sum (see kernel_checks.gemm_excess)
+NAN = float("nan")
+
+
+class Guards:
+    """The guarded tensors of one case."""
+
+    def __init__(self):
+        self.items = []
+
+    def op(self, t, pad=0, name="operand"):
+        """guarded copy of an operand; pad > 0: row stride = row width + pad"""
+        if t is None:
+            return None
+        v, g = kc.guarded(tuple(t.shape), t.dtype, G.DEV, src=t, ld=(t.shape[-1] + pad) if pad else None, name=name)
+        self.items.append(g)
+        return v
+
+    def out(self, shape, dtype, pad=0, src=None, fill=None, name="result"):
+        """guarded result: NaN body unless the op accumulates (src / fill)"""
+        v, g = kc.guarded(tuple(shape), dtype, G.DEV, src=src, fill=fill, ld=(shape[-1] + pad) if pad else None, name=name)
+        self.items.append(g)
+        return v
+
+    def group(self, shapes, dtype, srcs=None, fills=None, name="group"):
+        vs, g = kc.guarded_group(shapes, dtype, G.DEV, srcs=srcs, fills=fills, name=name)
+        self.items.append(g)
+        return vs
+
+    def check(self):
+        kc.check_all(self.items)
+
+
+def sync():
+    torch.cuda.synchronize()
+
+
+def nan_like(shape, dtype):
+    return torch.full(tuple(shape), NAN, device=G.DEV, dtype=dtype)
+
+
+def finite(t):
+    """(b): True, or an AssertionError that says how much of the result is not finite and where"""
+    bad = ~torch.isfinite(t.float() if t.dtype != torch.float64 else t)
+    if bool(bad.any()):
+        idx = bad.nonzero()
+        rows = bad.reshape(-1, bad.shape[-1]).any(-1).nonzero().flatten()
+        raise AssertionError(f"non-finite result (an over-read reached an MFMA or a sum?): {int(bad.sum())} of {bad.numel()} element(s) of a {tuple(t.shape)} "
+                             f"tensor, first at {idx[0].tolist()}, last at {idx[-1].tolist()}; {rows.numel()} row(s) affected, first {int(rows[0])}, last {int(rows[-1])}")
+    return True
+
+
+def same(a, b):
+    """bit-identical (torch.equal treats NaN as unequal: a NaN result fails here as well)"""
+    return a.shape == b.shape and torch.equal(a.contiguous(), b.contiguous())
+
+
+def u_add(compute):
+    return kc.U32 if compute == ops.F32 else U_MFMA16
+
+
+def assert_excess(what, got, ref, mag, nadd, uadd, extra=0.0, tile=None, abs_extra=None):
+    """(c) for products.  `mag` is the magnitude sum of everything that enters an element in fp32 before the single rounding — |A| |B| plus
+    the absolute values of the epilogue's addends, times the absolute values of its factors — and `nadd` the number of fp32 roundings on
+    that path: K for the contraction, one more per epilogue operation.  Every one of them is at most u * (a partial magnitude) <= u * mag."""
+    worst, idx = kc.gemm_excess(got, ref, mag, nadd, kc.UNIT[got.dtype], extra=extra, u_add=uadd, abs_extra=abs_extra)
+    print(f"worst excess {what}: {worst:.3f} at {idx}")
+    assert worst <= 1.0, f"{what}: element {idx} is {worst:.2f} x its bound; {kc.describe_worst(got, ref, tile=tile)}"
+    return worst
+
+
+# =========================================================================================================================== GEMM
+def _operands(layout, compute, mixed, M, N, K):
+    adt = F32 if compute in (ops.F32, ops.X3) else ops.half_dtype()
+    bdt = F32 if mixed else adt
+    if layout == ops.NT:
+        return G.rnd(M, K, dtype=adt), G.rnd(N, K, dtype=bdt, scale=K ** -0.5, seed=1)
+    if layout == ops.NN:
+        return G.rnd(M, K, dtype=adt), G.rnd(K, N, dtype=bdt, scale=K ** -0.5, seed=1)
+    return G.rnd(K, M, dtype=adt), G.rnd(K, N, dtype=bdt, scale=K ** -0.5, seed=1)
+
+
+def _product64(layout, compute, A, B):
+    """fp64 product and |A| |B| on the operands as the MFMA sees them (a fp32 B beside a 16-bit A is rounded while it is staged)"""
+    Aq = A.double()
+    Bq = (B.to(ops.half_dtype()) if compute == ops.BF16 else B).double()
+    if layout == ops.NT:
+        return Aq @ Bq.t(), Aq.abs() @ Bq.abs().t()
+    if layout == ops.NN:
+        return Aq @ Bq, Aq.abs() @ Bq.abs()
+    return Aq.t() @ Bq, Aq.abs().t() @ Bq.abs()
+
+
+class _gemm_config:
+    """library-wide tile / K-slice policy for one case, restored afterwards"""
+
+    def __init__(self, wide=None, splitk=(-1, 0)):
+        self.wide, self.splitk = wide, splitk
+
+    def __enter__(self):
+        lib = ops.L()
+        if self.wide is not None:
+            lib.scot_gemm_wide_config(*self.wide)
+        lib.scot_gemm_splitk_config(*self.splitk)
+        return lib
+
+    def __exit__(self, *exc):
+        lib = ops.L()
+        lib.scot_gemm_wide_config(1, 0)
+        lib.scot_gemm_splitk_config(0, 1)
+
+
+GEMM_PADS = [(c, 0) for c in G.GEMM_CASES] + [(c, 8) for c in G.GEMM_CASES] + \
+            [(c, 3) for c in G.GEMM_CASES if c[3:] in ((257, 130, 72), (520, 64, 40))]       # 3: rows off every vector alignment (scalar loaders)
+
+
+@pytest.mark.parametrize("case,pad", GEMM_PADS, ids=lambda v: "-".join(str(int(x)) for x in v) if isinstance(v, tuple) else f"pad{v}")
+def test_gemm_layouts_guarded(case, pad):
+    gemm_layouts_guarded(*case, pad)
+
+
+def gemm_layouts_guarded(compute, layout, mixed, M, N, K, pad):
+    """scot_gemm NT / NN / TN, operands in the compute type (gemm_panel / gemm_fast) and fp32 B beside 16-bit A (the generic kernel), fp32 and
+    16-bit results, with `lda / ldb / ldc / ldres` = width + pad.  K slices with atomics are off here (their own test below), so NT / NN are
+    deterministic; TN (split K, atomics or partial tiles) and colsum_out are order-dependent."""
+    A, B = _operands(layout, compute, mixed, M, N, K)
+    ref, ab = _product64(layout, compute, A, B)
+    tn = layout == ops.TN
+    ua = u_add(compute)
+    with _gemm_config():
+        gd = Guards()
+        Ag, Bg = gd.op(A, pad, "A"), gd.op(B, pad, "B")
+        lda, ldb = A.shape[1] + pad, B.shape[1] + pad
+        tol = 2e-5 if compute == ops.F32 else 2e-3
+        for cdt in ([F32] if tn or compute != ops.BF16 else [F32, ops.half_dtype()]):
+            C0 = G.rnd(M, N, seed=9) if tn else None
+            Cg = gd.out((M, N), cdt, pad, src=C0, name="C")
+            Cp = C0.clone() if tn else nan_like((M, N), cdt)
+            ncs = M if tn else N
+            csg, csp = gd.out((ncs,), F32, fill=0.0, name="colsum_out"), torch.zeros(ncs, device=G.DEV)
+            ops.gemm(layout, compute, M, N, K, Ag, lda, Bg, ldb, Cg, N + pad, accumulate=tn, colsum_out=csg)
+            ops.gemm(layout, compute, M, N, K, A, A.shape[1], B, B.shape[1], Cp, N, accumulate=tn, colsum_out=csp)
+            sync()
+            gd.check()
+            assert finite(Cg) and finite(csg)
+            if tn:      # C0 + sum of K products, in slices: at most K + (number of slices) + 1 additions, a slice is at least 32 deep
+                assert_excess(f"gemm TN {M}x{N}x{K} compute {compute}", Cg, C0.double() + ref, ab + C0.double().abs(), K + K // 32 + 2, ua)
+                assert G.rel(Cg, C0.double() + ref) < tol and G.rel(Cg, Cp) < 2e-6
+                assert G.rel(csg, A.double().sum(0)) < 1e-4
+            else:
+                assert_excess(f"gemm layout {layout} {M}x{N}x{K} compute {compute} mixed {mixed} -> {cdt}", Cg, ref, ab, K, ua)
+                assert same(Cg, Cp), kc.describe_worst(Cg, Cp.double())
+                # fp32 C: sums of the stored result.  16-bit C (include/scot_hip.h): the tiled kernels (csrc/gemm_fast.hip: operands in the
+                # compute type, N, K and the leading dimensions multiples of 8) sum the fp32 values BEFORE the store rounds them, the generic
+                # kernel (csrc/gemm.hip: everything else) sums what it stored
+                tiled = not mixed and pad % 8 == 0 and N % 8 == 0 and K % 8 == 0 and (layout == ops.NT or N >= 8)
+                assert G.rel(csg, ref.sum(0) if (cdt != F32 and tiled) else Cg.double().sum(0)) < 1e-4
+        if not tn:      # bias + residual (strided too), no column sums: small grids take the split-K + epilogue-pass route
+            bias, res = G.rnd(N, seed=5), G.rnd(M, N, seed=6)
+            bg, rg = gd.op(bias, name="bias"), gd.op(res, pad, "resid")
+            C2g, C2p = gd.out((M, N), F32, pad, name="C (bias + resid)"), nan_like((M, N), F32)
+            ops.gemm(layout, compute, M, N, K, Ag, lda, Bg, ldb, C2g, N + pad, bias=bg, resid=rg, ldres=N + pad)
+            ops.gemm(layout, compute, M, N, K, A, A.shape[1], B, B.shape[1], C2p, N, bias=bias, resid=res, ldres=N)
+            sync()
+            gd.check()
+            assert finite(C2g)
+            assert_excess(f"gemm layout {layout} {M}x{N}x{K} compute {compute} mixed {mixed} + bias + resid", C2g, ref + bias.double() + res.double(),
+                          ab + bias.double().abs() + res.double().abs(), K + 2, ua)
+            assert same(C2g, C2p), kc.describe_worst(C2g, C2p.double())
+
+
+def _gelu64(u):
+    return torch.nn.functional.gelu(u)
+
+
+def _gelu_grad64(u):
+    return 0.5 * (1 + torch.erf(u / math.sqrt(2))) + u * torch.exp(-0.5 * u * u) / math.sqrt(2 * math.pi)
+
+
+# The library's GELU (csrc/common.h, gelu_terms): Phi(x) = 0.5 + sign(x) (0.5 - poly(t) e), t = rcp(1 + p z), e = exp2(-z^2 log2 e), z = |x| / sqrt 2,
+# Abramowitz-Stegun 7.1.26, for which the source states |abs err of erf| <= 1.5e-7, i.e. 0.75e-7 on Phi.  On top of that its evaluation in fp32:
+# every quantity of the chain lies in [0, 1]; v_rcp_f32 and v_exp_f32 are 1-ulp instructions, the argument of the exponential carries two
+# roundings and x e^-x <= 0.37, the five Horner steps, the two fused multiply-adds and the final add one rounding each on values <= 1 — twelve
+# roundings of at most 2^-24 in all, taken at full size.  The Gaussian term e alone: its instruction, and its argument's two roundings: 4 x 2^-24.
+D_CDF = 0.75e-7 + 12 * kc.U32
+D_EXP = 4 * kc.U32
+INV_SQRT_2PI = 0.3989422804014327
+
+
+def gelu_eval_err(v64):
+    """absolute error of the library's gelu(v) and gelu'(v) evaluated in fp32 AT the fp32 value v: (|v| dPhi + one product rounding,
+    dPhi + |v| c dE + two product roundings and an add)"""
+    g, gp = _gelu64(v64), _gelu_grad64(v64)
+    gauss = v64.abs() * INV_SQRT_2PI * torch.exp(-0.5 * v64 * v64)
+    return v64.abs() * D_CDF + kc.U32 * g.abs(), D_CDF + v64.abs() * INV_SQRT_2PI * D_EXP + 2 * kc.U32 * gauss + kc.U32 * gp.abs()
+
+
+# |gelu'| <= 1.13 and |gelu''| = |(2 - x^2) phi(x)| <= 2 phi(0) < 0.8: how an error dv of the epilogue's fp32 value v moves gelu(v) and gelu'(v)
+LIP_GELU, LIP_GELU_GRAD = 1.13, 0.8
+
+
+def gelu_operand_err(u64, u_op):
+    """elementwise bound on |operand the MFMA sees - gelu64(u)| when gelu(u) is evaluated on load and rounded to an operand format of unit
+    roundoff u_op (0 for fp32 operands): the evaluation error, then one rounding of a value within that error of gelu64(u)"""
+    ev, _ = gelu_eval_err(u64)
+    return ev + u_op * (_gelu64(u64).abs() + ev)
+
+
+@pytest.mark.parametrize("pad", [0, 8, 16])
+@pytest.mark.parametrize("compute", [ops.F32, ops.BF16])
+def test_gemm_epilogues_guarded(compute, pad):
+    gemm_epilogues_guarded(compute, 520, 192, 96, pad)
+
+
+def gemm_epilogues_guarded(compute, M, N, K, pad):
+    """The epilogue forms of test_gemm_epilogues with every operand guarded and strided: bias -> 16-bit u; GELU-on-load + bias + colscale +
+    residual; gelu' multiply from aux; aux_mul; accumulate; TN with GELU on the B operand + colsum_out; the gelu / gelu' dual store.
+    (c): gemm_excess on every form.  Where the epilogue evaluates erf / exp (GELU on load, gelu', the dual store) the bound takes the
+    library's own statement on its erf approximation (csrc/common.h: |abs err| <= 1.5e-7) plus its fp32 evaluation (D_CDF, D_EXP above) as
+    an absolute term: gelu / gelu' move by at most 1.13 / 0.8 times the error of the fp32 value they are taken of, plus their own
+    evaluation error; an operand that is gelu(u) evaluated on load differs from gelu64(u) by gelu_operand_err, which enters as E |B|."""
+    cdt = F32 if compute == ops.F32 else ops.half_dtype()
+    tol = 2e-5 if compute == ops.F32 else 1e-2
+    ua = u_add(compute)
+    u_op = 0.0 if compute == ops.F32 else kc.UNIT[cdt]
+    x, w, b = G.rnd(M, K, dtype=cdt), G.rnd(N, K, dtype=cdt, scale=0.1, seed=1), G.rnd(N, seed=2)
+    with _gemm_config():
+        gd = Guards()
+        xg, wg, bg = gd.op(x, pad, "x"), gd.op(w, pad, "w"), gd.op(b, name="bias")
+        # fc1: u = x w^T + b in the compute type
+        ug, up = gd.out((M, N), cdt, pad, name="u"), nan_like((M, N), cdt)
+        ops.gemm(ops.NT, compute, M, N, K, xg, K + pad, wg, K + pad, ug, N + pad, bias=bg)
+        ops.gemm(ops.NT, compute, M, N, K, x, K, w, K, up, N, bias=b)
+        sync()
+        gd.check()
+        ref_u = x.double() @ w.double().t() + b.double()
+        assert finite(ug) and same(ug, up)
+        assert_excess(f"epilogue bias compute {compute}", ug, ref_u, x.double().abs() @ w.double().abs().t() + b.double().abs(), K + 1, ua)
+        # fc2 with GELU on load: y = (gelu(u) w2^T + b2) * cs + res
+        w2, b2, cs, res = G.rnd(K, N, dtype=cdt, scale=0.1, seed=3), G.rnd(K, seed=4), G.rnd(K, seed=5), G.rnd(M, K, seed=6)
+        w2g, b2g, csg, resg = gd.op(w2, pad, "w2"), gd.op(b2, name="b2"), gd.op(cs, name="colscale"), gd.op(res, pad, "resid")
+        yg, yp = gd.out((M, K), F32, pad, name="y"), nan_like((M, K), F32)
+        ops.gemm(ops.NT, compute, M, K, N, ug, N + pad, w2g, N + pad, yg, K + pad, bias=b2g, colscale=csg, resid=resg, ldres=K + pad, a_gelu=True)
+        ops.gemm(ops.NT, compute, M, K, N, up, N, w2, N, yp, K, bias=b2, colscale=cs, resid=res, ldres=K, a_gelu=True)
+        sync()
+        gd.check()
+        g64 = _gelu64(up.double())
+        assert finite(yg) and same(yg, yp)
+        assert G.rel(yg, (g64 @ w2.double().t() + b2.double()) * cs.double() + res.double()) < tol
+        e_a = gelu_operand_err(up.double(), u_op)            # the A operand as the MFMA sees it against gelu64 of the stored u
+        assert_excess(f"epilogue GELU on load, bias * colscale + resid compute {compute}", yg, (g64 @ w2.double().t() + b2.double()) * cs.double() + res.double(),
+                      ((g64.abs() + e_a) @ w2.double().abs().t() + b2.double().abs()) * cs.double().abs() + res.double().abs(), N + 3, ua,
+                      abs_extra=(e_a @ w2.double().abs().t()) * cs.double().abs())
+        # the rational part of the same epilogue without GELU on load: per element
+        y2g, y2p = gd.out((M, K), F32, pad, name="y2"), nan_like((M, K), F32)
+        ops.gemm(ops.NT, compute, M, K, N, ug, N + pad, w2g, N + pad, y2g, K + pad, bias=b2g, colscale=csg, resid=resg, ldres=K + pad)
+        ops.gemm(ops.NT, compute, M, K, N, up, N, w2, N, y2p, K, bias=b2, colscale=cs, resid=res, ldres=K)
+        sync()
+        gd.check()
+        u64 = up.double()
+        assert finite(y2g) and same(y2g, y2p)
+        assert_excess(f"epilogue bias * colscale + resid compute {compute}", y2g, (u64 @ w2.double().t() + b2.double()) * cs.double() + res.double(),
+                      (u64.abs() @ w2.double().abs().t() + b2.double().abs()) * cs.double().abs() + res.double().abs(), N + 3, ua)
+        # dgrad (NN): du = (dy w2) * gelu'(u); * aux as is; accumulate
+        dy = G.rnd(M, K, dtype=cdt, seed=7)
+        dyg = gd.op(dy, pad, "dy")
+        dug, dup = gd.out((M, N), cdt, pad, name="du"), nan_like((M, N), cdt)
+        ops.gemm(ops.NN, compute, M, N, K, dyg, K + pad, w2g, N + pad, dug, N + pad, aux=ug, ldaux=N + pad)
+        ops.gemm(ops.NN, compute, M, N, K, dy, K, w2, N, dup, N, aux=up, ldaux=N)
+        sync()
+        gd.check()
+        prod, aprod = dy.double() @ w2.double(), dy.double().abs() @ w2.double().abs()
+        assert finite(dug) and same(dug, dup) and G.rel(dug, prod * _gelu_grad64(u64)) < tol
+        # v = acc * gelu'(aux): the factor carries its evaluation error (aux is a stored operand: no error of its own), then one product rounding
+        assert_excess(f"epilogue * gelu'(aux) compute {compute}", dug, prod * _gelu_grad64(u64), aprod * _gelu_grad64(u64).abs(), K + 1, ua,
+                      abs_extra=(prod.abs() + K * ua * aprod) * gelu_eval_err(u64)[1])
+        aux = G.rnd(M, N, dtype=cdt, seed=8)
+        auxg = gd.op(aux, pad, "aux")
+        dmg, dmp = gd.out((M, N), cdt, pad, name="du (aux_mul)"), nan_like((M, N), cdt)
+        ops.gemm(ops.NN, compute, M, N, K, dyg, K + pad, w2g, N + pad, dmg, N + pad, aux=auxg, ldaux=N + pad, aux_mul=True)
+        ops.gemm(ops.NN, compute, M, N, K, dy, K, w2, N, dmp, N, aux=aux, ldaux=N, aux_mul=True)
+        sync()
+        gd.check()
+        assert finite(dmg) and same(dmg, dmp)
+        assert_excess(f"epilogue aux_mul compute {compute}", dmg, prod * aux.double(), aprod * aux.double().abs(), K + 1, ua)
+        acc0 = G.rnd(M, N, seed=9)
+        ag, ap = gd.out((M, N), F32, pad, src=acc0, name="accumulated"), acc0.clone()
+        ops.gemm(ops.NN, compute, M, N, K, dyg, K + pad, w2g, N + pad, ag, N + pad, accumulate=True)
+        ops.gemm(ops.NN, compute, M, N, K, dy, K, w2, N, ap, N, accumulate=True)
+        sync()
+        gd.check()
+        assert finite(ag) and same(ag, ap)
+        assert_excess(f"epilogue accumulate compute {compute}", ag, acc0.double() + prod, aprod + acc0.double().abs(), K + 1, ua)
+        # wgrad (TN) with GELU on the B operand + bias gradient
+        dw0, db0 = G.rnd(K, N, seed=10), G.rnd(K, seed=11)
+        dwg, dbg = gd.out((K, N), F32, pad, src=dw0, name="dw"), gd.out((K,), F32, src=db0, name="dbias")
+        ops.gemm(ops.TN, compute, K, N, M, dyg, K + pad, ug, N + pad, dwg, N + pad, b_gelu=True, accumulate=True, colsum_out=dbg)
+        sync()
+        gd.check()
+        assert finite(dwg) and G.rel(dwg - dw0, dy.double().t() @ g64) < tol and G.rel(dbg - db0, dy.double().sum(0)) < 1e-4
+        assert_excess(f"epilogue TN with GELU on the B operand compute {compute}", dwg, dw0.double() + dy.double().t() @ g64,
+                      dy.double().abs().t() @ (g64.abs() + e_a) + dw0.double().abs(), M + M // 32 + 2, ua, abs_extra=dy.double().abs().t() @ e_a)
+        # the fc1 form: gelu(v) and gelu'(v) from one pass
+        a_g, gp_g = gd.out((M, N), cdt, pad, name="gelu(u)"), gd.out((M, N), cdt, pad, name="gelu'(u)")
+        a_p, gp_p = nan_like((M, N), cdt), nan_like((M, N), cdt)
+        ops.gemm(ops.NT, compute, M, N, K, xg, K + pad, wg, K + pad, a_g, N + pad, bias=bg, gelu_deriv_out=gp_g)
+        ops.gemm(ops.NT, compute, M, N, K, x, K, w, K, a_p, N, bias=b, gelu_deriv_out=gp_p)
+        sync()
+        gd.check()
+        assert finite(a_g) and finite(gp_g) and same(a_g, a_p) and same(gp_g, gp_p)
+        assert G.rel(a_g, _gelu64(ref_u)) < tol and G.rel(gp_g, _gelu_grad64(ref_u)) < tol
+        dv = (K + 1) * ua * (x.double().abs() @ w.double().abs().t() + b.double().abs())       # error of the fp32 value v the two are taken of
+        ev_g, ev_gp = gelu_eval_err(ref_u)
+        zero = torch.zeros_like(ref_u)
+        assert_excess(f"epilogue gelu(v) of the dual store compute {compute}", a_g, _gelu64(ref_u), zero, 0, ua, abs_extra=LIP_GELU * dv + ev_g + D_CDF * dv)
+        assert_excess(f"epilogue gelu'(v) of the dual store compute {compute}", gp_g, _gelu_grad64(ref_u), zero, 0, ua, abs_extra=LIP_GELU_GRAD * dv + ev_gp)
+
+
+WIDE_GUARDED = G.WIDE_CASES + [(384, 256, 192, 0), (384, 256, 192, 1), (384, 256, 192, 2)]      # + three tile rows / two tile columns per variant
+
+
+@pytest.mark.parametrize("pad", [0, 8])
+@pytest.mark.parametrize("kind", ["f16", "bf16"])
+@pytest.mark.parametrize("M,N,K,variant", WIDE_GUARDED)
+def test_gemm_wide_tiles_guarded(kind, M, N, K, variant, pad):
+    gemm_wide_tiles_guarded(kind, M, N, K, variant, pad)
+
+
+def gemm_wide_tiles_guarded(kind, M, N, K, variant, pad):
+    """csrc/gemm_wide.hip (128 x 128 tiles; the three instantiations forced as test_gemm_wide_tiles does, -1 = the library's policy): the
+    engine's forms — bias to fp32 and to 16 bits, the gelu / gelu' dual store, the data gradient times aux, the accumulating data gradient —
+    guarded and strided.  16-bit results are where one global norm is blind: here every element is held to its own bound."""
+    prev = ops.use(kind)
+    try:
+        hd = ops.half_dtype()
+        tol16 = 1.2e-3 if kind == "f16" else 6e-3
+        x, w, b = G.rnd(M, K, dtype=hd), G.rnd(N, K, dtype=hd, scale=K ** -0.5, seed=1), G.rnd(N, seed=2)
+        u = x.double() @ w.double().t() + b.double()
+        mag = x.double().abs() @ w.double().abs().t() + b.double().abs()
+        with _gemm_config(wide=(1 if variant < 0 else 2, max(variant, 0))):
+            gd = Guards()
+            xg, wg, bg = gd.op(x, pad, "x"), gd.op(w, pad, "w"), gd.op(b, name="bias")
+            for odt in (F32, hd):
+                yg, yp = gd.out((M, N), odt, pad, name=f"y {odt}"), nan_like((M, N), odt)
+                ops.gemm(ops.NT, ops.BF16, M, N, K, xg, K + pad, wg, K + pad, yg, N + pad, bias=bg)
+                ops.gemm(ops.NT, ops.BF16, M, N, K, x, K, w, K, yp, N, bias=b)
+                sync()
+                gd.check()
+                assert finite(yg) and same(yg, yp), kc.describe_worst(yg, yp.double(), tile=128)
+                assert_excess(f"gemm_wide {kind} {M}x{N}x{K} variant {variant} -> {odt}", yg, u, mag, K + 1, U_MFMA16, tile=128)
+            gvg, gdg = gd.out((M, N), hd, pad, name="gelu"), gd.out((M, N), hd, pad, name="gelu'")
+            gvp, gdp = nan_like((M, N), hd), nan_like((M, N), hd)
+            ops.gemm(ops.NT, ops.BF16, M, N, K, xg, K + pad, wg, K + pad, gvg, N + pad, bias=bg, gelu_deriv_out=gdg)
+            ops.gemm(ops.NT, ops.BF16, M, N, K, x, K, w, K, gvp, N, bias=b, gelu_deriv_out=gdp)
+            sync()
+            gd.check()
+            assert finite(gvg) and finite(gdg) and same(gvg, gvp) and same(gdg, gdp)
+            assert G.rel(gvg, _gelu64(u)) < tol16 and G.rel(gdg, _gelu_grad64(u)) < tol16
+            dv = (K + 1) * U_MFMA16 * mag                     # error of the fp32 value v = x w^T + b that gelu and gelu' are taken of
+            ev_g, ev_gp = gelu_eval_err(u)
+            zero = torch.zeros_like(u)
+            assert_excess(f"gemm_wide {kind} {M}x{N}x{K} variant {variant} gelu(v)", gvg, _gelu64(u), zero, 0, U_MFMA16, tile=128,
+                          abs_extra=LIP_GELU * dv + ev_g + D_CDF * dv)
+            assert_excess(f"gemm_wide {kind} {M}x{N}x{K} variant {variant} gelu'(v)", gdg, _gelu_grad64(u), zero, 0, U_MFMA16, tile=128,
+                          abs_extra=LIP_GELU_GRAD * dv + ev_gp)
+            if K % 128 == 0 and N % 64 == 0:      # data gradients dx[M, K] = dy[M, N] w[N, K]: an NT product on the transposed copy
+                dy, wt, aux = G.rnd(M, N, dtype=hd, seed=3), w.t().contiguous(), G.rnd(M, K, dtype=hd, seed=4)
+                dyg, wtg, auxg = gd.op(dy, pad, "dy"), gd.op(wt, pad, "wt"), gd.op(aux, pad, "aux")
+                prod, aprod = dy.double() @ w.double(), dy.double().abs() @ w.double().abs()
+                dxg, dxp = gd.out((M, K), hd, pad, name="dx"), nan_like((M, K), hd)
+                ops.gemm(ops.NT, ops.BF16, M, K, N, dyg, N + pad, wtg, N + pad, dxg, K + pad, aux=auxg, ldaux=K + pad, aux_mul=True)
+                ops.gemm(ops.NT, ops.BF16, M, K, N, dy, N, wt, N, dxp, K, aux=aux, ldaux=K, aux_mul=True)
+                g0 = G.rnd(M, K, seed=5)
+                gg, gp = gd.out((M, K), F32, pad, src=g0, name="g (accumulated)"), g0.clone()
+                ops.gemm(ops.NT, ops.BF16, M, K, N, dyg, N + pad, wtg, N + pad, gg, K + pad, accumulate=True)
+                ops.gemm(ops.NT, ops.BF16, M, K, N, dy, N, wt, N, gp, K, accumulate=True)
+                sync()
+                gd.check()
+                assert finite(dxg) and finite(gg) and same(dxg, dxp) and same(gg, gp)
+                assert_excess(f"gemm_wide {kind} dgrad * aux {M}x{K}x{N} variant {variant}", dxg, prod * aux.double(), aprod * aux.double().abs(), N + 1,
+                              U_MFMA16, tile=128)
+                assert_excess(f"gemm_wide {kind} dgrad accumulate {M}x{K}x{N} variant {variant}", gg, g0.double() + prod, aprod + g0.double().abs(), N + 1,
+                              U_MFMA16, tile=128)
+    finally:
+        ops.use(prev)
+
+
+@pytest.mark.parametrize("pad", [0, 8])
+@pytest.mark.parametrize("kind", ["f16", "bf16"])
+@pytest.mark.parametrize("M,N,K,S", [(1024, 768, 3072, 2), (1024, 768, 2304, 3), (4096, 384, 1536, 4), (1000, 200, 1088, 2)])
+def test_gemm_split_k_atomic_guarded(kind, M, N, K, S, pad):
+    gemm_split_k_atomic_guarded(kind, M, N, K, S, pad)
+
+
+def gemm_split_k_atomic_guarded(kind, M, N, K, S, pad):
+    """K slices adding into an fp32 result with atomics (csrc/gemm_fast.hip): the zeroed forward form and the accumulating data-gradient form.
+    Order-dependent, so no bit compare; but the componentwise bound holds in ANY order: K products + S partial sums + bias / C0."""
+    prev = ops.use(kind)
+    try:
+        hd = ops.half_dtype()
+        x, w, b = G.rnd(M, K, dtype=hd), G.rnd(N, K, dtype=hd, scale=K ** -0.5, seed=1), G.rnd(N, seed=2)
+        prod, aprod = x.double() @ w.double().t(), x.double().abs() @ w.double().abs().t()
+        with _gemm_config(wide=(0, 0), splitk=(S, 1)):
+            gd = Guards()
+            xg, wg, bg = gd.op(x, pad, "x"), gd.op(w, pad, "w"), gd.op(b, name="bias")
+            yg = gd.out((M, N), F32, pad, name="y (zeroed by the launcher)")
+            ops.gemm(ops.NT, ops.BF16, M, N, K, xg, K + pad, wg, K + pad, yg, N + pad, bias=bg)
+            g0 = G.rnd(M, N, seed=5)
+            gg = gd.out((M, N), F32, pad, src=g0, name="g (accumulated)")
+            ops.gemm(ops.NT, ops.BF16, M, N, K, xg, K + pad, wg, K + pad, gg, N + pad, accumulate=True)
+            sync()
+            gd.check()
+            assert finite(yg) and finite(gg)
+            assert_excess(f"split-K {kind} {M}x{N}x{K} S={S} forward", yg, prod + b.double(), aprod + b.double().abs(), K + S + 1, U_MFMA16)
+            assert_excess(f"split-K {kind} {M}x{N}x{K} S={S} accumulate", gg, g0.double() + prod, aprod + g0.double().abs(), K + S + 1, U_MFMA16)
+            assert G.rel(yg, prod + b.double()) < 2e-6 and G.rel(gg, g0.double() + prod) < 1e-6
+    finally:
+        ops.use(prev)
+
+
+@pytest.mark.parametrize("pad", [0, 8])
+@pytest.mark.parametrize("layout,M,N,K", [(ops.NT, 4096, 288, 96), (ops.NN, 1000, 384, 96), (ops.TN, 96, 288, 4100 // 4 * 4), (ops.NT, 300, 72, 40)])
+def test_gemm_bf16x3_guarded(layout, M, N, K, pad):
+    gemm_bf16x3_guarded(layout, M, N, K, pad)
+
+
+def gemm_bf16x3_guarded(layout, M, N, K, pad):
+    """compute = bf16x3 (fp32 operands split into hi + lo while staged).  Its operand error (~2^-17 per product) is a property of
+    the split, not of the accumulation, so the per-element bound is the fp32 one with that operand term added: 3 * 2^-17 |A| |B| (hi·lo,
+    lo·hi kept, lo·lo dropped, two operand roundings)."""
+    A, B = _operands(layout, ops.X3, False, M, N, K)
+    ref, ab = _product64(layout, ops.X3, A, B)
+    tn = layout == ops.TN
+    with _gemm_config():
+        gd = Guards()
+        Ag, Bg = gd.op(A, pad, "A"), gd.op(B, pad, "B")
+        C0 = G.rnd(M, N, seed=9) if tn else None
+        Cg, Cp = gd.out((M, N), F32, pad, src=C0, name="C"), (C0.clone() if tn else nan_like((M, N), F32))
+        bias = None if tn else G.rnd(N, seed=2)
+        ops.gemm(layout, ops.X3, M, N, K, Ag, A.shape[1] + pad, Bg, B.shape[1] + pad, Cg, N + pad, bias=gd.op(bias, name="bias"), accumulate=tn)
+        ops.gemm(layout, ops.X3, M, N, K, A, A.shape[1], B, B.shape[1], Cp, N, bias=bias, accumulate=tn)
+        sync()
+        gd.check()
+        full = ref + (C0.double() if tn else bias.double())
+        mag = ab + (C0.double().abs() if tn else bias.double().abs())
+        assert finite(Cg) and G.rel(Cg, full) < 2e-5
+        # K * u_add * mag covers the accumulation; the split's operand error enters as a multiple of the same |A| |B| term
+        nadd = 3 * K + K // 32 + 2 + math.ceil(3 * 2.0 ** -17 / U_MFMA16)
+        assert_excess(f"bf16x3 layout {layout} {M}x{N}x{K}", Cg, full, mag, nadd, U_MFMA16)
+        if not tn:
+            assert same(Cg, Cp)
+
+
+NAN_CASES = [("generic (fp32 B beside 16-bit A)", ops.NT, True, 257, 130, 72), ("gemm_fast 64 x 64", ops.NT, False, 520, 64, 40),
+             ("gemm_fast NN", ops.NN, False, 520, 64, 40), ("gemm_panel", ops.NT, False, 4096, 384, 96), ("gemm_wide", ops.NT, False, 384, 256, 192)]
+
+
+@pytest.mark.parametrize("what,layout,mixed,M,N,K", NAN_CASES, ids=[c[0] for c in NAN_CASES])
+def test_gemm_nan_stays_in_its_row_and_column(what, layout, mixed, M, N, K):
+    gemm_nan_stays_in_its_row_and_column(layout, mixed, M, N, K, wide=(2, 0) if what == "gemm_wide" else None)
+
+
+def gemm_nan_stays_in_its_row_and_column(layout, mixed, M, N, K, wide=None):
+    """A NaN inside one row of A makes exactly that row of C non-finite and leaves every other element bit-equal to the clean run; likewise
+    one column through B.  (Shapes chosen so that each kernel file of scot_gemm's dispatch takes one.)"""
+    A, B = _operands(layout, ops.BF16, mixed, M, N, K)
+    with _gemm_config(wide=wide):
+        def run(A_, B_):
+            gd = Guards()
+            C = gd.out((M, N), F32, name="C")
+            ops.gemm(layout, ops.BF16, M, N, K, gd.op(A_, name="A"), A_.shape[1], gd.op(B_, name="B"), B_.shape[1], C, N)
+            sync()
+            gd.check()
+            return C
+        clean = run(A, B)
+        assert finite(clean)
+        r, c = M - 2, N // 2 + 1
+        An = A.clone()
+        An[r, K // 3] = NAN
+        got = run(An, B)
+        keep = torch.ones(M, dtype=torch.bool, device=G.DEV)
+        keep[r] = False
+        assert not bool(torch.isfinite(got[r]).any()), "the poisoned row must be non-finite in every column"
+        assert torch.equal(got[keep], clean[keep]), "a NaN in one row of A changed other rows"
+        Bn = B.clone()
+        if layout == ops.NT:
+            Bn[c, K // 2] = NAN
+        else:
+            Bn[K // 2, c] = NAN
+        got = run(A, Bn)
+        keepc = torch.ones(N, dtype=torch.bool, device=G.DEV)
+        keepc[c] = False
+        assert not bool(torch.isfinite(got[:, c]).any())
+        assert torch.equal(got[:, keepc], clean[:, keepc]), "a NaN in one column of B changed other columns"
+
+
+@pytest.mark.parametrize("M,N,K", [(257, 136, 72), (512, 256, 128)])
+def test_gemm_operands_near_binary16_maximum(M, N, K):
+    gemm_operands_near_binary16_maximum(M, N, K)
+
+
+def gemm_operands_near_binary16_maximum(M, N, K):
+    """binary16 build, operands up to the format's largest finite value (65504) and an fp32 result: products reach 4e9 and sums 1e11, all
+    inside fp32 — the result is finite and within the per-element bound (nothing is formed in 16 bits on the way)."""
+    prev = ops.use("f16")
+    try:
+        hd = ops.half_dtype()
+        g = torch.Generator().manual_seed(M + N + K)
+        big = lambda *s: ((torch.rand(*s, generator=g) * 2 - 1) * 65504.0).to(G.DEV).to(hd)
+        A, B = big(M, K), big(N, K)
+        A[0, :], B[0, :] = 65504.0, 65504.0                # the extreme corner: K * 65504^2
+        A[1, :] = -65504.0
+        assert finite(A) and finite(B)
+        ref, ab = _product64(ops.NT, ops.BF16, A, B)
+        with _gemm_config():
+            gd = Guards()
+            C = gd.out((M, N), F32, name="C")
+            ops.gemm(ops.NT, ops.BF16, M, N, K, gd.op(A, name="A"), K, gd.op(B, name="B"), K, C, N)
+            sync()
+            gd.check()
+        assert finite(C)
+        assert_excess(f"binary16-maximum operands {M}x{N}x{K}", C, ref, ab, K, U_MFMA16)
+    finally:
+        ops.use(prev)
+
+
+# ======================================================================================================= grouped weight gradients
+def _wgroup_dims(C):
+    return [(C, 4 * C), (4 * C, C), (C, C), (3 * C, C)]            # (M_i, N_i) of fc2, fc1, proj, qkv: dW_i [M_i, N_i]
+
+
+WGROUP_GUARDED = [(K, C, -1, False) for K, C in G.WGROUP_CASES] + [(K, C, -1, True) for K, C in G.WGROUP_CASES if C % 8 == 0 and K % 8 == 0] + \
+                 [(1024, 768, 0, False), (1024, 768, 2, True), (4096, 384, 1 | (4 << 4), True), (4096, 384, 2 | (2 << 4), False), (512, 128, 1, True),
+                  (192, 256, 0 | (3 << 4), True), (2048, 1536, -1, False), (8192, 768, -1, True)]
+
+
+@pytest.mark.parametrize("kind", ["f16", "bf16"])
+@pytest.mark.parametrize("K,C,forced,scaled", WGROUP_GUARDED)
+def test_wgrad_group_guarded(kind, K, C, forced, scaled):
+    wgrad_group_guarded(kind, K, _wgroup_dims(C), forced, scaled)
+
+
+def wgrad_group_guarded(kind, K, dims, forced, scaled):
+    """scot_wgrad_group with the dW of a layer BACK TO BACK in one guarded flat buffer at the gradient arena's 64-float alignment, the bias
+    gradients likewise; the padding between neighbours is checked like a band.  forced: -1 = the library's tile policy, else kernel
+    instantiation | K slices << 4 of the 128 x 128 tiles (scot_gemm_wide_config mode 2).  scaled: the modes of the lazy zero-grad —
+    GRAD_STORE_SCALED writes over NaN (what the arena holds beside a first writer), GRAD_ADD_SCALED, GRAD_ADD.
+    (c): gemm_excess with K = the token count (loose for fp32 at K = 65536, so the existing rel() < 1e-6 stays beside it)."""
+    prev = ops.use(kind)
+    try:
+        hd = ops.half_dtype()
+        n = len(dims)
+        modes = [(ops.GRAD_STORE_SCALED, ops.GRAD_ADD_SCALED, ops.GRAD_ADD)[i % 3] for i in range(n)] if scaled else [ops.GRAD_ADD] * n
+        sval = 2.0 ** -7 if scaled else 1.0
+        s = torch.tensor([sval], device=G.DEV) if scaled else None
+        dys = [G.rnd(K, m, dtype=hd, scale=0.5, seed=10 + i) for i, (m, _) in enumerate(dims)]
+        xs = [G.rnd(K, nn, dtype=hd, seed=20 + i) for i, (_, nn) in enumerate(dims)]
+        dws0 = [G.rnd(m, nn, seed=30 + i) for i, (m, nn) in enumerate(dims)]
+        dbs0 = [G.rnd(m, seed=40 + i) for i, (m, _) in enumerate(dims)]
+        covered = all(m % 8 == 0 and nn % 8 == 0 for m, nn in dims) and K % 8 == 0
+        with _gemm_config(wide=(2, forced) if forced >= 0 else None, splitk=(0, 1)) as lib:
+            gd = Guards()
+            dyg, xg = [gd.op(t, name=f"dY{i}") for i, t in enumerate(dys)], [gd.op(t, name=f"X{i}") for i, t in enumerate(xs)]
+            store = [md == ops.GRAD_STORE_SCALED for md in modes]
+            dwg = gd.group([tuple(t.shape) for t in dws0], F32, srcs=[None if st else t for t, st in zip(dws0, store)], name="dW arena")
+            dbg = gd.group([tuple(t.shape) for t in dbs0], F32, srcs=dbs0, name="dbias arena")
+            dwp = [nan_like(t.shape, F32) if st else t.clone() for t, st in zip(dws0, store)]
+            dbp = [t.clone() for t in dbs0]
+            sg = gd.op(s, name="grad_scale")
+            ok = ops.wgrad_group(ops.BF16, list(zip(dyg, xg, dwg, dbg)), modes if scaled else None, sg)
+            assert ok == covered
+            if not ok:      # shapes the grouped kernel declines go through the per-problem path (same contract), guarded as well
+                for dy, x, dw, db in zip(dyg, xg, dwg, dbg):
+                    ops.linear_wgrad(ops.BF16, dy, x, dw, dbias=db)
+            else:
+                assert ops.wgrad_group(ops.BF16, list(zip(dys, xs, dwp, dbp)), modes if scaled else None, s)
+            sync()
+            gd.check()
+        worst = 0.0
+        for i, (dy, x, dw0, dw, db0, db, md) in enumerate(zip(dys, xs, dws0, dwg, dbs0, dbg, modes)):
+            prod, aprod = dy.double().t() @ x.double(), dy.double().abs().t() @ x.double().abs()
+            base = 0.0 if md == ops.GRAD_STORE_SCALED else dw0.double()
+            sv = 1.0 if md == ops.GRAD_ADD else sval                    # the plain accumulation takes no scale
+            ref = base + sv * prod
+            mag = (0.0 if md == ops.GRAD_STORE_SCALED else dw0.double().abs()) + sv * aprod
+            assert finite(dw) and finite(db), i
+            # K products, the partial sums of the K slices (each at least 32 tokens deep), the scale and the add into the arena
+            worst = max(worst, assert_excess(f"wgrad_group {kind} K={K} dW{i} {tuple(dw.shape)} mode {md} forced {forced}", dw, ref, mag, K + K // 32 + 3,
+                                             U_MFMA16))
+            assert G.rel(dw.double() - base, sv * prod) < 1e-6, (K, i, md)
+            assert G.rel(db.double() - db0.double(), dy.double().sum(0)) < 2e-6
+            if ok:      # the weight gradients are deterministic (partial tiles + one grouped pass); the bias gradients are atomics
+                assert same(dw, dwp[i]), (i, kc.describe_worst(dw, dwp[i].double()))
+        print(f"worst excess wgrad_group {kind} K={K} forced {forced} scaled {scaled}: {worst:.3f}")
+    finally:
+        ops.use(prev)
+
+
+@pytest.mark.parametrize("kind", ["f16", "bf16"])
+@pytest.mark.parametrize("mode", [ops.GRAD_ADD, ops.GRAD_STORE_SCALED, ops.GRAD_ADD_SCALED])
+@pytest.mark.parametrize("M,C", [(2048, 96), (4096, 96), (1000, 96), (1024, 192), (2056, 192)])
+def test_wgrad_mlp_guarded(kind, M, C, mode):
+    wgrad_mlp_guarded(kind, M, C, mode)
+
+
+def wgrad_mlp_guarded(kind, M, C, mode):
+    """scot_wgrad_mlp (fc1 / fc2 weight + bias gradients with gelu(u), gelu'(u), du recomputed on the fly) writing dW1 | db1 | dW2 | db2 into ONE
+    guarded contiguous range — the gradient arena's layout for these four — with bands on both sides.
+    Reference: the chain restated in fp64 on the operands as stored (csrc/wgrad_mlp.hip's header):
+        u = h16 W1^T + b1,   act = gelu(u),   D = dz W2,   du = D ⊙ gelu'(u),   dW1 = du^T h16,  db1 = Σ du,  dW2 = dz^T act,  db2 = Σ dz
+    (c): gemm_excess with K = the token count on dW1 and dW2.  act and du never exist in HBM: the kernel forms them in fp32 from its own
+    accumulators and rounds them ONCE to the operand format as MFMA operands.  Their deviation from the fp64 act / du is bounded elementwise —
+      u and D carry the roundoff of a C-term (hid-term) fp32 contraction: du_acc = (C + 1) u_add (|h| |W1| + |b1|),  dD = hid u_add |dz| |W2|;
+      act:  1.13 du_acc + gelu's evaluation error + one operand rounding;
+      du:   |gelu'| dD + (|D| + dD) (0.8 du_acc + gelu' evaluation error) + one product rounding + one operand rounding —
+    and enters the bound as an operand term E^T |h| resp. |dz|^T E, as the hi + lo split's does for bf16x3.  The bias gradients are sums of the
+    same du / dz over the tokens and are held to the same kind of bound.  (d): the whole range bit-identical to the plain launch."""
+    prev = ops.use(kind)
+    try:
+        hd = ops.half_dtype()
+        hid = 4 * C
+        h16, dz = G.rnd(M, C, dtype=hd, seed=1), G.rnd(M, C, dtype=hd, scale=0.5, seed=2)
+        w1, b1 = G.rnd(hid, C, scale=C ** -0.5, seed=3).to(hd), G.rnd(hid, seed=4, scale=0.2)
+        w2 = G.rnd(C, hid, scale=hid ** -0.5, seed=5).to(hd)
+        w2t = w2.t().contiguous()
+        sizes = [hid * C, hid, C * hid, C]
+        tot = sum(sizes)
+        sval = 2.0 ** -7 if mode != ops.GRAD_ADD else 1.0
+        s = torch.tensor([sval], device=G.DEV) if mode != ops.GRAD_ADD else None
+        flat0 = G.rnd(tot, seed=6)
+
+        def views(flat):
+            o, out = 0, []
+            for sz in sizes:
+                out.append(flat[o:o + sz])
+                o += sz
+            return out[0].view(hid, C), out[1], out[2].view(C, hid), out[3]
+
+        def start(flat):
+            dW1, db1, dW2, db2 = views(flat)
+            if mode == ops.GRAD_STORE_SCALED:      # what zero_grad leaves for a storing first writer
+                dW1.fill_(NAN)
+                dW2.fill_(NAN)
+            return dW1, db1, dW2, db2
+        gd = Guards()
+        fg = gd.out((tot,), F32, src=flat0, name="dW1|db1|dW2|db2")
+        fp = flat0.clone()
+        outs_g, outs_p = start(fg), start(fp)
+        args = [gd.op(h16, name="h16"), gd.op(dz, name="dz"), gd.op(w1, name="w1"), gd.op(b1, name="b1"), gd.op(w2t, name="w2t")]
+        assert ops.wgrad_mlp(*args, *outs_g, mode=mode, grad_scale=gd.op(s, name="grad_scale"))
+        assert ops.wgrad_mlp(h16, dz, w1, b1, w2t, *outs_p, mode=mode, grad_scale=s)
+        sync()
+        gd.check()
+        assert finite(fg)
+        assert same(fg, fp)      # partial planes + one flat reduce: deterministic, bias gradients included
+        # ---- the fp64 restatement and the operands' deviation from it
+        D64 = torch.float64
+        h, z, W1, W2, B1 = h16.to(D64), dz.to(D64), w1.to(D64), w2.to(D64), b1.to(D64)
+        uop = kc.UNIT[hd]
+        u = h @ W1.t() + B1
+        du_acc = (C + 1) * U_MFMA16 * (h.abs() @ W1.abs().t() + B1.abs())
+        act, gp = _gelu64(u), _gelu_grad64(u)
+        ev_g, ev_gp = gelu_eval_err(u)
+        e_act32 = LIP_GELU * du_acc + ev_g + D_CDF * du_acc                       # the fp32 value before the operand rounding
+        e_act = e_act32 + uop * (act.abs() + e_act32)
+        Dm = z @ W2
+        dD = hid * U_MFMA16 * (z.abs() @ W2.abs())
+        du = Dm * gp
+        e_du32 = gp.abs() * dD + (Dm.abs() + dD) * (LIP_GELU_GRAD * du_acc + ev_gp) + kc.U32 * du.abs()
+        e_du = e_du32 + uop * (du.abs() + e_du32)
+        base = [t.double() for t in views(flat0.clone())]
+        wscale = sval                                                             # mode 0: plain +=; 1: store s * acc; 2: += s * acc
+        if mode == ops.GRAD_STORE_SCALED:
+            base[0], base[2] = torch.zeros_like(base[0]), torch.zeros_like(base[2])
+        nadd = M + M // 32 + 3       # M products, the partial sums of the token slices (each at least 32 rows), the scale, the add into the arena
+        for name, got, ref, mag, ex, b0 in (
+                ("dW1", outs_g[0], du.t() @ h, (du.abs() + e_du).t() @ h.abs(), e_du.t() @ h.abs(), base[0]),
+                ("dW2", outs_g[2], z.t() @ act, z.abs().t() @ (act.abs() + e_act), z.abs().t() @ e_act, base[2])):
+            assert_excess(f"wgrad_mlp {kind} M={M} C={C} mode {mode} {name}", got, b0 + wscale * ref, b0.abs() + wscale * mag, nadd, U_MFMA16,
+                          abs_extra=wscale * ex)
+        # bias gradients (always a plain accumulation): sums over the tokens of the same du / dz
+        for name, got, col, ecol, b0 in (("db1", outs_g[1], du, e_du, base[1]), ("db2", outs_g[3], z, torch.zeros_like(z), base[3])):
+            ref = b0 + col.sum(0)
+            within(got, ref, nadd * kc.U32 * (col.abs().sum(0) + ecol.sum(0) + b0.abs()) + ecol.sum(0) + kc.U32 * ref.abs(), f"wgrad_mlp {name}")
+        # beside it, as for the grouped gradients: the global norm against the same restatement on the operands the kernel rounds (16-bit act / du)
+        act16, du16 = act.to(hd).to(D64), du.to(hd).to(D64)
+        tol = 4e-3 if kind == "bf16" else 6e-4      # act / du are rounded to 16 bits at possibly different last places than the fp64 values
+        assert G.rel(outs_g[0].double() - base[0], wscale * (du16.t() @ h)) < tol and G.rel(outs_g[2].double() - base[2], wscale * (z.t() @ act16)) < tol
+    finally:
+        ops.use(prev)
+
+
+# ====================================================================================== rounding models (attention, conditional layer norm)
+# A rigorous bound through a softmax or a normalisation is not practical.  Instead the test computes, on its own inputs, a ROUNDING MODEL: the
+# fp64 restatement with a rounding at the points the kernels document (attention: normalised q and k, P, dS and the stored result in the
+# operand format — test_kernels_gpu.py's comment on its 16-bit tolerances, csrc/attention*.hip; CLN: the stored result and, for 16-bit x,
+# the input, which already is 16-bit).  Its per-row error against the exact fp64 result is e_model[row]; every row of the kernel's result must
+# satisfy  e_kernel[row] <= MARGIN * max(e_model[row], median(e_model))  (kernel_checks.row_model_excess; no row left out).
+# MARGIN covers what the model leaves out — fp32 accumulation order, the hardware's exp / rsqrt — and is measured against the REFERENCE,
+# never against a kernel:  python tests/test_kernels_guarded_gpu.py --measure-margins  runs the model on the CPU over ATTN_CASES and the CLN
+# shapes with its arithmetic in fp32 instead of fp64, in two summation orders, and prints the worst per-row ratio of those runs to the fp64
+# model per class; MARGIN is twice that ratio (the factor two: the hardware's transcendental error is not in the model either).
+# (run from the repository root with PYTHONPATH=.; numbers beside MARGIN below and in DESIGN.md §4)
+class _RoundST(torch.autograd.Function):
+    """round in the forward, pass the gradient through: the kernels differentiate the unrounded expression"""
+
+    @staticmethod
+    def forward(ctx, x, fn):
+        return fn(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+class _RoundGrad(torch.autograd.Function):
+    """identity in the forward, round the gradient (dS)"""
+
+    @staticmethod
+    def forward(ctx, x, fn):
+        ctx.fn = fn
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.fn(g), None
+
+
+def _round_bits(x, bits):
+    m, e = torch.frexp(x)
+    return torch.ldexp(torch.round(m * 2.0 ** bits) / 2.0 ** bits, e)
+
+
+def _rounders(klass, half):
+    """(operand rounding, result dtype) of a compute class: "f32" exact fp32 MFMA, "x3" hi + lo split (~2^-17), "16" the operand format"""
+    if klass == "16":
+        return (lambda x: x.to(half).to(x.dtype)), half
+    if klass == "x3":
+        return (lambda x: _round_bits(x, 17)), F32
+    return (lambda x: x.to(F32).to(x.dtype)), F32
+
+
+def _to_windows(x, Hp, Wp, ws, shift):
+    """[B, Hp*Wp, heads] per token -> [B*nW, heads, N] in G._attn_ref's window layout (roll, partition)"""
+    B, heads = x.shape[0], x.shape[-1]
+    x = x.view(B, Hp, Wp, heads)
+    if shift:
+        x = torch.roll(x, (-shift, -shift), (1, 2))
+    return x.view(B, Hp // ws, ws, Wp // ws, ws, heads).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws * ws, heads).transpose(1, 2)
+
+
+def attn_model(qkv, table, ls, dout, case, klass, half, dtype=torch.float64, reverse=False, exact=False, out_fwd=None):
+    """(out, dqkv) in fp64 of G._attn_ref evaluated in `dtype`, with the class's roundings (exact: without any): normalised q and k, P and
+    dS in the operand format, out and dqkv in the result type.  One more point that the sources state: every backward kernel takes the
+    softmax backward's row term delta = rowsum(dO ∘ O) from the STORED, rounded forward output (csrc/attention.hip: "delta = rowsum(dO ∘ O)
+    comes from the forward output"; csrc/attention_w16.hip: "dS uses delta from the stored (rounded) forward output").  With 16-bit
+    results this is the largest single contribution to the error of dq / dk where the attention is peaked: P (dP - delta) cancels and the
+    rounding of O does not.
+    With delta = sum_k P dP (what the softmax backward subtracts) the kernel's dS is P (dP - delta) - P (delta~ - delta); the
+    second term is the gradient of -(delta~ - delta) · logsumexp(s) and is added to the model's backward in that form.  out_fwd: the stored
+    forward output the backward is given (an OPERAND of scot_window_attn_bwd); default: the model's own rounded output."""
+    B, Hp, Wp, C, heads, ws, shift = case
+    rop, rdt = _rounders(klass, half)
+    rres = lambda x: x.to(rdt).to(x.dtype)
+    stash = {}
+
+    def hook(name, t):
+        if exact:
+            return t
+        if name == "s":
+            stash["s"] = t = _RoundGrad.apply(t, rop)
+            return t
+        r = _RoundST.apply(t, rres if name == "out" else rop)
+        if name == "p":
+            stash["p"], stash["p_r"] = t.detach(), r
+        return r
+    q = qkv.detach().to(dtype).clone().requires_grad_(True)
+    out = G._attn_ref(q, table.to(dtype), ls.to(dtype), B, Hp, Wp, C, heads, ws, shift, hook=hook, reverse=reverse)
+    loss = (out * dout.to(dtype)).sum()
+    if not exact:
+        stored = out.detach() if out_fwd is None else out_fwd.to(dtype)
+        delta_k = _to_windows((stored * dout.to(dtype)).view(B, Hp * Wp, heads, C // heads).sum(-1), Hp, Wp, ws, shift)
+        (dP,) = torch.autograd.grad(loss, stash["p_r"], retain_graph=True)
+        delta = (stash["p"] * dP).sum(-1)                   # what autograd's softmax backward subtracts
+        loss = loss - ((delta_k - delta) * torch.logsumexp(stash["s"], -1)).sum()
+    loss.backward()
+    return out.detach().double(), (q.grad if exact else rres(q.grad)).double()
+
+
+def cln_model(x, res, t, gw_w, gw_b, bw_w, bw_b, sc, dout, cond, klass_dt, dtype=torch.float64, reverse=False, exact=False):
+    """(out, dx) in fp64 of the conditional layer norm restated as in test_cln_fwd_bwd, evaluated in `dtype`; the model rounds the stored
+    results: out to fp32, dx to x's type."""
+    B, L, C = x.shape
+    fl = (lambda v: v.flip(-1)) if reverse else (lambda v: v)
+    xx = x.detach().to(dtype).clone().requires_grad_(True)
+    xs = fl(xx)
+    mu = xs.mean(-1, keepdim=True)
+    xh = (xx - mu) / torch.sqrt(((xs - mu) ** 2).mean(-1, keepdim=True) + 1e-5)
+    tt = t.to(dtype).view(B, 1, 1)
+    g = tt * gw_w.to(dtype) + gw_b.to(dtype) if cond else gw_b.to(dtype)
+    b = tt * bw_w.to(dtype) + bw_b.to(dtype) if cond else bw_b.to(dtype)
+    y = g * xh + b
+    out = res.to(dtype) + (sc.to(dtype).view(B, 1, 1) * y if sc is not None else y)
+    out.backward(dout.to(dtype))
+    if exact:
+        return out.detach().double(), xx.grad.double()
+    return out.detach().to(F32).double(), xx.grad.to(klass_dt).double()
+
+
+# class -> MARGIN = 2 x the worst per-row ratio printed by --measure-margins (fp32 model, plain and reversed order, against the fp64 model)
+# worst ratios measured: 16-bit operands 1.65 (a rounding that falls the other way), hi + lo split 3.33, exact fp32 MFMA 40.10 (the model's
+# only rounding there is the stored result's, so fp32 arithmetic IS the error), conditional layer norm 6.61
+MARGIN = {"attn16": 2 * 1.65, "attnx3": 2 * 3.33, "attnf32": 2 * 40.10, "cln": 2 * 6.61}
+
+
+def _attn_inputs(case, cdt):
+    B, Hp, Wp, C, heads, ws, shift = case
+    L, TS = Hp * Wp, (2 * ws - 1) ** 2
+    qkv = G.rnd(B, L, 3 * C, dtype=cdt)
+    table = (16 * torch.sigmoid(G.rnd(heads, TS, seed=1))).contiguous()
+    ls = torch.linspace(math.log(3.0), math.log(20.0), heads, device=G.DEV)
+    dout = G.rnd(B, L, C, dtype=cdt, seed=2)
+    return qkv, table, ls, dout
+
+
+@pytest.mark.parametrize("compute", [ops.F32, ops.BF16, ops.X3, "f16"])
+@pytest.mark.parametrize("case", G.ATTN_CASES)
+def test_window_attention_guarded(compute, case):
+    f16 = compute == "f16"
+    window_attention_guarded("f16" if f16 else "bf16", ops.BF16 if f16 else compute, case)
+
+
+def window_attention_guarded(kind, compute, case):
+    """scot_window_attn_fwd / bwd / bwd_rep + scot_replica_reduce / scot_window_attn_probs with every tensor guarded: (a), (b), the per-row bound
+    against the rounding model for out and dqkv, (d) for out, lse, dqkv and the probabilities; dbias_table / dlogit_scale (atomics) at
+    the tolerances of test_window_attention_fwd_bwd."""
+    prev = ops.use(kind)
+    try:
+        half = ops.half_dtype()
+        B, Hp, Wp, C, heads, ws, shift = case
+        klass = "16" if compute == ops.BF16 else "x3" if compute == ops.X3 else "f32"
+        cdt = half if compute == ops.BF16 else F32
+        L, TS, N = Hp * Wp, (2 * ws - 1) ** 2, ws * ws
+        nW = (Hp // ws) * (Wp // ws)
+        qkv, table, ls, dout = _attn_inputs(case, cdt)
+        gd = Guards()
+        qg, tg, lg, dg = gd.op(qkv, name="qkv"), gd.op(table, name="bias_table"), gd.op(ls, name="logit_scale"), gd.op(dout, name="dout")
+        og, lseg = gd.out((B, L, C), cdt, name="out"), gd.out((B * nW, heads, N), F32, name="lse")
+        dqg, dtg, dlg = gd.out((B, L, 3 * C), cdt, name="dqkv"), gd.out((heads, TS), F32, fill=0.0, name="dbias_table"), \
+            gd.out((heads,), F32, fill=0.0, name="dlogit_scale")
+        ops.window_attn_fwd(compute, qg, og, lseg, tg, lg, B, Hp, Wp, C, heads, ws, shift)
+        ops.window_attn_bwd(compute, qg, og, dg, lseg, tg, lg, dqg, dtg, dlg, B, Hp, Wp, C, heads, ws, shift)
+        op_, lsep, dqp = nan_like((B, L, C), cdt), nan_like((B * nW, heads, N), F32), nan_like((B, L, 3 * C), cdt)
+        dtp, dlp = torch.zeros(heads, TS, device=G.DEV), torch.zeros(heads, device=G.DEV)
+        ops.window_attn_fwd(compute, qkv, op_, lsep, table, ls, B, Hp, Wp, C, heads, ws, shift)
+        ops.window_attn_bwd(compute, qkv, op_, dout, lsep, table, ls, dqp, dtp, dlp, B, Hp, Wp, C, heads, ws, shift)
+        # the replica entry + the fold, replicas and destination guarded (strides with odd padding, as in the existing test)
+        R, pad = 3, 5
+        st, sl = heads * TS + pad, heads + pad
+        rtg, rlg = gd.out((R * st,), F32, fill=0.0, name="table replicas"), gd.out((R * sl,), F32, fill=0.0, name="logit-scale replicas")
+        dq2g = gd.out((B, L, 3 * C), cdt, name="dqkv (replica entry)")
+        ops.window_attn_bwd_rep(compute, qg, og, dg, lseg, tg, lg, dq2g, rtg, rlg, B, Hp, Wp, C, heads, ws, shift, R, st, sl)
+        dstg = gd.out((heads + 2,), F32, fill=0.0, name="replica_reduce dst")
+        d1 = gd.op(torch.tensor([0, 0, heads * TS], dtype=torch.int32, device=G.DEV), name="desc")
+        d2 = gd.op(torch.tensor([0, 2, heads], dtype=torch.int32, device=G.DEV), name="desc")
+        ops.replica_reduce(rtg, 1, R, st, d1, 1, heads * TS, rtg)
+        ops.replica_reduce(rlg, 0, R, sl, d2, 1, heads, dstg)
+        sync()
+        gd.check()
+        for name, t in (("out", og), ("lse", lseg), ("dqkv", dqg), ("dbias_table", dtg), ("dlogit_scale", dlg), ("dqkv rep", dq2g), ("rt", rtg), ("dst", dstg)):
+            assert finite(t), name
+        assert same(og, op_) and same(lseg, lsep) and same(dqg, dqp) and same(dq2g, dqg)
+        # (c) per row against the rounding model
+        ex_out, ex_dq = attn_model(qkv, table, ls, dout, case, klass, half, exact=True)
+        mo_out, mo_dq = attn_model(qkv, table, ls, dout, case, klass, half, out_fwd=og)
+        margin = MARGIN["attn" + klass]
+        r_out, row_o = kc.row_model_excess(og.reshape(-1, C), ex_out.reshape(-1, C), mo_out.reshape(-1, C), margin)
+        r_dq, row_d = kc.row_model_excess(dqg.reshape(-1, 3 * C), ex_dq.reshape(-1, 3 * C), mo_dq.reshape(-1, 3 * C), margin)
+        print(f"worst ratio attention {kind} compute {compute} {case}: out {r_out * margin:.2f} x model (row {row_o}), dqkv {r_dq * margin:.2f} x model "
+              f"(row {row_d}); margin {margin:.1f}")
+        assert r_out <= 1.0, f"out row {row_o} (window row {row_o // Wp}): {r_out * margin:.2f} x the model's error; {kc.describe_worst(og, ex_out)}"
+        assert r_dq <= 1.0, f"dqkv row {row_d}: {r_dq * margin:.2f} x the model's error; {kc.describe_worst(dqg, ex_dq)}"
+        # the same against the model run on its OWN rounded forward output (nothing of the kernel enters the reference): a forward / backward
+        # pair that is wrong in a self-consistent way cannot pass this one
+        _, mo_dq0 = attn_model(qkv, table, ls, dout, case, klass, half)
+        r_dq0, row_d0 = kc.row_model_excess(dqg.reshape(-1, 3 * C), ex_dq.reshape(-1, 3 * C), mo_dq0.reshape(-1, 3 * C), margin)
+        print(f"worst ratio attention {kind} compute {compute} {case}: dqkv against the model on its own forward output {r_dq0 * margin:.2f} x model (row {row_d0})")
+        assert r_dq0 <= 1.0, f"dqkv row {row_d0}: {r_dq0 * margin:.2f} x the independent model's error; {kc.describe_worst(dqg, ex_dq)}"
+        # order-dependent sums: the tolerances of test_window_attention_fwd_bwd
+        q64, t64, l64 = qkv.double().requires_grad_(True), table.double().requires_grad_(True), ls.double().requires_grad_(True)
+        exact_p = {}
+        keep_p = lambda name, v: (exact_p.__setitem__("p", v.detach()) if name == "p" else None, v)[1]
+        G._attn_ref(q64, t64, l64, B, Hp, Wp, C, heads, ws, shift, hook=keep_p).backward(dout.double())
+        t16 = ((1.2e-3, 2e-3), 2e-2) if half == torch.float16 else ((8e-3, 1.2e-2), 0.1)
+        tol_g = 5e-5 if compute == ops.F32 else 2e-4 if compute == ops.X3 else t16[0][1]
+        tol_ls = 2e-4 if compute == ops.F32 else 2e-3 if compute == ops.X3 else t16[1]
+        assert G.rel(dtg, t64.grad) < tol_g and G.rel(dlg, l64.grad) < tol_ls
+        assert G.rel(dtg, dtp) < 1e-5 and G.rel(dlg, dlp) < 5e-4
+        assert G.rel(rtg[:heads * TS].view(heads, TS), dtg) < 1e-5 and G.rel(dstg[2:], dlg) < 5e-4 and bool(torch.all(dstg[:2] == 0))
+        # the probabilities (output_attentions), where the entry covers the shape
+        d = C // heads
+        if d <= 64 and N * d * 4 <= 65536:
+            pg, pp = gd.out((B * nW, heads, N, N), F32, name="probs"), nan_like((B * nW, heads, N, N), F32)
+            ops.window_attn_probs(qg, lseg, tg, lg, pg, B, Hp, Wp, C, heads, ws, shift)
+            ops.window_attn_probs(qkv, lsep, table, ls, pp, B, Hp, Wp, C, heads, ws, shift)
+            sync()
+            gd.check()
+            assert finite(pg) and same(pg, pp)
+            # per element: P = exp(s - lse).  With 16-bit operands every cosine carries two operand roundings (|cos| <= 1), so a logit is
+            # off by at most 2 * scale * u and the forward's lse — a log-sum-exp of such logits — by as much: P is within exp(+-4 scale u) of
+            # the exact value (+ 1e-5 for the fp32 arithmetic and the hardware exp).  Rows then sum to 1 within the same factor.
+            uop = kc.UNIT[half] if klass == "16" else 2.0 ** -17 if klass == "x3" else kc.U32
+            fac = math.expm1(4 * float(torch.exp(ls.max())) * uop) + 1e-5
+            pe = exact_p["p"]
+            bad = (pg.double() - pe).abs() > fac * pe + 1e-30
+            assert not bool(bad.any()), f"{int(bad.sum())} probabilities beyond exp(4 scale u) of the reference; first at {bad.nonzero()[0].tolist()}"
+            assert float((pg.double().sum(-1) - 1).abs().max()) <= fac
+    finally:
+        ops.use(prev)
+
+
+@pytest.mark.parametrize("kind,compute", [("bf16", ops.F32), ("bf16", ops.BF16), ("f16", ops.BF16), ("bf16", ops.X3)])
+@pytest.mark.parametrize("case", [(1, 32, 32, 96, 3, 16, 8), (2, 8, 8, 32, 2, 4, 2), (1, 14, 14, 32, 1, 7, 3)])
+def test_window_attention_zero_token(kind, compute, case):
+    window_attention_zero_token(kind, compute, case)
+
+
+def window_attention_zero_token(kind, compute, case):
+    """A token whose q and k are exactly zero (a padded position): F.normalize's clamp_min(1e-12) path.  Forward: the zero query attends by
+    the bias table alone, the zero key scores cos = 0 — against the fp64 restatement, which states the reference's semantics.  Backward: the
+    reference's gradient of a clamped row is g / eps; the fp32 kernels store that, the 16-bit kernels store 0 for a clamped row (g / eps
+    overflows binary16, and the row's input is zero — csrc/attention.hip): pinned as documented.  Every other row is held to
+    the tolerance of test_window_attention_fwd_bwd."""
+    prev = ops.use(kind)
+    try:
+        half = ops.half_dtype()
+        B, Hp, Wp, C, heads, ws, shift = case
+        cdt = half if compute == ops.BF16 else F32
+        L, TS, N = Hp * Wp, (2 * ws - 1) ** 2, ws * ws
+        nW = (Hp // ws) * (Wp // ws)
+        qkv, table, ls, dout = _attn_inputs(case, cdt)
+        zt = [(0, 0), (B - 1, L - 1), (0, L // 2 + 1)]
+        for b, tok in zt:
+            qkv[b, tok, :2 * C] = 0
+        gd = Guards()
+        qg, tg, lg, dg = gd.op(qkv, name="qkv"), gd.op(table, name="bias_table"), gd.op(ls, name="logit_scale"), gd.op(dout, name="dout")
+        og, lseg = gd.out((B, L, C), cdt, name="out"), gd.out((B * nW, heads, N), F32, name="lse")
+        dqg, dtg, dlg = gd.out((B, L, 3 * C), cdt, name="dqkv"), gd.out((heads, TS), F32, fill=0.0), gd.out((heads,), F32, fill=0.0)
+        ops.window_attn_fwd(compute, qg, og, lseg, tg, lg, B, Hp, Wp, C, heads, ws, shift)
+        ops.window_attn_bwd(compute, qg, og, dg, lseg, tg, lg, dqg, dtg, dlg, B, Hp, Wp, C, heads, ws, shift)
+        sync()
+        gd.check()
+        q64 = qkv.double().requires_grad_(True)
+        ref = G._attn_ref(q64, table.double(), ls.double(), B, Hp, Wp, C, heads, ws, shift)
+        ref.backward(dout.double())
+        t16 = (1.2e-3, 2e-3) if half == torch.float16 else (8e-3, 1.2e-2)
+        tol_o, tol_g = (2e-5, 5e-5) if compute == ops.F32 else (5e-5, 2e-4) if compute == ops.X3 else t16
+        assert finite(og) and G.rel(og, ref.detach()) < tol_o
+        zrow = torch.zeros(B, L, dtype=torch.bool, device=G.DEV)
+        for b, tok in zt:
+            zrow[b, tok] = True
+            assert G.rel(og[b, tok], ref.detach()[b, tok]) < 4 * tol_o, "the zero token's own output row"
+        gref = q64.grad.clone()
+        got = dqg.double()
+        # v's gradient of the zero token is an ordinary one; its q / k gradient is the clamped row
+        if compute == ops.BF16:
+            assert bool((got[zrow][:, :2 * C] == 0).all()), "16-bit build: a clamped row's gradient is stored as 0 (documented)"
+            gref[zrow, :2 * C] = 0
+        else:
+            assert finite(dqg)
+            assert G.rel(got[zrow][:, :2 * C], gref[zrow][:, :2 * C]) < 10 * tol_g, "fp32 results: g / eps, the reference's value"
+            gref[zrow, :2 * C] = 0
+            got[zrow, :2 * C] = 0        # (1e12-sized entries would drown every other row in one norm)
+        assert bool(torch.isfinite(got).all()) and G.rel(got, gref) < tol_g
+    finally:
+        ops.use(prev)
+
+
+# ----------------------------------------------------------------------------------------------------------- conditional layer norm
+CLN_SHAPES = [(3, 64, 96), (2, 16, 768), (2, 9, 20), (2, 300, 48), (2, 1024, 192), (2, 5, 1536), (3, 33, 16), (64, 16, 768), (64, 64, 384), (5, 6, 128)]
+
+
+def _cln_inputs(xdt, B, L, C):
+    x, res, t = G.rnd(B, L, C, dtype=xdt), G.rnd(B, L, C, seed=1), torch.rand(B, generator=torch.Generator().manual_seed(B + L + C)).to(G.DEV)
+    ps = [G.rnd(C, seed=2, scale=0.3), 1 + G.rnd(C, seed=3, scale=0.1), G.rnd(C, seed=4, scale=0.1), G.rnd(C, seed=5, scale=0.1)]
+    return x, res, t, ps, G.rnd(B, L, C, seed=6)
+
+
+@pytest.mark.parametrize("cond", [True, False])
+@pytest.mark.parametrize("xdt", [F32, torch.bfloat16])
+@pytest.mark.parametrize("B,L,C", CLN_SHAPES)
+def test_cln_guarded(cond, xdt, B, L, C):
+    cln_guarded(cond, xdt, B, L, C)
+
+
+def cln_guarded(cond, xdt, B, L, C, constant_row=False):
+    """scot_cln_fwd / bwd / bwd_finish with every tensor guarded — the four parameter gradients and d_xbias back to back at the arena's
+    alignment.  (c): out and dx per row against the rounding model; mean / rstd against fp64 at one fp32 rounding each plus the sum's
+    roundoff (C * 2^-24 relative to the row's magnitude); the parameter gradients (atomics) at the tolerances of test_cln_fwd_bwd.
+    constant_row: one row of x is constant (variance exactly 0: rstd = 1 / sqrt(eps), x-hat = 0, out = resid + beta)."""
+    x, res, t, ps, dout = _cln_inputs(xdt, B, L, C)
+    if constant_row:
+        x[0, L // 2, :] = 1.75
+        x[B - 1, 0, :] = 0.0
+    tt = t if cond else None
+    gd = Guards()
+    xg, rg, tg, dog = gd.op(x, name="x"), gd.op(res, name="resid"), gd.op(tt, name="time"), gd.op(dout, name="dout")
+    pg = [gd.op(p, name=f"param{i}") if (cond or i in (1, 3)) else None for i, p in enumerate(ps)]
+    pp = [p if (cond or i in (1, 3)) else None for i, p in enumerate(ps)]
+    og, o16g = gd.out((B, L, C), F32, name="out"), gd.out((B, L, C), torch.bfloat16, name="out2")
+    mg, sg = gd.out((B * L,), F32, name="mean"), gd.out((B * L,), F32, name="rstd")
+    ops.cln_fwd(xg, rg, og, mg, sg, tg, pg[0], pg[1], pg[2], pg[3], B * L, L, C, 1e-5, out2=o16g)
+    dxg = gd.out((B, L, C), xdt, name="dx")
+    gr = gd.group([(C,)] * 5, F32, fills=[0.0] * 5, name="d_gw_w|d_gw_b|d_bw_w|d_bw_b|d_xbias")
+    ops.cln_bwd(dog, xg, mg, sg, tg, pg[0], pg[1], dxg, gr[0], gr[1], gr[2], gr[3], B * L, L, C, d_xbias=gr[4])
+    op_, o16p, mp, sp, dxp = nan_like((B, L, C), F32), nan_like((B, L, C), torch.bfloat16), nan_like((B * L,), F32), nan_like((B * L,), F32), \
+        nan_like((B, L, C), xdt)
+    grp = [torch.zeros(C, device=G.DEV) for _ in range(5)]
+    ops.cln_fwd(x, res, op_, mp, sp, tt, pp[0], pp[1], pp[2], pp[3], B * L, L, C, 1e-5, out2=o16p)
+    ops.cln_bwd(dout, x, mp, sp, tt, pp[0], pp[1], dxp, grp[0], grp[1], grp[2], grp[3], B * L, L, C, d_xbias=grp[4])
+    sync()
+    gd.check()
+    for name, v in (("out", og), ("out2", o16g), ("mean", mg), ("rstd", sg), ("dx", dxg), ("grads", torch.cat(gr))):
+        assert finite(v), name
+    assert same(og, op_) and same(o16g, o16p) and same(mg, mp) and same(sg, sp) and same(dxg, dxp)
+    assert same(o16g, og.to(torch.bfloat16))
+    args = (x, res, t, ps[0], ps[1], ps[2], ps[3], None, dout, cond, xdt)
+    ex_out, ex_dx = cln_model(*args, exact=True)
+    mo_out, mo_dx = cln_model(*args)
+    margin = MARGIN["cln"]
+    r_out, row_o = kc.row_model_excess(og.reshape(-1, C), ex_out.reshape(-1, C), mo_out.reshape(-1, C), margin)
+    r_dx, row_d = kc.row_model_excess(dxg.reshape(-1, C), ex_dx.reshape(-1, C), mo_dx.reshape(-1, C), margin)
+    print(f"worst ratio cln cond {cond} {xdt} {(B, L, C)}: out {r_out * margin:.2f} x model (row {row_o}), dx {r_dx * margin:.2f} x model (row {row_d}); "
+          f"margin {margin:.1f}")
+    assert r_out <= 1.0, f"out row {row_o}: {r_out * margin:.2f} x the model's error; {kc.describe_worst(og, ex_out)}"
+    assert r_dx <= 1.0, f"dx row {row_d}: {r_dx * margin:.2f} x the model's error; {kc.describe_worst(dxg, ex_dx)}"
+    x64 = x.double().reshape(-1, C)
+    mu64 = x64.mean(-1)
+    var64 = ((x64 - mu64.unsqueeze(1)) ** 2).mean(-1)
+    amean = x64.abs().mean(-1)
+    assert bool(((mg.double() - mu64).abs() <= (C + 2) * kc.U32 * amean + 1e-37).all()), "mean: beyond the roundoff of a C-term fp32 sum"
+    rs64 = 1.0 / torch.sqrt(var64 + 1e-5)
+    assert G.rel(sg, rs64) < 1e-5
+    if constant_row:
+        for b, l in ((0, L // 2), (B - 1, 0)):
+            r = b * L + l
+            assert float(mg[r]) == float(x[b, l, 0]) and abs(float(sg[r]) / (1e-5 ** -0.5) - 1) < 1e-6
+            beta = (float(t[b]) * ps[2].double() + ps[3].double()) if cond else ps[3].double()
+            assert float((og[b, l].double() - (res[b, l].double() + beta)).abs().max()) < 1e-6, "constant row: out = resid + beta"
+    # parameter gradients: atomics — the tolerances of test_cln_fwd_bwd
+    xr = x.double().requires_grad_(True)
+    p64 = [p.double().requires_grad_(True) for p in ps]
+    mu = xr.mean(-1, keepdim=True)
+    xh = (xr - mu) / torch.sqrt((xr * xr).mean(-1, keepdim=True) - mu * mu + 1e-5)
+    g_ = t.double().view(B, 1, 1) * p64[0] + p64[1] if cond else p64[1]
+    b_ = t.double().view(B, 1, 1) * p64[2] + p64[3] if cond else p64[3]
+    (res.double() + g_ * xh + b_).backward(dout.double())
+    if not constant_row:
+        assert G.rel(gr[4], xr.grad.sum((0, 1))) < (2e-3 if xdt == F32 else 5e-2)
+        for i in ([0, 1, 2, 3] if cond else [1, 3]):
+            assert G.rel(gr[i], p64[i].grad) < 1e-4 and G.rel(gr[i], grp[i]) < 1e-5, i
+    # mode 3: dx + per-block partial sums (the header sizes the scratch: scot_cln_bwd_workspace_bytes), finished into contiguous gradients
+    nf = ops.cln_bwd_partial_floats(B * L, L, C, cond)
+    if nf:
+        part = gd.out((nf,), F32, name="mode-3 partial sums")
+        dx3 = gd.out((B, L, C), xdt, name="dx (mode 3)")
+        g3 = gd.group([(C,)] * 4, F32, fills=[0.25] * 4, name="mode-3 gradients")
+        sel = g3 if cond else [None, g3[0], None, g3[1]]
+        ops.cln_bwd(dog, xg, mg, sg, tg, pg[0], pg[1], dx3, None, None, None, None, B * L, L, C, sample_scale=None, mode=3, partial=part)
+        ops.cln_bwd_finish(part, B * L, L, C, sel[0], sel[1], sel[2], sel[3])
+        sync()
+        gd.check()
+        assert finite(dx3) and (same(dx3, dxg) or G.rel(dx3, dxg) < 1e-6)
+        if not constant_row:
+            for i in ([0, 1, 2, 3] if cond else [1, 3]):
+                assert G.rel(sel[i] - 0.25, p64[i].grad) < 1e-4, i
+
+
+@pytest.mark.parametrize("xdt", [F32, torch.bfloat16])
+@pytest.mark.parametrize("B,L,C", [(3, 64, 96), (2, 9, 20), (2, 16, 768)])
+def test_cln_constant_row(xdt, B, L, C):
+    cln_guarded(True, xdt, B, L, C, constant_row=True)
+
+
+# ================================================================================================================ fused layer tails
+TAIL_CASES = [(kind, C, B, L) for kind in ("bf16", "f16") for C, B, L in ((48, 3, 200), (48, 2, 1024), (96, 3, 200), (96, 2, 1024), (192, 5, 72), (192, 2, 256))]
+
+
+def _tail_inputs(C, B, L, cond, hd):
+    M, hid = B * L, 4 * C
+    d = dict(a=G.rnd(M, C, seed=11).to(hd), x=G.rnd(M, C, seed=12),
+             wo=G.rnd(C, C, scale=C ** -0.5, seed=13).to(hd), bo=G.rnd(C, seed=14, scale=0.2),
+             w1=G.rnd(hid, C, scale=C ** -0.5, seed=2).to(hd), b1=G.rnd(hid, seed=3, scale=0.2),
+             w2=G.rnd(C, hid, scale=hid ** -0.5, seed=4).to(hd), b2=G.rnd(C, seed=5, scale=0.2),
+             wq=G.rnd(3 * C, C, scale=C ** -0.5, seed=41).to(hd), bq=G.rnd(3 * C, seed=42, scale=0.2),
+             t=torch.rand(B, generator=torch.Generator().manual_seed(1)).to(G.DEV) if cond else None,
+             s1=((torch.rand(B, generator=torch.Generator().manual_seed(2)) > 0.3).float() / 0.7).to(G.DEV),
+             s2=((torch.rand(B, generator=torch.Generator().manual_seed(3)) > 0.3).float() / 0.7).to(G.DEV))
+    for i, (sd, sc, one) in enumerate(((20, 0.3, 0), (21, 0.1, 1), (22, 0.1, 0), (23, 0.1, 0))):
+        d[f"n1_{i}"] = (one + G.rnd(C, seed=sd, scale=sc)) if (cond or i in (1, 3)) else None
+    for i, (sd, sc, one) in enumerate(((6, 0.3, 0), (7, 0.1, 1), (8, 0.1, 0), (9, 0.1, 0))):
+        d[f"n2_{i}"] = (one + G.rnd(C, seed=sd, scale=sc)) if (cond or i in (1, 3)) else None
+    return d
+
+
+# the lean form (16-bit z, no 4C-wide saves) is a training form of C = 96 / 192
+TAIL_FWD = [(*c, train, cond, nq, lean) for c in TAIL_CASES for train, cond, nq in ((True, True, True), (True, False, False), (False, True, False), (False, False, True))
+            for lean in (False, True) if not (lean and (c[1] == 48 or not train))]
+
+
+@pytest.mark.parametrize("kind,C,B,L,train,cond,next_qkv,lean", TAIL_FWD)
+def test_block_tail_fwd_guarded(kind, C, B, L, train, cond, next_qkv, lean):
+    block_tail_fwd_guarded(kind, C, B, L, train, cond, next_qkv, lean)
+
+
+def block_tail_fwd_guarded(kind, C, B, L, train, cond, next_qkv, lean):
+    """scot_block_tail_fwd (+ the next layer's q/k/v epilogue) at C = 48 / 96 / 192 with ragged L.  Its arithmetic is already pinned by
+    torch.equal against the unfused chain; here every tensor it reads lies in NaN bands and every tensor it writes — h, h16, z, mean,
+    rstd, gelu(u), gelu'(u), out, the 16-bit copies, qkv — is held to (a), (b) and (d).  lean: 16-bit z1 / z2 and no 4C-wide saves."""
+    prev = ops.use(kind)
+    try:
+        hd = ops.half_dtype()
+        M, hid = B * L, 4 * C
+        d = _tail_inputs(C, B, L, cond, hd)
+        gd = Guards()
+        gi = {k: gd.op(v, name=k) for k, v in d.items()}
+        zdt = hd if lean else F32
+        shapes = dict(h=((M, C), F32), h16=((M, C), hd), out=((M, C), F32), out16=((M, C), hd))
+        if train:
+            shapes.update(z1=((M, C), zdt), m1=((M,), F32), r1=((M,), F32), z2=((M, C), zdt), m2=((M,), F32), r2=((M,), F32))
+            if not lean:
+                shapes.update(u=((M, hid), hd), gp=((M, hid), hd))
+        if next_qkv:
+            shapes["q"] = ((M, 3 * C), hd)
+        og = {k: gd.out(sh, dt_, name=k) for k, (sh, dt_) in shapes.items()}
+        op_ = {k: nan_like(sh, dt_) for k, (sh, dt_) in shapes.items()}
+
+        def run(i, o):
+            g = o.get
+            return ops.block_tail_fwd((i["a"], i["wo"], i["bo"], i["x"], o["h"], o["h16"], g("z1"), g("m1"), g("r1"), i["n1_0"], i["n1_1"], i["n1_2"],
+                                       i["n1_3"], i["s1"]),
+                                      (i["w1"], i["b1"], i["w2"], i["b2"], o["out"], o["out16"], g("u"), g("gp"), g("z2"), g("m2"), g("r2"), i["n2_0"],
+                                       i["n2_1"], i["n2_2"], i["n2_3"], i["s2"]),
+                                      i["t"], M, L, C, hid, 1e-5, *((i["wq"], i["bq"], o["q"]) if next_qkv else ()), z16=lean)
+        assert run(gi, og) and run(d, op_)
+        sync()
+        gd.check()
+        for k in shapes:
+            assert finite(og[k]), k
+            assert same(og[k], op_[k]), (k, kc.describe_worst(og[k].reshape(M, -1), op_[k].double().reshape(M, -1), tile=64))
+        return d, op_
+    finally:
+        ops.use(prev)
+
+
+# samples of whole 64-row tiles: guarded launches of the backward.  C = 48 has the stored-gelu' form only.
+TAIL_BWD = [(*c, cond, form) for c in [t for t in TAIL_CASES if t[3] % 64 == 0] + [(k, C, 3, 192) for k in ("bf16", "f16") for C in (48, 96, 192)]
+            for cond in (True, False) for form in ("stored", "prologue", "lean") if not (c[1] == 48 and form != "stored")]
+# ragged samples (L = 200, 72): NOT launches of the backward — the entry point must decline them (-3) and write nothing anywhere
+TAIL_BWD_DECLINED = [(*c, True, "stored") for c in TAIL_CASES if c[3] % 64]
+
+
+@pytest.mark.parametrize("kind,C,B,L,cond,form", TAIL_BWD)
+def test_block_tail_bwd_guarded(kind, C, B, L, cond, form):
+    block_tail_bwd_guarded(kind, C, B, L, cond, form)
+
+
+@pytest.mark.parametrize("kind,C,B,L,cond,form", TAIL_BWD_DECLINED)
+def test_block_tail_bwd_declines_ragged_samples(kind, C, B, L, cond, form):
+    block_tail_bwd_guarded(kind, C, B, L, cond, form)
+
+
+def block_tail_bwd_guarded(kind, C, B, L, cond, form):
+    """scot_block_tail_bwd: stored gelu'(u) and atomics; with the qkv data-gradient prologue in place; the lean form (gelu'(u) recomputed from
+    h16 / b1, no du, 16-bit z, per-workgroup partial sums finished by scot_partial_colsum).  The norms' eight parameter gradients lie
+    back to back in one guarded buffer at the arena's alignment, the partial-sum matrices are guarded to the size the header gives
+    ([scot_block_tail_workgroups, (4 | 2) x C rounded up to 64])."""
+    prev = ops.use(kind)
+    try:
+        hd = ops.half_dtype()
+        M, hid = B * L, 4 * C
+        lean, prologue = form == "lean", form == "prologue"
+        d = _tail_inputs(C, B, L, cond, hd)
+        g0 = G.rnd(M, C, seed=31)
+        z2, z1 = G.rnd(M, C, seed=32), G.rnd(M, C, seed=33)
+        st = lambda z: (z.mean(-1).contiguous(), (1.0 / torch.sqrt(z.var(-1, unbiased=False) + 1e-5)).contiguous())
+        (m2, r2), (m1, r1) = st(z2), st(z1)
+        if lean:
+            z2, z1 = z2.to(hd), z1.to(hd)
+        extra = dict(g0=g0, z2=z2, z1=z1, m2=m2, r2=r2, m1=m1, r1=r1, gp=G.rnd(M, hid, seed=34).to(hd), h16=G.rnd(M, C, seed=35).to(hd),
+                     dqkv=G.rnd(M, 3 * C, seed=41).to(hd) if prologue else None,
+                     wqkv=G.rnd(3 * C, C, scale=(3 * C) ** -0.5, seed=42).to(hd) if prologue else None)
+        d.update(extra)
+        gd = Guards()
+        gi = {k: gd.op(v, name=k) for k, v in d.items()}
+        shapes = dict(dz2=((M, C), hd), dz1=((M, C), hd), da=((M, C), hd))
+        if not lean:
+            shapes["du"] = ((M, hid), hd)
+        Cp = (C + 63) // 64 * 64
+        nwg = ops.tail_workgroups(M, L, C)
+        ncol = (4 if cond else 2) * Cp
+
+        def run(i, guarded):
+            o = {k: (gd.out(sh, dt_, name=k) if guarded else nan_like(sh, dt_)) for k, (sh, dt_) in shapes.items()}
+            if prologue:      # in place: g is read, added to and overwritten
+                o["g"] = gd.out((M, C), F32, src=g0, name="g (in place)") if guarded else g0.clone()
+                gin = o["g"]
+            else:
+                o["g"] = gd.out((M, C), F32, name="g_out") if guarded else nan_like((M, C), F32)
+                gin = i["g0"]
+            if guarded:
+                flat2 = gd.group([(C,)] * 4, F32, fills=[0.0] * 4, name="norm-2 parameter gradients")
+                flat1 = gd.group([(C,)] * 4, F32, fills=[0.0] * 4, name="norm-1 parameter gradients")
+            else:
+                flat2, flat1 = [torch.zeros(C, device=G.DEV) for _ in range(4)], [torch.zeros(C, device=G.DEV) for _ in range(4)]
+            p2 = flat2 if cond else [None, flat2[1], None, flat2[3]]
+            p1 = flat1 if cond else [None, flat1[1], None, flat1[3]]
+            part2 = part1 = None
+            if lean:
+                part2 = gd.out((nwg, ncol), F32, name="partial2") if guarded else nan_like((nwg, ncol), F32)
+                part1 = gd.out((nwg, ncol), F32, name="partial1") if guarded else nan_like((nwg, ncol), F32)
+            o["ok"] = ops.block_tail_bwd(gin, o["g"], (i["z2"], i["m2"], i["r2"], i["n2_0"], i["n2_1"], i["s2"], None if lean else i["gp"], i["w1"], i["w2"],
+                                                    o["dz2"], o.get("du"), p2[0], p2[1], p2[2], p2[3]),
+                                      (i["z1"], i["m1"], i["r1"], i["n1_0"], i["n1_1"], i["s1"], i["wo"], o["dz1"], o["da"], p1[0], p1[1], p1[2], p1[3]),
+                                      i["t"], M, L, C, hid, dqkv=i["dqkv"], wqkv=i["wqkv"], h16=i["h16"] if lean else None, b1=i["b1"] if lean else None,
+                                      z16=lean, partial2=part2, partial1=part1)
+            o["p2"], o["p1"], o["part2"], o["part1"] = p2, p1, part2, part1
+            return o
+        og = run(gi, True)
+        if L % 64:      # samples that are not whole 64-row tiles are declined (-3): nothing may have been written anywhere
+            sync()
+            gd.check()
+            assert not og["ok"] and all(bool(torch.isnan(og[k].float()).all()) for k in shapes)
+            return
+        op_ = run(d, False)
+        assert og["ok"] and op_["ok"]
+        sync()
+        gd.check()
+        for k in list(shapes) + ["g"]:
+            assert finite(og[k]), k
+            assert same(og[k], op_[k]), (k, kc.describe_worst(og[k].reshape(M, -1), op_[k].double().reshape(M, -1), tile=64))
+        if lean:      # the written part of the partial-sum rows: [nwg, (4 | 2) blocks of Cp] of which C columns each carry sums
+            for part_g, part_p in ((og["part2"], op_["part2"]), (og["part1"], op_["part1"])):
+                pgv, ppv = part_g.view(nwg, -1, Cp)[:, :, :C], part_p.view(nwg, -1, Cp)[:, :, :C]
+                assert finite(pgv) and same(pgv, ppv)
+        else:         # atomics: the tolerance of test_block_tail_bwd_fused
+            for a_, b_ in zip(og["p2"] + og["p1"], op_["p2"] + op_["p1"]):
+                if a_ is not None:
+                    assert finite(a_) and G.rel(a_, b_) < 1e-4
+    finally:
+        ops.use(prev)
+
+
+@pytest.mark.parametrize("train,cond", [(True, True), (False, False)])
+@pytest.mark.parametrize("C,B,L", [(96, 3, 200), (96, 2, 1024), (192, 5, 72), (192, 2, 256)])
+def test_fused_halves_fwd_guarded(C, B, L, train, cond):
+    fused_halves_fwd_guarded(C, B, L, train, cond)
+
+
+def fused_halves_fwd_guarded(C, B, L, train, cond):
+    """scot_proj_cln_fwd and scot_mlp_block_fwd on their own (the two launches the block tail replaces): (a), (b), (d) on every tensor."""
+    hd = ops.half_dtype()
+    M, hid = B * L, 4 * C
+    d = _tail_inputs(C, B, L, cond, hd)
+    d["h"], d["h16"] = G.rnd(M, C, seed=50), G.rnd(M, C, seed=50).to(hd)
+    gd = Guards()
+    gi = {k: gd.op(v, name=k) for k, v in d.items()}
+    shapes = dict(po=((M, C), F32), po16=((M, C), hd), mo=((M, C), F32), mo16=((M, C), hd))
+    if train:
+        shapes.update(z1=((M, C), F32), m1=((M,), F32), r1=((M,), F32), z2=((M, C), F32), m2=((M,), F32), r2=((M,), F32), u=((M, hid), hd), gp=((M, hid), hd))
+    og = {k: gd.out(sh, dt_, name=k) for k, (sh, dt_) in shapes.items()}
+    op_ = {k: nan_like(sh, dt_) for k, (sh, dt_) in shapes.items()}
+
+    def run(i, o):
+        g = o.get
+        assert ops.proj_cln_fwd(i["a"], i["wo"], i["bo"], i["x"], o["po"], o["po16"], g("z1"), g("m1"), g("r1"), i["t"], i["n1_0"], i["n1_1"], i["n1_2"],
+                                i["n1_3"], i["s1"], M, L, C, 1e-5)
+        assert ops.mlp_block_fwd(i["h16"], i["h"], i["w1"], i["b1"], i["w2"], i["b2"], o["mo"], o["mo16"], g("u"), g("gp"), g("z2"), g("m2"), g("r2"), i["t"],
+                                 i["n2_0"], i["n2_1"], i["n2_2"], i["n2_3"], i["s2"], M, L, C, hid, 1e-5)
+    run(gi, og)
+    run(d, op_)
+    sync()
+    gd.check()
+    for k in shapes:
+        assert finite(og[k]), k
+        assert same(og[k], op_[k]), (k, kc.describe_worst(og[k].reshape(M, -1), op_[k].double().reshape(M, -1), tile=64))
+
+
+@pytest.mark.parametrize("cond", [True, False])
+@pytest.mark.parametrize("C,B,L", [(96, 3, 192), (96, 2, 1024), (192, 5, 64), (192, 2, 256)])
+def test_fused_halves_bwd_guarded(C, B, L, cond):
+    fused_halves_bwd_guarded(C, B, L, cond)
+
+
+def fused_halves_bwd_guarded(C, B, L, cond):
+    """scot_proj_cln_bwd and scot_mlp_block_bwd (out of place) on their own: data tensors (a), (b), (d); the norm-parameter gradients
+    (atomics) back to back at the arena's alignment, at the tolerance of test_proj_cln_bwd_fused / test_mlp_block_bwd_fused."""
+    hd = ops.half_dtype()
+    M, hid = B * L, 4 * C
+    d = _tail_inputs(C, B, L, cond, hd)
+    z = G.rnd(M, C, seed=2, scale=1.5) + 0.3
+    d.update(g=G.rnd(M, C, seed=1), z=z, mean=z.mean(-1).contiguous(), rstd=(1.0 / torch.sqrt(z.var(-1, unbiased=False) + 1e-5)).contiguous(),
+             gp=G.rnd(M, hid, seed=3, scale=0.5).to(hd))
+    gd = Guards()
+    gi = {k: gd.op(v, name=k) for k, v in d.items()}
+    shapes = dict(pdz=((M, C), hd), pda=((M, C), hd), mdz=((M, C), hd), mdu=((M, hid), hd), mg=((M, C), F32))
+
+    def run(i, guarded):
+        o = {k: (gd.out(sh, dt_, name=k) if guarded else nan_like(sh, dt_)) for k, (sh, dt_) in shapes.items()}
+        if guarded:
+            fp, fm = gd.group([(C,)] * 4, F32, fills=[0.0] * 4, name="proj norm gradients"), gd.group([(C,)] * 4, F32, fills=[0.0] * 4, name="mlp norm gradients")
+        else:
+            fp, fm = [torch.zeros(C, device=G.DEV) for _ in range(4)], [torch.zeros(C, device=G.DEV) for _ in range(4)]
+        sel = lambda f: f if cond else [None, f[1], None, f[3]]
+        pp, pm = sel(fp), sel(fm)
+        assert ops.proj_cln_bwd(i["g"], i["z"], i["mean"], i["rstd"], i["t"], i["n1_0"], i["n1_1"], i["s1"], i["wo"], o["pdz"], o["pda"], pp[0], pp[1], pp[2], pp[3],
+                                M, L, C)
+        assert ops.mlp_block_bwd(i["g"], o["mg"], i["z"], i["mean"], i["rstd"], i["t"], i["n2_0"], i["n2_1"], i["s2"], i["gp"], i["w1"], i["w2"], o["mdz"], o["mdu"],
+                                 pm[0], pm[1], pm[2], pm[3], M, L, C, hid)
+        o["grads"] = [t for t in pp + pm if t is not None]
+        return o
+    og, op_ = run(gi, True), run(d, False)
+    sync()
+    gd.check()
+    for k in shapes:
+        assert finite(og[k]), k
+        assert same(og[k], op_[k]), (k, kc.describe_worst(og[k].reshape(M, -1), op_[k].double().reshape(M, -1), tile=64))
+    for a_, b_ in zip(og["grads"], op_["grads"]):
+        assert finite(a_) and G.rel(a_, b_) < 1e-4
+
+
+# ===================================================================================================== data movement and small ops
+def within(got, exact64, bound64, what):
+    """every element within its own bound of the fp64 value (a NaN fails)"""
+    bad = ~((got.double() - exact64).abs() <= bound64)
+    assert not bool(bad.any()), f"{what}: {int(bad.sum())} element(s) beyond their bound, first at {bad.nonzero()[0].tolist()}"
+
+
+SMALL_SIZES = [1000 * 4 + 3, 8192]          # one odd size (scalar tails), one multiple of every vector width
+
+
+@pytest.mark.parametrize("n", SMALL_SIZES)
+def test_flat_ops_guarded(n):
+    flat_ops_guarded(n)
+
+
+def flat_ops_guarded(n):
+    """scot_scale_inplace(_dev), scot_segments_scale, scot_axpy_dev, scot_pow2_rescale, scot_dp_pack / unpack, scot_add, the cast form of
+    scot_scale_residual: flat fp32 ranges the way the arenas hold them, in NaN bands.  A product or a conversion is ONE rounding, so
+    the compare is exact against torch's fp32 arithmetic; fmaf(a, x, y) is held to one rounding of the fp64 value."""
+    gd = Guards()
+    x0 = G.rnd(n, seed=1)
+    # x *= scale (host factor), non-finite results counted per wave
+    xg, cnt = gd.out((n,), F32, src=x0, name="x"), gd.out((1,), torch.int32, fill=0, name="nonfinite")
+    ops.scale_inplace(xg, 0.375, cnt)
+    sync()
+    gd.check()
+    assert torch.equal(xg, x0 * 0.375) and int(cnt) == 0
+    # the factor read from the device; one Inf makes one wave report
+    sdev = gd.op(torch.tensor([4.0], device=G.DEV), name="scale_dev")
+    xg[n // 2] = float("inf")
+    ops.scale_inplace_dev(xg, sdev, cnt)
+    sync()
+    gd.check()
+    ref = x0 * 0.375 * 4.0
+    ref[n // 2] = float("inf")
+    assert torch.equal(xg, ref) and int(cnt) == 1
+    # a list of pieces: offsets multiples of 4, the last piece ends inside a 4-float group and at the range's very end
+    segs = [(0, 64), (128, min(4096, n // 2 // 4 * 4)), (n - 61 - (n - 61) % 4, 61 + (n - 61) % 4)]
+    chunks = gd.op(torch.tensor(segs, dtype=torch.int64, device=G.DEV), name="chunks")
+    yg = gd.out((n,), F32, src=x0, name="x (segments)")
+    cnt2 = gd.out((1,), torch.int32, fill=0, name="nonfinite")
+    ops.segments_scale(yg, chunks, len(segs), sdev, cnt2)
+    sync()
+    gd.check()
+    ref = x0.clone()
+    for o, c in segs:
+        ref[o:o + c] *= 4.0
+    assert torch.equal(yg, ref) and int(cnt2) == 0
+    ops.segments_scale(yg, chunks, len(segs), None)
+    sync()
+    gd.check()
+    for o, c in segs:
+        ref[o:o + c] = 0.0
+    assert torch.equal(yg, ref)
+    # dst += alpha * src, src cleared in the same pass
+    d0, s0 = G.rnd(n, seed=2), G.rnd(n, seed=3)
+    dg, sg, al = gd.out((n,), F32, src=d0, name="dst"), gd.out((n,), F32, src=s0, name="src"), gd.op(torch.tensor([0.3], device=G.DEV), name="alpha")
+    ops.axpy_dev(dg, sg, al, clear_src=True)
+    sync()
+    gd.check()
+    exact = d0.double() + float(al[0]) * s0.double()
+    within(dg, exact, kc.U32 * exact.abs() + 1e-45, "axpy_dev (one fmaf)")
+    assert bool((sg == 0).all())
+    # power-of-two rescale: c = 2^k, k >= 0, with max|v| * c in [1/2, 1) (never scaled down), out2[1] = 1 / c
+    for vmax in (3e-5, 0.5, 0.7, 1.0, 6.0):
+        v = x0[:n].clone()
+        v = v / v.abs().max() * vmax
+        o2 = gd.out((2,), F32, name="pow2 out")
+        ops.pow2_rescale(gd.op(v, name="v"), o2)
+        sync()
+        gd.check()
+        m = float(v.abs().max())
+        c, ci = float(o2[0]), float(o2[1])
+        assert c >= 1.0 and math.log2(c) == int(math.log2(c)) and c * ci == 1.0
+        assert (0.5 <= m * c < 1.0) if m < 1.0 else c == 1.0, (m, c)
+    # the wire format of the data-parallel exchange: bfloat16 in both builds
+    wire = gd.out((n,), torch.bfloat16, name="wire")
+    srcg = gd.op(x0, name="src")
+    ops.dp_pack(srcg, wire, 0.25)
+    sync()
+    gd.check()
+    assert torch.equal(wire, (x0 * 0.25).to(torch.bfloat16))
+    back = gd.out((n,), F32, name="unpacked")
+    ops.dp_unpack(wire, back, 4.0)
+    sync()
+    gd.check()
+    assert torch.equal(back, wire.float() * 4.0)
+    # conversions and the periodic add
+    hd = ops.half_dtype()
+    c16, c32 = gd.out((n,), hd, name="cast to 16 bits"), gd.out((n,), F32, name="cast back")
+    ops.cast(srcg, c16)
+    ops.cast(c16, c32)
+    sync()
+    gd.check()
+    assert torch.equal(c16, x0.to(hd)) and torch.equal(c32, x0.to(hd).float())
+    per = next(q for q in (96, 61, 48, 13, 8, 7, 3, 1) if n % q == 0)
+    pe = G.rnd(per, seed=4)
+    ag = gd.out((n,), F32, name="a + periodic b")
+    ops.add(srcg, gd.op(pe, name="b"), ag, period=per)
+    sync()
+    gd.check()
+    assert torch.equal(ag, x0 + pe.repeat(n // per))
+
+
+@pytest.mark.parametrize("rows,C", [(37, 24), (128, 96)])
+def test_column_ops_guarded(rows, C):
+    column_ops_guarded(rows, C)
+
+
+def column_ops_guarded(rows, C):
+    """scot_colscale_dev (C % 8 == 0), scot_mask_tokens(_bwd), scot_batch_sum, scot_partial_colsum(_batch), scot_colsum with a row stride."""
+    gd = Guards()
+    hd = ops.half_dtype()
+    g, gamma, mul = G.rnd(rows, C, seed=1), G.rnd(C, seed=2, scale=1e-3), torch.tensor([64.0], device=G.DEV)
+    gg, gag, mg = gd.op(g, name="g"), gd.op(gamma, name="gamma"), gd.op(mul, name="mul")
+    exact = g.double() * gamma.double() * 64.0
+    for odt in (F32, hd):      # two fp32 products, then one rounding to the result format
+        out = gd.out((rows, C), odt, name=f"colscale {odt}")
+        ops.colscale_dev(gg, gag, mg, out, rows, C)
+        sync()
+        gd.check()
+        within(out, exact, ((kc.UNIT[odt] if odt != F32 else 0.0) + 2.5 * kc.U32) * exact.abs() + kc.SUBNORMAL_HALF_ULP[kc.UNIT[odt]], f"colscale_dev -> {odt}")
+    # mask tokens, in place; backward: d_token += sum of masked rows (atomics over 64-row blocks), masked rows zeroed
+    x0, tok = G.rnd(rows, C, seed=3), G.rnd(C, seed=4)
+    mask = (torch.arange(rows) % 3 == 1).to(torch.uint8).to(G.DEV)
+    mask[rows - 1] = 1
+    xg, mk, tg = gd.out((rows, C), F32, src=x0, name="x"), gd.op(mask, name="mask"), gd.op(tok, name="token")
+    ops.mask_tokens(xg, mk, tg, rows, C)
+    sync()
+    gd.check()
+    assert torch.equal(xg, torch.where(mask.bool().unsqueeze(1), tok.unsqueeze(0), x0))
+    g0, dt0 = G.rnd(rows, C, seed=5), G.rnd(C, seed=6)
+    gg2, dtg = gd.out((rows, C), F32, src=g0, name="g"), gd.out((C,), F32, src=dt0, name="d_token")
+    ops.mask_tokens_bwd(gg2, mk, dtg, rows, C)
+    sync()
+    gd.check()
+    assert torch.equal(gg2, torch.where(mask.bool().unsqueeze(1), torch.zeros_like(g0), g0))
+    msum, mabs = (g0.double() * mask.double().unsqueeze(1)).sum(0), (g0.double().abs() * mask.double().unsqueeze(1)).sum(0)
+    within(dtg, dt0.double() + msum, (rows + 2) * kc.U32 * (mabs + dt0.double().abs()) + 1e-45, "mask_tokens_bwd")
+    # column / batch sums: a sum of n terms in fp32 in any order is within n * u * sum|x| of the exact one
+    for dt_ in (F32, hd):
+        xs = G.rnd(rows, C, seed=7, dtype=dt_)
+        o0 = G.rnd(C, seed=8)
+        o = gd.out((C,), F32, src=o0, name="batch_sum out (+=)")
+        ops.batch_sum(gd.op(xs, name="x"), o, rows, C)
+        sync()
+        gd.check()
+        within(o, o0.double() + xs.double().sum(0), (rows + 1) * kc.U32 * (xs.double().abs().sum(0) + o0.double().abs()) + 1e-45, f"batch_sum {dt_}")
+        o2, xs_s = gd.out((C,), F32, src=o0, name="colsum out"), gd.op(xs, pad=8, name="x (strided)")
+        lib_rc = ops.L().scot_colsum(ops.ptr(xs_s), ops.dt(xs_s), None, 0, ops.ptr(o2), rows, C, C + 8, ops.stream())
+        assert lib_rc == 0
+        sync()
+        gd.check()
+        within(o2, o0.double() + xs.double().sum(0), (rows + 1) * kc.U32 * (xs.double().abs().sum(0) + o0.double().abs()) + 1e-45, f"colsum ld {dt_}")
+    part, o0 = G.rnd(rows, C, seed=9), G.rnd(C, seed=10)
+    pg, og = gd.op(part, name="partial"), gd.out((C,), F32, src=o0, name="out")
+    ops.partial_colsum(pg, rows, C, og)
+    items = []
+    for j, (nb, nc) in enumerate(((rows, C), (5, 3 * C), (1, 8))):
+        pj, oj = G.rnd(nb, nc, seed=20 + j), G.rnd(nc, seed=30 + j)
+        items.append((gd.op(pj, name=f"partial{j}"), nb, nc, gd.out((nc,), F32, src=oj, name=f"out{j}"), pj, oj))
+    ops.partial_colsum_batch([it[:4] for it in items])
+    sync()
+    gd.check()
+    within(og, o0.double() + part.double().sum(0), (rows + 1) * kc.U32 * (part.double().abs().sum(0) + o0.double().abs()) + 1e-45, "partial_colsum")
+    for pjg, nb, nc, ojg, pj, oj in items:
+        within(ojg, oj.double() + pj.double().sum(0), (nb + 1) * kc.U32 * (pj.double().abs().sum(0) + oj.double().abs()) + 1e-45, "partial_colsum_batch")
+
+
+@pytest.mark.parametrize("H,W,transpose", [(12, 12, True), (9, 13, False), (16, 16, False)])
+def test_gather_guarded(H, W, transpose):
+    gather_guarded(H, W, transpose)
+
+
+def gather_guarded(H, W, transpose):
+    """scot_gather_pairs / scot_gather_planes: out = fmaf(a[c], plane, b[c]) with the plane picked per (sample, channel); constant channels
+    (src = -1), fixed planes (src <= -2, never transposed), the transposed read of square planes."""
+    n, T, nsrc, B, C = 3, 4, 3, 4, 5
+    gd = Guards()
+    data = G.rnd(n, T, nsrc, H, W, seed=1)
+    it = torch.tensor([[2, 0, 1, 2], [0, 1, 3, 2], [1, 3, 0, 3]], dtype=torch.int32, device=G.DEV)
+    src = torch.tensor([1, -1, 0, 2, 1], dtype=torch.int32, device=G.DEV)
+    a, b = G.rnd(C, seed=2), G.rnd(C, seed=3)
+    dg, ig, sg, ag, bg = gd.op(data, name="data"), gd.op(it, name="it"), gd.op(src, name="src"), gd.op(a, name="a"), gd.op(b, name="b")
+    pv, lab = gd.out((B, C, H, W), F32, name="pv"), gd.out((B, C, H, W), F32, name="lab")
+    ops.gather_pairs(dg, ig, sg, ag, bg, pv, lab, T, nsrc, H, W, transpose)
+    sync()
+    gd.check()
+
+    def ref(tidx_row, src_list, planes=None):
+        out = torch.empty(B, C, H, W, dtype=torch.float64, device=G.DEV)
+        mag = torch.empty_like(out)
+        for bi in range(B):
+            for c in range(C):
+                sc = int(src_list[c])
+                if sc == -1:
+                    out[bi, c], mag[bi, c] = b[c].double(), b[c].double().abs()
+                    continue
+                P = data[int(it[0, bi]), int(tidx_row[bi]), sc].double() if sc >= 0 else planes[-2 - sc].double()
+                if transpose and sc >= 0:
+                    P = P.t()
+                out[bi, c] = a[c].double() * P + b[c].double()
+                mag[bi, c] = out[bi, c].abs()
+        return out, mag
+    for got, row in ((pv, it[1]), (lab, it[2])):
+        r, m = ref(row, src)
+        within(got, r, kc.U32 * m + 1e-45, "gather_pairs (one fmaf)")
+    planes = G.rnd(2, H, W, seed=4)
+    src2 = torch.tensor([1, -1, -2, 2, -3], dtype=torch.int32, device=G.DEV)
+    out = gd.out((B, C, H, W), F32, name="out")
+    ops.gather_planes(dg, gd.op(it[0].contiguous(), name="traj"), gd.op(it[1].contiguous(), name="tidx"), gd.op(src2, name="src"), ag, bg,
+                      gd.op(planes, name="planes"), out, T, nsrc, H, W, transpose)
+    sync()
+    gd.check()
+    r, m = ref(it[1], src2, planes)
+    within(out, r, kc.U32 * m + 1e-45, "gather_planes (one fmaf)")
+
+
+def test_data_movement_guarded():
+    data_movement_guarded()
+
+
+def data_movement_guarded():
+    """scot_copy2d, scot_space_to_depth / depth_to_space, scot_patchify / unpatchify and scot_transpose_cast (rows, cols multiples of 8: its
+    documented precondition) on guarded tensors: exact compares, matrices of the transposed arena back to back WITHOUT slack."""
+    gd = Guards()
+    hd = ops.half_dtype()
+    B, H, W, C = 2, 5, 7, 12
+    x = G.rnd(B, H, W, C)
+    xg = gd.op(x, name="x")
+    pad, crop = gd.out((B, 8, 8, C), F32, name="padded"), gd.out((B, 4, 6, C), F32, name="cropped")
+    ops.copy2d(xg, pad, B, H, W, 8, 8, C)
+    ops.copy2d(xg, crop, B, H, W, 4, 6, C)
+    sync()
+    gd.check()
+    assert torch.equal(pad, torch.nn.functional.pad(x, (0, 0, 0, 1, 0, 3))) and torch.equal(crop, x[:, :4, :6])
+    for (H, W), C in (((9, 5), 6), ((9, 5), 16), ((8, 8), 96)):      # 6: element-wise kernel; multiples of 8: eight channels per thread
+        a, b = G.rnd(B, H, W, C), G.rnd(B, H, W, C, seed=1)
+        H2, W2 = (H + 1) // 2, (W + 1) // 2
+        co = gd.out((B, H2, W2, 4 * C), F32, name="coarse")
+        ops.space_to_depth(gd.op(a, name="fine"), gd.op(b, name="fine2"), co, B, H, W, C, 0)
+        s_ = torch.nn.functional.pad(a + b, (0, 0, 0, W % 2, 0, H % 2))
+        fine = gd.out((B, H, W, C), F32, name="fine back")
+        ops.depth_to_space(co, fine, B, H, W, H2, W2, C, 0)
+        z = G.rnd(B, H2, W2, 4 * C, seed=2)
+        fine2 = gd.out((B, H, W, C), F32, name="pixel shuffle")
+        ops.depth_to_space(gd.op(z, name="z"), fine2, B, H, W, H2, W2, C, 1)
+        sync()
+        gd.check()
+        assert torch.equal(co, torch.cat([s_[:, 0::2, 0::2], s_[:, 1::2, 0::2], s_[:, 0::2, 1::2], s_[:, 1::2, 1::2]], -1))
+        assert torch.equal(fine, a + b)
+        assert torch.equal(fine2, z.view(B, H2, W2, 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B, 2 * H2, 2 * W2, C)[:, :H, :W])
+    for H, W, Cc, cdt in ((18, 14, 3, F32), (16, 16, 3, F32), (64, 32, 5, hd)):
+        p = 4
+        img = G.rnd(B, Cc, H, W)
+        gh, gw = (H + p - 1) // p, (W + p - 1) // p
+        cols = gd.out((B * gh * gw, Cc * p * p), cdt, name="cols")
+        imgg = gd.op(img, name="img")
+        ops.patchify(imgg, cols, B, Cc, H, W, p)
+        sync()
+        gd.check()
+        padded = torch.nn.functional.pad(img, (0, gw * p - W, 0, gh * p - H))
+        assert torch.equal(cols, padded.view(B, Cc, gh, p, gw, p).permute(0, 2, 4, 1, 3, 5).reshape(B * gh * gw, Cc * p * p).to(cdt))
+        if cdt == F32:
+            bias = G.rnd(Cc, seed=1)
+            back = gd.out((B, Cc, H, W), F32, name="unpatchified")
+            ops.unpatchify(cols, gd.op(bias, name="bias"), back, B, Cc, H, W, gh, gw, p)
+            sync()
+            gd.check()
+            assert torch.equal(back, img + bias.view(1, -1, 1, 1))
+    mats = [(96, 288), (288, 96), (40, 72), (8, 8), (72, 200)]
+    offs, cur = [], 0
+    for r, c in mats:
+        offs.append(cur)
+        cur += (r * c + 63) // 64 * 64                    # the arena's alignment, nothing more
+    cur = offs[-1] + mats[-1][0] * mats[-1][1]             # the last matrix ends the range
+    arena = G.rnd(cur, seed=3)
+    desc, tile = [], 0
+    for (r, c), o in zip(mats, offs):
+        desc.append((o, r, c, tile))
+        tile += ((r + 63) // 64) * ((c + 63) // 64)
+    wt = gd.out((cur,), hd, name="transposed copies")
+    ops.transpose_cast(gd.op(arena, name="fp32 arena"), wt, gd.op(torch.tensor(desc, dtype=torch.int32, device=G.DEV), name="desc"), len(mats), tile)
+    sync()
+    gd.check()
+    for (r, c), o in zip(mats, offs):
+        assert torch.equal(wt[o:o + r * c].view(c, r), arena[o:o + r * c].view(r, c).to(hd).t()), (r, c)
+
+
+def measure_margins():
+    """prints, per class, the worst per-row ratio of the fp32-evaluated rounding model (two summation orders) to the fp64-evaluated one"""
+    G.DEV = "cpu"
+    worst = {}
+    for klass, half in (("16", torch.bfloat16), ("16", torch.float16), ("x3", None), ("f32", None)):
+        cdt = half if klass == "16" else F32
+        for case in G.ATTN_CASES:
+            qkv, table, ls, dout = _attn_inputs(case, cdt)
+            ex = attn_model(qkv, table, ls, dout, case, klass, half, exact=True)
+            m64 = attn_model(qkv, table, ls, dout, case, klass, half)
+            for rev in (False, True):
+                m32 = attn_model(qkv, table, ls, dout, case, klass, half, dtype=F32, reverse=rev)
+                for k in (0, 1):
+                    n = ex[k].shape[-1]
+                    r, row = kc.row_model_excess(m32[k].reshape(-1, n), ex[k].reshape(-1, n), m64[k].reshape(-1, n), 1.0)
+                    key = "attn" + klass
+                    worst[key] = max(worst.get(key, 0.0), r)
+                    print(f"attn {klass} {half} {case} {'dqkv' if k else 'out'} reversed {rev}: ratio {r:.2f} (row {row})")
+    for xdt in (F32, torch.bfloat16):
+        for cond in (True, False):
+            for B, L, C in CLN_SHAPES:
+                x, res, t, ps, dout = _cln_inputs(xdt, B, L, C)
+                args = (x, res, t, ps[0], ps[1], ps[2], ps[3], None, dout, cond, xdt)
+                ex, m64 = cln_model(*args, exact=True), cln_model(*args)
+                for rev in (False, True):
+                    m32 = cln_model(*args, dtype=F32, reverse=rev)
+                    for k in (0, 1):
+                        r, row = kc.row_model_excess(m32[k].reshape(-1, C), ex[k].reshape(-1, C), m64[k].reshape(-1, C), 1.0)
+                        worst["cln"] = max(worst.get("cln", 0.0), r)
+                        print(f"cln {xdt} cond {cond} {(B, L, C)} {'dx' if k else 'out'} reversed {rev}: ratio {r:.2f} (row {row})")
+    for k, v in worst.items():
+        print(f"WORST {k}: {v:.2f}  -> MARGIN {2 * v:.2f}")
+
+
+if __name__ == "__main__":
+    import sys
+    if "--measure-margins" in sys.argv:
+        measure_margins()
