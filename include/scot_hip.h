@@ -26,7 +26,8 @@ typedef struct ihipStream_t* scot_stream_t; /* = hipStream_t */
 #define SCOT_LAYOUT_NN 1 /* C[M,N] = A[M,K] B[K,N]   : dgrad of nn.Linear; ConvTranspose2d k=s (ref:616-621)      */
 #define SCOT_LAYOUT_TN 2 /* C[M,N] += A[K,M]^T B[K,N] : wgrad of nn.Linear (autograd of the above)                 */
 
-int scot_abi_version(void);   /* 5 (round 6: 4 = scot_wgrad_group / scot_wgrad_mlp modes, scot_segments_scale, scot_gemm_splitk_config; 5 = scot_dp_init .. finalize); the bindings check it at load */
+int scot_abi_version(void);   /* 6 (round 6: 4 = scot_wgrad_group / scot_wgrad_mlp modes, scot_segments_scale, scot_gemm_splitk_config; 5 = scot_dp_init .. finalize;
+                                 6 = scot_cln_dtime, scot_zero_masked, scot_add_channels); the bindings check it at load */
 /* Format of dtype code 1 in THIS build of the library: 0 = bfloat16 (libscot_hip.so), 1 = IEEE binary16 (libscot_hip_f16.so, the
  * same sources compiled with -DSCOT_OPERAND_FP16).  The reference computes in fp32 (ref:1318-1509); 16-bit operands are this
  * library's choice and binary16 is the one that keeps ScOT.forward within 1e-3 of it. */
@@ -235,6 +236,28 @@ int scot_cln_bwd(const void* dout, int dout_dt, const void* x, int x_dt, const f
 size_t scot_cln_bwd_workspace_bytes(int rows, int rows_per_sample, int C, int conditional);
 int scot_cln_bwd_finish(const void* partial, int rows, int rows_per_sample, int C, float* d_gw_w, float* d_gw_b, float* d_bw_w,
                         float* d_bw_b, scot_stream_t stream);
+
+/* The head's part of the gradient with respect to pixel_values (ref:1411-1422).  scot_zero_masked: g [B, Cc, HW] fp32 is zeroed in place
+ * where the pixel mask (uint8; mask_full: [B, Cc, HW], else [B, Cc] whole planes) replaced the prediction by the label.
+ * scot_add_channels: dst[b, c, :] += src[b, c, :] for c < Cc, dst [B, dst_ch >= Cc, HW], src [B, Cc, HW] (learn_residual). */
+int scot_zero_masked(float* g, const unsigned char* mask, int mask_full, int B, int Cc, int HW, scot_stream_t stream);
+int scot_add_channels(float* dst, int dst_ch, const float* src, int B, int Cc, int HW, scot_stream_t stream);
+
+/* The TIME gradient of one conditional layer norm (csrc/cln_dtime.hip), ref:143-160: gamma = W_g·t + b_g and beta = W_b·t + b_b are the
+ * only places the conditioning time enters  out = resid + s_b·(gamma ∘ xhat + beta)  (ref:570,574), hence
+ *   d_time[b] += s_b · Σ_{rows r of sample b} Σ_c dout[r,c] · (gw_w[c]·(x[r,c] − mean[r])·rstd[r] + bw_w[c]).
+ * dout / x: fp32 or the build's 16-bit operand format (dtype codes as everywhere), [rows, C]; mean / rstd: the forward's statistics;
+ * gw_w / bw_w: the `.weight` of the norm's two nn.Linear(1, C); sample_scale: optional s_b (drop path), one float per sample;
+ * d_time: fp32 [rows / rows_per_sample], ACCUMULATED into.  Any C >= 1 and any rows_per_sample (rows_per_sample·C < 2^31); fp32
+ * accumulation; deterministic (no floating-point atomics, fixed summation order: two calls on the same operands agree bit for bit).
+ * Reads rows·C elements of dout and x and rows of mean / rstd, writes d_time[0 .. rows / rows_per_sample) and `workspace`
+ * (>= scot_cln_dtime_workspace_bytes, 4-byte aligned; per-block partial sums of a sample that a second launch adds in order).
+ * Anything else — a NULL operand, another dtype code, sizes that do not divide, too little workspace — returns -3 before anything is
+ * written (workspace query: 0). */
+size_t scot_cln_dtime_workspace_bytes(int rows, int rows_per_sample, int C);
+int scot_cln_dtime(const void* dout, int dout_dt, const void* x, int x_dt, const float* mean, const float* rstd, const float* gw_w,
+                   const float* bw_w, const float* sample_scale, float* d_time, int rows, int rows_per_sample, int C, void* workspace,
+                   size_t ws_bytes, scot_stream_t stream);
 
 /* EXPERIMENTAL (off unless SCOT_FUSED_MLP=1; see poseidon_amd/csrc/mlp_fused.hip) — the MLP half of a ScOTLayer in one launch:
  *   z = gelu(h16·W1^T + b1)·W2^T + b2   (Swinv2Intermediate + Swinv2Output, HF modeling_swinv2.py:533-561)

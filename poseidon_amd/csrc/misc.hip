@@ -1035,6 +1035,37 @@ extern "C" int scot_loss_bwd(const float* pred, const float* labels, const unsig
   return scot_check_launch();
 }
 
+// ------------------------------------------------------------------ input gradient of the head (learn_residual / pixel_mask)
+// g[b,c,i] = 0 where the pixel mask overwrote the prediction with the label (model.py:1416-1422): nothing upstream of the overwrite
+// sees a gradient there — scot_loss_bwd already writes 0, this covers a caller's own gradient of the prediction added on top
+__global__ void zero_masked_kernel(float* g, const unsigned char* mask, int mask_full, int Cc, int HW, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    if (mask_full ? mask[i] : mask[i / HW]) g[i] = 0.f;
+}
+extern "C" int scot_zero_masked(float* g, const unsigned char* mask, int mask_full, int B, int Cc, int HW, hipStream_t s) {
+  if (!g || !mask || B <= 0 || Cc <= 0 || HW <= 0) return SCOT_ERR_SHAPE;
+  const size_t n = (size_t)B * Cc * HW;
+  size_t blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(zero_masked_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g, mask, mask_full, Cc, HW, n);
+  return scot_check_launch();
+}
+// dst[b, c, i] += src[b, c, i] for c < Cc (dst has dst_ch >= Cc channels): pred = head + pixel_values[:, :Cout] (learn_residual,
+// model.py:1411-1414) hands the prediction's gradient to the first Cout input channels
+__global__ void add_channels_kernel(float* dst, int dst_ch, const float* src, int Cc, int HW, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t plane = (size_t)Cc * HW;
+    const size_t b = i / plane, r = i - b * plane;
+    dst[b * (size_t)dst_ch * HW + r] += src[i];
+  }
+}
+extern "C" int scot_add_channels(float* dst, int dst_ch, const float* src, int B, int Cc, int HW, hipStream_t s) {
+  if (!dst || !src || B <= 0 || Cc <= 0 || HW <= 0 || dst_ch < Cc) return SCOT_ERR_SHAPE;
+  const size_t n = (size_t)B * Cc * HW;
+  size_t blocks = (n + 255) / 256; if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(add_channels_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dst, dst_ch, src, Cc, HW, n);
+  return scot_check_launch();
+}
+
 // ------------------------------------------------------------------ continuous relative position bias MLP
 // reference HF:376-378, 418-428:  table[h][e] = 16·sigmoid( relu(coords[e]·W0^T + b0) · W2[h]^T ),  e over (2ws-1)^2.
 // Batch-independent: once per layer per step.  z (pre-sigmoid) is saved for the backward.
@@ -1348,7 +1379,7 @@ extern "C" int scot_selftest_tr(hipStream_t s) {
 }
 extern "C" void scot_set_use_tr(int v) { g_scot_use_tr = v ? 1 : 0; }
 extern "C" int scot_get_use_tr() { return g_scot_use_tr; }
-extern "C" int scot_abi_version() { return 5; }      // 3: scot_gemm_wide_config; 4: scot_gemm_splitk_config; 5: scot_dp_* (dp.hip)
+extern "C" int scot_abi_version() { return 6; }      // 3: scot_gemm_wide_config; 4: scot_gemm_splitk_config; 5: scot_dp_* (dp.hip); 6: scot_cln_dtime
 // Format of the 16-bit operand type this build of the library computes with: 0 = bfloat16, 1 = IEEE binary16 (common.h).
 extern "C" int scot_operand_format() {
 #if defined(SCOT_OPERAND_FP16)

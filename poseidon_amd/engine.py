@@ -215,6 +215,11 @@ class ScOTEngine:
         self.weights_version = None
         self._shadow_v = self._shadow_t_v = object()
         self._copies_maintained = False      # True once an optimizer (FusedAdamW) writes the 16-bit copies itself
+        # the backward in flight (see forward's input_grads / param_grads): is any parameter trainable, the fp32 [2, B] accumulator of the
+        # time gradient (row 0: main stream, row 1: tasks on the side stream — two streams must not add into one word) or None, and a
+        # ConvNeXt block's detour for it (its branch runs under an extra power of two)
+        self._pgr, self._dt, self._dt_to = True, None, None
+        self._fwd_flags = ((), True)
         self._build_cpb_plan()
         if self.compute == ops.BF16 and arena.grad is not None:
             self._plan_grad_partition()
@@ -626,8 +631,13 @@ class ScOTEngine:
         rows = x.numel() // C
         dx = self.new(rows, C, dtype=dx_dtype)
         gw_w, gw_b, _, _ = self._norm_params(prefix)
-        g = self._norm_grads(prefix)
         t = time if self.cond else None
+        self.dtime(prefix, dout, x, stats, rows_per_sample, C, sample_scale)
+        if not self._pgr:       # no trainable parameter: the data gradient alone (no column sums, no atomics)
+            ops.cln_bwd(dout, x, stats[0], stats[1], t, gw_w, gw_b, dx, None, None, None, None, rows, rows_per_sample, C,
+                        sample_scale=sample_scale, mode=1)
+            return dx
+        g = self._norm_grads(prefix)
         nf = ops.cln_bwd_partial_floats(rows, rows_per_sample, C, self.cond)
         if nf and self._norm_grads_contiguous(prefix, C):
             # the deep stages' norms (1024 / 4096 rows): dx on the chain with every row's loads in flight at once, the cross-block
@@ -641,6 +651,15 @@ class ScOTEngine:
         ops.cln_bwd(dout, x, stats[0], stats[1], t, gw_w, gw_b, dx, g[0], g[1], g[2], g[3], rows, rows_per_sample, C,
                     sample_scale=sample_scale)
         return dx
+
+    def dtime(self, prefix, dout, x, stats, rows_per_sample, C, sample_scale=None):
+        """the time gradient of the conditional norm `prefix` into the accumulator of the backward in flight (nothing unless asked for):
+        dout = gradient of the norm's output branch, x = its pre-norm rows, stats = the forward's (mean, rstd)"""
+        if self._dt is None:
+            return
+        acc = self._dt_to if self._dt_to is not None else self._dt[1 if self._in_side is not None else 0]
+        ops.cln_dtime(dout, x, stats[0], stats[1], self.P(prefix + ".weight.weight"), self.P(prefix + ".bias.weight"), acc,
+                      x.numel() // C, rows_per_sample, C, sample_scale=sample_scale)
 
     def tail_plan(self, blk: BlockGeom, B: int, train: bool) -> TailPlan:
         """How this ScOTLayer's tail runs in each direction, made once per (layer, batch, train) — the prefix fixes the width, the hidden
@@ -700,6 +719,8 @@ class ScOTEngine:
         """Run fn() (kernel launches that only WRITE parameter gradients) on the side stream, ordered after everything
         enqueued so far on the current stream.  `tensors` are kept alive until the join so the allocator cannot recycle
         them.  The launches are queued and handed over by flush_side(): ONE fork per block instead of one per weight gradient."""
+        if not self._pgr:      # no trainable parameter: what is handed over here only writes parameter gradients
+            return
         if not self.use_side or self._in_side is not None:     # no side stream, or already running on it
             fn()
             return
@@ -812,7 +833,8 @@ class ScOTEngine:
     def wgrad(self, cm, dy, x, gw, dbias=None):
         """dW += dy^T x (+ dbias), or the store grad_mode(gw) asks for: queued until the next flush_side(), where the queued problems
         that share a compute mode and a token count — the four Linear layers of a ScOTLayer — go out as ONE grouped launch (ops.wgrad_group)."""
-        self._wgq.append((cm, dy, x, gw, dbias))
+        if self._pgr:
+            self._wgq.append((cm, dy, x, gw, dbias))
 
     def _drain_wgrads(self):
         q, self._wgq = self._wgq, []
@@ -1004,7 +1026,8 @@ class ScOTEngine:
         L, Lp = H * W, Hp * Wp
         hid = int(cfg.mlp_ratio * C)
         plan: TailPlan = rec["plan"]
-        can_prologue = plan.bwd in ("lean", "tail") and C in FUSED_QKV_DGRAD and not padded
+        # (with the time gradient asked for, layernorm_after's dout has to exist in memory before the tail runs: no prologue then)
+        can_prologue = plan.bwd in ("lean", "tail") and C in FUSED_QKV_DGRAD and not padded and self._dt is None
         if pend is not None and not can_prologue:
             g = self.dgrad_into(cm, pend[0], pend[1], g, wt=pend[2])
             pend = None
@@ -1020,6 +1043,7 @@ class ScOTEngine:
             part2, part1 = self.new(nwg, ncol), self.new(nwg, ncol)
             w1n, w2n = pre + ".intermediate.dense.weight", pre + ".output.dense.weight"
             b1 = self.P(pre + ".intermediate.dense.bias")
+            self.dtime(pre + ".layernorm_after", g, rec["y2"], rec["st2"], L, C, rec["dp"][1])
             if not ops.block_tail_bwd(
                     g, g,
                     (rec["y2"], rec["st2"][0], rec["st2"][1], n2[0], n2[1], rec["dp"][1], rec["gp"], self.W(w1n), self.W(w2n), d_y2, None,
@@ -1030,11 +1054,13 @@ class ScOTEngine:
                     h16=rec["h16"], b1=b1, z16=True, partial2=part2, partial1=part1):
                 raise RuntimeError("scot_block_tail_bwd rejected a shape the engine selected it for")
             pend = None
+            self.dtime(pre + ".layernorm_before", g, rec["proj"], rec["st1"], L, C, rec["dp"][0])      # (g is g_out now)
             first2, first1 = next(t for t in g2 if t is not None), next(t for t in g1 if t is not None)
             h16r, w2t = rec["h16"], self.WT(w2n)
             gW1, gb1, gW2, gb2 = self.G(w1n), self.G(pre + ".intermediate.dense.bias"), self.G(w2n), self.G(pre + ".output.dense.bias")
 
-            self._finq += [(part2, nwg, ncol, first2), (part1, nwg, ncol, first1)]
+            if self._pgr:
+                self._finq += [(part2, nwg, ncol, first2), (part1, nwg, ncol, first1)]
 
             mlp_mode = self.grad_mode(gW1)
             assert mlp_mode == self.grad_mode(gW2)
@@ -1050,6 +1076,7 @@ class ScOTEngine:
             d_y2, d_u, d_proj = self.new(B * L, C, dtype=adt), self.new(B * L, hid, dtype=adt), self.new(B * L, C, dtype=adt)
             n2, g2 = self._norm_params(pre + ".layernorm_after"), self._norm_grads(pre + ".layernorm_after")
             n1, g1 = self._norm_params(pre + ".layernorm_before"), self._norm_grads(pre + ".layernorm_before")
+            self.dtime(pre + ".layernorm_after", g, rec["y2"], rec["st2"], L, C, rec["dp"][1])
             if not ops.block_tail_bwd(
                     g, g,
                     (rec["y2"], rec["st2"][0], rec["st2"][1], n2[0], n2[1], rec["dp"][1], rec["gp"], self.W(pre + ".intermediate.dense.weight"),
@@ -1059,6 +1086,7 @@ class ScOTEngine:
                     time if self.cond else None, B * L, L, C, hid, dqkv=pend[0] if pend else None, wqkv=pend[1] if pend else None):
                 raise RuntimeError("scot_block_tail_bwd rejected a shape the engine selected it for")
             pend = None
+            self.dtime(pre + ".layernorm_before", g, rec["proj"], rec["st1"], L, C, rec["dp"][0])      # (g is g_out now)
             self.linear_bwd_params(pre + ".output.dense.weight", pre + ".output.dense.bias", d_y2, rec["u"])
             self.linear_bwd_params(pre + ".intermediate.dense.weight", pre + ".intermediate.dense.bias", d_u, rec["h16"])
             self.linear_bwd_params(pre + ".attention.output.dense.weight", pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
@@ -1078,6 +1106,7 @@ class ScOTEngine:
                 d_proj = self.new(B * L, C, dtype=adt)
                 gw_w, gw_b, _, _ = self._norm_params(pre + ".layernorm_before")
                 gg = self._norm_grads(pre + ".layernorm_before")
+                self.dtime(pre + ".layernorm_before", g, rec["proj"], rec["st1"], L, C, rec["dp"][0])
                 if not ops.proj_cln_bwd(g, rec["proj"], rec["st1"][0], rec["st1"][1], time if self.cond else None, gw_w, gw_b, rec["dp"][0],
                                         self.W(pre + ".attention.output.dense.weight"), d_proj, d_attn, gg[0], gg[1], gg[2], gg[3], B * L,
                                         L, C):
@@ -1204,15 +1233,21 @@ class ScOTEngine:
             self._gredirect = ls["views"]
         else:
             ops.scale_residual(g, self.P(pre + ".weight"), None, d_y2, B * L, C)
+        if ls is not None and self._dt is not None:
+            self._dt_to = self.zeros(B)       # the block's share of the time gradient, times c: handed over divided by c below
         try:
-            return self._convnext_bwd_chain(pre, rec, g, d_y2, B, H, W, C, time, ls)
+            g = self._convnext_bwd_chain(pre, rec, g, d_y2, B, H, W, C, time, ls)
+            if self._dt_to is not None:
+                ops.axpy_dev(self._dt[1 if self._in_side is not None else 0], self._dt_to, ls["cs"][1:2])
+            return g
         finally:
-            self._gredirect = None
+            self._gredirect, self._dt_to = None, None
 
     def _convnext_bwd_chain(self, pre, rec, g, d_y2, B, H, W, C, time, ls):
         L = H * W
         # layer-scale gradient Σ g·y2: reads g BEFORE the in-place `g += d_s` at the end of this function — keep it on this stream
-        ops.colsum(g, self.arena.gview(pre + ".weight"), y=rec["y2"])
+        if self._pgr:
+            ops.colsum(g, self.arena.gview(pre + ".weight"), y=rec["y2"])
         self.linear_bwd_params(pre + ".pwconv2.weight", pre + ".pwconv2.bias", d_y2, rec["u"])
         d_u = self.new(B * L, 4 * C, dtype=self.adt)
         ops.linear_dgrad(self.compute, d_y2, self.W(pre + ".pwconv2.weight"), d_u, aux=rec["gp"], aux_mul=True, wt=self.WT(pre + ".pwconv2.weight"))
@@ -1264,7 +1299,15 @@ class ScOTEngine:
         if self.shadow_t is not None:
             self._shadow_t_v = v
 
-    def forward(self, pixel_values, time=None, labels=None, pixel_mask=None, train=True, stochastic=None, bool_masked_pos=None):
+    def forward(self, pixel_values, time=None, labels=None, pixel_mask=None, train=True, stochastic=None, bool_masked_pos=None,
+                input_grads=(), param_grads=True):
+        """input_grads: which of ("pixel_values", "time") the backward of this call also differentiates with respect to (`backward`
+        returns them); param_grads=False: no parameter is trainable — the backward launches no weight-gradient work and announces no
+        range (the frozen surrogate: gradient descent on an input through a fixed model).  Neither changes the forward's launches."""
+        igr = tuple(sorted(set(input_grads or ())))
+        if not set(igr) <= {"pixel_values", "time"}:
+            raise ValueError(f"input_grads: unknown input(s) {sorted(set(igr) - {'pixel_values', 'time'})}")
+        self._fwd_flags = (igr, bool(param_grads))
         prev = ops.use(self.lib_kind)
         try:
             if not self._capturing():
@@ -1288,6 +1331,7 @@ class ScOTEngine:
             ops.use(prev)
 
     def backward(self, tape, dloss=None, dpred=None):
+        """-> (d_pixel_values, d_time): fresh tensors for the inputs the forward named in `input_grads`, None for the others."""
         prev = ops.use(self.lib_kind)
         try:
             return self._backward_step(tape, dloss, dpred)
@@ -1314,7 +1358,8 @@ class ScOTEngine:
         # (inference forwards are taped too — an autoregressive rollout is hundreds of forwards of one signature, and issued through the
         # Python op wrappers a forward is host-bound: 400 launches at ~10 us each against ~5.5 ms of GPU time)
         key = (tuple(pixel_values.shape), None if time is None else tuple(time.shape), None if labels is None else tuple(labels.shape),
-               None if pixel_mask is None else (tuple(pixel_mask.shape), pixel_mask.dtype), self._stream_id(), self.stochastic, bool(train))
+               None if pixel_mask is None else (tuple(pixel_mask.shape), pixel_mask.dtype), self._stream_id(), self.stochastic,
+               self._fwd_flags if train else None, bool(train))
         ent = self._taped.get(key)
         if ent is None:
             # a recorded step pins all of its buffers (GBs): keep at most `tape_max` signatures (e.g. the full batch and the
@@ -1445,7 +1490,8 @@ class ScOTEngine:
                 ent["dloss"].copy_(dloss.reshape(1))
             self._lazy_now = variant
             self._replay(*have)
-            return
+            # (the recorded step owns the two buffers: the caller gets its own, as it does for loss / prediction / hidden states)
+            return tuple(None if t is None else t.clone() for t in ent["igrads"][variant])
         if ent["state"] not in ("fwd", "ready"):
             return self._backward(tape, dloss, dpred)
         if "dloss" not in ent:
@@ -1457,7 +1503,7 @@ class ScOTEngine:
         self._rec, self._rec_keep = [], ent["keep"]
         prev = ops.set_recorder(self._rec)
         try:
-            self._backward(tape, ent["dloss"], None)
+            igrads = self._backward(tape, ent["dloss"], None)
         except BaseException:
             # never replayed: the signature is recorded afresh by its next steps (a failed forward recording already did that)
             self._taped = {k: v for k, v in self._taped.items() if v is not ent}
@@ -1470,7 +1516,9 @@ class ScOTEngine:
             rec = self._rec
             self._rec = self._rec_keep = None
         ent["bwd"][variant] = (rec, ops.compile_tape(rec) if self.tape_c else None)
+        ent.setdefault("igrads", {})[variant] = igrads
         ent["state"] = "ready"
+        return tuple(None if t is None else t.clone() for t in igrads)
 
     def reset_tapes(self):
         """Forget recorded steps (call after changing anything a tape bakes in: hooks, environment knobs)."""
@@ -1489,7 +1537,7 @@ class ScOTEngine:
         gh, gw = self.grid
         C0 = cfg.embed_dim
         L0 = gh * gw
-        tape = dict(B=B, time=time, enc=[], dec=[], res=[]) if train else None
+        tape = dict(B=B, time=time, enc=[], dec=[], res=[], flags=getattr(self, "_fwd_flags", ((), True))) if train else None
         if train:
             self._init_grad_scale(B * cfg.num_out_channels * H * W)
         self.attn_sink = []
@@ -1622,7 +1670,7 @@ class ScOTEngine:
             ops.loss_finish(sums, meta["counts"], meta["G"], meta["normalized"], loss)
         if train:
             tape["head"] = dict(x=x, img=img, pred=pred, labels=labels, mask=mask_u8, mask_full=mask_full, sums=sums, meta=meta,
-                                shape=(B, Cout, H, W))
+                                shape=(B, Cout, H, W), residual=pv_res is not None)
             tape["hidden"] = (hidden_dec, hidden_enc)
         self.last_hidden = (hidden_dec, hidden_enc)
         self.last_hidden_aliased = self._rec is not None      # rows of a step being recorded: its replays overwrite them
@@ -1656,9 +1704,22 @@ class ScOTEngine:
         return meta
 
     def _backward(self, tape, dloss=None, dpred=None):
+        """-> (d_pixel_values, d_time), each None unless the forward asked for it"""
+        igr, pgr = tape.get("flags", ((), True))
+        self._pgr = bool(pgr)
+        self._dt = self.zeros(2, tape["B"]) if ("time" in igr and self.cond) else None
+        try:
+            return self._backward_chain(tape, dloss, dpred, "pixel_values" in igr)
+        finally:
+            self._pgr, self._dt, self._dt_to = True, None, None
+            if not pgr:
+                self._wgq, self._finq = [], []
+
+    def _backward_chain(self, tape, dloss, dpred, want_pv):
         cfg, cm, adt = self.cfg, self.compute, self.adt
         B, time = tape["B"], tape["time"]
         hd = tape["head"]
+        pgr = self._pgr
         self._lazy_now = bool(self.lazy_grads and self._small_chunks is not None)
         def fill_done():        # ScOT.zero_grad(overlap=True): the arena's fill runs on the side stream beside the forward
             ev, self.grad_fill_event = self.grad_fill_event, None
@@ -1680,7 +1741,8 @@ class ScOTEngine:
             def prescale():
                 if not self.grads_are_zero:
                     self.scale_grad_range(S_dev)
-            self.tdo_dynamic(prescale)
+            if pgr:      # (no trainable parameter: whatever the fused kernels leave in the arena is never read — ScOT clears it before use)
+                self.tdo_dynamic(prescale)
             if dpred is not None:
                 dpred = self.clone(dpred.contiguous())
                 ops.scale_inplace_dev(dpred.view(-1), S_dev)
@@ -1699,6 +1761,8 @@ class ScOTEngine:
                          meta["normalized"], dloss, g_pred, B, Cout, H * W, cfg.p)
             if dpred is not None:
                 ops.add(g_pred, dpred.contiguous(), g_pred)
+                if hd["mask"] is not None:      # the overwritten pixels are the labels: no gradient reaches the model through them
+                    ops.zero_masked(g_pred, hd["mask"], hd["mask_full"], B, Cout, H * W)
         elif dpred is not None:
             g_pred = self.clone(dpred.contiguous())
         else:
@@ -1717,7 +1781,10 @@ class ScOTEngine:
                                                 accumulate=True), hd["x"], d_rc)
         g = self.new(B * L0, C0)
         ops.gemm(ops.NT, self.tcm, B * L0, C0, Cout * p * p, d_rc, Cout * p * p, wrec, Cout * p * p, g, C0)
-        if self.on_grads_final is not None:
+        if not pgr:
+            def done(prefix):
+                return None
+        elif self.on_grads_final is not None:
             from .dp import group_ranges
 
             def announce(prefix, _cb=self.on_grads_final):
@@ -1841,16 +1908,37 @@ class ScOTEngine:
         self.mark("bwd embed")
         emb = tape["emb"]
         Cin = cfg.num_channels
-        if cfg.use_absolute_embeddings:
+        if cfg.use_absolute_embeddings and pgr:
             ops.batch_sum(g, self.G("embeddings.position_embeddings").view(-1), B, L0 * C0)
         if emb.get("tokmask") is not None:
             ops.mask_tokens_bwd(g, emb["tokmask"], self.G("embeddings.mask_token").view(-1), B * L0, C0)
         d_e = self.norm_bwd("embeddings.norm", g, emb["e"], emb["stats"], L0, C0, time, torch.float32)
         self.wgrad(self.tcm, d_e, emb["cols"], self.G("embeddings.patch_embeddings.projection.weight").view(C0, Cin * p * p),
                    dbias=self.G("embeddings.patch_embeddings.projection.bias"))
-        if scaled and self.on_grads_final is None and not self.use_side:
+        # input gradients (reference: autograd through model.py:295-366 and the conditional norms, model.py:143-160)
+        d_pv = d_t = None
+        if want_pv:
+            # d cols = d_e · W_embed on the trunk's compute mode, folded back to (B, Cin, H, W); the crop of the fold drops what the
+            # forward's right / bottom padding read as zeros
+            K0 = Cin * p * p
+            wemb = self.P("embeddings.patch_embeddings.projection.weight").view(C0, K0)
+            d_cols = self.new(B * L0, K0)
+            ops.gemm(ops.NN, self.tcm, B * L0, K0, C0, d_e, C0, wemb, K0, d_cols, K0)
+            d_pv = self.new(B, Cin, H, W)
+            ops.unpatchify(d_cols, None, d_pv, B, Cin, H, W, gh, gw, p)
+            if hd.get("residual"):      # learn_residual: pred = head + pixel_values[:, :Cout]; g_pred is zero where the mask overwrote it
+                ops.add_channels(d_pv, Cin, g_pred, B, Cout, H * W)
+            if scaled:
+                ops.scale_inplace_dev(d_pv.view(-1), Sinv_dev, self.grad_overflow)
+        if self._dt is not None:
+            d_t = self.new(B)
+            ops.add(self._dt[0], self._dt[1], d_t)      # (the side-stream tasks were joined by the encoder stages)
+            if scaled:
+                ops.scale_inplace_dev(d_t, Sinv_dev, self.grad_overflow)
+        if scaled and pgr and self.on_grads_final is None and not self.use_side:
             self.join_side()
             self.scale_grad_range(Sinv_dev, count=True)
         self.mark("end")
         done("embeddings.")
         self.join_side()
+        return d_pv, d_t

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libscot_hip.so")
 # The same sources built twice (build.py): the format of the 16-bit operand type is a compile-time property (csrc/common.h).
 LIB_PATHS = {"bf16": LIB_PATH, "f16": os.path.join(_HERE, "libscot_hip_f16.so")}
 OPERAND_FORMAT = {"bf16": 0, "f16": 1}
-ABI_VERSION = 5      # scot_abi_version() of the library these prototypes describe (checked at load)
+ABI_VERSION = 6      # scot_abi_version() of the library these prototypes describe (checked at load)
 
 P, I, F, Z = c_void_p, c_int, c_float, c_size_t
 
@@ -64,6 +64,8 @@ PROTOTYPES = {
     "scot_cln_bwd": [P, I, P, I, P, P, P, P, P, P, I, P, P, P, P, P, I, I, I, P, Z, P, I, P],
     "scot_cln_bwd_workspace_bytes": [I, I, I, I],
     "scot_cln_bwd_finish": [P, I, I, I, P, P, P, P, P],
+    "scot_cln_dtime_workspace_bytes": [I, I, I],
+    "scot_cln_dtime": [P, I, P, I, P, P, P, P, P, P, I, I, I, P, Z, P],
     "scot_add": [P, I, P, I, P, I, Z, Z, P],
     "scot_batch_sum": [P, I, P, I, Z, P],
     "scot_gather_pairs": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
@@ -88,6 +90,8 @@ PROTOTYPES = {
     "scot_head_finalize": [P, P, I, P, P, I, P, P, I, I, I, I, P],
     "scot_loss_finish": [P, P, I, I, P, P],
     "scot_loss_bwd": [P, P, P, I, P, P, P, I, I, P, P, I, I, I, I, P],
+    "scot_zero_masked": [P, P, I, I, I, I, P],
+    "scot_add_channels": [P, I, P, I, I, I, P],
     "scot_spectral_apply": [P, P, P, P, I, I, I, P],
     "scot_dp_pack": [P, P, Z, F, P],
     "scot_dp_unpack": [P, P, Z, F, P],
@@ -104,7 +108,8 @@ PROTOTYPES = {
     "scot_optim_finish": [P, P, P, F, F, I, F, P],
 }
 _VOID = {"scot_set_use_tr", "scot_gemm_wide_config", "scot_gemm_splitk_config"}
-_SIZE = {"scot_gemm_workspace_bytes", "scot_wgrad_group_workspace_bytes", "scot_cln_bwd_workspace_bytes", "scot_wgrad_mlp_workspace_bytes"}      # return size_t
+_SIZE = {"scot_gemm_workspace_bytes", "scot_wgrad_group_workspace_bytes", "scot_cln_bwd_workspace_bytes", "scot_wgrad_mlp_workspace_bytes",
+         "scot_cln_dtime_workspace_bytes"}      # return size_t
 
 
 def restype(name):

@@ -505,6 +505,27 @@ def cln_bwd_finish(partial, rows, rows_per_sample, C, d_gw_w, d_gw_b, d_bw_w, d_
                "scot_cln_bwd_finish")
 
 
+def cln_dtime(dout, x, mean, rstd, gw_w, bw_w, d_time, rows, rows_per_sample, C, sample_scale=None):
+    """d_time[b] += s_b · Σ_{rows of sample b} Σ_c dout·(gw_w·xhat + bw_w): the time gradient of one conditional layer norm
+    (scot_cln_dtime; dout / x fp32 or 16-bit, d_time fp32 [rows / rows_per_sample]; deterministic)."""
+    need = int(_raw().scot_cln_dtime_workspace_bytes(rows, rows_per_sample, C))
+    if need == 0:
+        raise _lib.ScotLibraryError(f"scot_cln_dtime does not cover rows={rows}, rows_per_sample={rows_per_sample}, C={C}")
+    ws = workspace(need)
+    _lib.check(L().scot_cln_dtime(ptr(dout), dt(dout), ptr(x), dt(x), ptr(mean), ptr(rstd), ptr(gw_w), ptr(bw_w), ptr(sample_scale),
+                                  ptr(d_time), rows, rows_per_sample, C, ws.data_ptr(), ws.numel(), stream()), "scot_cln_dtime")
+
+
+def zero_masked(g, mask_u8, mask_full, B, Cc, HW):
+    """g [B, Cc, HW] = 0 where the pixel mask overwrote the prediction (in place)."""
+    _lib.check(L().scot_zero_masked(ptr(g), ptr(mask_u8), int(mask_full), B, Cc, HW, stream()), "scot_zero_masked")
+
+
+def add_channels(dst, dst_ch, src, B, Cc, HW):
+    """dst[:, :Cc] += src  (dst [B, dst_ch, HW], src [B, Cc, HW], fp32)."""
+    _lib.check(L().scot_add_channels(ptr(dst), dst_ch, ptr(src), B, Cc, HW, stream()), "scot_add_channels")
+
+
 def add(a, b, out, period=None):
     n = a.numel()
     _lib.check(L().scot_add(ptr(a), dt(a), ptr(b), dt(b), ptr(out), dt(out), n, period if period is not None else n, stream()),

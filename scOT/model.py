@@ -134,13 +134,19 @@ def _convnext(cfg, dim):
 
 class _ScOTFunction(torch.autograd.Function):
     """Connects the engine's explicit forward/backward to torch.autograd.  Parameter gradients are accumulated by the
-    kernels directly into the gradient arena whose slices are the parameters' `.grad` (no per-tensor AccumulateGrad)."""
+    kernels directly into the gradient arena whose slices are the parameters' `.grad` (no per-tensor AccumulateGrad); the gradients
+    with respect to `pixel_values` and `time` are returned to autograd when it asks for them (`ctx.needs_input_grad`).  First order
+    only: the backward is a fixed program of kernels, so a `create_graph=True` request fails instead of returning a graph that
+    stops here."""
 
     @staticmethod
     def forward(ctx, anchor, model, pixel_values, time, labels, pixel_mask, bool_masked_pos=None):
         # activations are kept because a gradient was asked for; stochastic depth follows module.training (HF:565-586)
+        need = ctx.needs_input_grad
+        igr = (("pixel_values",) if need[2] else ()) + (("time",) if (time is not None and need[3]) else ())
+        ctx.param_grads = model._param_grads_now      # (decided by ScOT.forward for this call: one walk over the parameters per step)
         loss, pred, tape = model._engine.forward(pixel_values, time, labels, pixel_mask, train=True, stochastic=model.training,
-                                                 bool_masked_pos=bool_masked_pos)
+                                                 bool_masked_pos=bool_masked_pos, input_grads=igr, param_grads=ctx.param_grads)
         ctx.model, ctx.tape = model, tape
         ctx.has_loss = loss is not None
         ctx.set_materialize_grads(False)  # unused outputs arrive as None instead of zero tensors
@@ -149,19 +155,27 @@ class _ScOTFunction(torch.autograd.Function):
         return loss.view(()), pred
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, dloss, dpred):
         model, tape = ctx.model, ctx.tape
         ctx.tape = None
         if tape is None:
             raise RuntimeError("ScOT backward called twice (activations are freed after the first backward)")
-        model._prepare_grads()
+        if ctx.param_grads:
+            model._prepare_grads()
         dl = None
         if ctx.has_loss:
             dl = (dloss.reshape(1).to(torch.float32).contiguous() if dloss is not None
                   else torch.zeros(1, device=model._arena.data.device))
-        model._engine.backward(tape, dl, dpred)
-        model._after_backward()
-        return None, None, None, None, None, None, None
+        d_pv, d_t = model._engine.backward(tape, dl, dpred)
+        if ctx.param_grads:
+            model._after_backward()
+        else:
+            # every parameter is frozen: nothing was differentiated with respect to them.  The fused kernels' by-products may sit in
+            # the gradient arena, so no `.grad` stays attached to it: the next trainable backward finds None and clears the arena first
+            for p in model._params:
+                p.grad = None
+        return None, None, d_pv, d_t, None, None, None
 
 
 class ScOT(nn.Module):
@@ -241,6 +255,7 @@ class ScOT(nn.Module):
         self._engine: Optional[ScOTEngine] = None
         self._anchor = None
         self._grad_hooks = []
+        self._param_grads_now = True
 
     # ------------------------------------------------------------------------------------------ init / io
     def _init_weights(self):
@@ -469,12 +484,16 @@ class ScOT(nn.Module):
             t = torch.as_tensor(time, device=dev).reshape(-1).to(torch.float32).contiguous()
             if t.numel() == 1 and B > 1:
                 t = t.expand(B).contiguous()
+        if labels is not None and torch.is_grad_enabled() and labels.requires_grad:
+            raise NotImplementedError("the gradient with respect to `labels` is not implemented (pixel_values and time are); "
+                                      "detach the labels, or compute the loss from `output` in torch")
         lab = labels.to(device=dev, dtype=torch.float32).contiguous() if labels is not None else None
         in_size = pv.shape[2]
         resized = in_size != cfg.image_size
         if resized:
             pv = self._upsample(pv, cfg.image_size) if in_size < cfg.image_size else self._downsample(pv, cfg.image_size)
-        want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self._params)
+        self._param_grads_now = any(p.requires_grad for p in self._params)
+        want_grad = torch.is_grad_enabled() and (self._param_grads_now or pv.requires_grad or (t is not None and t.requires_grad))
         bmp = None
         if bool_masked_pos is not None:
             if resized:
