@@ -672,3 +672,72 @@ def test_guarded_small_ops(guarded_bodies, kind):
 def test_guarded_fused_halves(guarded_bodies, C, B, L, train, cond):
     guarded_bodies.fused_halves_fwd_guarded(C, B, L, train, cond)
     guarded_bodies.fused_halves_bwd_guarded(C, B, 64, cond)
+
+
+# ---- the second ring (csrc/misc.hip, csrc/optim.hip): stencils, head and loss, position-bias MLP, spectral apply, optimizer
+@pytest.mark.parametrize("kind,shape,x16,y16", [("bf16", (2, 5, 9, 6), False, False), ("f16", (1, 13, 6, 30), True, True), ("bf16", (2, 11, 9, 33), True, False),
+                                                ("bf16", (2, 12, 20, 24), False, True), ("f16", (3, 3, 4, 40), True, True)])
+def test_guarded_dwconv7(guarded_bodies, kind, shape, x16, y16):
+    """the scalar loader (C % 4 != 0: 6, 30, 33) and the 4-channel loader (24, 40) of dwconv7_tiled_kernel, 16-bit x and y"""
+    guarded_bodies.dwconv7_guarded(kind, *shape, x16, y16)
+
+
+@pytest.mark.parametrize("x16", [False, True])
+def test_guarded_dwconv7_misaligned_base(guarded_bodies, x16):
+    guarded_bodies.dwconv7_guarded("bf16", 2, 10, 7, 24, x16, False, misaligned=True)
+
+
+@pytest.mark.parametrize("kind,shape,g16,x16", [("bf16", (2, 5, 9, 6), False, False), ("f16", (1, 13, 6, 30), True, False), ("bf16", (2, 11, 9, 33), False, True),
+                                                ("bf16", (2, 12, 20, 24), True, True), ("f16", (3, 3, 4, 40), True, False)])
+def test_guarded_dwconv7_wgrad(guarded_bodies, kind, shape, g16, x16):
+    guarded_bodies.dwconv7_wgrad_guarded(kind, *shape, g16, x16)
+    if shape[3] == 24:
+        guarded_bodies.dwconv7_wgrad_guarded(kind, 2, 10, 7, 24, g16, False, misaligned=True)
+
+
+@pytest.mark.parametrize("Cc,H,W,B,misaligned", [(1, 6, 133, 1, False), (2, 9, 10, 2, False), (3, 5, 131, 1, False), (4, 12, 16, 2, False), (5, 13, 10, 1, False),
+                                                 (6, 9, 9, 2, False), (8, 7, 13, 1, False), (4, 9, 14, 2, True)])
+def test_guarded_conv5(guarded_bodies, Cc, H, W, B, misaligned):
+    """conv5_tiled_kernel<1..5> (ragged rows, a ragged second column tile with the scalar store), conv5_kernel at Cc = 6, 8 and through
+    the alignment fallback at Cc = 4"""
+    guarded_bodies.conv5_guarded(Cc, H, W, B, misaligned=misaligned)
+
+
+def test_guarded_declines(guarded_bodies):
+    guarded_bodies.conv5_declines()
+    guarded_bodies.spectral_apply_declines()
+
+
+@pytest.mark.parametrize("p,mk,HW,resid,goc,normalized", [(1, "none", 256, True, [0, 0, -1, 1], True), (2, "plane", 4097, False, [0, 0, 0, 0], False),
+                                                          (1, "pixel", 5000, False, [1, 0, 2, -1], True), (2, "pixel", 4097, True, [0, 0, -1, 1], True),
+                                                          (1, "plane", 256, True, [0, 0, 0, 0], False), (2, "none", 5000, True, [1, 0, 2, -1], False)])
+def test_guarded_head_loss(guarded_bodies, p, mk, HW, resid, goc, normalized):
+    """mask_full on and off, HW above one workgroup's 4096 elements (4097: a second workgroup with ONE element; 5000), a -1 channel, dloss,
+    labels = NULL, scot_zero_masked, scot_add_channels"""
+    guarded_bodies.head_loss_guarded(p, mk, HW, resid, goc, normalized)
+
+
+def test_guarded_nchw_channel_sum(guarded_bodies):
+    for B, Cc, HW in ((3, 4, 1000), (2, 5, 4097), (1, 3, 255)):
+        guarded_bodies.nchw_channel_sum_guarded(B, Cc, HW)
+
+
+@pytest.mark.parametrize("ws,heads", [(4, 24), (7, 2)])
+def test_guarded_cpb(guarded_bodies, ws, heads):
+    guarded_bodies.cpb_guarded(ws, heads)
+
+
+@pytest.mark.parametrize("first", [0, 2])
+def test_guarded_cpb_batched(guarded_bodies, first):
+    guarded_bodies.cpb_batched_guarded([(8, 3), (4, 24), (7, 2), (4, 6)], first)
+
+
+@pytest.mark.parametrize("s,t,nimg", [(32, 64, 1), (64, 32, 3), (24, 40, 2), (128, 128, 1)])
+def test_guarded_spectral_apply(guarded_bodies, s, t, nimg):
+    guarded_bodies.spectral_apply_guarded(s, t, nimg)
+
+
+@pytest.mark.parametrize("kind", ["bf16", "f16"])
+def test_guarded_optimizer(guarded_bodies, kind):
+    """small on the emulation (one workgroup's worth of 8-element cells per member); the grid-stride case runs on the GPU"""
+    guarded_bodies.optimizer_guarded(kind, guarded_bodies.OPT_SMALL)

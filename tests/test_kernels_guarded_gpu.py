@@ -1646,10 +1646,802 @@ def data_movement_guarded():
         assert torch.equal(wt[o:o + r * c].view(c, r), arena[o:o + r * c].view(r, c).to(hd).t()), (r, c)
 
 
+# =============================================================== second ring: stencils, head and loss, position-bias MLP, spectral apply, optimizer
+# csrc/misc.hip and csrc/optim.hip: entry points of every training step that the older suite judges by one global rel() on two to five shapes.
+# Same four assertions as above.  The local bounds: a stencil is an inner product over its taps (gemm_excess, K = the taps + the bias); a sum
+# that meets in atomicAdd is an inner product in ANY order over everything added; an elementwise formula is held to the number of fp32
+# roundings on its path, counted and stated at the call site, each at most u times the magnitude sum of the expression it sits in.
+class _build:
+    """route the wrappers to one build of the library for the length of a case"""
+
+    def __init__(self, kind):
+        self.kind = kind
+
+    def __enter__(self):
+        self.prev = ops.use(self.kind)
+        return ops.half_dtype()
+
+    def __exit__(self, *exc):
+        ops.use(self.prev)
+
+
+def still_poison(t):
+    """a result that a declined call must not touch: every element still the band's NaN, bit for bit"""
+    idt, poison = kc._POISON[t.dtype]
+    return bool((t.contiguous().view(idt) == poison).all())
+
+
+def off_by_one(gd, t, name):
+    """(guarded copy of t whose first element lies ONE element behind a 256-byte boundary, plain copy at the same misalignment): the view is
+    taken from the inside of a guarded allocation, the element in front of it keeps the band's NaN (asserted by the caller's finite check:
+    a loader that reads it poisons the result).  What the entry points do with it: the 16-byte vector loaders are not taken."""
+    v = gd.out((t.numel() + 1,), t.dtype, name=name)
+    v[1:].copy_(t.reshape(-1))
+    p = torch.empty(t.numel() + 64, dtype=t.dtype, device=G.DEV)
+    o = 1 + ((-p.data_ptr()) % 16) // p.element_size()
+    p[o:o + t.numel()].copy_(t.reshape(-1))
+    gv, pv = v[1:].view(t.shape), p[o:o + t.numel()].view(t.shape)
+    assert gv.data_ptr() % 16 == t.element_size() and pv.data_ptr() % 16 == t.element_size()
+    return gv, pv
+
+
+# ------------------------------------------------------------------------------------------------------------------------ depthwise 7 x 7
+def _dwconv64(x64, w64, b64, flip):
+    """NHWC depthwise 7 x 7, padding 3; flip: the data gradient's form, conv(dy, flip(w))"""
+    ww = w64.flip(-1, -2) if flip else w64
+    return torch.nn.functional.conv2d(x64.permute(0, 3, 1, 2), ww, b64, padding=3, groups=x64.shape[-1]).permute(0, 2, 3, 1).contiguous()
+
+
+def _dwconv_wgrad64(dy64, x64):
+    B, H, W, C = x64.shape
+    xp = torch.nn.functional.pad(x64, (0, 0, 3, 3, 3, 3))
+    dw = torch.empty(C, 1, 7, 7, dtype=torch.float64, device=x64.device)
+    for ki in range(7):
+        for kj in range(7):
+            dw[:, 0, ki, kj] = (dy64 * xp[:, ki:ki + H, kj:kj + W, :]).sum((0, 1, 2))
+    return dw
+
+
+# (B, H, W, C).  The loaders of dwconv7_tiled_kernel / dwconv7_wgrad_tiled_kernel: VEC = false for C % 4 != 0 (6 and 30: one channel block,
+# C < 32; 33: a second block with ONE live channel), VEC = true for C % 4 == 0 (24, 40: not multiples of 32; 96).  H != W, H and W below the
+# 7-wide stencil, H and W off the 8 x 8 tile.  Last: stage 0 of the timed model.
+DW_SHAPES = [(2, 5, 9, 6), (1, 13, 6, 30), (2, 9, 11, 33), (2, 12, 20, 24), (3, 3, 4, 40), (2, 64, 64, 96)]
+DW_IDS = lambda v: "x".join(str(i) for i in v) if isinstance(v, tuple) else None
+
+
+@pytest.mark.parametrize("y16", [False, True], ids=["y_f32", "y_16"])
+@pytest.mark.parametrize("x16", [False, True], ids=["x_f32", "x_16"])
+@pytest.mark.parametrize("kind", ["bf16", "f16"])
+@pytest.mark.parametrize("shape", DW_SHAPES, ids=DW_IDS)
+def test_dwconv7_guarded(shape, kind, x16, y16):
+    dwconv7_guarded(kind, *shape, x16, y16)
+
+
+@pytest.mark.parametrize("x16", [False, True], ids=["x_f32", "x_16"])
+@pytest.mark.parametrize("shape", [(2, 10, 7, 24), (1, 11, 8, 64)], ids=DW_IDS)
+def test_dwconv7_guarded_misaligned_base_falls_back_from_vec(shape, x16):
+    dwconv7_guarded("bf16", *shape, x16, False, misaligned=True)
+
+
+def dwconv7_guarded(kind, B, H, W, C, x16, y16, misaligned=False):
+    """scot_dwconv7, forward (bias) and flip = 1 (the data gradient, no bias), x_dt x y_dt in {fp32, 16 bit}; misaligned: C % 4 == 0 with a
+    base one element off 16-byte alignment, the fallback from VEC.  (c): an inner product over 49 taps and the bias, K = 50, accumulated in
+    fp32, one rounding to the result format.  gridDim.z = B, gridDim.y = ceil(C / 32): both above 1 in most shapes."""
+    with _build(kind) as hd:
+        xdt, ydt = (hd if x16 else F32), (hd if y16 else F32)
+        gd = Guards()
+        x, dy = G.rnd(B, H, W, C, dtype=xdt), G.rnd(B, H, W, C, seed=3, dtype=xdt)
+        w, bias = G.rnd(C, 1, 7, 7, seed=1, scale=0.2), G.rnd(C, seed=2)
+        wg, bg = gd.op(w, name="w"), gd.op(bias, name="bias")
+        for flip, src, b_, b_g in ((False, x, bias, bg), (True, dy, None, None)):
+            sg, sp = off_by_one(gd, src, "x (misaligned)") if misaligned else (gd.op(src, name="x"), src)
+            yg, yp = gd.out((B, H, W, C), ydt, name="y"), nan_like((B, H, W, C), ydt)
+            ops.dwconv7(sg, wg, b_g, yg, B, H, W, C, flip=flip)
+            ops.dwconv7(sp, w, b_, yp, B, H, W, C, flip=flip)
+            sync()
+            gd.check()
+            ref = _dwconv64(src.double(), w.double(), None if b_ is None else b_.double(), flip)
+            mag = _dwconv64(src.double().abs(), w.double().abs(), None if b_ is None else b_.double().abs(), flip)
+            assert finite(yg) and same(yg, yp), kc.describe_worst(yg, yp.double())
+            assert_excess(f"dwconv7 {kind} {(B, H, W, C)} flip {flip} x {xdt} -> {ydt} misaligned {misaligned}", yg, ref, mag, 50, kc.U32)
+
+
+@pytest.mark.parametrize("x16", [False, True], ids=["x_f32", "x_16"])
+@pytest.mark.parametrize("g16", [False, True], ids=["dy_f32", "dy_16"])
+@pytest.mark.parametrize("kind", ["bf16", "f16"])
+@pytest.mark.parametrize("shape", DW_SHAPES, ids=DW_IDS)
+def test_dwconv7_wgrad_guarded(shape, kind, g16, x16):
+    dwconv7_wgrad_guarded(kind, *shape, g16, x16)
+
+
+@pytest.mark.parametrize("g16,x16", [(False, False), (True, False)])
+def test_dwconv7_wgrad_guarded_misaligned_base_falls_back_from_vec(g16, x16):
+    dwconv7_wgrad_guarded("bf16", 2, 10, 7, 24, g16, x16, misaligned=True)
+
+
+def dwconv7_wgrad_guarded(kind, B, H, W, C, g16, x16, misaligned=False):
+    """scot_dwconv7_wgrad, all four dy_dt x x_dt pairs: dw += sum dy x (49 taps), db += sum dy, into an arena group that already holds values
+    (the entry point accumulates).  Sums of B H W products that meet in atomicAdd: gemm_excess with K = B H W + 1 and the prior value in the
+    magnitude; no bit-identity, rel() < 1e-5 stays beside the bound.  (The entry point fixes its tile groups at one: gridDim.z = 1 always.)"""
+    with _build(kind) as hd:
+        gd = Guards()
+        x, dy = G.rnd(B, H, W, C, dtype=hd if x16 else F32), G.rnd(B, H, W, C, seed=3, dtype=hd if g16 else F32)
+        dw0, db0 = G.rnd(C, 1, 7, 7, seed=4), G.rnd(C, seed=5)
+        if misaligned:
+            (xg, _), (dyg, _) = off_by_one(gd, x, "x (misaligned)"), off_by_one(gd, dy, "dy (misaligned)")
+        else:
+            xg, dyg = gd.op(x, name="x"), gd.op(dy, name="dy")
+        dwg, dbg = gd.group([(C, 1, 7, 7), (C,)], F32, srcs=[dw0, db0], name="dw | db")
+        ops.dwconv7_wgrad(dyg, xg, dwg, dbg, B, H, W, C)
+        sync()
+        gd.check()
+        assert finite(dwg) and finite(dbg)
+        n = B * H * W
+        ref_w = dw0.double() + _dwconv_wgrad64(dy.double(), x.double())
+        mag_w = dw0.double().abs() + _dwconv_wgrad64(dy.double().abs(), x.double().abs())
+        ref_b, mag_b = db0.double() + dy.double().sum((0, 1, 2)), db0.double().abs() + dy.double().abs().sum((0, 1, 2))
+        what = f"dwconv7_wgrad {kind} {(B, H, W, C)} dy 16-bit {g16} x 16-bit {x16} misaligned {misaligned}"
+        assert_excess(what + " dw", dwg.view(C, 49), ref_w.view(C, 49), mag_w.view(C, 49), n + 1, kc.U32)
+        assert_excess(what + " db", dbg, ref_b, mag_b, n + 1, kc.U32)
+        assert G.rel(dwg, ref_w) < 1e-5 and G.rel(dbg, ref_b) < 1e-5
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ 5 x 5 mixup
+def _conv5_wgrad64(dy64, x64):
+    B, Cc, H, W = x64.shape
+    xp = torch.nn.functional.pad(x64, (2, 2, 2, 2))
+    dw = torch.empty(Cc, Cc, 5, 5, dtype=torch.float64, device=x64.device)
+    for ki in range(5):
+        for kj in range(5):
+            dw[:, :, ki, kj] = torch.einsum("boyx,biyx->oi", dy64, xp[:, :, ki:ki + H, kj:kj + W])
+    return dw
+
+
+# (Cc, H, W, B): conv5_tiled_kernel<1..5> (133 and 131: two column tiles, the second one ragged and W % 4 != 0: the scalar column store;
+# H % 8 != 0: ragged row tiles), conv5_kernel (per pixel) at Cc = 6 and 8
+CONV5_SHAPES = [(1, 13, 133, 2), (2, 9, 10, 2), (3, 20, 131, 1), (4, 32, 32, 2), (4, 17, 136, 1), (5, 13, 10, 3), (6, 9, 9, 2), (8, 7, 13, 2)]
+
+
+@pytest.mark.parametrize("shape", CONV5_SHAPES, ids=DW_IDS)
+def test_conv5_guarded(shape):
+    conv5_guarded(*shape)
+
+
+@pytest.mark.parametrize("shape", [(4, 9, 14, 2), (2, 5, 133, 1)], ids=DW_IDS)
+def test_conv5_guarded_misaligned_base_takes_the_per_pixel_kernel(shape):
+    conv5_guarded(*shape, misaligned=True)
+
+
+def conv5_guarded(Cc, H, W, B, misaligned=False):
+    """scot_conv5 (transpose off and on) and scot_conv5_wgrad.  misaligned: `in` one element off 16-byte alignment at Cc <= 5, the alignment
+    fallback to conv5_kernel.  (c): K = 25 Cc for the products, K = B H W + 1 for the weight gradient (atomics, prior values)."""
+    gd = Guards()
+    x, w, dy = G.rnd(B, Cc, H, W), G.rnd(Cc, Cc, 5, 5, seed=1, scale=0.2), G.rnd(B, Cc, H, W, seed=2)
+    wg = gd.op(w, name="w")
+    held = {}
+    for transpose, src in ((False, x), (True, dy)):
+        sg, sp = off_by_one(gd, src, "in (misaligned)") if misaligned else (gd.op(src, name="in"), src)
+        held[transpose] = sg
+        yg, yp = gd.out((B, Cc, H, W), F32, name="out"), nan_like((B, Cc, H, W), F32)
+        ops.conv5(sg, wg, yg, B, Cc, H, W, transpose=transpose)
+        ops.conv5(sp, w, yp, B, Cc, H, W, transpose=transpose)
+        sync()
+        gd.check()
+        f = torch.nn.functional.conv_transpose2d if transpose else torch.nn.functional.conv2d
+        ref, mag = f(src.double(), w.double(), None, padding=2), f(src.double().abs(), w.double().abs(), None, padding=2)
+        assert finite(yg) and same(yg, yp), kc.describe_worst(yg, yp.double())
+        assert_excess(f"conv5 Cc {Cc} {(B, H, W)} transpose {transpose} misaligned {misaligned}", yg, ref, mag, 25 * Cc, kc.U32)
+    dw0 = G.rnd(Cc, Cc, 5, 5, seed=3)
+    dwg = gd.out((Cc, Cc, 5, 5), F32, src=dw0, name="dw")
+    ops.conv5_wgrad(held[True], held[False], dwg, B, Cc, H, W)
+    sync()
+    gd.check()
+    ref = dw0.double() + _conv5_wgrad64(dy.double(), x.double())
+    mag = dw0.double().abs() + _conv5_wgrad64(dy.double().abs(), x.double().abs())
+    assert finite(dwg)
+    assert_excess(f"conv5_wgrad Cc {Cc} {(B, H, W)}", dwg.view(Cc * Cc, 25), ref.view(Cc * Cc, 25), mag.view(Cc * Cc, 25), B * H * W + 1, kc.U32)
+    assert G.rel(dwg, ref) < 1e-5
+
+
+def test_conv5_declines_leave_the_result_untouched():
+    conv5_declines()
+
+
+def conv5_declines():
+    """Cc = 9 (scot_conv5, scot_conv5_wgrad) and a W whose two LDS strips exceed 64 KB (scot_conv5_wgrad: Cc (12 W + 32) floats; Cc = 8,
+    W = 172) return -3 on the host, before any launch, and leave the result's NaN intact."""
+    gd = Guards()
+    lib = ops.L()
+    for Cc, H, W, fwd in ((9, 4, 8, True), (8, 4, 172, False)):
+        x, w, dy = G.rnd(1, Cc, H, W), G.rnd(Cc, Cc, 5, 5, seed=1), G.rnd(1, Cc, H, W, seed=2)
+        xg, wg, dyg = gd.op(x, name="in"), gd.op(w, name="w"), gd.op(dy, name="dout")
+        out, dw = gd.out((1, Cc, H, W), F32, name="out"), gd.out((Cc, Cc, 5, 5), F32, name="dw")
+        if fwd:
+            for tr in (0, 1):
+                assert lib.scot_conv5(ops.ptr(xg), ops.ptr(wg), ops.ptr(out), 1, Cc, H, W, tr, ops.stream()) == -3
+        assert lib.scot_conv5_wgrad(ops.ptr(dyg), ops.ptr(xg), ops.ptr(dw), 1, Cc, H, W, ops.stream()) == -3
+        sync()
+        gd.check()
+        assert still_poison(out) and still_poison(dw)
+
+
+# ------------------------------------------------------------------------------------------------------- head, loss, input-gradient helpers
+EPS_LOSS = float(torch.tensor(1e-10, dtype=F32))       # the 1e-10f of loss_finish_kernel / loss_bwd_kernel as the kernels see it
+
+# p x mask x HW is the full matrix; the residual, the channel groups (a -1 channel: in no group) and `normalized` alternate over it so
+# that both settings of each meet both p and every mask form.  HW: 256 = one workgroup per plane with idle lanes of the last stride,
+# 4097 = two workgroups, the second with ONE element, 16384 = the timed problem: four workgroups per plane meeting in atomicAdd.
+HEAD_CASES = [(p, mk, HW, (i + j + k) % 2 == 0, [0, 0, -1, 1] if (i + k) % 2 == 0 else ([0, 0, 0, 0] if j == 0 else [1, 0, 2, -1]), (j + k) % 2 == 0)
+              for i, p in enumerate((1, 2)) for j, mk in enumerate(("none", "plane", "pixel")) for k, HW in enumerate((256, 4097, 16384))]
+
+
+@pytest.mark.parametrize("p,mk,HW,resid,goc,normalized", HEAD_CASES,
+                         ids=[f"p{c[0]}-mask_{c[1]}-HW{c[2]}-resid{int(c[3])}-groups{'_'.join(str(g) for g in c[4])}-norm{int(c[5])}" for c in HEAD_CASES])
+def test_head_loss_guarded(p, mk, HW, resid, goc, normalized):
+    head_loss_guarded(p, mk, HW, resid, goc, normalized)
+
+
+def head_loss_guarded(p, mk, HW, resid, goc, normalized, B=2):
+    """scot_head_finalize (labels given, and NULL: inference), scot_loss_finish, scot_loss_bwd (dloss NULL and a device scalar),
+    scot_zero_masked, scot_add_channels (dst_ch == Cc and > Cc).  mk: "none", "plane" (mask_full = 0: one byte per (b, c)), "pixel"
+    (mask_full = 1: one byte per element)."""
+    u = kc.U32
+    Cc, pv_ch = len(goc), len(goc) + 1
+    ngroups = max(goc) + 1
+    gd = Guards()
+    pred0, lab, pv = G.rnd(B, Cc, HW), G.rnd(B, Cc, HW, seed=1), G.rnd(B, pv_ch, HW, seed=2)
+    full = mk == "pixel"
+    if mk == "plane":
+        m = torch.zeros(B, Cc, dtype=torch.uint8, device=G.DEV)
+        m[:, -1] = 1
+        m[0, 0] = 1
+        mexp = m.bool().view(B, Cc, 1).expand(B, Cc, HW)
+    elif full:
+        m = (G.rnd(B, Cc, HW, seed=3) > 0.3).to(torch.uint8)
+        m[B - 1, Cc - 1, HW - 1] = 1          # the last element of all: the tail of the last workgroup
+        mexp = m.bool()
+    else:
+        m, mexp = None, torch.zeros(B, Cc, HW, dtype=torch.bool, device=G.DEV)
+    gt = torch.tensor(goc, dtype=torch.int32, device=G.DEV)
+    cnt = torch.tensor([B * goc.count(g) * HW for g in range(ngroups)], dtype=F32, device=G.DEV)
+    sums0 = G.rnd(2 * ngroups, seed=4).abs()
+    labg, pvg, mg, gg, cg = gd.op(lab, name="labels"), gd.op(pv, name="pixel_values"), gd.op(m, name="mask"), gd.op(gt, name="groups"), gd.op(cnt, name="counts")
+    predg, predp = gd.out((B, Cc, HW), F32, src=pred0, name="pred"), pred0.clone()
+    sumsg, sumsp = gd.out((2 * ngroups,), F32, src=sums0, name="sums"), sums0.clone()
+    ops.head_finalize(predg, pvg if resid else None, pv_ch, labg, mg, full, gg, sumsg, B, Cc, HW, p)
+    ops.head_finalize(predp, pv if resid else None, pv_ch, lab, m, full, gt, sumsp, B, Cc, HW, p)
+    sync()
+    gd.check()
+    # pred: v = pred + pv is ONE fp32 addition (no residual: unchanged), a masked element IS the label
+    v64 = pred0.double() + (pv[:, :Cc].double() if resid else 0.0)
+    ev = torch.where(mexp, 0.0, u * v64.abs() if resid else torch.zeros_like(v64))
+    vq = torch.where(mexp, lab.double(), v64)
+    assert finite(predg) and same(predg, predp)
+    within(predg, vq, ev, f"head_finalize pred (p {p}, mask {mk}, HW {HW}, residual {resid})")
+    assert torch.equal(predg[mexp], lab[mexp])
+    # sums[g] += sum over the group of |d|^p and |y|^p, d = fl(v - y): partial sums per lane, wave, workgroup, then atomicAdd — any order, K =
+    # the group's element count + the prior value.  The roundings INSIDE a term are not relative to it (v ~ y: d is small, v's rounding is
+    # not), so they enter as an absolute term: d carries ev (the rounding of v) and u |d| (its own); |d| passes that on; d d squares it
+    # ((2 |d| + ed) ed) and rounds once more; y y rounds once.  A masked element has d = 0 exactly.
+    lab64 = lab.double()
+    d = vq - lab64
+    ed = torch.where(mexp, 0.0, ev + u * (d.abs() + ev))
+    if p == 1:
+        t1, e1, t2, e2 = d.abs(), ed, lab64.abs(), torch.zeros_like(d)
+    else:
+        t1, e1, t2, e2 = d * d, (2 * d.abs() + ed) * ed + u * (d.abs() + ed) ** 2, lab64 * lab64, u * lab64 * lab64
+    assert finite(sumsg)
+    for g in range(ngroups):
+        sel = [c for c in range(Cc) if goc[c] == g]
+        for k, (t_, e_) in enumerate(((t1, e1), (t2, e2))):
+            s0 = sums0[2 * g + k].double()
+            assert_excess(f"head_finalize sums[{g}][{k}] (p {p}, mask {mk}, HW {HW})", sumsg[2 * g + k].view(1), (s0 + t_[:, sel].sum()).view(1),
+                          (s0.abs() + t_[:, sel].sum()).view(1), B * len(sel) * HW + 1, u, abs_extra=e_[:, sel].sum().view(1))
+    # labels = NULL (inference): pred is updated, sums are not touched
+    p2, s2 = gd.out((B, Cc, HW), F32, src=pred0, name="pred (inference)"), gd.out((2 * ngroups,), F32, src=sums0, name="sums (inference)")
+    ops.head_finalize(p2, pvg, pv_ch, None, None, False, gg, s2, B, Cc, HW, p)
+    sync()
+    gd.check()
+    vi = pred0.double() + pv[:, :Cc].double()
+    within(p2, vi, u * vi.abs(), "head_finalize without labels")
+    assert torch.equal(s2, sums0)
+    # loss = (1 / G) sum_g num_g [/ (den_g + 1e-10)] from the sums as stored (operands of this entry point).  Roundings on a term's path:
+    # num = s / c (1); normalized: den = s / c (1), + 1e-10f (1), the quotient (1); then at most G additions and the division by G (1):
+    # G + 2, normalized G + 5.  Every term is positive: the magnitude sum is the loss itself.
+    s64, c64 = sumsg.double(), cnt.double()
+    terms = s64[0::2] / c64
+    if normalized:
+        terms = terms / (s64[1::2] / c64 + EPS_LOSS)
+    loss64 = (terms.sum() / ngroups).view(1)
+    lossg = gd.out((1,), F32, name="loss")
+    ops.loss_finish(sumsg, cg, ngroups, normalized, lossg)
+    sync()
+    gd.check()
+    within(lossg, loss64, (ngroups + (5 if normalized else 2)) * u * 1.01 * loss64, f"loss_finish (G {ngroups}, normalized {normalized})")
+    # dpred = dloss * coef * (sign(diff) | 2 diff), exact zeros where masked or in no group.  Roundings of coef = dloss / (G c) [/ (s / c + 1e-10f)]:
+    # the product G c (1), the quotient (1), normalized: s / c (1), + 1e-10f (1), the second quotient (1) -> 2, normalized 5.  p = 2 adds
+    # diff = fl(pred - y) (1) and the product with coef (1; the factor 2 is exact) -> 4, normalized 7.  p = 1: the sign of an fp32
+    # subtraction is the sign of the exact difference — equality, not a tolerance.
+    goc_e = gt.long().view(1, Cc, 1).expand(B, Cc, HW)
+    live = (goc_e >= 0) & ~mexp
+    gsafe = goc_e.clamp_min(0)
+    coef = 1.0 / (ngroups * c64[gsafe])
+    if normalized:
+        coef = coef / (s64[1::2][gsafe] / c64[gsafe] + EPS_LOSS)
+    diff = predg.double() - lab64
+    nround = (2 if p == 1 else 4) + (3 if normalized else 0)
+    sums_plain = sumsg.clone()
+    for dl in (None, torch.tensor([0.37], device=G.DEV)):
+        dpg, dpp = gd.out((B, Cc, HW), F32, name="dpred"), nan_like((B, Cc, HW), F32)
+        ops.loss_bwd(predg, labg, mg, full, gg, sumsg, cg, ngroups, normalized, gd.op(dl, name="dloss"), dpg, B, Cc, HW, p)
+        ops.loss_bwd(predp, lab, m, full, gt, sums_plain, cnt, ngroups, normalized, dl, dpp, B, Cc, HW, p)
+        sync()
+        gd.check()
+        gl = 1.0 if dl is None else float(dl[0])
+        exact = torch.where(live, gl * coef * (torch.sign(diff) if p == 1 else 2.0 * diff), 0.0)
+        assert finite(dpg) and same(dpg, dpp)
+        within(dpg, exact, nround * u * 1.01 * exact.abs() + 1e-45, f"loss_bwd (p {p}, mask {mk}, HW {HW}, normalized {normalized}, dloss {dl is not None})")
+        assert bool((dpg[~live] == 0).all())
+        if p == 1:
+            assert torch.equal(torch.sign(dpg).double(), torch.where(live, torch.sign(diff), 0.0))
+    # the head's part of the input gradient: exact data movement / one fp32 addition, against torch
+    g0 = G.rnd(B, Cc, HW, seed=6)
+    if m is not None:
+        zg = gd.out((B, Cc, HW), F32, src=g0, name="g (zero_masked)")
+        ops.zero_masked(zg, mg, full, B, Cc, HW)
+        sync()
+        gd.check()
+        assert torch.equal(zg, torch.where(mexp, torch.zeros_like(g0), g0))
+    srcg = gd.op(g0, name="src")
+    for dst_ch in (Cc, Cc + 2):
+        d0 = G.rnd(B, dst_ch, HW, seed=7)
+        dg = gd.out((B, dst_ch, HW), F32, src=d0, name=f"dst ({dst_ch} channels)")
+        ops.add_channels(dg, dst_ch, srcg, B, Cc, HW)
+        sync()
+        gd.check()
+        want = d0.clone()
+        want[:, :Cc] += g0
+        assert torch.equal(dg, want)
+
+
+@pytest.mark.parametrize("B,Cc,HW", [(3, 4, 1000), (2, 5, 4097), (1, 3, 255), (4, 1, 16384)])
+def test_nchw_channel_sum_guarded(B, Cc, HW):
+    nchw_channel_sum_guarded(B, Cc, HW)
+
+
+def nchw_channel_sum_guarded(B, Cc, HW):
+    """scot_nchw_channel_sum: out[c] += sum over (b, i) — one workgroup per plane, B atomics per channel: any order, K = B HW + 1"""
+    gd = Guards()
+    x, o0 = G.rnd(B, Cc, HW), G.rnd(Cc, seed=1)
+    og = gd.out((Cc,), F32, src=o0, name="out")
+    ops.nchw_channel_sum(gd.op(x, name="x"), og, B, Cc, HW)
+    sync()
+    gd.check()
+    assert finite(og)
+    ref, mag = o0.double() + x.double().sum((0, 2)), o0.double().abs() + x.double().abs().sum((0, 2))
+    assert_excess(f"nchw_channel_sum {(B, Cc, HW)}", og, ref, mag, B * HW + 1, kc.U32)
+    assert G.rel(og, ref) < 1e-5
+
+
+# ------------------------------------------------------------------------------------------------------------------------ position-bias MLP
+# table[h][e] = 16 sigmoid(z[e][h]), z = relu(coords W0^T + b0) W2^T (512 hidden units).  z is a product and gets the product bound.  The
+# sigmoid is `16.0f / (1.0f + __expf(-z))`, and __expf is v_exp_f32 of the argument times log2(e) (clang's __clang_hip_math.h).  Neither the
+# ROCm headers nor any document shipped with them states an accuracy for that instruction, so the table gets no derived bound: it is held
+# per row (= per head) to a ROUNDING MODEL, the way attention and the conditional layer norm are — the fp64 restatement with a rounding
+# where the kernel rounds (the scaled argument, the exponential, 1 + e, the quotient; for the whole chain also the three operations of
+# a hidden unit and the stored z), MARGIN = twice the worst per-row ratio of that model evaluated in fp32 (two summation orders) to the
+# model evaluated in fp64, measured on the CPU by --measure-margins.  The table is judged twice: against the fp64 sigmoid of the kernel's
+# OWN stored z (an operand of that last step: isolates the exponential and the division), and against the exact chain with a model into
+# which nothing of the kernel enters.
+LOG2E_F32 = float(torch.tensor(1.4426950408889634, dtype=F32))         # 0x1.715476p+0
+CPB_LAYERS = [(16, 3), (16, 6), (8, 12), (4, 24), (7, 2)]              # (window, heads) of test_cpb_batched_layers
+# worst ratios measured over CPB_LAYERS + (16, 24) with the inputs of the cases below and with a six times wider z: the last step 1.11 (the
+# model's exponential is correctly rounded, fp32 libm's is not quite), the whole chain 6.81 (the model rounds z once, fp32 arithmetic sums
+# 512 products)
+MARGIN.update({"cpb_sigmoid": 2 * 1.11, "cpb_chain": 2 * 6.81})
+
+
+def _r32(x):
+    return x.to(F32).to(x.dtype)
+
+
+def _cpb_coords(ws):
+    r = torch.arange(-(ws - 1), ws, dtype=F32)
+    tab = torch.stack(torch.meshgrid(r, r, indexing="ij"), -1) / max(ws - 1, 1) * 8
+    return (torch.sign(tab) * torch.log2(tab.abs() + 1) / 3).reshape(-1, 2).to(G.DEV)
+
+
+def cpb_sigmoid_model(z, dtype=torch.float64, exact=False):
+    """16 / (1 + exp2(-z log2 e)) evaluated in `dtype` with a rounding to fp32 where cpb_fwd_kernel rounds; exact: 16 sigmoid(z) in fp64"""
+    if exact:
+        return 16.0 * torch.sigmoid(z.double())
+    zz = z.to(dtype)
+    e = _r32(torch.exp2(_r32(-zz * LOG2E_F32)))
+    return _r32(16.0 / _r32(1.0 + e)).double()
+
+
+def cpb_chain_model(coords, w0, b0, w2, dtype=torch.float64, reverse=False, exact=False):
+    """(z [TS, heads], table [heads, TS]) of the whole chain in `dtype`; roundings: the two products and two additions of a hidden unit, the
+    stored z, then cpb_sigmoid_model's"""
+    r = (lambda v: v) if exact else _r32
+    c, w0_, b0_, w2_ = (t.to(torch.float64 if exact else dtype) for t in (coords, w0, b0, w2))
+    hid = torch.relu(r(r(r(c[:, 0:1] * w0_[:, 0]) + r(c[:, 1:2] * w0_[:, 1])) + b0_))
+    z = r(hid.flip(-1) @ w2_.flip(-1).t() if reverse else hid @ w2_.t())
+    return z.double(), cpb_sigmoid_model(z, dtype, exact).t()
+
+
+def _cpb_fwd64(coords, w0, b0, w2):
+    """(pre, e_pre, hid, z) in fp64.  e_pre: a hidden unit is w0y cy + w0x cx + b0 in at most three roundings (fewer where the compiler
+    contracts), each at most u times the magnitude sum; relu passes the deviation on unchanged."""
+    c = coords.double()
+    pre = c @ w0.double().t() + b0.double()
+    e_pre = 3 * kc.U32 * (c.abs() @ w0.double().abs().t() + b0.double().abs())
+    hid = torch.relu(pre)
+    return pre, e_pre, hid, hid @ w2.double().t()
+
+
+def _cpb_check_fwd(what, coords, w0, b0, w2, zg, tg):
+    """zg [TS, heads], tg [heads, TS] as the kernels stored them"""
+    _, e_pre, hid, z64 = _cpb_fwd64(coords, w0, b0, w2)
+    aw2 = w2.double().abs().t()
+    assert finite(zg) and finite(tg)
+    # z: 512 products accumulated in fp32 (per lane, wave, workgroup: any order); the hidden units enter with their deviation as E |W2|
+    assert_excess(what + " z", zg, z64, (hid + e_pre) @ aw2, 512, kc.U32, abs_extra=e_pre @ aw2)
+    ex1, m1 = cpb_sigmoid_model(zg, exact=True).t(), cpb_sigmoid_model(zg).t()
+    r1, row1 = kc.row_model_excess(tg, ex1, m1, MARGIN["cpb_sigmoid"])
+    ex2, m2 = cpb_chain_model(coords, w0, b0, w2, exact=True)[1], cpb_chain_model(coords, w0, b0, w2)[1]
+    r2, row2 = kc.row_model_excess(tg, ex2, m2, MARGIN["cpb_chain"])
+    print(f"worst ratio {what} table: sigmoid of the stored z {r1 * MARGIN['cpb_sigmoid']:.2f} (head {row1}), whole chain {r2 * MARGIN['cpb_chain']:.2f} (head {row2})")
+    assert r1 <= 1.0, f"{what}: table head {row1} is {r1:.2f} x its allowance against the sigmoid of the stored z; {kc.describe_worst(tg, ex1)}"
+    assert r2 <= 1.0, f"{what}: table head {row2} is {r2:.2f} x its allowance against the exact chain; {kc.describe_worst(tg, ex2)}"
+
+
+def _cpb_check_bwd(what, coords, w0, b0, w2, z, dtab, prior, got):
+    """prior / got: (dw0 [512, 2], db0 [512], dw2 [heads, 512]) before and after `+=`.  z [TS, heads] is the STORED operand, dtab [heads, TS].
+    dz = dtable 16 s (1 - s), s = 1 / (1 + exp2(-z log2 e)): the deviation of the kernel's dz from the fp64 value takes the exponential as
+    a 1-ulp (= 2 u) instruction, the assumption D_CDF above makes for the same v_exp_f32 — it enters the bound only through this
+    second-order operand term.  e = exp(-z): its argument's rounding and the fp32 log2 e move it by 2 |z| u, the instruction by 2 u; s:
+    the sum and the quotient, one rounding each, and the error of e times de s / s = (1 - s); 1 - s: the error of s and one rounding;
+    dz: two more products.  dh = dz W2 (`heads` terms); dpre = dh where pre > 0 — where the fp64 pre lies within e_pre of zero the kernel may
+    decide either way, and the whole of |dh| is allowed there.  Then sums over the TS table entries + the prior value, in any order."""
+    u = kc.U32
+    TS, heads = z.shape
+    pre, e_pre, hid, _ = _cpb_fwd64(coords, w0, b0, w2)
+    z64, dt64, w264, c = z.double(), dtab.double().t(), w2.double(), coords.double()
+    sg, om = torch.sigmoid(z64), torch.sigmoid(-z64)
+    d_sg = sg * ((2 * z64.abs() + 2) * u * om + 2 * u)
+    d_om = d_sg + u * om
+    dz = dt64 * 16.0 * sg * om
+    e_dz = 1.01 * (dt64.abs() * 16.0 * (d_sg * om + sg * d_om) + 2 * u * dz.abs())
+    dh = dz @ w264
+    e_dh = 1.01 * (heads * u * (dz.abs() @ w264.abs()) + e_dz @ w264.abs())
+    livep = pre > 0
+    dpre = torch.where(livep, dh, 0.0)
+    e_dpre = torch.where(livep, e_dh, 0.0) + torch.where(pre.abs() <= e_pre, dh.abs() + e_dh, 0.0)
+    refs = (dpre.t() @ c, dpre.sum(0), dz.t() @ hid)
+    mags = (dpre.abs().t() @ c.abs(), dpre.abs().sum(0), dz.abs().t() @ (hid + e_pre))
+    extras = (e_dpre.t() @ c.abs(), e_dpre.sum(0), e_dz.t() @ (hid + e_pre) + dz.abs().t() @ e_pre)
+    for name, g0, g1, ref, mag, ex in zip(("dw0", "db0", "dw2"), prior, got, refs, mags, extras):
+        assert finite(g1)
+        assert_excess(f"{what} {name}", g1, g0.double() + ref, g0.double().abs() + mag, TS + 1, u, abs_extra=ex)
+        assert G.rel(g1.double() - g0.double(), ref) < 1e-4
+
+
+@pytest.mark.parametrize("ws,heads", [(16, 3), (8, 12), (4, 24), (7, 2)])
+def test_cpb_guarded(ws, heads):
+    cpb_guarded(ws, heads)
+
+
+def cpb_guarded(ws, heads):
+    """scot_cpb_fwd / scot_cpb_bwd (one layer): deterministic by design (a workgroup owns its hidden units' gradients, no atomics) — two
+    launches and the plain launch agree bit for bit"""
+    TS = (2 * ws - 1) ** 2
+    gd = Guards()
+    coords = _cpb_coords(ws)
+    w0, b0, w2 = G.rnd(512, 2), G.rnd(512, seed=1, scale=0.5), G.rnd(heads, 512, seed=2, scale=0.05)
+    cg, w0g, b0g, w2g = gd.op(coords, name="coords"), gd.op(w0, name="w0"), gd.op(b0, name="b0"), gd.op(w2, name="w2")
+    tg, zg = gd.out((heads, TS), F32, name="table"), gd.out((TS, heads), F32, name="z")
+    tp, zp = nan_like((heads, TS), F32), nan_like((TS, heads), F32)
+    ops.cpb_fwd(cg, w0g, b0g, w2g, tg, zg, ws, heads)
+    ops.cpb_fwd(coords, w0, b0, w2, tp, zp, ws, heads)
+    sync()
+    gd.check()
+    assert same(tg, tp) and same(zg, zp)
+    _cpb_check_fwd(f"cpb_fwd ws {ws} heads {heads}", coords, w0, b0, w2, zg, tg)
+    dtab = G.rnd(heads, TS, seed=3)
+    dtg = gd.op(dtab, name="dtable")
+    prior = (G.rnd(512, 2, seed=4, scale=0.1), G.rnd(512, seed=5, scale=0.1), G.rnd(heads, 512, seed=6, scale=0.1))
+    runs = []
+    for k in range(2):
+        gs = gd.group([(512, 2), (512,), (heads, 512)], F32, srcs=list(prior), name=f"dw0 | db0 | dw2 (launch {k})")
+        ops.cpb_bwd(cg, w0g, b0g, w2g, zg, dtg, gs[0], gs[1], gs[2], ws, heads)
+        runs.append(gs)
+    plain = [t.clone() for t in prior]
+    ops.cpb_bwd(coords, w0, b0, w2, zp, dtab, plain[0], plain[1], plain[2], ws, heads)
+    sync()
+    gd.check()
+    for a, b, c in zip(runs[0], runs[1], plain):
+        assert same(a, b) and same(a, c)
+    _cpb_check_bwd(f"cpb_bwd ws {ws} heads {heads}", coords, w0, b0, w2, zg, dtab, prior, runs[0])
+
+
+@pytest.mark.parametrize("first", [0, 1, 3])
+def test_cpb_batched_guarded(first):
+    cpb_batched_guarded(CPB_LAYERS, first)
+
+
+def cpb_batched_guarded(layers, first):
+    """scot_cpb_fwd_batched over all layers, scot_cpb_bwd_batched over layers first.. of the list.  Parameters and gradients lie the way the
+    arenas hold them: a layer's w0 | b0 | w2 back to back, a neighbour that is no CPB parameter (100 floats + padding to 64) behind every
+    layer.  The gradients hold prior values; layers in front of `first`, every neighbour and all padding must come back bit-unchanged."""
+    gd = Guards()
+    wss = sorted({w for w, _ in layers})
+    coff, cur, cl = {}, 0, []
+    for ws in wss:
+        coff[ws] = cur
+        cl.append(_cpb_coords(ws).reshape(-1))
+        cur += cl[-1].numel()
+    coords = torch.cat(cl)
+    shapes, srcs_p, srcs_g = [], [], []
+    for li, (ws, heads) in enumerate(layers):
+        shapes += [(1536 + heads * 512,), (100,)]
+        lp = torch.cat([G.rnd(1024, seed=10 * li), G.rnd(512, seed=10 * li + 1, scale=0.5), G.rnd(heads * 512, seed=10 * li + 2, scale=0.05)])
+        srcs_p += [lp, G.rnd(100, seed=10 * li + 3)]
+        srcs_g += [G.rnd(1536 + heads * 512, seed=10 * li + 4, scale=0.1), G.rnd(100, seed=10 * li + 5)]
+    pviews = gd.group(shapes, F32, srcs=srcs_p, name="parameter arena")
+    offs = [(v.data_ptr() - pviews[0].data_ptr()) // 4 for v in pviews]
+    span = offs[-1] + 100
+    desc, toff = [], 0
+    for li, (ws, heads) in enumerate(layers):
+        o = offs[2 * li]
+        desc += [o, o + 1024, o + 1536, coff[ws], ws, heads, toff, toff]
+        toff += heads * (2 * ws - 1) ** 2
+    d = torch.tensor(desc, dtype=torch.int32, device=G.DEV)
+    dtab = G.rnd(toff, seed=5)
+    cg, dg, dtg = gd.op(coords, name="coords"), gd.op(d, name="desc"), gd.op(dtab, name="dtables")
+    tabg, zg = gd.out((toff,), F32, name="tables"), gd.out((toff,), F32, name="z")
+    pplain = torch.zeros(span, device=G.DEV)
+    for v, o in zip(srcs_p, offs):
+        pplain[o:o + v.numel()] = v
+    tabp, zp = nan_like((toff,), F32), nan_like((toff,), F32)
+    max_ws, max_heads = max(w for w, _ in layers), max(h for _, h in layers)
+    ops.cpb_fwd_batched(pviews[0], dg, len(layers), max_ws, cg, tabg, zg)
+    ops.cpb_fwd_batched(pplain, d, len(layers), max_ws, coords, tabp, zp)
+    sync()
+    gd.check()
+    assert same(tabg, tabp) and same(zg, zp)
+    runs = []
+    for k in range(2):
+        gv = gd.group(shapes, F32, srcs=srcs_g, name=f"gradient arena (launch {k})")
+        assert [(v.data_ptr() - gv[0].data_ptr()) // 4 for v in gv] == offs
+        ops.cpb_bwd_batched(pviews[0], dg, first, len(layers) - first, max_ws, max_heads, cg, zg, dtg, gv[0])
+        runs.append(gv)
+    gplain = torch.zeros(span, device=G.DEV)
+    for v, o in zip(srcs_g, offs):
+        gplain[o:o + v.numel()] = v
+    ops.cpb_bwd_batched(pplain, d, first, len(layers) - first, max_ws, max_heads, coords, zp, dtab, gplain)
+    sync()
+    gd.check()
+    for i, (a, b, o) in enumerate(zip(runs[0], runs[1], offs)):
+        assert same(a, b) and same(a, gplain[o:o + a.numel()]), f"arena member {i}"
+        if i % 2 == 1 or i // 2 < first:
+            assert same(a, srcs_g[i]), f"arena member {i} lies outside the range and was changed"
+    for li, (ws, heads) in enumerate(layers):
+        ts = (2 * ws - 1) ** 2
+        lp, t0 = srcs_p[2 * li], desc[8 * li + 6]
+        w0, b0, w2 = lp[:1024].view(512, 2), lp[1024:1536], lp[1536:].view(heads, 512)
+        cs = coords[coff[ws]:coff[ws] + 2 * ts].view(ts, 2)
+        zl, tl = zg[t0:t0 + heads * ts].view(ts, heads), tabg[t0:t0 + heads * ts].view(heads, ts)
+        _cpb_check_fwd(f"cpb_fwd_batched layer {li} (ws {ws}, heads {heads})", cs, w0, b0, w2, zl, tl)
+        if li >= first:
+            g0, g1 = srcs_g[2 * li], runs[0][2 * li]
+            cut = lambda g: (g[:1024].view(512, 2), g[1024:1536], g[1536:].view(heads, 512))
+            _cpb_check_bwd(f"cpb_bwd_batched first {first} layer {li} (ws {ws}, heads {heads})", cs, w0, b0, w2, zl, dtab[t0:t0 + heads * ts].view(heads, ts),
+                           cut(g0), cut(g1))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- spectral apply
+@pytest.mark.parametrize("nimg", [1, 5])
+@pytest.mark.parametrize("s,t", [(32, 64), (64, 32), (24, 40), (128, 128)])
+def test_spectral_apply_guarded(s, t, nimg):
+    spectral_apply_guarded(s, t, nimg)
+
+
+def spectral_apply_guarded(s, t, nimg):
+    """scot_spectral_apply at kernel level: Y[b] = Pr U_r[b] - Pi U_i[b], one chain of 2 s fused multiply-adds per element: K = 2 s.
+    (24, 40): t off the 16-row / 16-column tile, clamped rows of Pr / Pi and clamped columns of U."""
+    gd = Guards()
+    U, Pr, Pi = G.rnd(nimg * s, 2 * t), G.rnd(t, s, seed=1, scale=s ** -0.5), G.rnd(t, s, seed=2, scale=s ** -0.5)
+    Yg, Yp = gd.out((nimg, t, t), F32, name="Y"), nan_like((nimg, t, t), F32)
+    ops.spectral_apply(gd.op(U, name="U"), gd.op(Pr, name="Pr"), gd.op(Pi, name="Pi"), Yg, nimg, s, t)
+    ops.spectral_apply(U, Pr, Pi, Yp, nimg, s, t)
+    sync()
+    gd.check()
+    U3 = U.double().view(nimg, s, 2 * t)
+    ref = Pr.double() @ U3[:, :, :t] - Pi.double() @ U3[:, :, t:]
+    mag = Pr.double().abs() @ U3[:, :, :t].abs() + Pi.double().abs() @ U3[:, :, t:].abs()
+    assert finite(Yg) and same(Yg, Yp)
+    assert_excess(f"spectral_apply s {s} t {t} nimg {nimg}", Yg, ref, mag, 2 * s, kc.U32)
+
+
+def test_spectral_apply_declines_s_513():
+    spectral_apply_declines()
+
+
+def spectral_apply_declines():
+    """s = 513: the two 16 x s strips of Pr and Pi exceed 64 KB of LDS — -3 from the host, nothing launched, Y untouched"""
+    gd = Guards()
+    s, t = 513, 16
+    U, Pr, Pi = G.rnd(s, 2 * t), G.rnd(t, s, seed=1), G.rnd(t, s, seed=2)
+    Y = gd.out((1, t, t), F32, name="Y")
+    rc = ops.L().scot_spectral_apply(ops.ptr(gd.op(U, name="U")), ops.ptr(gd.op(Pr, name="Pr")), ops.ptr(gd.op(Pi, name="Pi")), ops.ptr(Y), 1, s, t, ops.stream())
+    sync()
+    gd.check()
+    assert rc == -3 and still_poison(Y)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------- optimizer
+def _opt_group(gd, sizes, dtype, srcs=None, fills=None, name="arena"):
+    """an arena group with a 4096-element band (the default band is 128 rows of the widest member: 128 x 8 M elements here)"""
+    vs, g = kc.guarded_group([(s,) for s in sizes], dtype, G.DEV, srcs=srcs, fills=fills, band=kc.MIN_BAND, name=name)
+    gd.items.append(g)
+    return vs
+
+
+# (size, parameter group) of the arena's members; sizes are multiples of 8 and not of 64, so every member is followed by padding
+OPT_SMALL = [(1000, 0), (24, 1), (2056, 0), (40, 2)]
+OPT_LARGE = [(1000, 0), (8400000, 1), (24, 2), (4104, 0)]            # > 4096 x 256 x 8 elements: the grid-stride loops of both kernels iterate
+
+
+@pytest.mark.parametrize("kind", ["bf16", "f16"])
+@pytest.mark.parametrize("members", [OPT_SMALL, OPT_LARGE], ids=["small", "grid_stride"])
+def test_optimizer_guarded(members, kind):
+    optimizer_guarded(kind, members)
+
+
+def optimizer_guarded(kind, members):
+    """scot_grad_sqnorm, scot_clip_coef, scot_adamw_step, scot_optim_finish on the device.  params, grads, exp_avg, exp_avg_sq and the 16-bit
+    copy are arena groups whose padding is marked 255 in map8 and holds the poison NaN — in the gradient too, the state the lazy
+    zero-grad leaves.  Three steps: clipped (coefficient below 1, Adam's clock read from the device), unclipped (clip = NULL, the host's
+    step number), and a step whose norm is not finite, which must change nothing."""
+    import ctypes
+    u = kc.U32
+    with _build(kind) as hd:
+        lib, st = ops.L(), ops.stream()
+        gd = Guards()
+        sizes = [s for s, _ in members]
+        lr_, wd_ = [1e-2, 3e-3, 1e-3], [0.1, 0.0, 0.05]
+        lr32, wd32 = (ctypes.c_float * 3)(*lr_), (ctypes.c_float * 3)(*wd_)
+        beta1, beta2, eps = (float(torch.tensor(v, dtype=F32)) for v in (0.9, 0.999, 1e-8))
+        p0 = [G.rnd(s, seed=i) for i, s in enumerate(sizes)]
+        g0 = [G.rnd(s, seed=10 + i, scale=0.5) for i, s in enumerate(sizes)]
+        m0 = [G.rnd(s, seed=20 + i, scale=0.1) for i, s in enumerate(sizes)]
+        v0 = [G.rnd(s, seed=30 + i, scale=0.3) ** 2 for i, s in enumerate(sizes)]
+        P, Gr, M, V = (_opt_group(gd, sizes, F32, srcs=src, name=nm) for src, nm in ((p0, "params"), (g0, "grads"), (m0, "exp_avg"), (v0, "exp_avg_sq")))
+        S = _opt_group(gd, sizes, hd, fills=[-7.0] * len(sizes), name="shadow16")
+        offs = [(v.data_ptr() - P[0].data_ptr()) // 4 for v in P]
+        for grp in (Gr, M, V):
+            assert [(v.data_ptr() - grp[0].data_ptr()) // 4 for v in grp] == offs
+        assert [(v.data_ptr() - S[0].data_ptr()) // 2 for v in S] == offs
+        n = offs[-1] + sizes[-1]
+        assert n % 8 == 0 and all(o % 8 == 0 for o in offs)
+        map8 = torch.full((n // 8,), 255, dtype=torch.uint8)
+        for (s, gi), o in zip(members, offs):
+            map8[o // 8:(o + s) // 8] = gi
+        mapg = gd.op(map8.to(G.DEV), name="map8")
+        nblk = int(lib.scot_optim_blocks(n))
+        partial, clip = gd.out((nblk,), F32, name="partial"), gd.out((3,), F32, src=torch.tensor([1.0, 0.0, 0.0], device=G.DEV), name="clip")
+        state = gd.out((2,), torch.int32, src=torch.tensor([4, 0], dtype=torch.int32, device=G.DEV), name="step_state")
+        nlive = sum(sizes)
+
+        def norm_step(max_norm):
+            assert lib.scot_grad_sqnorm(ops.ptr(Gr[0]), ops.ptr(mapg), n, ops.ptr(partial), st) == 0
+            assert lib.scot_clip_coef(ops.ptr(partial), nblk, max_norm, ops.ptr(clip), st) == 0
+            sync()
+            gd.check()
+
+        def adam(clip_t, state_t, host_step):
+            assert lib.scot_adamw_step(ops.ptr(P[0]), ops.ptr(Gr[0]), ops.ptr(M[0]), ops.ptr(V[0]), ops.ptr(mapg), n, ctypes.cast(lr32, ctypes.c_void_p),
+                                       ctypes.cast(wd32, ctypes.c_void_p), 3, beta1, beta2, eps, host_step, ops.ptr(clip_t), ops.ptr(state_t), ops.ptr(S[0]), st) == 0
+            sync()
+            gd.check()          # the padding of all five arrays, bit for bit
+
+        def check_update(before, cc, t, what):
+            """p, m, v per element against the update of csrc/optim.hip's header comment in fp64 on the operands as the kernel receives them
+            (lr, wd, the betas and eps as fp32 values, cc = the stored clip coefficient).  Roundings, each at most u times the magnitude sum
+            of the expression it sits in:
+              m' = m + (g cc - m)(1 - b1): g cc, the difference, 1 - b1, the product, the sum — 5, on |m| + (|g cc| + |m|)(1 - b1);
+              v' = b2 v + (1 - b2)(g cc)^2: g cc (twice), 1 - b2, two products, b2 v, the sum — 7, all terms positive: on v';
+              p' = p (1 - lr wd) - (lr / bc1) m' / (sqrt(v') rsqrt_bc2 + eps): lr wd, the difference, the product — 3 on |p (1 - lr wd)|;
+                   denominator: half of v's 7, the square root, rsqrt_bc2 (rounded to fp32), the product, + eps — 7.5, positive terms;
+                   bc1 (rounded to fp32), lr / bc1, the quotient, the product — 4; together 11.5, taken as 12, on |update|; the carried
+                   error of m' times step / denominator; the final subtraction — 1 on |p'|."""
+            bc1, rbc2 = 1.0 - beta1 ** t, 1.0 / math.sqrt(1.0 - beta2 ** t)
+            for i, ((s, gi), o) in enumerate(zip(members, offs)):
+                pb, mb, vb = (x[i].double() for x in before)
+                lr, wd = float(lr32[gi]), float(wd32[gi])
+                gj = Gr[i].double() * cc
+                m1 = mb + (gj - mb) * (1.0 - beta1)
+                e_m = 5 * u * 1.01 * (mb.abs() + (gj.abs() + mb.abs()) * (1.0 - beta1))
+                v1 = beta2 * vb + (1.0 - beta2) * gj * gj
+                den = torch.sqrt(v1) * rbc2 + eps
+                step = lr / bc1
+                upd = step * m1 / den
+                pd = pb * (1.0 - lr * wd)
+                p1 = pd - upd
+                e_p = 1.01 * (u * p1.abs() + 3 * u * pd.abs() + 12 * u * upd.abs() + step * e_m / den)
+                assert finite(P[i]) and finite(M[i]) and finite(V[i])
+                within(M[i], m1, e_m + 1e-45, f"{what}: exp_avg of member {i}")
+                within(V[i], v1, 7 * u * 1.01 * v1 + 1e-45, f"{what}: exp_avg_sq of member {i}")
+                within(P[i], p1, e_p + 1e-45, f"{what}: params of member {i}")
+                assert torch.equal(S[i], P[i].to(hd)), f"{what}: shadow16 of member {i} is not the round-to-nearest conversion of the stored p"
+
+        snapshot = lambda: tuple([t.clone() for t in grp] for grp in (P, M, V))
+        # ---- step 1: clipped.  norm^2 = sum of nlive squares: per-workgroup partial sums in fp32 in any order (K = n), their sum in fp64, the
+        # square root halves the relative error, the conversion to fp32 rounds once
+        g64 = torch.cat([g.double() for g in Gr])
+        exact_norm = g64.norm()
+        norm_step(float(exact_norm) * 0.5)
+        c = clip.double()
+        assert finite(clip) and float(c[2]) == 0.0
+        within(clip[1:2], exact_norm.view(1), ((nlive + 1) * u / 2 * 1.01 + u) * exact_norm.view(1), "gradient norm (any order, K = n)")
+        print(f"gradient norm: relative error {abs(float(c[1]) - float(exact_norm)) / float(exact_norm):.2e} of an allowance of {(nlive + 1) * u / 2 + u:.2e}")
+        # coef = max_norm / (norm + 1e-6f) from the STORED norm: the sum and the quotient, 2 roundings
+        mx = float(torch.tensor(float(exact_norm) * 0.5, dtype=F32))
+        coef = mx / (float(c[1]) + float(torch.tensor(1e-6, dtype=F32)))
+        assert coef < 1.0 and abs(float(c[0]) - coef) <= 2 * u * 1.01 * coef
+        before = snapshot()
+        adam(clip, state, 99)                   # the host's step number is ignored when the device clock is given: t = step_state[0] + 1 = 5
+        check_update(before, float(c[0]), 5, "clipped step")
+        assert lib.scot_optim_finish(ops.ptr(state), ops.ptr(clip), None, 2.0, 0.5, 0, float(2 ** 20), st) == 0
+        sync()
+        gd.check()
+        assert state.tolist() == [5, 0]
+        # ---- step 2: clip = NULL, step_state = NULL: no clipping, no skip, the bias corrections of the host's step number
+        before = snapshot()
+        adam(None, None, 3)
+        check_update(before, 1.0, 3, "unclipped step")
+        # ---- step 3: one Inf in a live gradient: the norm is not finite, and the step changes NOTHING — p, m, v, the 16-bit copy, bit for bit
+        Gr[1][sizes[1] // 2] = float("inf")
+        norm_step(1.0)
+        assert float(clip[2]) == 1.0
+        before, sbefore = snapshot(), [t.clone() for t in S]
+        adam(clip, state, 1)
+        for grp, old in zip((P, M, V), before):
+            for a, b in zip(grp, old):
+                assert same(a, b)
+        for a, b in zip(S, sbefore):
+            assert same(a, b)
+        assert lib.scot_optim_finish(ops.ptr(state), ops.ptr(clip), None, 2.0, 0.5, 0, float(2 ** 20), st) == 0
+        sync()
+        gd.check()
+        assert state.tolist() == [5, 1]
+
+
 def measure_margins():
     """prints, per class, the worst per-row ratio of the fp32-evaluated rounding model (two summation orders) to the fp64-evaluated one"""
     G.DEV = "cpu"
     worst = {}
+    for li, (ws, heads) in enumerate(CPB_LAYERS + [(16, 24)]):
+        coords = _cpb_coords(ws)
+        for src, w2s in (("cpb_guarded", 0.05), ("cpb_batched_guarded", 0.05), ("a wider z", 0.3)):
+            if src == "cpb_guarded":
+                w0, b0, w2 = G.rnd(512, 2), G.rnd(512, seed=1, scale=0.5), G.rnd(heads, 512, seed=2, scale=w2s)
+            else:
+                w0, b0 = G.rnd(1024, seed=10 * li).view(512, 2), G.rnd(512, seed=10 * li + 1, scale=0.5)
+                w2 = G.rnd(heads * 512, seed=10 * li + 2, scale=w2s).view(heads, 512)
+            zex, tex = cpb_chain_model(coords, w0, b0, w2, exact=True)
+            z64, t64 = cpb_chain_model(coords, w0, b0, w2)
+            zs = _r32(zex)          # a stored z: the last step's operand
+            s_ex, s64, s32 = cpb_sigmoid_model(zs, exact=True).t(), cpb_sigmoid_model(zs).t(), cpb_sigmoid_model(zs, dtype=F32).t()
+            r, row = kc.row_model_excess(s32, s_ex, s64, 1.0)
+            worst["cpb_sigmoid"] = max(worst.get("cpb_sigmoid", 0.0), r)
+            print(f"cpb sigmoid ws {ws} heads {heads} inputs of {src}: ratio {r:.2f} (head {row})")
+            for rev in (False, True):
+                t32 = cpb_chain_model(coords, w0, b0, w2, dtype=F32, reverse=rev)[1]
+                r, row = kc.row_model_excess(t32, tex, t64, 1.0)
+                worst["cpb_chain"] = max(worst.get("cpb_chain", 0.0), r)
+                print(f"cpb chain ws {ws} heads {heads} inputs of {src} reversed {rev}: ratio {r:.2f} (head {row})")
     for klass, half in (("16", torch.bfloat16), ("16", torch.float16), ("x3", None), ("f32", None)):
         cdt = half if klass == "16" else F32
         for case in G.ATTN_CASES:
