@@ -113,7 +113,8 @@ int scot_get_use_tr(void);
  * fp32 operands split into hi + lo bf16 on the way into LDS, hi·hi + hi·lo + lo·hi on the bf16 MFMA (~2^-17 operand error).
  * Dense contraction with fused prologue/epilogue.  a_gelu/b_gelu: apply erf-GELU to the operand while loading
  * (Swinv2Intermediate's activation, HF:545-548).  Epilogue: (+bias[n]) (*colscale[n]) (*gelu'(aux[m,n])) (+resid[m,n]);
- * accumulate=1: C += result (required for TN, which splits K and uses fp32 atomics). */
+ * accumulate=1: C += result (required for TN: the weight-gradient form, which may split K over workgroups — see `workspace` below).
+ * The call is offered to four kernel families in a fixed order (csrc/gemm.hip); the first that covers it runs it. */
 int scot_gemm(int layout, int compute, int M, int N, int K,
               const void* A, int a_dt, int lda, int a_gelu,
               const void* B, int b_dt, int ldb, int b_gelu,
@@ -127,14 +128,16 @@ int scot_gemm(int layout, int compute, int M, int N, int K,
  * kernels (csrc/gemm_fast.hip) sum the fp32 values before the store rounds them, the generic kernel (csrc/gemm.hip) what it stored;
  * TN: Σ_k A[k][m] — i.e. the bias gradient when A = dY, taken from the dY tile already staged in LDS.
  * workspace (optional, 32-byte aligned device scratch owned by the caller): TN splits K over workgroups and writes
- * partial tiles there, reduced by one extra pass; without it TN falls back to fp32 atomics.
+ * partial tiles there, reduced by one extra pass (bit-reproducible).  With fewer bytes than scot_gemm_workspace_bytes answers it
+ * splits less; with none it runs unsplit, every tile added into C by its one owner.  fp32 atomics are the fallback only for a
+ * workspace that is not 32-byte aligned, and what the generic kernel (operands gemm_fast declines) always uses for TN.
  * C2 (optional, NT/NN): the epilogue stores gelu(v) to C and gelu'(v) to C2 (same dtype/ld; C2 == C: gelu(v) only, the
  * inference form) — the fc1 form, so that no
  * later kernel re-evaluates erf; aux_mul=1: `aux` already holds that derivative and is multiplied in as is. */
 
 /* Scratch the call above would use with these dimensions (dense operands in the compute mode's operand type; TN: fp32 result with
  * accumulate = 1): bytes of split-K partial tiles, 0 when it runs unsplit.  scot_gemm adapts to a SMALLER workspace (fewer K slices,
- * fp32 atomics without any) — this is the size at which nothing is clipped.  SURVEY.md §8(b): `scot_<op>_workspace_bytes(dims…)`. */
+ * none without any) — this is the size at which nothing is clipped.  SURVEY.md §8(b): `scot_<op>_workspace_bytes(dims…)`. */
 size_t scot_gemm_workspace_bytes(int layout, int compute, int M, int N, int K);
 
 /* NT products with 16-bit operands, M % 128 == 0, N % 128 == 0, K % 64 == 0 whose grid of 128 x 128 output tiles still gives every CU

@@ -4,20 +4,28 @@
 //   layout NT : C[M,N] = A[M,K] · B[N,K]^T     forward of every nn.Linear (weights are [out,in]; reference
 //                                              HF:545-561, HF:389-410, model.py:709,747,760)
 //   layout NN : C[M,N] = A[M,K] · B[K,N]       dgrad (dX = dY · W) and the ConvTranspose2d of model.py:616-621
-//   layout TN : C[M,N] += A[K,M]^T · B[K,N]    wgrad (dW = dY^T · X), split over K with fp32 atomics
+//   layout TN : C[M,N] += A[K,M]^T · B[K,N]    wgrad (dW = dY^T · X), split over K
 //
-// One workgroup = 256 threads = 4 waves (2x2) computing a BMxBN tile with 16x16 MFMA fragments, BK = 32.
+// scot_gemm (bottom of this file) validates the arguments once, writes them into a GemmCall (gemm_call.h) and offers it to four kernel
+// families, most specialised first; the first that does not answer SCOT_ERR_UNSUPPORTED has run the call:
+//   1. gemm_panel  weights resident in LDS, no barriers: 16-bit NT / NN with K = 96 / 192 and M >= 4096 (stages 0 / 1), where a tiled
+//                  kernel has 2-3 K-tiles per workgroup and is latency-bound.  First, because every shape it takes would also fit 3.
+//   2. gemm_wide   128 x 128 tiles: 16-bit NT with M, N multiples of 128 where that grid still fills the chip (policy in gemm_wide.hip).
+//                  Before 3, which takes all of these shapes at twice the L2 -> LDS bytes per flop.
+//   3. gemm_fast   the production tiled kernel (64 x 64, 64 x 96, 96 x 96; table and policy in gemm_fast.hip): operands in the compute
+//                  type, 16-byte aligned, leading dimensions whole vectors, no GELU on load; TN splits K through the workspace.
+//   4. the kernel below: any alignment and leading dimension, mixed operand dtypes, GELU on load, column sums by a second launch
+//                  (scot_colsum), TN with fp32 atomics.  What it declines is what scot_gemm answers.
+// Each family keeps its own decline conditions (the panel wants an aligned bias, the wide kernel does not; only 4 converts operands);
+// one that accepts a call launches it or reports the launch error: there is no other route.
+//
+// The kernel of this file: one workgroup = 256 threads = 4 waves (2x2) computing a BMxBN tile with 16x16 MFMA fragments, BK = 32.
 // Operands are staged HBM → registers (coalesced 16-byte loads along the contiguous dimension, optional GELU,
 // convert to the compute type) → LDS.  An operand whose contiguous dimension is NOT the contraction (B of NN,
 // both of TN) stays in its source orientation in LDS and is read with the transposing fragment read
 // (ds_read_b64_tr_b16 for bf16) — no transposed copies of activations or weights are ever written to HBM.
-// Epilogue (fused): + bias[n], * colscale[n], * gelu'(aux[m,n]), + resid[m,n], store f32/bf16 or atomicAdd.
-#include "common.h"
-#include <stdlib.h>
-
-#define LAYOUT_NT 0
-#define LAYOUT_NN 1
-#define LAYOUT_TN 2
+// Epilogue (fused): + bias[n], * colscale[n], * gelu'(aux[m,n]), + resid[m,n], store f32/bf16 or atomicAdd (TN).
+#include "gemm_call.h"
 
 struct GemmArgs {
   const void* A; const void* B; void* C;
@@ -204,26 +212,46 @@ static int launch_layout(const GemmArgs& a, int layout, int nsplit, hipStream_t 
   return scot_check_launch();
 }
 
-template <typename CT>
-static int launch_tile(const GemmArgs& a, int layout, int nsplit, hipStream_t s) {
-  return launch_layout<CT, 64, 64>(a, layout, nsplit, s);  // generic fallback: one tile shape (the fast path has the rest)
-}
-
-extern int g_scot_use_tr;
-int scot_gemm_fast(int layout, int compute, int M, int N, int K, const void* A, int a_dt, int lda, int a_gelu,
-                   const void* B, int b_dt, int ldb, int b_gelu, void* C, int c_dt, int ldc, const float* bias,
-                   const float* colscale, const void* aux, int aux_dt, int ldaux, const void* resid, int res_dt, int ldres,
-                   int accumulate, float* colsum_out, void* workspace, size_t ws_bytes, int aux_mul, void* C2, hipStream_t stream);
-// gemm_wide.hip: 128 x 128 tiles for the NT products whose grid keeps every CU busy with them (policy there)
-int scot_gemm_wide(int layout, int compute, int M, int N, int K, const void* A, int a_dt, int lda, int a_gelu,
-                   const void* B, int b_dt, int ldb, int b_gelu, void* C, int c_dt, int ldc, const float* bias,
-                   const float* colscale, const void* aux, int aux_dt, int ldaux, const void* resid, int res_dt, int ldres,
-                   int accumulate, float* colsum_out, int aux_mul, void* C2, hipStream_t stream);
 extern "C" int scot_colsum(const void* x, int x_dt, const void* y, int y_dt, float* out, int M, int N, int ld, hipStream_t s);
-int scot_gemm_panel(int layout, int compute, int M, int N, int K, const void* A, int a_dt, int lda, int a_gelu, const void* B,
-                    int b_dt, int ldb, int b_gelu, void* C, int c_dt, int ldc, const float* bias, const float* colscale,
-                    const void* aux, int aux_dt, int ldaux, const void* resid, int res_dt, int ldres, int accumulate,
-                    float* colsum_out, int aux_mul, void* C2, hipStream_t stream);
+
+// The last candidate: one 64 x 64 tile shape, any alignment, mixed operand dtypes, GELU on load.
+int scot_gemm_generic(const GemmCall& c, hipStream_t stream) {
+  if (c.C2 && c.layout == LAYOUT_TN) return SCOT_ERR_UNSUPPORTED;
+  GemmArgs a;
+  a.A = c.A; a.B = c.B; a.C = c.C; a.bias = c.bias; a.colscale = c.colscale; a.aux = c.aux; a.resid = c.resid;
+  a.M = c.M; a.N = c.N; a.K = c.K; a.lda = c.lda; a.ldb = c.ldb; a.ldc = c.ldc; a.ldaux = c.ldaux; a.ldres = c.ldres;
+  a.a_dt = c.a_dt; a.b_dt = c.b_dt; a.c_dt = c.c_dt; a.aux_dt = c.aux_dt; a.res_dt = c.res_dt;
+  a.a_gelu = c.a_gelu; a.b_gelu = c.b_gelu; a.aux_gelu_grad = c.aux != nullptr; a.use_tr = g_scot_use_tr;
+  a.C2 = c.C2; a.aux_mul = c.aux_mul;
+  a.a_vec = aligned16(c.A) && c.lda % 8 == 0;
+  a.b_vec = aligned16(c.B) && c.ldb % 8 == 0;
+  int nsplit = 1;
+  a.atomic = 0;
+  a.ksplit = ((c.K + 31) / 32) * 32;
+  if (c.layout == LAYOUT_TN) {
+    // wgrad: tiny output, huge K (= tokens) → split K so that >= ~512 workgroups exist; fp32 atomics into C.
+    if (c.c_dt != SCOT_F32) return SCOT_ERR_DTYPE;
+    const long tiles = (long)((c.M + 127) / 128) * ((c.N + 95) / 96);
+    long want = (768 + tiles - 1) / tiles;
+    long maxsplit = (c.K + 255) / 256;
+    nsplit = (int)(want < 1 ? 1 : (want > maxsplit ? maxsplit : want));
+    int per = (c.K + nsplit - 1) / nsplit;
+    per = ((per + 31) / 32) * 32;
+    a.ksplit = per;
+    nsplit = (c.K + per - 1) / per;
+    a.atomic = 1;
+    if (!c.accumulate) return SCOT_ERR_UNSUPPORTED;  // caller zeroes C (gradient arena semantics: +=)
+  } else {
+    const GemmResid r = gemm_resid(c);
+    a.resid = r.p; a.res_dt = r.dt; a.ldres = r.ld;
+  }
+  int rc = c.compute == SCOT_BF16 ? launch_layout<bf16_t, 64, 64>(a, c.layout, nsplit, stream) : launch_layout<float, 64, 64>(a, c.layout, nsplit, stream);
+  if (rc == SCOT_OK && c.colsum_out) {   // this kernel has no column sums of its own: a second launch
+    if (c.layout == LAYOUT_TN) rc = scot_colsum(c.A, c.a_dt, nullptr, 0, c.colsum_out, c.K, c.M, c.lda, stream);  // Σ_k A[k][m]
+    else rc = scot_colsum(c.C, c.c_dt, nullptr, 0, c.colsum_out, c.M, c.N, c.ldc, stream);
+  }
+  return rc;
+}
 
 extern "C" int scot_gemm(int layout, int compute, int M, int N, int K,
                          const void* A, int a_dt, int lda, int a_gelu,
@@ -238,55 +266,13 @@ extern "C" int scot_gemm(int layout, int compute, int M, int N, int K,
   if (layout < 0 || layout > 2 || compute < 0 || compute > SCOT_BF16X3) return SCOT_ERR_UNSUPPORTED;
   if ((a_dt | b_dt | c_dt) & ~1) return SCOT_ERR_DTYPE;
   if (compute == SCOT_BF16X3 && (a_dt != SCOT_F32 || b_dt != SCOT_F32)) return SCOT_ERR_DTYPE;   // bf16x3 splits fp32 operands
-  {
-    const int rc = scot_gemm_panel(layout, compute, M, N, K, A, a_dt, lda, a_gelu, B, b_dt, ldb, b_gelu, C, c_dt, ldc, bias, colscale,
-                                   aux, aux_dt, ldaux, resid, res_dt, ldres, accumulate, colsum_out, aux_mul, C2, stream);
-    if (rc != SCOT_ERR_UNSUPPORTED) return rc;
-  }
-  {
-    const int rc = scot_gemm_wide(layout, compute, M, N, K, A, a_dt, lda, a_gelu, B, b_dt, ldb, b_gelu, C, c_dt, ldc, bias, colscale,
-                                  aux, aux_dt, ldaux, resid, res_dt, ldres, accumulate, colsum_out, aux_mul, C2, stream);
-    if (rc != SCOT_ERR_UNSUPPORTED) return rc;
-  }
-  {
-    const int rc = scot_gemm_fast(layout, compute, M, N, K, A, a_dt, lda, a_gelu, B, b_dt, ldb, b_gelu, C, c_dt, ldc, bias, colscale,
-                                  aux, aux_dt, ldaux, resid, res_dt, ldres, accumulate, colsum_out, workspace, ws_bytes, aux_mul, C2, stream);
-    if (rc != SCOT_ERR_UNSUPPORTED) return rc;
-  }
-  GemmArgs a;
-  a.A = A; a.B = B; a.C = C; a.bias = bias; a.colscale = colscale; a.aux = aux; a.resid = resid;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldaux = ldaux; a.ldres = ldres;
-  a.a_dt = a_dt; a.b_dt = b_dt; a.c_dt = c_dt; a.aux_dt = aux_dt; a.res_dt = res_dt;
-  a.a_gelu = a_gelu; a.b_gelu = b_gelu; a.aux_gelu_grad = aux != nullptr; a.use_tr = g_scot_use_tr;
-  a.C2 = C2; a.aux_mul = aux_mul;
-  if (C2 && layout == LAYOUT_TN) return SCOT_ERR_UNSUPPORTED;
-  a.a_vec = (((uintptr_t)A & 15) == 0) && (lda % 8 == 0);
-  a.b_vec = (((uintptr_t)B & 15) == 0) && (ldb % 8 == 0);
-  int nsplit = 1;
-  a.atomic = 0;
-  a.ksplit = ((K + 31) / 32) * 32;
-  if (layout == LAYOUT_TN) {
-    // wgrad: tiny output, huge K (= tokens) → split K so that >= ~512 workgroups exist; fp32 atomics into C.
-    if (c_dt != SCOT_F32) return SCOT_ERR_DTYPE;
-    const long tiles = (long)((M + 127) / 128) * ((N + 95) / 96);
-    long want = (768 + tiles - 1) / tiles;
-    long maxsplit = (K + 255) / 256;
-    nsplit = (int)(want < 1 ? 1 : (want > maxsplit ? maxsplit : want));
-    int per = (K + nsplit - 1) / nsplit;
-    per = ((per + 31) / 32) * 32;
-    a.ksplit = per;
-    nsplit = (K + per - 1) / per;
-    a.atomic = 1;
-    if (!accumulate) return SCOT_ERR_UNSUPPORTED;  // caller zeroes C (gradient arena semantics: +=)
-  } else if (accumulate) {
-    // C += result  ≡ residual = C itself
-    if (resid != nullptr) return SCOT_ERR_UNSUPPORTED;
-    a.resid = C; a.res_dt = c_dt; a.ldres = ldc;
-  }
-  int rc = compute == SCOT_BF16 ? launch_tile<bf16_t>(a, layout, nsplit, stream) : launch_tile<float>(a, layout, nsplit, stream);
-  if (rc == SCOT_OK && colsum_out) {
-    if (layout == LAYOUT_TN) rc = scot_colsum(A, a_dt, nullptr, 0, colsum_out, K, M, lda, stream);  // Σ_k A[k][m]
-    else rc = scot_colsum(C, c_dt, nullptr, 0, colsum_out, M, N, ldc, stream);
-  }
+  // C += result is "the residual is C" in every NT / NN kernel (gemm_resid), so a call that names a residual as well has no kernel
+  if (layout != LAYOUT_TN && accumulate && resid != nullptr) return SCOT_ERR_UNSUPPORTED;
+  const GemmCall c = {layout, compute, M, N, K, A, a_dt, lda, a_gelu, B, b_dt, ldb, b_gelu, C, c_dt, ldc, bias, colscale,
+                      aux, aux_dt, ldaux, resid, res_dt, ldres, accumulate, colsum_out, workspace, ws_bytes, aux_mul, C2};
+  int rc = scot_gemm_panel(c, stream);
+  if (rc == SCOT_ERR_UNSUPPORTED) rc = scot_gemm_wide(c, stream);
+  if (rc == SCOT_ERR_UNSUPPORTED) rc = scot_gemm_fast(c, stream);
+  if (rc == SCOT_ERR_UNSUPPORTED) rc = scot_gemm_generic(c, stream);
   return rc;
 }

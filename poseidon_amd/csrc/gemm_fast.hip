@@ -8,16 +8,11 @@
 //   * LDS double buffering, one barrier per K-tile (BK = 64 bf16 / 32 f32);
 //   * the accumulator tile goes through LDS so that the fused epilogue (bias, column scale, gelu'(aux), residual,
 //     column sums for bias gradients) reads and writes 16/32-byte row segments — fully coalesced;
-//   * wgrad (TN): split-K with fp32 atomics, and the bias gradient (column sums of dY) comes for free from the
+//   * wgrad (TN): split-K through partial tiles in the caller's workspace + one reduce pass, and the bias gradient (column sums of dY) comes for free from the
 //     dY tile that is already in LDS.
 #include <type_traits>
-#include "common.h"
+#include "gemm_call.h"
 #include "wgrad_group.h"   // the grouped weight-gradient argument block, and how a gradient meets the arena (grad_commit8)
-#include <stdlib.h>
-
-#define LAYOUT_NT 0
-#define LAYOUT_NN 1
-#define LAYOUT_TN 2
 
 struct FastArgs {
   const void* A; const void* B; void* C;
@@ -607,82 +602,77 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
-template <typename CT, int BM, int BN, int WM, int WN, int BKT = FT<CT>::BK, int NSET = 2>
-static int flaunch_layout(const FastArgs& a, int layout, int nsplit, hipStream_t s) {
+// ------------------------------------------------------------------------------------------------------------------------
+// Host side: the tile table, the policy that picks a row, the plan (tile, K split, how the result is committed) and the launch.
+// One row per tile the policy can name; launch[layout] is NULL where no policy line picks the row for that layout: only what the
+// table holds is instantiated.  bk is the K-tile of the row's kernels (bf16x3 and fp32 rows: 32).
+struct FastTile {
+  int bm, bn, bk, nset, x3, glds;
+  int (*launch[3])(const FastArgs& a, int nsplit, hipStream_t s);   // by layout
+};
+template <typename CT, int BM, int BN, int BKT, int NSET, int LAYOUT, bool X3, int GLDS>
+static int flaunch(const FastArgs& a, int nsplit, hipStream_t s) {
   dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, nsplit), block(256);
-  switch (layout) {
-    case LAYOUT_NT: hipLaunchKernelGGL((gemm_fast_kernel<CT, BM, BN, WM, WN, BKT, NSET, LAYOUT_NT>), grid, block, 0, s, a); break;
-    case LAYOUT_NN: hipLaunchKernelGGL((gemm_fast_kernel<CT, BM, BN, WM, WN, BKT, NSET, LAYOUT_NN>), grid, block, 0, s, a); break;
-    case LAYOUT_TN: hipLaunchKernelGGL((gemm_fast_kernel<CT, BM, BN, WM, WN, BKT, NSET, LAYOUT_TN>), grid, block, 0, s, a); break;
-    default: return SCOT_ERR_UNSUPPORTED;
-  }
+  hipLaunchKernelGGL((gemm_fast_kernel<CT, BM, BN, 2, 2, BKT, NSET, LAYOUT, X3, 1, GLDS>), grid, block, 0, s, a);
   return scot_check_launch();
 }
-// tile ids: 0 = 64x64 (2x2 waves), 1 = 128x96 (4x1), 2 = 64x96 (2x2), 3 = 128x128 (2x2), 4 = 96x96 (2x2)... bf16 only beyond 0/3
-template <typename CT> static int flaunch_tile(int tile, const FastArgs& a, int layout, int nsplit, hipStream_t s);
-template <> int flaunch_tile<bf16_t>(int tile, const FastArgs& a, int layout, int nsplit, hipStream_t s) {
-  switch (tile) {
-    case 1: return flaunch_layout<bf16_t, 128, 96, 4, 1>(a, layout, nsplit, s);
-    case 2: return flaunch_layout<bf16_t, 64, 96, 2, 2>(a, layout, nsplit, s);
-    case 3: return flaunch_layout<bf16_t, 128, 128, 2, 2>(a, layout, nsplit, s);
-    case 4: return flaunch_layout<bf16_t, 96, 96, 2, 2, 64>(a, layout, nsplit, s);
-    case 5: return flaunch_layout<bf16_t, 96, 96, 2, 2, 32>(a, layout, nsplit, s);
-    case 6: return flaunch_layout<bf16_t, 64, 64, 2, 2, 32>(a, layout, nsplit, s);
-    case 7: return flaunch_layout<bf16_t, 128, 96, 4, 1, 32>(a, layout, nsplit, s);
-    case 8: return flaunch_layout<bf16_t, 64, 64, 2, 2, 64, 4>(a, layout, nsplit, s);   // deep pipeline (small grids)
-    case 9: {                                                                           // three direct-to-LDS stages (NT only)
-      if (layout != LAYOUT_NT) return flaunch_layout<bf16_t, 64, 64, 2, 2>(a, layout, nsplit, s);
-      dim3 grid((a.N + 63) / 64, (a.M + 63) / 64, nsplit), block(256);
-      hipLaunchKernelGGL((gemm_fast_kernel<bf16_t, 64, 64, 2, 2, 64, 2, LAYOUT_NT, false, 1, 3>), grid, block, 0, s, a);
-      return scot_check_launch();
-    }
-    default: return flaunch_layout<bf16_t, 64, 64, 2, 2>(a, layout, nsplit, s);
-  }
+// a row and, for the layouts it is marked for, its kernels: the one place a tile's parameters are written
+template <typename CT, int BM, int BN, int BKT, int NSET, bool X3, int GLDS, bool NT, bool NN, bool TN>
+constexpr FastTile fast_row() {
+  FastTile t = {BM, BN, BKT, NSET, X3, GLDS, {nullptr, nullptr, nullptr}};
+  if constexpr (NT) t.launch[LAYOUT_NT] = flaunch<CT, BM, BN, BKT, NSET, LAYOUT_NT, X3, GLDS>;
+  if constexpr (NN) t.launch[LAYOUT_NN] = flaunch<CT, BM, BN, BKT, NSET, LAYOUT_NN, X3, GLDS>;
+  if constexpr (TN) t.launch[LAYOUT_TN] = flaunch<CT, BM, BN, BKT, NSET, LAYOUT_TN, X3, GLDS>;
+  return t;
 }
-template <> int flaunch_tile<float>(int tile, const FastArgs& a, int layout, int nsplit, hipStream_t s) {
-  return tile == 3 ? flaunch_layout<float, 128, 128, 2, 2>(a, layout, nsplit, s) : flaunch_layout<float, 64, 64, 2, 2>(a, layout, nsplit, s);
+enum { T_64x64, T_64x64_GLDS, T_64x64_BK32, T_64x64_DEEP, T_64x96, T_96x96, T_F32_64x64, T_X3_64x64, T_X3_64x96, T_X3_96x96 };
+static const FastTile kFastTiles[] = {
+    //                           BM  BN  BK NSET  X3  GLDS   NT     NN     TN
+    /* T_64x64      */ fast_row<bf16_t, 64, 64, 64, 2, false, 0, true, true, true>(),
+    /* T_64x64_GLDS */ fast_row<bf16_t, 64, 64, 64, 2, false, 3, true, false, false>(),   // K loop through three direct-to-LDS stages
+    /* T_64x64_BK32 */ fast_row<bf16_t, 64, 64, 32, 2, false, 0, true, true, false>(),
+    /* T_64x64_DEEP */ fast_row<bf16_t, 64, 64, 64, 4, false, 0, true, true, false>(),    // four register sets of loads in flight
+    /* T_64x96      */ fast_row<bf16_t, 64, 96, 64, 2, false, 0, true, true, true>(),
+    /* T_96x96      */ fast_row<bf16_t, 96, 96, 64, 2, false, 0, false, false, true>(),
+    /* T_F32_64x64  */ fast_row<float, 64, 64, 32, 2, false, 0, true, true, true>(),
+    /* T_X3_64x64   */ fast_row<bf16_t, 64, 64, 32, 2, true, 0, true, true, true>(),
+    /* T_X3_64x96   */ fast_row<bf16_t, 64, 96, 32, 2, true, 0, true, true, true>(),
+    /* T_X3_96x96   */ fast_row<bf16_t, 96, 96, 32, 2, true, 0, false, false, true>(),
+};
+
+// Tile policy (DESIGN.md §3 has the measurements; the SCOT_GEMM_TILE* / SCOT_GEMM_GLDS overrides of rounds 1-4 are retired, their sweeps
+// are under profiles/round2..4 — micro_deep_gemm_tiles_r3.txt, gemm_lds_ring_depth_r4.txt — and in profiles/HISTORY.md).  One selector
+// per layout group; each returns only rows that have a kernel for its layouts.  fp32 has the 64 x 64 tile only, bf16x3 (fp32 operands in
+// memory, BK = 32) has 64 x 64, 64 x 96 and, for TN, 96 x 96.
+static const FastTile& pick_tile_tn(int compute, int M, int N, int K) {
+  const bool x3 = compute == SCOT_BF16X3;
+  if (compute != SCOT_BF16 && !x3) return kFastTiles[T_F32_64x64];
+  // wgrad with a long token dimension (stages 0/1): 96x96 (cold-cache sweep: 25.6 vs 38.5 us at stage 1); with K <= 4096
+  // (stages 2/3) the 64x64 grid is already large enough to run unsplit (no partials, no reduce pass): 22 vs 27 us
+  if (M % 96 == 0 && N % 96 == 0 && K >= 8192) return kFastTiles[x3 ? T_X3_96x96 : T_96x96];
+  if (N == 96) return kFastTiles[x3 ? T_X3_64x96 : T_64x96];   // one 64x96 column tile: the A operand streams once (64x64 would read it twice)
+  return kFastTiles[x3 ? T_X3_64x64 : T_64x64];
 }
-// bf16x3 (fp32 operands in memory): 64x64, 64x96 and 96x96 tiles, BK = 32
-template <int BM, int BN>
-static int flaunch_x3_layout(const FastArgs& a, int layout, int nsplit, hipStream_t s) {
-  dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, nsplit), block(256);
-  switch (layout) {
-    case LAYOUT_NT: hipLaunchKernelGGL((gemm_fast_kernel<bf16_t, BM, BN, 2, 2, 32, 2, LAYOUT_NT, true>), grid, block, 0, s, a); break;
-    case LAYOUT_NN: hipLaunchKernelGGL((gemm_fast_kernel<bf16_t, BM, BN, 2, 2, 32, 2, LAYOUT_NN, true>), grid, block, 0, s, a); break;
-    case LAYOUT_TN: hipLaunchKernelGGL((gemm_fast_kernel<bf16_t, BM, BN, 2, 2, 32, 2, LAYOUT_TN, true>), grid, block, 0, s, a); break;
-    default: return SCOT_ERR_UNSUPPORTED;
-  }
-  return scot_check_launch();
-}
-static int flaunch_x3(int tile, const FastArgs& a, int layout, int nsplit, hipStream_t s) {
-  switch (tile) {
-    case 2: return flaunch_x3_layout<64, 96>(a, layout, nsplit, s);
-    case 4: return flaunch_x3_layout<96, 96>(a, layout, nsplit, s);
-    default: return flaunch_x3_layout<64, 64>(a, layout, nsplit, s);
-  }
-}
-static void tile_dims(int tile, int& bm, int& bn, int& bkt) {
-  bkt = 64;
-  switch (tile) {
-    case 1: bm = 128; bn = 96; break;
-    case 2: bm = 64; bn = 96; break;
-    case 3: bm = 128; bn = 128; break;
-    case 4: bm = 96; bn = 96; break;
-    case 5: bm = 96; bn = 96; bkt = 32; break;
-    case 6: bm = 64; bn = 64; bkt = 32; break;
-    case 8: case 9: bm = 64; bn = 64; break;
-    case 7: bm = 128; bn = 96; bkt = 32; break;
-    default: bm = 64; bn = 64;
-  }
+static const FastTile& pick_tile_nt_nn(int layout, int compute, int M, int N, int K) {
+  if (compute == SCOT_BF16X3) return kFastTiles[N == 96 ? T_X3_64x96 : T_X3_64x64];
+  if (compute != SCOT_BF16) return kFastTiles[T_F32_64x64];
+  if (N == 96) return kFastTiles[T_64x96];                     // (as for TN)
+  if (K <= 128) return kFastTiles[T_64x64_BK32];               // K = 96: BK = 32 halves LDS -> more workgroups/CU (-12 %)
+  // whole K-tiles in NT: three LDS stages filled by global_load_lds (alone -6 % at K = 384, -14..21 % from K = 1536; in step 19.60 -> 19.45 ms;
+  // two stages lose to the register pipeline in step, four to three; register-staged instead: +0.15 ms per step, round 3)
+  if (layout == LAYOUT_NT && K % 64 == 0) return kFastTiles[T_64x64_GLDS];
+  // small grids walking a long contraction (stage 3: fc2 forward, fc1 / qkv data gradients — 192 workgroups x 36-48 K-tiles): four
+  // register sets of loads in flight instead of two (26.4 -> 22.4 / 24.5 -> 21.7 us alone, in step 19.76 -> 19.59 ms; shorter
+  // contractions lose to the padded trip count)
+  if (K >= 36 * 64 && (long)((M + 63) / 64) * ((N + 63) / 64) <= 512) return kFastTiles[T_64x64_DEEP];
+  return kFastTiles[T_64x64];
 }
 
-extern int g_scot_use_tr;
-
-// K slices of the fp32-result NT products (see gemm_fast_impl).  g_nt_splitk: 0 = the policy below, -1 = never, S > 0 = S slices for
+// K slices of the fp32-result NT products (see plan_fast).  g_nt_splitk: 0 = the policy below, -1 = never, S > 0 = S slices for
 // every eligible call (sweeps: tools/bench_deep_gemm.py).
 static int g_nt_splitk = 0, g_nt_splitk_zeroed = 1;
 extern "C" void scot_gemm_splitk_config(int slices, int zeroed_too) { g_nt_splitk = slices; g_nt_splitk_zeroed = zeroed_too; }
-static int nt_splitk_policy(int M, int N, int K, int accumulate, long tiles, long nkt) {
+static int nt_splitk_policy(int accumulate, long nkt) {
   if (g_nt_splitk < 0) return 1;
   if (!accumulate && !g_nt_splitk_zeroed) return 1;
   if (g_nt_splitk > 0) return nkt >= 2 * g_nt_splitk ? g_nt_splitk : 1;
@@ -693,150 +683,133 @@ static int nt_splitk_policy(int M, int N, int K, int accumulate, long tiles, lon
   // ... and in the step those two launches change nothing (profiles/round6/splitk_in_step_ab.txt: 18.70 / 18.55 ms without, 18.54 / 18.53 with,
   // `gemm NT` family 7.00-7.10 ms either way), so the policy splits NOTHING: results stay bit-reproducible run to run, the mechanism stays
   // for scot_gemm_splitk_config (tests, tools/bench_splitk.py).
-  (void)M; (void)N; (void)K; (void)tiles;
   return 1;
 }
 
-// Returns SCOT_ERR_UNSUPPORTED when the call does not qualify (the caller then uses the generic kernel).
+// K elements per slice for `nsplit` slices: whole K-tiles; with `xcd8` the length is grown (up to 64 K-tiles) until the slice count is a
+// multiple of 8, so that the XCD remap applies (one token chunk per XCD at a time), and stays as it was when no such length exists.
+static int kslice_len(int K, long nsplit, int bk, bool xcd8) {
+  const int per0 = (int)(((K + nsplit - 1) / nsplit + bk - 1) / bk * bk);
+  if (!xcd8) return per0;
+  int per = per0;
+  for (int tries = 0; tries < 64 && ((K + per - 1) / per) % 8 != 0; ++tries) per += bk;
+  return ((K + per - 1) / per) % 8 != 0 ? per0 : per;
+}
 
-// `query` != NULL: plan only — the tile / split policy below runs against an unlimited workspace and *query receives the bytes it
-// would use; nothing is launched (scot_gemm_workspace_bytes: one policy, two readers).
-static int gemm_fast_impl(int layout, int compute, int M, int N, int K, const void* A, int a_dt, int lda, int a_gelu,
-                          const void* B, int b_dt, int ldb, int b_gelu, void* C, int c_dt, int ldc, const float* bias,
-                          const float* colscale, const void* aux, int aux_dt, int ldaux, const void* resid, int res_dt, int ldres,
-                          int accumulate, float* colsum_out, void* workspace, size_t ws_bytes, int aux_mul, void* C2, hipStream_t stream,
-                          size_t* query) {
-  if (query) { *query = 0; workspace = (void*)(uintptr_t)64; ws_bytes = (size_t)1 << 60; }
-  const bool x3 = compute == SCOT_BF16X3;
-  const int want = compute == SCOT_BF16 ? SCOT_BF16 : SCOT_F32;   // bf16x3 keeps its operands in fp32
-  const int epc = compute == SCOT_BF16 ? 8 : 4;
-  if (a_dt != want || b_dt != want) return SCOT_ERR_UNSUPPORTED;
-  if ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)aux | (uintptr_t)resid) & 15) != 0) return SCOT_ERR_UNSUPPORTED;
-  if (lda % epc || ldb % epc || ldc % 8 || (aux && ldaux % 8) || (resid && ldres % 8) || N % 8 || K % epc) return SCOT_ERR_UNSUPPORTED;
-  if (layout == LAYOUT_TN ? (M % epc || M < epc) : false) return SCOT_ERR_UNSUPPORTED;
-  if (layout != LAYOUT_NT && N < epc) return SCOT_ERR_UNSUPPORTED;
-  if (K < epc || M < 1) return SCOT_ERR_UNSUPPORTED;
-  FastArgs a;
-  a.A = A; a.B = B; a.C = C; a.bias = bias; a.colscale = colscale; a.aux = aux; a.resid = resid; a.colsum_out = colsum_out;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldaux = ldaux; a.ldres = ldres;
-  a.c_dt = c_dt; a.aux_dt = aux_dt; a.res_dt = res_dt; a.a_gelu = a_gelu; a.b_gelu = b_gelu; a.aux_gelu_grad = aux != nullptr;
-  a.use_tr = g_scot_use_tr; a.atomic = 0; a.ws = nullptr; a.ws_plane = 0; a.rmw = 0; a.C2 = C2; a.aux_mul = aux_mul;
-  a.out_mode = 0; a.out_scale = nullptr;
-  a.xcd_swizzle = 1;
-  a.pre = 1;         // epilogue operands requested before the K loop (round 4: dgrad fc2 · gelu' 43.2 -> 36.6 us in step)
-  if (C2 && ((((uintptr_t)C2) & 15) != 0 || layout == LAYOUT_TN)) return SCOT_ERR_UNSUPPORTED;
-  if (a_gelu || b_gelu) return SCOT_ERR_UNSUPPORTED;   // GELU-on-load is the general kernel's (the engine stores GELU(u) from the fc1 epilogue)
-  int bk = compute == SCOT_BF16 ? 64 : 32;
-  int nsplit = 1;
-  // tile choice: the per-layout policy below (the SCOT_GEMM_TILE* / SCOT_GEMM_GLDS overrides of rounds 1-4 are retired: their sweeps are
-  // under profiles/round2..4 — micro_deep_gemm_tiles_r3.txt, gemm_lds_ring_depth_r4.txt — and in profiles/HISTORY.md)
-  int tile = -1;
-  const int glds = 1;   // direct-to-LDS K loop for the NT products it covers (register-staged: +0.15 ms per step, round 3)
-  const int deep = 1;   // four-register-set pipeline for the long-K small-grid products (round 3, in step: 19.76 -> 19.59 ms)
-  if (tile < 0) {
-    tile = 0;   // policy (see DESIGN.md §3 for the measurements behind it)
-    // wgrad with a long token dimension (stages 0/1): 96x96 (cold-cache sweep: 25.6 vs 38.5 us at stage 1); with K <= 4096
-    // (stages 2/3) the 64x64 grid is already large enough to run unsplit (no partials, no reduce pass): 22 vs 27 us
-    if ((compute == SCOT_BF16 || x3) && layout == LAYOUT_TN && M % 96 == 0 && N % 96 == 0 && K >= 8192) tile = 4;
-    else if ((compute == SCOT_BF16 || x3) && N == 96) tile = 2;   // one 64x96 column tile: the A operand streams once (64x64 would read it twice)
-    else if (compute == SCOT_BF16 && layout != LAYOUT_TN && K <= 128) tile = 6;   // K = 96: BK = 32 halves LDS -> more workgroups/CU (-12 %)
-    // small grids walking a long contraction (stage 3: fc2 forward, fc1 / qkv data gradients — 192 workgroups x 36-48 K-tiles): four
-    // register sets of loads in flight instead of two (26.4 -> 22.4 / 24.5 -> 21.7 us alone; shorter contractions lose to the padded trip count)
-    else if (compute == SCOT_BF16 && layout != LAYOUT_TN && K >= 36 * 64 && (long)((M + 63) / 64) * ((N + 63) / 64) <= 512 && deep) tile = 8;
-  }
-  // 64 x 64-tile NT products whose K is whole tiles: three LDS stages filled by global_load_lds (alone -6 % at K = 384, -14..21 % from
-  // K = 1536; in step 19.60 -> 19.45 ms; two stages lose to the register pipeline in step, four to three)
-  if (glds && compute == SCOT_BF16 && layout == LAYOUT_NT && (tile == 0 || tile == 8) && K % 64 == 0 && lda % 8 == 0 && ldb % 8 == 0) tile = 9;
-  if (x3 && tile != 2 && tile != 4) tile = 0;                     // bf16x3 instantiates 64x64, 64x96, 96x96
-  if (compute == SCOT_F32 && tile != 0 && tile != 3) tile = 0;    // fp32 instantiates 64x64 and 128x128 only
-  int bm, bn, bkt;
-  tile_dims(tile, bm, bn, bkt);
-  if (compute == SCOT_BF16) bk = bkt;
-  a.ksplit = ((K + bk - 1) / bk) * bk;
-  const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+constexpr size_t WS_UNLIMITED = (size_t)1 << 60;   // what the workspace queries offer
+// How a workgroup's accumulator tile meets C — EPILOGUE: NT / NN unsplit, the fused epilogue stores it; OWNER: TN unsplit, C += acc by the
+// tile's only owner; WORKSPACE: TN split, partial tiles + one reduce pass with zl lanes per 8 results; ATOMIC: split without a usable
+// workspace (TN) or by scot_gemm_splitk_config (NT), fp32 atomics into C.
+enum { COMMIT_EPILOGUE, COMMIT_OWNER, COMMIT_WORKSPACE, COMMIT_ATOMIC };
+struct FastPlan {
+  const FastTile* tile;
+  int nsplit, ksplit, commit, zl;   // K slices; K elements per slice
+  size_t ws_used;                   // bytes of workspace the launch writes
+};
+
+// Everything scot_gemm_fast decides from shapes, dtypes and flags (no pointer is read, only whether an operand is present), given
+// `ws_offer` bytes of workspace, `ws_aligned` telling whether it is on a 32-byte boundary.  false: the call is not this kernel's.
+static bool plan_fast(const GemmCall& c, size_t ws_offer, bool ws_aligned, FastPlan& p) {
+  const int want = c.compute == SCOT_BF16 ? SCOT_BF16 : SCOT_F32;   // bf16x3 keeps its operands in fp32
+  const int epc = c.compute == SCOT_BF16 ? 8 : 4;
+  const int M = c.M, N = c.N, K = c.K;
+  if (c.a_dt != want || c.b_dt != want) return false;
+  if (!ld_vectors(c, epc) || N % 8 || K % epc) return false;
+  if (c.layout == LAYOUT_TN && (M % epc || M < epc)) return false;
+  if (c.layout != LAYOUT_NT && N < epc) return false;
+  if (K < epc || M < 1) return false;
+  if (c.C2 && c.layout == LAYOUT_TN) return false;
+  if (c.a_gelu || c.b_gelu) return false;   // GELU-on-load is the general kernel's (the engine stores GELU(u) from the fc1 epilogue)
+  const FastTile& t = c.layout == LAYOUT_TN ? pick_tile_tn(c.compute, M, N, K) : pick_tile_nt_nn(c.layout, c.compute, M, N, K);
+  const int bk = t.bk;
+  p.tile = &t;
+  p.nsplit = 1; p.ksplit = ((K + bk - 1) / bk) * bk;
+  p.zl = 1; p.ws_used = 0;
+  const long tiles = (long)((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn);
   const long nkt = (K + bk - 1) / bk;
-  if (layout == LAYOUT_TN) {
+  if (c.layout == LAYOUT_TN) {
     // wgrad: small output, contraction over all tokens.  Split K so that ~512 workgroups stream the operands; each split
     // writes a partial tile into the workspace and ONE reduce pass adds them into the gradient (12.6 M fp32 atomics per
     // call in the first version of this kernel cost 300 us; the partials cost < 20 MB of traffic).
-    if (c_dt != SCOT_F32 || !accumulate) return SCOT_ERR_UNSUPPORTED;
+    if (c.c_dt != SCOT_F32 || !c.accumulate) return false;
     const int tn_wgs = 512;
-    long wantsplit = (tn_wgs + tiles - 1) / tiles;
+    const long wantsplit = (tn_wgs + tiles - 1) / tiles;
     const long maxsplit = (K + 8 * bk - 1) / (8 * bk);       // >= 8 K-tiles per workgroup
-    long wsmax = workspace ? (long)(ws_bytes / ((size_t)M * N * sizeof(float))) : 1;
-    nsplit = (int)(wantsplit < 1 ? 1 : (wantsplit > maxsplit ? maxsplit : wantsplit));
+    const long wsmax = (long)(ws_offer / ((size_t)M * N * sizeof(float)));
+    int nsplit = (int)(wantsplit < 1 ? 1 : (wantsplit > maxsplit ? maxsplit : wantsplit));
     if (nsplit > wsmax) nsplit = (int)(wsmax < 1 ? 1 : wsmax);
-    int per = (K + nsplit - 1) / nsplit;
-    per = ((per + bk - 1) / bk) * bk;
-    if (nsplit >= 8) {   // make the split count a multiple of 8 so that the XCD remap applies (one token chunk per XCD at a time)
-      for (int tries = 0; tries < 64 && ((K + per - 1) / per) % 8 != 0; ++tries) per += bk;
-      if (((K + per - 1) / per) % 8 != 0) per = ((((K + nsplit - 1) / nsplit) + bk - 1) / bk) * bk;
+    p.ksplit = kslice_len(K, nsplit, bk, nsplit >= 8);
+    p.nsplit = (K + p.ksplit - 1) / p.ksplit;
+    p.commit = p.nsplit == 1 ? COMMIT_OWNER : ws_aligned ? COMMIT_WORKSPACE : COMMIT_ATOMIC;
+    if (p.commit == COMMIT_WORKSPACE) {
+      p.zl = p.nsplit >= 64 ? 32 : p.nsplit >= 16 ? 8 : p.nsplit >= 4 ? 4 : 1;
+      p.ws_used = (size_t)p.nsplit * M * N * sizeof(float);
     }
-    a.ksplit = per;
-    nsplit = (K + per - 1) / per;
-    if (nsplit == 1) a.rmw = 1;
-    else if (workspace && (((uintptr_t)workspace & 31) == 0)) a.ws = (float*)workspace;
-    else a.atomic = 1;
   } else {
     // K slices with fp32 atomics into the result (round 6; the hand-off-free form of split-K: partial planes + an epilogue pass lost in
     // rounds 2-3, an in-launch ticket + combine in round 5).  Only where the result is fp32 and the epilogue is bias-only: the deep stages'
-    // fc2 forward (result zeroed here first) and the fc1 / qkv data gradients, which accumulate into the fp32 residual-stream gradient.
-    int S = 1;
-    const bool split_ok = compute == SCOT_BF16 && layout == LAYOUT_NT && c_dt == SCOT_F32 && !aux && !C2 && !colsum_out && !colscale &&
-                          resid == nullptr && (accumulate || ldc == N) && (tile == 9 || tile == 8 || tile == 0);
-    if (split_ok) S = nt_splitk_policy(M, N, K, accumulate, tiles, nkt);
+    // fc2 forward (result zeroed by the launcher first) and the fc1 / qkv data gradients, which accumulate into the fp32 residual-stream gradient.
+    const bool split_ok = c.compute == SCOT_BF16 && c.layout == LAYOUT_NT && c.c_dt == SCOT_F32 && !c.aux && !c.C2 && !c.colsum_out && !c.colscale &&
+                          c.resid == nullptr && (c.accumulate || c.ldc == N) && t.bm == 64 && t.bn == 64 && t.bk == 64;
+    const int S = split_ok ? nt_splitk_policy(c.accumulate, nkt) : 1;
     if (S > 1) {
       const long per = (nkt + S - 1) / S;
-      a.ksplit = (int)(per * bk);
-      nsplit = (int)((nkt + per - 1) / per);
+      p.ksplit = (int)(per * bk);
+      p.nsplit = (int)((nkt + per - 1) / per);
     }
-    if (nsplit > 1) {
-      a.atomic = 1;
-      if (!accumulate && !query && hipMemsetAsync(C, 0, (size_t)M * N * sizeof(float), stream) != hipSuccess) return SCOT_ERR_LAUNCH;
-    } else if (accumulate) {
-      if (resid != nullptr) return SCOT_ERR_UNSUPPORTED;
-      a.resid = C; a.res_dt = c_dt; a.ldres = ldc;
-    }
+    p.commit = p.nsplit > 1 ? COMMIT_ATOMIC : COMMIT_EPILOGUE;
   }
-  if (query) {
-    *query = a.ws ? (size_t)nsplit * M * N * sizeof(float) : 0;
-    return SCOT_OK;
-  }
-  int rc = x3 ? flaunch_x3(tile, a, layout, nsplit, stream)
-              : compute == SCOT_BF16 ? flaunch_tile<bf16_t>(tile, a, layout, nsplit, stream) : flaunch_tile<float>(tile, a, layout, nsplit, stream);
+  return true;
+}
+
+// Returns SCOT_ERR_UNSUPPORTED when the call does not qualify (scot_gemm then uses the generic kernel).
+int scot_gemm_fast(const GemmCall& c, hipStream_t stream) {
+  if (!aligned16(c.A, c.B, c.C, c.aux, c.resid, c.C2)) return SCOT_ERR_UNSUPPORTED;
+  FastPlan p;
+  if (!plan_fast(c, c.workspace ? c.ws_bytes : 0, c.workspace && ((uintptr_t)c.workspace & 31) == 0, p)) return SCOT_ERR_UNSUPPORTED;
+  // (the unsplit NT / NN epilogue is the one place that reads a residual: `accumulate` there means C itself)
+  const GemmResid r = p.commit == COMMIT_EPILOGUE ? gemm_resid(c) : GemmResid{c.resid, c.res_dt, c.ldres};
+  FastArgs a;
+  a.A = c.A; a.B = c.B; a.C = c.C; a.bias = c.bias; a.colscale = c.colscale; a.aux = c.aux; a.resid = r.p; a.colsum_out = c.colsum_out;
+  a.M = c.M; a.N = c.N; a.K = c.K; a.lda = c.lda; a.ldb = c.ldb; a.ldc = c.ldc; a.ldaux = c.ldaux; a.ldres = r.ld;
+  a.c_dt = c.c_dt; a.aux_dt = c.aux_dt; a.res_dt = r.dt; a.a_gelu = c.a_gelu; a.b_gelu = c.b_gelu; a.aux_gelu_grad = c.aux != nullptr;
+  a.use_tr = g_scot_use_tr; a.C2 = c.C2; a.aux_mul = c.aux_mul;
+  a.out_mode = 0; a.out_scale = nullptr;
+  a.xcd_swizzle = 1;
+  a.pre = 1;         // epilogue operands requested before the K loop (round 4: dgrad fc2 · gelu' 43.2 -> 36.6 us in step)
+  a.ksplit = p.ksplit;
+  a.atomic = p.commit == COMMIT_ATOMIC;
+  a.rmw = p.commit == COMMIT_OWNER;
+  a.ws = p.commit == COMMIT_WORKSPACE ? (float*)c.workspace : nullptr; a.ws_plane = 0;
+  if (a.atomic && c.layout != LAYOUT_TN && !c.accumulate &&
+      hipMemsetAsync(c.C, 0, (size_t)c.M * c.N * sizeof(float), stream) != hipSuccess) return SCOT_ERR_LAUNCH;
+  if (!p.tile->launch[c.layout]) return SCOT_ERR_LAUNCH;   // a policy line named a row outside its layouts: a bug to fix there, never a reroute
+  int rc = p.tile->launch[c.layout](a, p.nsplit, stream);
   if (rc == SCOT_OK && a.ws) {
-    const size_t n8 = (size_t)M * N / 8;
-    const int zl = (nsplit >= 64 && layout == LAYOUT_TN) ? 32 : nsplit >= 16 ? 8 : nsplit >= 4 ? 4 : 1;
-    size_t blocks = (n8 * zl + 255) / 256; if (blocks > 4096) blocks = 4096;
+    const size_t n8 = (size_t)c.M * c.N / 8;
+    size_t blocks = (n8 * p.zl + 255) / 256; if (blocks > 4096) blocks = 4096;
     const dim3 g((unsigned)blocks), b(256);
-    if (zl == 32) hipLaunchKernelGGL(splitk_reduce_kernel<32>, g, b, 0, stream, a.ws, (float*)C, M, N, ldc, nsplit);      // (only TN products split K)
-    else if (zl == 8) hipLaunchKernelGGL(splitk_reduce_kernel<8>, g, b, 0, stream, a.ws, (float*)C, M, N, ldc, nsplit);
-    else if (zl == 4) hipLaunchKernelGGL(splitk_reduce_kernel<4>, g, b, 0, stream, a.ws, (float*)C, M, N, ldc, nsplit);
-    else hipLaunchKernelGGL(splitk_reduce_kernel<1>, g, b, 0, stream, a.ws, (float*)C, M, N, ldc, nsplit);
+    if (p.zl == 32) hipLaunchKernelGGL(splitk_reduce_kernel<32>, g, b, 0, stream, a.ws, (float*)c.C, c.M, c.N, c.ldc, p.nsplit);
+    else if (p.zl == 8) hipLaunchKernelGGL(splitk_reduce_kernel<8>, g, b, 0, stream, a.ws, (float*)c.C, c.M, c.N, c.ldc, p.nsplit);
+    else if (p.zl == 4) hipLaunchKernelGGL(splitk_reduce_kernel<4>, g, b, 0, stream, a.ws, (float*)c.C, c.M, c.N, c.ldc, p.nsplit);
+    else hipLaunchKernelGGL(splitk_reduce_kernel<1>, g, b, 0, stream, a.ws, (float*)c.C, c.M, c.N, c.ldc, p.nsplit);
     rc = scot_check_launch();
   }
   return rc;
 }
 
-
-int scot_gemm_fast(int layout, int compute, int M, int N, int K, const void* A, int a_dt, int lda, int a_gelu,
-                   const void* B, int b_dt, int ldb, int b_gelu, void* C, int c_dt, int ldc, const float* bias,
-                   const float* colscale, const void* aux, int aux_dt, int ldaux, const void* resid, int res_dt, int ldres,
-                   int accumulate, float* colsum_out, void* workspace, size_t ws_bytes, int aux_mul, void* C2, hipStream_t stream) {
-  return gemm_fast_impl(layout, compute, M, N, K, A, a_dt, lda, a_gelu, B, b_dt, ldb, b_gelu, C, c_dt, ldc, bias, colscale, aux, aux_dt,
-                        ldaux, resid, res_dt, ldres, accumulate, colsum_out, workspace, ws_bytes, aux_mul, C2, stream, nullptr);
-}
-
 // include/scot_hip.h: scot_gemm_workspace_bytes — dense operands (leading dimensions = row lengths) in the compute mode's
 // operand type, fp32 result for TN (accumulate) / 16-bit otherwise; 0 = the call would not touch the workspace.
 extern "C" size_t scot_gemm_workspace_bytes(int layout, int compute, int M, int N, int K) {
+  if (layout < 0 || layout > 2) return 0;
   const int dt = compute == SCOT_BF16 ? SCOT_BF16 : SCOT_F32;
-  const int lda = layout == LAYOUT_TN ? M : K, ldb = layout == LAYOUT_NT ? K : N;
-  void* al = (void*)(uintptr_t)64;
-  size_t q = 0;
-  const int rc = gemm_fast_impl(layout, compute, M, N, K, al, dt, lda, 0, al, dt, ldb, 0, al, layout == LAYOUT_TN ? SCOT_F32 : dt, N, nullptr,
-                                nullptr, nullptr, 0, 0, nullptr, 0, 0, layout == LAYOUT_TN ? 1 : 0, nullptr, nullptr, 0, 0, nullptr, nullptr, &q);
-  return rc == SCOT_OK ? q : 0;
+  GemmCall c = {};
+  c.layout = layout; c.compute = compute; c.M = M; c.N = N; c.K = K;
+  c.a_dt = c.b_dt = dt; c.lda = layout == LAYOUT_TN ? M : K; c.ldb = layout == LAYOUT_NT ? K : N;
+  c.c_dt = layout == LAYOUT_TN ? SCOT_F32 : dt; c.ldc = N;
+  c.accumulate = layout == LAYOUT_TN;
+  FastPlan p;
+  return plan_fast(c, WS_UNLIMITED, true, p) ? p.ws_used : 0;
 }
 
 // C_i[m][n] += Σ_z ws[z·plane + ws_off_i + m·N_i + n] for every problem of the group (one launch)
@@ -864,14 +837,21 @@ static int launch_wgrad_group(const WgradGroupArgs& g, hipStream_t s) {
   return scot_check_launch();
 }
 
-int scot_wgrad_group_wide_launch(const WgradGroupArgs& g, int variant, hipStream_t s);      // wgrad_wide.hip
-int scot_gemm_wide_mode(int* variant);                                                       // gemm_wide.hip
-// include/scot_hip.h: scot_wgrad_group.  dY_i: [K, M_i] (16-bit operands), X_i: [K, N_i], dW_i: [M_i, N_i] fp32 (+=),
-// dbias_i: [M_i] fp32 (+= column sums of dY_i) or NULL.  All leading dimensions = the row lengths (dense).
-static int wgrad_group_impl(int compute, int n, int K, const void* const* dY, const void* const* X, float* const* dW,
-                            float* const* dbias, const int* Ms, const int* Ns, void* workspace, size_t ws_bytes,
-                            const int* modes, const float* grad_scale, hipStream_t stream, size_t* query) {
-  if (query) { *query = 0; workspace = (void*)(uintptr_t)64; ws_bytes = (size_t)1 << 60; }
+// which kernel runs a group: 64 x 64 with four waves, or eight (two K groups per workgroup); 96 x 96; wgrad_wide.hip's 128 x 128 (`wide`)
+enum { GROUP_64x64, GROUP_64x64_KG2, GROUP_96x96, GROUP_WIDE };
+struct WgradGroupPlan {
+  int kernel, wide;
+  int tiles, nsplit, ksplit, zl;
+  size_t plane, ws_used;           // floats per K-slice plane of the workspace (Σ M_i N_i); bytes the launch writes
+  int tiles_n[SCOT_WGRAD_GROUP_MAX], tile0[SCOT_WGRAD_GROUP_MAX];
+  unsigned ws_off[SCOT_WGRAD_GROUP_MAX];
+};
+
+// Everything scot_wgrad_group decides from the shapes and flags, given `ws_offer` bytes of workspace (`ws_aligned`: on a 32-byte
+// boundary).  `unaligned` has bit i set when an operand of problem i is off a 16-byte boundary (0 from the workspace query).
+// Returns SCOT_OK or the code scot_wgrad_group answers.
+static int plan_wgrad_group(int compute, int n, int K, const int* Ms, const int* Ns, const int* modes, unsigned unaligned, size_t ws_offer,
+                            bool ws_aligned, WgradGroupPlan& p) {
   if (n <= 0 || n > SCOT_WGRAD_GROUP_MAX || K <= 0) return SCOT_ERR_SHAPE;
   if (compute != SCOT_BF16) return SCOT_ERR_UNSUPPORTED;     // fp32 / split modes use scot_gemm per problem
   if (K % 8) return SCOT_ERR_UNSUPPORTED;
@@ -879,16 +859,15 @@ static int wgrad_group_impl(int compute, int n, int K, const void* const* dY, co
   for (int i = 0; i < n; ++i) {
     if (Ms[i] <= 0 || Ns[i] <= 0) return SCOT_ERR_SHAPE;
     if (Ms[i] % 8 || Ns[i] % 8) return SCOT_ERR_UNSUPPORTED;
-    if (!query && (((uintptr_t)dY[i] | (uintptr_t)X[i] | (uintptr_t)dW[i]) & 15) != 0) return SCOT_ERR_UNSUPPORTED;
+    if (unaligned >> i & 1) return SCOT_ERR_UNSUPPORTED;
     all96 = all96 && Ms[i] % 96 == 0 && Ns[i] % 96 == 0;
   }
   // 128 x 128 tiles (wgrad_wide.hip) for groups of 128-multiples: eight waves, two LDS stages (two workgroups per CU) — unsplit from 256 tiles,
   // below that, from 8192 tokens, with K cut so that ~860 workgroups exist (>= 8 K-tiles each).  profiles/round5/wgrad_wide_sweep_r5.txt, us per launch,
   // 64 x 64 grouped kernel -> this: Poseidon-B stage 3 57.0 -> 42.8, stage 2 (108 tiles) 58.6 -> 54.4; Poseidon-L 299.8 -> 210.1,
   // 393.5 -> 267.2, 433.7 -> 293.9 (four waves or four stages lose everywhere: 243.9 / 347.5 at L's stage 3)
-  int wide = -1, wide_split = 1;
+  int wide = -1, wide_split = 1, forced = 0;
   {
-    int forced = 0;
     const int mode = scot_gemm_wide_mode(&forced);
     bool all128 = K % 64 == 0;
     long t128 = 0;
@@ -911,81 +890,82 @@ static int wgrad_group_impl(int compute, int n, int K, const void* const* dY, co
   // tile policy of the single-problem path: 96x96 for the long-K gradients of the token-heavy stages, 64x64 otherwise
   const bool t96 = wide < 0 && all96 && K >= 8192;
   const int bm = wide >= 0 ? 128 : (t96 ? 96 : 64), bn = bm, bk = 64;
-  WgradGroupArgs g;
-  g.n = n; g.K = K; g.use_tr = g_scot_use_tr;
-  int tiles = 0;
-  size_t plane = 0;
+  p.wide = wide;
+  p.tiles = 0; p.plane = 0;
   for (int i = 0; i < n; ++i) {
-    WgradProblem& p = g.p[i];
-    p.A = query ? nullptr : dY[i]; p.B = query ? nullptr : X[i]; p.C = query ? nullptr : dW[i]; p.colsum = (dbias && !query) ? dbias[i] : nullptr;
-    p.M = Ms[i]; p.N = Ns[i]; p.lda = Ms[i]; p.ldb = Ns[i]; p.ldc = Ns[i];
-    p.mode = modes ? modes[i] : SCOT_GRAD_ADD;
-    if (p.mode < 0 || p.mode > SCOT_GRAD_ADD_SCALED) return SCOT_ERR_SHAPE;
-    p.tiles_n = (Ns[i] + bn - 1) / bn;
-    p.tile0 = tiles;
-    p.ws_off = (unsigned)plane;
-    tiles += p.tiles_n * ((Ms[i] + bm - 1) / bm);
-    plane += (size_t)Ms[i] * Ns[i];
+    if (modes && (modes[i] < 0 || modes[i] > SCOT_GRAD_ADD_SCALED)) return SCOT_ERR_SHAPE;
+    p.tiles_n[i] = (Ns[i] + bn - 1) / bn;
+    p.tile0[i] = p.tiles;
+    p.ws_off[i] = (unsigned)p.plane;
+    p.tiles += p.tiles_n[i] * ((Ms[i] + bm - 1) / bm);
+    p.plane += (size_t)Ms[i] * Ns[i];
   }
-  for (int i = n; i < SCOT_WGRAD_GROUP_MAX; ++i) { g.p[i] = g.p[0]; g.p[i].tile0 = 0x7fffffff; g.p[i].ws_off = 0xffffffffu; }
-  g.tiles = tiles; g.plane = plane; g.scale = grad_scale;
   // K slices: enough workgroups to fill the chip (~2 per CU), at least 8 K-tiles each, a multiple of 8 so that one slice's
   // tiles share an XCD; none when the group already has >= 256 tiles
   const int want_wgs = 256;   // in-step optimum: 192-256 (448 filled the chip better alone and cost the chain 0.1 ms; 128 makes the side stream the wall)
   const long nkt = (K + bk - 1) / bk;
   // (groups with >= 256 tiles — the deep stages — are never split: two K slices for the 432-tile stage-2 group run 66 instead of 85 us
   // alone and cost the step 0.2 ms; the eight-wave workgroups below halve its serial K loop without a second pass)
-  long nsplit = tiles >= 256 ? 1 : (want_wgs + tiles - 1) / tiles;
+  long nsplit = p.tiles >= 256 ? 1 : (want_wgs + p.tiles - 1) / p.tiles;
   if (wide >= 0) nsplit = wide_split;
   if (nsplit < 1) nsplit = 1;
   const long maxsplit = nkt / 8 > 0 ? nkt / 8 : 1;
   if (nsplit > maxsplit) nsplit = maxsplit;
-  const long wsmax = (workspace && plane) ? (long)(ws_bytes / (plane * sizeof(float))) : 1;
+  const long wsmax = (long)(ws_offer / (p.plane * sizeof(float)));
   if (nsplit > wsmax) nsplit = wsmax < 1 ? 1 : wsmax;
-  int per = (int)(((K + nsplit - 1) / nsplit + bk - 1) / bk * bk);
-  if (nsplit >= 8 && wide < 0) {
-    for (int tries = 0; tries < 64 && ((K + per - 1) / per) % 8 != 0; ++tries) per += bk;
-    if (((K + per - 1) / per) % 8 != 0) per = (int)(((K + nsplit - 1) / nsplit + bk - 1) / bk * bk);
-  }
-  g.ksplit = per;
-  g.nsplit = (K + per - 1) / per;
-  g.ws = nullptr;
-  if (g.nsplit > 1) {
-    if (!workspace || (((uintptr_t)workspace) & 31) || (size_t)g.nsplit * plane * sizeof(float) > ws_bytes) return SCOT_ERR_UNSUPPORTED;
-    g.ws = (float*)workspace;
-  }
-  if (query) {
-    *query = g.nsplit > 1 ? (size_t)g.nsplit * plane * sizeof(float) : 0;
-    return SCOT_OK;
-  }
+  p.ksplit = kslice_len(K, nsplit, bk, nsplit >= 8 && wide < 0);
+  p.nsplit = (K + p.ksplit - 1) / p.ksplit;
+  p.ws_used = p.nsplit > 1 ? (size_t)p.nsplit * p.plane * sizeof(float) : 0;
+  if (p.nsplit > 1 && (!ws_aligned || p.ws_used > ws_offer)) return SCOT_ERR_UNSUPPORTED;
+  p.zl = p.nsplit >= 32 ? 8 : p.nsplit >= 4 ? 4 : 1;
   // unsplit 64x64-tile groups (the deep stages: 432 / 1728 tiles walking 64 / 16 K-tiles each): two K groups per workgroup
-  const int kg_env = 2;   // (measured: stage 2 84.5 -> 62.5 us alone, step -0.12 ms against four waves)
-  int rc;
-  if (wide >= 0) rc = scot_wgrad_group_wide_launch(g, wide, stream);
-  else if (!t96 && g.nsplit == 1 && kg_env == 2 && nkt >= 4) rc = launch_wgrad_group<64, 64, 64, 2, 2>(g, stream);
-  else rc = t96 ? launch_wgrad_group<96, 96, 64, 2>(g, stream) : launch_wgrad_group<64, 64, 64, 2>(g, stream);
+  // (measured: stage 2 84.5 -> 62.5 us alone, step -0.12 ms against four waves)
+  p.kernel = wide >= 0 ? GROUP_WIDE : t96 ? GROUP_96x96 : (p.nsplit == 1 && nkt >= 4) ? GROUP_64x64_KG2 : GROUP_64x64;
+  return SCOT_OK;
+}
+
+// include/scot_hip.h: scot_wgrad_group.  dY_i: [K, M_i] (16-bit operands), X_i: [K, N_i], dW_i: [M_i, N_i] fp32 (+=),
+// dbias_i: [M_i] fp32 (+= column sums of dY_i) or NULL.  All leading dimensions = the row lengths (dense).
+extern "C" int scot_wgrad_group(int compute, int n, int K, const void* const* dY, const void* const* X, float* const* dW,
+                                float* const* dbias, const int* Ms, const int* Ns, void* workspace, size_t ws_bytes,
+                                const int* modes, const float* grad_scale, hipStream_t stream) {
+  unsigned unaligned = 0;
+  for (int i = 0; i < n && i < SCOT_WGRAD_GROUP_MAX; ++i) unaligned |= (aligned16(dY[i], X[i], dW[i]) ? 0u : 1u) << i;
+  WgradGroupPlan p;
+  int rc = plan_wgrad_group(compute, n, K, Ms, Ns, modes, unaligned, workspace ? ws_bytes : 0, workspace && ((uintptr_t)workspace & 31) == 0, p);
+  if (rc != SCOT_OK) return rc;
+  WgradGroupArgs g;
+  g.n = n; g.K = K; g.use_tr = g_scot_use_tr;
+  for (int i = 0; i < n; ++i) {
+    WgradProblem& q = g.p[i];
+    q.A = dY[i]; q.B = X[i]; q.C = dW[i]; q.colsum = dbias ? dbias[i] : nullptr;
+    q.M = Ms[i]; q.N = Ns[i]; q.lda = Ms[i]; q.ldb = Ns[i]; q.ldc = Ns[i];
+    q.mode = modes ? modes[i] : SCOT_GRAD_ADD;
+    q.tiles_n = p.tiles_n[i]; q.tile0 = p.tile0[i]; q.ws_off = p.ws_off[i];
+  }
+  for (int i = n; i < SCOT_WGRAD_GROUP_MAX; ++i) { g.p[i] = g.p[0]; g.p[i].tile0 = 0x7fffffff; g.p[i].ws_off = 0xffffffffu; }
+  g.tiles = p.tiles; g.plane = p.plane; g.scale = grad_scale;
+  g.ksplit = p.ksplit; g.nsplit = p.nsplit;
+  g.ws = p.nsplit > 1 ? (float*)workspace : nullptr;
+  switch (p.kernel) {
+    case GROUP_WIDE: rc = scot_wgrad_group_wide_launch(g, p.wide, stream); break;
+    case GROUP_64x64_KG2: rc = launch_wgrad_group<64, 64, 64, 2, 2>(g, stream); break;
+    case GROUP_96x96: rc = launch_wgrad_group<96, 96, 64, 2>(g, stream); break;
+    default: rc = launch_wgrad_group<64, 64, 64, 2>(g, stream); break;
+  }
   if (rc == SCOT_OK && g.ws) {
-    const size_t n8 = plane / 8;
-    const int zl = g.nsplit >= 32 ? 8 : g.nsplit >= 4 ? 4 : 1;
-    size_t blocks = (n8 * zl + 255) / 256; if (blocks > 4096) blocks = 4096;
+    size_t blocks = (p.plane / 8 * p.zl + 255) / 256; if (blocks > 4096) blocks = 4096;
     const dim3 gr((unsigned)blocks), b(256);
-    if (zl == 8) hipLaunchKernelGGL(wgrad_group_reduce_kernel<8>, gr, b, 0, stream, g);
-    else if (zl == 4) hipLaunchKernelGGL(wgrad_group_reduce_kernel<4>, gr, b, 0, stream, g);
+    if (p.zl == 8) hipLaunchKernelGGL(wgrad_group_reduce_kernel<8>, gr, b, 0, stream, g);
+    else if (p.zl == 4) hipLaunchKernelGGL(wgrad_group_reduce_kernel<4>, gr, b, 0, stream, g);
     else hipLaunchKernelGGL(wgrad_group_reduce_kernel<1>, gr, b, 0, stream, g);
     rc = scot_check_launch();
   }
   return rc;
 }
 
-extern "C" int scot_wgrad_group(int compute, int n, int K, const void* const* dY, const void* const* X, float* const* dW,
-                                float* const* dbias, const int* Ms, const int* Ns, void* workspace, size_t ws_bytes,
-                                const int* modes, const float* grad_scale, hipStream_t stream) {
-  return wgrad_group_impl(compute, n, K, dY, X, dW, dbias, Ms, Ns, workspace, ws_bytes, modes, grad_scale, stream, nullptr);
-}
-
 // include/scot_hip.h: scot_wgrad_group_workspace_bytes (0: no split, or the shapes are not covered by the grouped kernel)
 extern "C" size_t scot_wgrad_group_workspace_bytes(int n, int K, const int* Ms, const int* Ns) {
-  size_t q = 0;
-  const int rc = wgrad_group_impl(SCOT_BF16, n, K, nullptr, nullptr, nullptr, nullptr, Ms, Ns, nullptr, 0, nullptr, nullptr, nullptr, &q);
-  return rc == SCOT_OK ? q : 0;
+  WgradGroupPlan p;
+  return plan_wgrad_group(SCOT_BF16, n, K, Ms, Ns, nullptr, 0, WS_UNLIMITED, true, p) == SCOT_OK ? p.ws_used : 0;
 }

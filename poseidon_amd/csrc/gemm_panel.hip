@@ -11,11 +11,7 @@
 //   * transposes its 16x32 accumulator blocks through a private 2.3 KB LDS patch so that the fused epilogue
 //     (bias, gelu value+derivative, gelu'/aux multiply, residual) stores 64–128-byte row segments.
 // bf16 operands only (the fp32 parity mode keeps the tiled kernel).  K must be a multiple of 96, N of BN.
-#include "common.h"
-#include <stdlib.h>
-
-#define LAYOUT_NT 0
-#define LAYOUT_NN 1
+#include "gemm_call.h"
 
 struct PanelArgs {
   const bf16_t* A; const bf16_t* B; void* C; void* C2;
@@ -164,8 +160,6 @@ __global__ __launch_bounds__(256, 2) void gemm_panel_kernel(PanelArgs p) {
   }
 }
 
-extern int g_scot_use_tr;
-
 template <int NF>
 static int launch_panel(const PanelArgs& a, int layout, hipStream_t s) {
   constexpr int BN = NF * 16;
@@ -190,25 +184,17 @@ static int launch_panel(const PanelArgs& a, int layout, hipStream_t s) {
 }
 
 // Returns SCOT_ERR_UNSUPPORTED when the call does not qualify (the caller then uses the tiled kernels).
-int scot_gemm_panel(int layout, int compute, int M, int N, int K, const void* A, int a_dt, int lda, int a_gelu, const void* B,
-                    int b_dt, int ldb, int b_gelu, void* C, int c_dt, int ldc, const float* bias, const float* colscale,
-                    const void* aux, int aux_dt, int ldaux, const void* resid, int res_dt, int ldres, int accumulate,
-                    float* colsum_out, int aux_mul, void* C2, hipStream_t stream) {
-  if (compute != SCOT_BF16 || (layout != LAYOUT_NT && layout != LAYOUT_NN)) return SCOT_ERR_UNSUPPORTED;
-  if (a_dt != SCOT_BF16 || b_dt != SCOT_BF16 || a_gelu || b_gelu || colscale || colsum_out) return SCOT_ERR_UNSUPPORTED;
+int scot_gemm_panel(const GemmCall& c, hipStream_t stream) {
+  if (c.compute != SCOT_BF16 || (c.layout != LAYOUT_NT && c.layout != LAYOUT_NN)) return SCOT_ERR_UNSUPPORTED;
+  if (c.a_dt != SCOT_BF16 || c.b_dt != SCOT_BF16 || c.a_gelu || c.b_gelu || c.colscale || c.colsum_out) return SCOT_ERR_UNSUPPORTED;
   const int kmax = 192;   // measured: K = 384 (48-col panels) only ties the tiled kernel
-  if (K % 96 || K > kmax || N % 48 || M < 4096) return SCOT_ERR_UNSUPPORTED;
-  if ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)C2 | (uintptr_t)aux | (uintptr_t)resid | (uintptr_t)bias) & 15) != 0)
-    return SCOT_ERR_UNSUPPORTED;
-  if (lda % 8 || ldb % 8 || ldc % 8 || (aux && ldaux % 8) || (resid && ldres % 8)) return SCOT_ERR_UNSUPPORTED;
+  if (c.K % 96 || c.K > kmax || c.N % 48 || c.M < 4096) return SCOT_ERR_UNSUPPORTED;
+  if (!aligned16(c.A, c.B, c.C, c.C2, c.aux, c.resid, c.bias) || !ld_vectors(c, 8)) return SCOT_ERR_UNSUPPORTED;
+  const GemmResid r = gemm_resid(c);
   PanelArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C; a.C2 = C2; a.bias = bias; a.aux = aux; a.resid = resid;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldaux = ldaux; a.ldres = ldres;
-  a.c_dt = c_dt; a.aux_dt = aux_dt; a.res_dt = res_dt; a.aux_on = aux != nullptr; a.aux_mul = aux_mul; a.use_tr = g_scot_use_tr;
-  if (accumulate) {
-    if (resid) return SCOT_ERR_UNSUPPORTED;
-    a.resid = C; a.res_dt = c_dt; a.ldres = ldc;
-  }
-  const bool wide = (N % 96 == 0) && K <= 192;   // 96-column panels while the panel stays <= 40 KB (3 workgroups per CU)
-  return wide ? launch_panel<6>(a, layout, stream) : launch_panel<3>(a, layout, stream);
+  a.A = (const bf16_t*)c.A; a.B = (const bf16_t*)c.B; a.C = c.C; a.C2 = c.C2; a.bias = c.bias; a.aux = c.aux; a.resid = r.p;
+  a.M = c.M; a.N = c.N; a.K = c.K; a.lda = c.lda; a.ldb = c.ldb; a.ldc = c.ldc; a.ldaux = c.ldaux; a.ldres = r.ld;
+  a.c_dt = c.c_dt; a.aux_dt = c.aux_dt; a.res_dt = r.dt; a.aux_on = c.aux != nullptr; a.aux_mul = c.aux_mul; a.use_tr = g_scot_use_tr;
+  const bool wide = (c.N % 96 == 0) && c.K <= 192;   // 96-column panels while the panel stays <= 40 KB (3 workgroups per CU)
+  return wide ? launch_panel<6>(a, c.layout, stream) : launch_panel<3>(a, c.layout, stream);
 }

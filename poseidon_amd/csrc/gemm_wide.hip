@@ -16,10 +16,7 @@
 // the hand-off still cost 6-9 us per launch — the last arriver reads (S - 1) x 64 KB alone — against 3-5 us saved in the K loop.
 // Reference shapes: the Linear layers of HF modeling_swinv2.py:396-410, 496-506, 536-561 at the widths of scOT/model.py:403-404 and
 // scOT/train.py:35-72 (MODEL_MAP).
-#include "common.h"
-#include <stdlib.h>
-
-#define LAYOUT_NT 0
+#include "gemm_call.h"
 
 struct WideArgs {
   const bf16_t* A; const bf16_t* B; void* C; void* C2;
@@ -249,26 +246,21 @@ static void wide_launch(int epi, unsigned grid, const WideArgs& a, hipStream_t s
 }
 
 // Returns SCOT_ERR_UNSUPPORTED when the call does not qualify (scot_gemm then asks gemm_fast).
-int scot_gemm_wide(int layout, int compute, int M, int N, int K, const void* A, int a_dt, int lda, int a_gelu,
-                   const void* B, int b_dt, int ldb, int b_gelu, void* C, int c_dt, int ldc, const float* bias,
-                   const float* colscale, const void* aux, int aux_dt, int ldaux, const void* resid, int res_dt, int ldres,
-                   int accumulate, float* colsum_out, int aux_mul, void* C2, hipStream_t stream) {
-  if (layout != LAYOUT_NT || compute != SCOT_BF16 || a_dt != SCOT_BF16 || b_dt != SCOT_BF16) return SCOT_ERR_UNSUPPORTED;
-  if (a_gelu || b_gelu || colscale || colsum_out || (aux && aux_dt != SCOT_BF16)) return SCOT_ERR_UNSUPPORTED;
-  if (aux && (resid || accumulate)) return SCOT_ERR_UNSUPPORTED;               // (one epilogue operand per instantiation: what the engine's calls use)
-  if ((resid && res_dt != SCOT_F32) || (accumulate && c_dt != SCOT_F32)) return SCOT_ERR_UNSUPPORTED;
-  if ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)C2 | (uintptr_t)aux | (uintptr_t)resid) & 15) != 0) return SCOT_ERR_UNSUPPORTED;
-  if (lda % 8 || ldb % 8 || ldc % 8 || (aux && ldaux % 8) || (resid && ldres % 8)) return SCOT_ERR_UNSUPPORTED;
-  if (accumulate && resid != nullptr) return SCOT_ERR_UNSUPPORTED;
-  const int epi = aux ? WIDE_EPI_AUX16 : ((resid || accumulate) ? WIDE_EPI_RES32 : WIDE_EPI_NONE);
-  const int variant = wide_variant(M, N, K, epi);
+int scot_gemm_wide(const GemmCall& c, hipStream_t stream) {
+  if (c.layout != LAYOUT_NT || c.compute != SCOT_BF16 || c.a_dt != SCOT_BF16 || c.b_dt != SCOT_BF16) return SCOT_ERR_UNSUPPORTED;
+  if (c.a_gelu || c.b_gelu || c.colscale || c.colsum_out || (c.aux && c.aux_dt != SCOT_BF16)) return SCOT_ERR_UNSUPPORTED;
+  if (c.aux && (c.resid || c.accumulate)) return SCOT_ERR_UNSUPPORTED;               // (one epilogue operand per instantiation: what the engine's calls use)
+  if ((c.resid && c.res_dt != SCOT_F32) || (c.accumulate && c.c_dt != SCOT_F32)) return SCOT_ERR_UNSUPPORTED;
+  if (!aligned16(c.A, c.B, c.C, c.C2, c.aux, c.resid) || !ld_vectors(c, 8)) return SCOT_ERR_UNSUPPORTED;      // (bias is read per column: any alignment)
+  const GemmResid r = gemm_resid(c);
+  const int epi = c.aux ? WIDE_EPI_AUX16 : (r.p ? WIDE_EPI_RES32 : WIDE_EPI_NONE);
+  const int variant = wide_variant(c.M, c.N, c.K, epi);
   if (variant < 0) return SCOT_ERR_UNSUPPORTED;
   WideArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C; a.C2 = C2; a.bias = bias; a.aux = aux; a.resid = resid;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldaux = ldaux; a.ldres = ldres;
-  a.c_dt = c_dt; a.aux_mul = aux_mul;
-  if (accumulate) { a.resid = C; a.ldres = ldc; }
-  const int tm = M / 128, tn = N / 128;
+  a.A = (const bf16_t*)c.A; a.B = (const bf16_t*)c.B; a.C = c.C; a.C2 = c.C2; a.bias = c.bias; a.aux = c.aux; a.resid = r.p;
+  a.M = c.M; a.N = c.N; a.K = c.K; a.lda = c.lda; a.ldb = c.ldb; a.ldc = c.ldc; a.ldaux = c.ldaux; a.ldres = r.ld;
+  a.c_dt = c.c_dt; a.aux_mul = c.aux_mul;
+  const int tm = c.M / 128, tn = c.N / 128;
   a.tiles = tm * tn; a.tiles_n = tn;
   a.tpx = (a.tiles + 7) / 8;
   // chunk of tpx consecutive tiles per XCD: along N it touches ~ceil(tpx / tn) A row blocks and min(tpx, tn) B row blocks, along M the mirror

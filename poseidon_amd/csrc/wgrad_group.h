@@ -38,3 +38,4 @@ __device__ __forceinline__ void grad_commit8(float* C, size_t ci, float (&v)[8],
   st8(C, SCOT_F32, ci, v);
 }
 
+int scot_wgrad_group_wide_launch(const WgradGroupArgs& g, int variant, hipStream_t s);   // wgrad_wide.hip: the 128 x 128-tile instantiations

@@ -581,7 +581,10 @@ def guarded_bodies(gpu_test_bodies):
 @pytest.mark.parametrize("compute,layout,mixed,M,N,K,pad", [
     (ops.F32, ops.NT, False, 70, 40, 24, 8), (ops.F32, ops.TN, False, 40, 24, 70, 0), (ops.BF16, ops.NT, False, 130, 72, 40, 8),
     (ops.BF16, ops.NN, False, 130, 72, 40, 0), (ops.BF16, ops.TN, False, 72, 40, 136, 8), (ops.BF16, ops.NT, True, 65, 34, 24, 3),
-    (ops.BF16, ops.NN, True, 65, 34, 24, 0), (ops.BF16, ops.NT, False, 257, 130, 72, 3), (ops.BF16, ops.NT, False, 192, 96, 96, 16)])
+    (ops.BF16, ops.NN, True, 65, 34, 24, 0), (ops.BF16, ops.NT, False, 257, 130, 72, 3), (ops.BF16, ops.NT, False, 192, 96, 96, 16),
+    # rows of gemm_fast's tile table the cases above do not select: direct-to-LDS, plain 64 x 64 in NT, four register sets (NT / NN)
+    (ops.BF16, ops.NT, False, 64, 64, 192, 8), (ops.BF16, ops.NT, False, 64, 64, 136, 8), (ops.BF16, ops.NT, False, 64, 64, 2312, 0),
+    (ops.BF16, ops.NN, False, 64, 64, 2304, 8)])
 def test_guarded_gemm_layouts(guarded_bodies, compute, layout, mixed, M, N, K, pad):
     guarded_bodies.gemm_layouts_guarded(compute, layout, mixed, M, N, K, pad)
 

@@ -36,6 +36,9 @@ GEMM_SHAPES = [(304, 96, 96), (1024, 288, 96), (257, 130, 72), (4096, 384, 96), 
 # mixed = False: operands in the compute dtype (gemm_fast); True: fp32 B beside 16-bit A (generic kernel; exists in the 16-bit mode only)
 GEMM_CASES = [(c, l, mx, *sh) for c in (ops.F32, ops.BF16) for l in (ops.NT, ops.NN, ops.TN) for mx in (False, True) for sh in GEMM_SHAPES
               if not (mx and (c == ops.F32 or sh[0] > 5000))]
+# + the smallest shapes that select the rows of gemm_fast's tile table (csrc/gemm_fast.hip: kFastTiles) which the list above leaves out:
+# 96 x 96 (TN, whole 96-tiles over >= 8192 tokens), four register sets in NT (K >= 2304 that is not whole 64-tiles), plain 64 x 64 in NT
+GEMM_CASES += [(ops.BF16, ops.TN, False, 96, 96, 8192), (ops.BF16, ops.NT, False, 64, 64, 2312), (ops.BF16, ops.NT, False, 64, 64, 136)]
 
 
 @pytest.mark.parametrize("compute,layout,mixed,M,N,K", GEMM_CASES)
@@ -778,7 +781,8 @@ def test_cpb_batched_layers():
 
 # ----------------------------------------------------------------------------------------------- bf16x3 GEMM
 @pytest.mark.parametrize("layout,M,N,K", [(ops.NT, 4096, 288, 96), (ops.NT, 1024, 96, 384), (ops.NN, 2048, 96, 384), (ops.NN, 1000, 384, 96),
-                                          (ops.TN, 384, 96, 8192), (ops.TN, 96, 288, 4100 // 4 * 4), (ops.NT, 300, 72, 40)])
+                                          (ops.TN, 384, 96, 8192), (ops.TN, 96, 288, 4100 // 4 * 4), (ops.NT, 300, 72, 40),
+                                          (ops.TN, 64, 96, 136)])      # (the 64 x 96 tile in TN)
 def test_gemm_bf16x3_is_fp32_class(layout, M, N, K):
     """compute = bf16x3: fp32 operands split into hi + lo bf16, three bf16 MFMAs per K-step.  Against an fp64 product the error
     must be in the fp32 class (operand error ~2^-17), two orders of magnitude below plain bf16 operands (2^-9)."""

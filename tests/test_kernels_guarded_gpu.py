@@ -447,7 +447,8 @@ def gemm_split_k_atomic_guarded(kind, M, N, K, S, pad):
 
 
 @pytest.mark.parametrize("pad", [0, 8])
-@pytest.mark.parametrize("layout,M,N,K", [(ops.NT, 4096, 288, 96), (ops.NN, 1000, 384, 96), (ops.TN, 96, 288, 4100 // 4 * 4), (ops.NT, 300, 72, 40)])
+@pytest.mark.parametrize("layout,M,N,K", [(ops.NT, 4096, 288, 96), (ops.NN, 1000, 384, 96), (ops.TN, 96, 288, 4100 // 4 * 4), (ops.NT, 300, 72, 40),
+                                          (ops.TN, 64, 96, 136), (ops.TN, 96, 96, 8192)])      # (the 64 x 96 and 96 x 96 tiles in TN)
 def test_gemm_bf16x3_guarded(layout, M, N, K, pad):
     gemm_bf16x3_guarded(layout, M, N, K, pad)
 
