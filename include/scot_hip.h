@@ -315,7 +315,9 @@ int scot_block_tail_bwd(const float* g, float* g_out, const void* z2, const floa
                         (needs g_out == g) = the qkv projection's data gradient (HF:396-410) of the layer processed before */,
                         const void* h16, const float* b1, int z_dt, float* partial2, float* partial1,
                         const float* time, int M, int rows_per_sample, int C, int hid, scot_stream_t stream);
-int scot_block_tail_workgroups(int M, int rows_per_sample, int C);      /* rows of partial2 / partial1 (0: shapes not covered) */
+/* Workgroups of scot_block_tail_bwd — the BACKWARD's grid — = rows of partial2 / partial1 (0: shapes not covered).  Not the forward's:
+ * at C = 96, M >= 65536 and rows_per_sample % 128 != 0 scot_block_tail_fwd runs 128-row workgroups, the backward 64-row ones. */
+int scot_block_tail_workgroups(int M, int rows_per_sample, int C);
 int scot_partial_colsum(const float* partial, int nblk, int ncol, float* out, scot_stream_t stream);   /* out[j] += Σ_b partial[b][j] */
 /* the same for n <= 32 matrices in ONE launch (HOST arrays of device pointers / sizes, read before the call returns): the engine
  * finishes a whole stage's norm backwards (scot_cln_bwd mode 3, scot_block_tail_bwd partial rows) with it */

@@ -219,57 +219,6 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_kernel(MlpArgs p) {
   mlp_fwd_body<C, HC, TT, false>(p, smem, nullptr);
 }
 
-// Hidden units per LDS weight chunk.  The chunk's 16-byte pieces must divide evenly over the 256 threads (HC·C/8 % 256 == 0:
-// with a ragged last piece the skipped LDS stores leave loads the compiler cannot prove consumed, and it then waits for all
-// memory traffic at the top of every chunk iteration): 64 (27 KB of LDS at C = 96, 54 KB at C = 192).
-static int mlp_chunk(int) { return 64; }     // (128-hidden chunks at C = 96: measured no change, round 2)
-
-template <int C, int HC, int TT>
-static int launch_mlp(const MlpArgs& a, hipStream_t s) {
-  static_assert((HC * C / 8) % 256 == 0, "ragged weight chunk");
-  const int rows_per_wg = 64 * TT;
-  dim3 grid((a.M + rows_per_wg - 1) / rows_per_wg), block(256);
-  hipLaunchKernelGGL((mlp_fused_kernel<C, HC, TT>), grid, block, 0, s, a);
-  return scot_check_launch();
-}
-
-// token rows per workgroup of the fused block kernels, forced (64 x SCOT_MLP_TT) by the sanitizer / emulator harness (tests/test_hipemu_cpu.py);
-// 0 = the launch policies' own choice.  The one environment read left in the library's launch paths.
-static int scot_mlp_tt_override() {
-  static int tt_env = -1;
-  if (tt_env < 0) { const char* e = getenv("SCOT_MLP_TT"); tt_env = e ? atoi(e) : 0; }
-  return tt_env;
-}
-
-// include/scot_hip.h: scot_mlp_block_fwd.  Returns SCOT_ERR_UNSUPPORTED for shapes this kernel does not cover (the caller
-// then runs linear + linear + cln).
-extern "C" int scot_mlp_block_fwd(const void* h16, const float* h, const void* W1, const float* b1, const void* W2, const float* b2,
-                                  float* out, void* out16, void* act, void* dact, float* z, float* mean, float* rstd,
-                                  const float* time, const float* gw_w, const float* gw_b, const float* bw_w, const float* bw_b,
-                                  const float* sample_scale, int M, int rows_per_sample, int C, int hid, float eps,
-                                  hipStream_t stream) {
-  if (M <= 0 || rows_per_sample <= 0) return SCOT_ERR_SHAPE;
-  if (C != 96 && C != 192) return SCOT_ERR_UNSUPPORTED;
-  const int hc = mlp_chunk(C);
-  if (hid < hc || hid % hc != 0) return SCOT_ERR_UNSUPPORTED;
-  if (!h16 || !h || !W1 || !b1 || !W2 || !b2 || !out || !gw_b || !bw_b) return SCOT_ERR_SHAPE;
-  if ((act == nullptr) != (dact == nullptr) || (mean == nullptr) != (rstd == nullptr) || (gw_w == nullptr) != (bw_w == nullptr))
-    return SCOT_ERR_SHAPE;
-  MlpArgs a;
-  a.h16 = (const bf16_t*)h16; a.h = h; a.W1 = (const bf16_t*)W1; a.b1 = b1; a.W2 = (const bf16_t*)W2; a.b2 = b2;
-  a.out = out; a.out16 = (bf16_t*)out16; a.act = (bf16_t*)act; a.dact = (bf16_t*)dact; a.z = z; a.z_dt = SCOT_F32; a.mean = mean; a.rstd = rstd;
-  a.time = time; a.gw_w = gw_w; a.gw_b = gw_b; a.bw_w = bw_w; a.bw_b = bw_b; a.sscale = sample_scale;
-  a.M = M; a.rows_per_sample = rows_per_sample; a.hid = hid; a.eps = eps;
-  const int tt_env = scot_mlp_tt_override();
-  // 64·TT rows per workgroup: TT = 2 halves the LDS weight reads per MFMA; TT = 1 when that would leave CUs without work
-  // (C = 192 with TT = 2 needs 256 VGPRs + spills: TT = 1 unless forced)
-  const int tt = tt_env ? tt_env : ((C == 96 && M >= 64 * 2 * 512) ? 2 : 1);
-  if (C == 96) {
-    return tt == 2 ? launch_mlp<96, 64, 2>(a, stream) : launch_mlp<96, 64, 1>(a, stream);
-  }
-  return tt == 2 ? launch_mlp<192, 64, 2>(a, stream) : launch_mlp<192, 64, 1>(a, stream);
-}
-
 // ------------------------------------------------------------------------------------------------------------------------
 // Backward of the same block along the dependent chain, in one launch (the two weight gradients stay separate GEMMs on
 // the side stream; they consume the dz and du written here):
@@ -575,42 +524,6 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_fused_kernel(MlpBwdArgs p) {
   mlp_bwd_body<C, HC, TT, false>(p, smem, nullptr);
 }
 
-extern int g_scot_use_tr;
-
-template <int C, int HC, int TT>
-static int launch_mlp_bwd(const MlpBwdArgs& a, hipStream_t s) {
-  dim3 grid((a.M + 64 * TT - 1) / (64 * TT)), block(256);
-  hipLaunchKernelGGL((mlp_bwd_fused_kernel<C, HC, TT>), grid, block, 0, s, a);
-  return scot_check_launch();
-}
-
-// include/scot_hip.h: scot_mlp_block_bwd
-extern "C" int scot_mlp_block_bwd(const float* g, float* g_out, const float* z, const float* mean, const float* rstd,
-                                  const float* time, const float* gw_w, const float* gw_b, const float* sample_scale,
-                                  const void* dact, const void* W1, const void* W2, void* dz, void* du, float* d_gw_w,
-                                  float* d_gw_b, float* d_bw_w, float* d_bw_b, int M, int rows_per_sample, int C, int hid,
-                                  hipStream_t stream) {
-  if (M <= 0 || rows_per_sample <= 0) return SCOT_ERR_SHAPE;
-  if (C != 96 && C != 192) return SCOT_ERR_UNSUPPORTED;
-  const int hc = mlp_chunk(C);
-  if (hid < hc || hid % hc != 0) return SCOT_ERR_UNSUPPORTED;
-  if (!g || !g_out || !z || !mean || !rstd || !gw_b || !dact || !W1 || !W2 || !dz || !du || !d_gw_b || !d_bw_b) return SCOT_ERR_SHAPE;
-  if ((gw_w == nullptr) != (d_gw_w == nullptr) || (d_gw_w == nullptr) != (d_bw_w == nullptr)) return SCOT_ERR_SHAPE;
-  const int tt_env = scot_mlp_tt_override();
-  int tt = tt_env ? tt_env : ((C == 96 && M >= 64 * 2 * 512) ? 2 : 1);
-  if (rows_per_sample % (64 * tt) != 0) tt = 1;
-  if (rows_per_sample % 64 != 0) return SCOT_ERR_UNSUPPORTED;      // the conditioning time must be uniform per workgroup
-  MlpBwdArgs a;
-  a.g = g; a.g_out = g_out; a.z = z; a.z_dt = SCOT_F32; a.mean = mean; a.rstd = rstd; a.time = time; a.gw_w = gw_w; a.gw_b = gw_b; a.sscale = sample_scale;
-  a.partial = nullptr; a.h16 = nullptr; a.b1 = nullptr;
-  a.dact = (const bf16_t*)dact; a.W1 = (const bf16_t*)W1; a.W2 = (const bf16_t*)W2; a.dz = (bf16_t*)dz; a.du = (bf16_t*)du;
-  a.d_gw_w = d_gw_w; a.d_gw_b = d_gw_b; a.d_bw_w = d_bw_w; a.d_bw_b = d_bw_b;
-  a.M = M; a.rows_per_sample = rows_per_sample; a.hid = hid; a.use_tr = g_scot_use_tr;
-  if (C == 96) {
-    return tt == 2 ? launch_mlp_bwd<96, 64, 2>(a, stream) : launch_mlp_bwd<96, 64, 1>(a, stream);
-  }
-  return tt == 2 ? launch_mlp_bwd<192, 64, 2>(a, stream) : launch_mlp_bwd<192, 64, 1>(a, stream);
-}
 
 // ------------------------------------------------------------------------------------------------------------------------
 // The attention half's tail, same row ownership:  out = x + s_b · CLN(a · W^T + b)   (Swinv2SelfOutput + res-post-norm,
@@ -805,13 +718,6 @@ __global__ __launch_bounds__(256, 2) void tail_fwd_fused_kernel(TailFwdArgs p) {
   }
 }
 
-template <int C, int HC, int TT>
-static int launch_tail_fwd(const TailFwdArgs& a, hipStream_t s) {
-  dim3 grid((a.m.M + 64 * TT - 1) / (64 * TT)), block(256);
-  if (a.qkv) hipLaunchKernelGGL((tail_fwd_fused_kernel<C, HC, TT, true>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((tail_fwd_fused_kernel<C, HC, TT, false>), grid, block, 0, s, a);
-  return scot_check_launch();
-}
 
 struct ProjClnBwdArgs {
   const bf16_t* W;                       // [C, C] (N x K): da[:, k] = Σ_n dz[:, n] · W[n, k]
@@ -1014,24 +920,166 @@ __global__ __launch_bounds__(256, 2) void tail_bwd_fused_kernel(TailBwdArgs p) {
   proj_cln_bwd_body<C, TT, true>(p.pj, smem, gk);
 }
 
-template <int C, int HC, int TT>
-static int launch_tail_bwd(const TailBwdArgs& a, hipStream_t s) {
-  dim3 grid((a.m.M + 64 * TT - 1) / (64 * TT)), block(256);
-  if (a.m.dact == nullptr) {     // gelu'(u) recomputed in the kernel
-    if (a.dqkv) hipLaunchKernelGGL((tail_bwd_fused_kernel<C, HC, TT, true, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((tail_bwd_fused_kernel<C, HC, TT, false, true>), grid, block, 0, s, a);
-  } else {
-    if (a.dqkv) hipLaunchKernelGGL((tail_bwd_fused_kernel<C, HC, TT, true, false>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((tail_bwd_fused_kernel<C, HC, TT, false, false>), grid, block, 0, s, a);
-  }
+// ------------------------------------------------------------------------------------------------------------------------
+// Host side: what can run (one table), which of it runs (one rule, one planner), then the entry points: plan, validate, fill, launch.
+// Every launcher takes its grid from its OWN template TT (64·TT rows per workgroup).
+extern int g_scot_use_tr;
+template <class A, void (*K)(A), int TT> static int launch_rows(const A& a, int M, hipStream_t s) {
+  hipLaunchKernelGGL(K, dim3((M + 64 * TT - 1) / (64 * TT)), dim3(256), 0, s, a);
   return scot_check_launch();
 }
+// HC = 64 (27 / 54 KB of LDS at C = 96 / 192): the chunk's 16-byte pieces must divide evenly over the 256 threads — with a ragged last piece the
+// skipped LDS stores leave loads the compiler cannot prove consumed, and it then waits for all memory traffic at the top of every chunk iteration
+template <int C, int HC, int TT> static int launch_mlp(const MlpArgs& a, int M, hipStream_t s) {
+  static_assert((HC * C / 8) % 256 == 0, "ragged weight chunk");
+  return launch_rows<MlpArgs, mlp_fused_kernel<C, HC, TT>, TT>(a, M, s);
+}
+template <int C, int HC, int TT> static int launch_tail_fwd(const TailFwdArgs& a, int M, bool qkv, hipStream_t s) {
+  return qkv ? launch_rows<TailFwdArgs, tail_fwd_fused_kernel<C, HC, TT, true>, TT>(a, M, s)
+             : launch_rows<TailFwdArgs, tail_fwd_fused_kernel<C, HC, TT, false>, TT>(a, M, s);
+}
+template <int C, int HC, int TT> static int launch_tail_bwd(const TailBwdArgs& a, int M, bool pro, bool recomp, hipStream_t s) {
+  if constexpr (C % 32 == 0) {       // (C = 48: the stored-gelu' form without the prologue is the one instantiation, see plan_tail_launch)
+    if (recomp) return pro ? launch_rows<TailBwdArgs, tail_bwd_fused_kernel<C, HC, TT, true, true>, TT>(a, M, s)
+                           : launch_rows<TailBwdArgs, tail_bwd_fused_kernel<C, HC, TT, false, true>, TT>(a, M, s);
+    if (pro) return launch_rows<TailBwdArgs, tail_bwd_fused_kernel<C, HC, TT, true, false>, TT>(a, M, s);
+  }
+  return launch_rows<TailBwdArgs, tail_bwd_fused_kernel<C, HC, TT, false, false>, TT>(a, M, s);
+}
 
-static int rows_tile_count(int C, int M, int rows_per_sample) {
-  const int tt_env = scot_mlp_tt_override();
-  int tt = tt_env ? tt_env : ((C == 96 && M >= 64 * 2 * 512) ? 2 : 1);
-  if (rows_per_sample % (64 * tt) != 0) tt = 1;
+// The instantiations of this file: channels C, hidden units per LDS weight chunk HC, 64·TT rows per workgroup, and per family the
+// launcher, or null where none exists.  A new width or tile is one row here.
+struct TailShape {
+  int C, HC, TT;
+  int (*mlp_fwd)(const MlpArgs&, int M, hipStream_t);
+  int (*mlp_bwd)(const MlpBwdArgs&, int M, hipStream_t);
+  int (*proj_fwd)(const ProjClnArgs&, int M, hipStream_t);
+  int (*proj_bwd)(const ProjClnBwdArgs&, int M, hipStream_t);
+  int (*tail_fwd)(const TailFwdArgs&, int M, bool qkv, hipStream_t);
+  int (*tail_bwd)(const TailBwdArgs&, int M, bool pro, bool recomp, hipStream_t);
+};
+#define MLP_HALVES(C, HC, TT) launch_mlp<C, HC, TT>, launch_rows<MlpBwdArgs, mlp_bwd_fused_kernel<C, HC, TT>, TT>
+#define PROJ_HALVES(C, TT) launch_rows<ProjClnArgs, proj_cln_fused_kernel<C, TT>, TT>, launch_rows<ProjClnBwdArgs, proj_cln_bwd_fused_kernel<C, TT>, TT>
+#define WHOLE_TAIL(C, HC, TT) launch_tail_fwd<C, HC, TT>, launch_tail_bwd<C, HC, TT>
+static const TailShape kTailShapes[] = {
+    // Poseidon-T / -S stage 0, one 192-wide hidden chunk: the whole tail only (its backward: stored gelu', no prologue)
+    {48, 192, 1, nullptr, nullptr, nullptr, nullptr, WHOLE_TAIL(48, 192, 1)},
+    {96, 64, 1, MLP_HALVES(96, 64, 1), PROJ_HALVES(96, 1), WHOLE_TAIL(96, 64, 1)},
+    {96, 64, 2, MLP_HALVES(96, 64, 2), PROJ_HALVES(96, 2), WHOLE_TAIL(96, 64, 2)},
+    {192, 64, 1, MLP_HALVES(192, 64, 1), PROJ_HALVES(192, 1), WHOLE_TAIL(192, 64, 1)},
+    {192, 64, 2, MLP_HALVES(192, 64, 2), nullptr, nullptr, nullptr, nullptr},      // 256 VGPRs + spills: through SCOT_MLP_TT=2 only
+};
+#undef MLP_HALVES
+#undef PROJ_HALVES
+#undef WHOLE_TAIL
+
+// token rows per workgroup of the fused block kernels, forced (64 x SCOT_MLP_TT, 1 or 2: any other value counts as unset) by the sanitizer /
+// emulator harness (tests/test_hipemu_cpu.py); 0 = the rule's own choice.  The one environment read left in the library's launch paths.
+static int scot_mlp_tt_override() {
+  static int tt_env = -1;
+  if (tt_env < 0) { const char* e = getenv("SCOT_MLP_TT"); const int v = e ? atoi(e) : 0; tt_env = (v == 1 || v == 2) ? v : 0; }
+  return tt_env;
+}
+
+// THE rule for 64·TT rows per workgroup.  TT = 2 halves the LDS weight reads per MFMA; TT = 1 when that would leave CUs without work, and at
+// C = 192 (256 VGPRs + spills).  needs_uniform_time: the backward kernels reduce the norm's parameter gradients over a workgroup's rows with ONE
+// conditioning time, so a workgroup must not straddle two samples; the forward kernels look the time up per row.
+static int tail_rows_tile(int C, int M, int rows_per_sample, bool needs_uniform_time, int override_tt) {
+  int tt = override_tt ? override_tt : ((C == 96 && M >= 64 * 2 * 512) ? 2 : 1);
+  if (needs_uniform_time && rows_per_sample % (64 * tt) != 0) tt = 1;
   return tt;
+}
+
+// What one launch does: rc (SCOT_OK: go), the table row, the grid (valid whenever `shape` is, also where rc declines), the template flags
+// (tail_fwd: the next layer's qkv epilogue; tail_bwd: the qkv-dgrad prologue, gelu'(u) recomputed)
+struct TailLaunchPlan { int rc; const TailShape* shape; int grid; bool qkv, pro, recomp; };
+enum { kNoHidden = -1 };      // the projection halves have no hidden width
+
+// Pure: the plan of one family (a launcher column of the table) at these dimensions.  The rule's TT runs where the family has that
+// instantiation, else its 64-row one (so SCOT_MLP_TT=2 reaches C = 192 in the two mlp_block families only).
+template <class Fn>
+static TailLaunchPlan plan_tail_launch(Fn TailShape::*family, bool needs_uniform_time, int override_tt, int C, int M, int rows_per_sample, int hid,
+                          bool qkv = false, bool pro = false, bool recomp = false) {
+  TailLaunchPlan p = {SCOT_ERR_SHAPE, nullptr, 0, qkv, pro, recomp};
+  if (M <= 0 || rows_per_sample <= 0) return p;
+  p.rc = SCOT_ERR_UNSUPPORTED;
+  const int tt = tail_rows_tile(C, M, rows_per_sample, needs_uniform_time, override_tt);
+  auto find = [&](int TT) -> const TailShape* {
+    for (const TailShape& s : kTailShapes) if (s.C == C && s.TT == TT && s.*family) return &s;
+    return nullptr;
+  };
+  p.shape = find(tt) ? find(tt) : find(1);      // the rule's TT where this family has that instantiation, else its 64-row one
+  if (!p.shape) return p;
+  const int HC = p.shape->HC, rows = 64 * p.shape->TT;
+  p.grid = (M + rows - 1) / rows;
+  const bool ragged = C % 32 != 0;      // C = 48: ONE hidden chunk, and neither the prologue nor the recomputation exist (static_asserts)
+  if (needs_uniform_time && rows_per_sample % 64 != 0) return p;
+  if (hid != kNoHidden && (hid < HC || hid % HC != 0 || (ragged && hid != HC))) return p;
+  if (ragged && (pro || recomp)) return p;
+  p.rc = SCOT_OK;
+  return p;
+}
+
+// The optional pointers of a conditional norm come in pairs (with per-workgroup partial rows the four gradient pointers are not read), and
+// the two row structs are filled in one place each.  Every argument struct is filled by NAME (designated initialisers, in declaration
+// order; fields left out are zero): a field that is moved or inserted is a compile error, never two silently swapped pointers.
+static bool pair_ok(const void* a, const void* b) { return (a == nullptr) == (b == nullptr); }
+static bool norm_fwd_ok(const float* mean, const float* rstd, const float* gw_w, const float* gw_b, const float* bw_w, const float* bw_b) {
+  return gw_b && bw_b && pair_ok(mean, rstd) && pair_ok(gw_w, bw_w);
+}
+static bool norm_bwd_ok(const float* gw_w, const float* gw_b, const float* d_gw_w, const float* d_gw_b, const float* d_bw_w,
+                        const float* d_bw_b, const float* partial) {
+  return gw_b && (partial || (d_gw_b && d_bw_b && pair_ok(gw_w, d_gw_w) && pair_ok(d_gw_w, d_bw_w)));
+}
+static ClnRowsOut cln_rows_out(const float* bias, void* z, int z_dt, float* mean, float* rstd, const float* time, const float* gw_w,
+                               const float* gw_b, const float* bw_w, const float* bw_b, const float* sscale, const float* resid, float* out,
+                               void* out16, int M, int rows_per_sample, float eps) {
+  return ClnRowsOut{.bias = bias, .z = z, .z_dt = z_dt, .mean = mean, .rstd = rstd, .time = time, .gw_w = gw_w, .gw_b = gw_b, .bw_w = bw_w,
+                    .bw_b = bw_b, .sscale = sscale, .resid = resid, .out = out, .out16 = (bf16_t*)out16, .M = M, .rows_per_sample = rows_per_sample,
+                    .eps = eps};
+}
+static ClnRowsBwd cln_rows_bwd(const float* g, const void* z, int z_dt, const float* mean, const float* rstd, const float* time,
+                               const float* gw_w, const float* gw_b, const float* sscale, void* dz, float* d_gw_w, float* d_gw_b,
+                               float* d_bw_w, float* d_bw_b, float* partial, int M, int rows_per_sample) {
+  return ClnRowsBwd{.g = g, .z = z, .z_dt = z_dt, .mean = mean, .rstd = rstd, .time = time, .gw_w = gw_w, .gw_b = gw_b, .sscale = sscale,
+                    .dz = (bf16_t*)dz, .d_gw_w = d_gw_w, .d_gw_b = d_gw_b, .d_bw_w = d_bw_w, .d_bw_b = d_bw_b, .partial = partial, .M = M,
+                    .rows_per_sample = rows_per_sample};
+}
+
+// include/scot_hip.h: scot_mlp_block_fwd.  Returns SCOT_ERR_UNSUPPORTED for shapes this kernel does not cover (the caller
+// then runs linear + linear + cln).
+extern "C" int scot_mlp_block_fwd(const void* h16, const float* h, const void* W1, const float* b1, const void* W2, const float* b2,
+                                  float* out, void* out16, void* act, void* dact, float* z, float* mean, float* rstd,
+                                  const float* time, const float* gw_w, const float* gw_b, const float* bw_w, const float* bw_b,
+                                  const float* sample_scale, int M, int rows_per_sample, int C, int hid, float eps,
+                                  hipStream_t stream) {
+  const TailLaunchPlan p = plan_tail_launch(&TailShape::mlp_fwd, false, scot_mlp_tt_override(), C, M, rows_per_sample, hid);
+  if (p.rc) return p.rc;
+  if (!h16 || !h || !W1 || !b1 || !W2 || !b2 || !out || !pair_ok(act, dact) || !norm_fwd_ok(mean, rstd, gw_w, gw_b, bw_w, bw_b))
+    return SCOT_ERR_SHAPE;
+  const MlpArgs a = {.h16 = (const bf16_t*)h16, .h = h, .W1 = (const bf16_t*)W1, .b1 = b1, .W2 = (const bf16_t*)W2, .b2 = b2, .out = out,
+                     .out16 = (bf16_t*)out16, .act = (bf16_t*)act, .dact = (bf16_t*)dact, .z = z, .z_dt = SCOT_F32, .mean = mean, .rstd = rstd,
+                     .time = time, .gw_w = gw_w, .gw_b = gw_b, .bw_w = bw_w, .bw_b = bw_b, .sscale = sample_scale, .M = M,
+                     .rows_per_sample = rows_per_sample, .hid = hid, .eps = eps};
+  return p.shape->mlp_fwd(a, M, stream);
+}
+
+// include/scot_hip.h: scot_mlp_block_bwd
+extern "C" int scot_mlp_block_bwd(const float* g, float* g_out, const float* z, const float* mean, const float* rstd,
+                                  const float* time, const float* gw_w, const float* gw_b, const float* sample_scale,
+                                  const void* dact, const void* W1, const void* W2, void* dz, void* du, float* d_gw_w,
+                                  float* d_gw_b, float* d_bw_w, float* d_bw_b, int M, int rows_per_sample, int C, int hid,
+                                  hipStream_t stream) {
+  const TailLaunchPlan p = plan_tail_launch(&TailShape::mlp_bwd, true, scot_mlp_tt_override(), C, M, rows_per_sample, hid);
+  if (p.rc) return p.rc;
+  if (!g || !g_out || !z || !mean || !rstd || !dact || !W1 || !W2 || !dz || !du ||
+      !norm_bwd_ok(gw_w, gw_b, d_gw_w, d_gw_b, d_bw_w, d_bw_b, nullptr))
+    return SCOT_ERR_SHAPE;
+  const MlpBwdArgs a = {.g = g, .g_out = g_out, .z = z, .z_dt = SCOT_F32, .mean = mean, .rstd = rstd, .time = time, .gw_w = gw_w, .gw_b = gw_b,
+                        .sscale = sample_scale, .dact = (const bf16_t*)dact, .W1 = (const bf16_t*)W1, .W2 = (const bf16_t*)W2, .dz = (bf16_t*)dz,
+                        .du = (bf16_t*)du, .d_gw_w = d_gw_w, .d_gw_b = d_gw_b, .d_bw_w = d_bw_w, .d_bw_b = d_bw_b, /* no partial, h16, b1 */
+                        .M = M, .rows_per_sample = rows_per_sample, .hid = hid, .use_tr = g_scot_use_tr};
+  return p.shape->mlp_bwd(a, M, stream);
 }
 
 // include/scot_hip.h: scot_proj_cln_fwd
@@ -1039,24 +1087,13 @@ extern "C" int scot_proj_cln_fwd(const void* a, const void* W, const float* bias
                                  float* z, float* mean, float* rstd, const float* time, const float* gw_w, const float* gw_b,
                                  const float* bw_w, const float* bw_b, const float* sample_scale, int M, int rows_per_sample,
                                  int C, float eps, hipStream_t stream) {
-  if (M <= 0 || rows_per_sample <= 0) return SCOT_ERR_SHAPE;
-  if (C != 96 && C != 192) return SCOT_ERR_UNSUPPORTED;
-  if (!a || !W || !bias || !resid || !out || !gw_b || !bw_b) return SCOT_ERR_SHAPE;
-  if ((mean == nullptr) != (rstd == nullptr) || (gw_w == nullptr) != (bw_w == nullptr)) return SCOT_ERR_SHAPE;
-  ProjClnArgs p;
-  p.a = (const bf16_t*)a; p.W = (const bf16_t*)W;
-  p.e.bias = bias; p.e.z = z; p.e.z_dt = SCOT_F32; p.e.mean = mean; p.e.rstd = rstd; p.e.time = time; p.e.gw_w = gw_w; p.e.gw_b = gw_b; p.e.bw_w = bw_w;
-  p.e.bw_b = bw_b; p.e.sscale = sample_scale; p.e.resid = resid; p.e.out = out; p.e.out16 = (bf16_t*)out16; p.e.M = M;
-  p.e.rows_per_sample = rows_per_sample; p.e.eps = eps;
-  const int tt = rows_tile_count(C, M, 64 * 2);    // no per-workgroup uniformity needed in the forward
-  dim3 grid((M + 64 * tt - 1) / (64 * tt)), block(256);
-  if (C == 96) {
-    if (tt == 2) hipLaunchKernelGGL((proj_cln_fused_kernel<96, 2>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((proj_cln_fused_kernel<96, 1>), grid, block, 0, stream, p);
-  } else {
-    hipLaunchKernelGGL((proj_cln_fused_kernel<192, 1>), dim3((M + 63) / 64), block, 0, stream, p);
-  }
-  return scot_check_launch();
+  const TailLaunchPlan p = plan_tail_launch(&TailShape::proj_fwd, false, scot_mlp_tt_override(), C, M, rows_per_sample, kNoHidden);
+  if (p.rc) return p.rc;
+  if (!a || !W || !bias || !resid || !out || !norm_fwd_ok(mean, rstd, gw_w, gw_b, bw_w, bw_b)) return SCOT_ERR_SHAPE;
+  const ProjClnArgs pa = {.a = (const bf16_t*)a, .W = (const bf16_t*)W,
+                          .e = cln_rows_out(bias, z, SCOT_F32, mean, rstd, time, gw_w, gw_b, bw_w, bw_b, sample_scale, resid, out, out16, M,
+                                            rows_per_sample, eps)};
+  return p.shape->proj_fwd(pa, M, stream);
 }
 
 // include/scot_hip.h: scot_proj_cln_bwd
@@ -1064,39 +1101,21 @@ extern "C" int scot_proj_cln_bwd(const float* g, const float* z, const float* me
                                  const float* gw_w, const float* gw_b, const float* sample_scale, const void* W, void* dz, void* da,
                                  float* d_gw_w, float* d_gw_b, float* d_bw_w, float* d_bw_b, int M, int rows_per_sample, int C,
                                  hipStream_t stream) {
-  if (M <= 0 || rows_per_sample <= 0) return SCOT_ERR_SHAPE;
-  if ((C != 96 && C != 192) || rows_per_sample % 64 != 0) return SCOT_ERR_UNSUPPORTED;
-  if (!g || !z || !mean || !rstd || !gw_b || !W || !dz || !da || !d_gw_b || !d_bw_b) return SCOT_ERR_SHAPE;
-  if ((gw_w == nullptr) != (d_gw_w == nullptr) || (d_gw_w == nullptr) != (d_bw_w == nullptr)) return SCOT_ERR_SHAPE;
-  ProjClnBwdArgs p;
-  p.W = (const bf16_t*)W; p.da = (bf16_t*)da; p.use_tr = g_scot_use_tr;
-  p.b.g = g; p.b.z = z; p.b.z_dt = SCOT_F32; p.b.partial = nullptr; p.b.mean = mean; p.b.rstd = rstd; p.b.time = time; p.b.gw_w = gw_w; p.b.gw_b = gw_b; p.b.sscale = sample_scale;
-  p.b.dz = (bf16_t*)dz; p.b.d_gw_w = d_gw_w; p.b.d_gw_b = d_gw_b; p.b.d_bw_w = d_bw_w; p.b.d_bw_b = d_bw_b; p.b.M = M;
-  p.b.rows_per_sample = rows_per_sample;
-  const int tt = C == 96 ? rows_tile_count(C, M, rows_per_sample) : 1;
-  dim3 grid((M + 64 * tt - 1) / (64 * tt)), block(256);
-  if (C == 96) {
-    if (tt == 2) hipLaunchKernelGGL((proj_cln_bwd_fused_kernel<96, 2>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((proj_cln_bwd_fused_kernel<96, 1>), grid, block, 0, stream, p);
-  } else {
-    hipLaunchKernelGGL((proj_cln_bwd_fused_kernel<192, 1>), grid, block, 0, stream, p);
-  }
-  return scot_check_launch();
+  const TailLaunchPlan p = plan_tail_launch(&TailShape::proj_bwd, true, scot_mlp_tt_override(), C, M, rows_per_sample, kNoHidden);
+  if (p.rc) return p.rc;
+  if (!g || !z || !mean || !rstd || !W || !dz || !da || !norm_bwd_ok(gw_w, gw_b, d_gw_w, d_gw_b, d_bw_w, d_bw_b, nullptr))
+    return SCOT_ERR_SHAPE;
+  const ProjClnBwdArgs pa = {.W = (const bf16_t*)W, .da = (bf16_t*)da,
+                             .b = cln_rows_bwd(g, z, SCOT_F32, mean, rstd, time, gw_w, gw_b, sample_scale, dz, d_gw_w, d_gw_b, d_bw_w, d_bw_b,
+                                               nullptr, M, rows_per_sample),
+                             .use_tr = g_scot_use_tr};
+  return p.shape->proj_bwd(pa, M, stream);
 }
 
-
-// Rows a workgroup of the block tail owns at (C, M, rows_per_sample) — the geometry both directions use; the backward's partial-sum
-// scratch is one row of 4C (2C without conditioning) floats per workgroup and per norm.
-static int tail_rows_per_wg(int C, int M, int rows_per_sample) {
-  const int tt_env = scot_mlp_tt_override();
-  int tt = tt_env ? tt_env : ((C == 96 && M >= 64 * 2 * 512) ? 2 : 1);
-  if (C != 96 || rows_per_sample % (64 * tt) != 0) tt = 1;
-  return 64 * tt;
-}
+// include/scot_hip.h: workgroups of scot_block_tail_bwd = the grid of ITS plan (the forward's may be half of it: it does not need whole
+// tiles per sample).  The backward's partial-sum scratch is one row of 4·Cp (2·Cp without conditioning) floats per workgroup and per norm.
 extern "C" int scot_block_tail_workgroups(int M, int rows_per_sample, int C) {
-  if (M <= 0 || rows_per_sample <= 0 || (C != 96 && C != 192 && C != 48)) return 0;
-  const int r = tail_rows_per_wg(C, M, rows_per_sample);
-  return (M + r - 1) / r;
+  return plan_tail_launch(&TailShape::tail_bwd, true, scot_mlp_tt_override(), C, M, rows_per_sample, kNoHidden).grid;
 }
 
 // out[j] += Σ_b partial[b][j]: finishes the per-workgroup column sums of scot_block_tail_bwd / scot_cln_bwd mode 3 (norm_fast.hip)
@@ -1121,44 +1140,30 @@ extern "C" int scot_block_tail_bwd(const float* g, float* g_out,
                                    /* optional per-workgroup column sums instead of atomics: [workgroups][4C | 2C] each */ float* partial2,
                                    float* partial1,
                                    const float* time, int M, int rows_per_sample, int C, int hid, hipStream_t stream) {
-  if (M <= 0 || rows_per_sample <= 0) return SCOT_ERR_SHAPE;
-  if (C != 96 && C != 192 && C != 48) return SCOT_ERR_UNSUPPORTED;
-  // C = 48 (Poseidon-T / -S stage 0): the stored-gelu' form without the qkv prologue, one 192-wide hidden chunk
-  if (C == 48 && (hid != 192 || dact == nullptr || dqkv != nullptr)) return SCOT_ERR_UNSUPPORTED;
-  if (mlp_chunk(C) != 64 || hid < 64 || hid % 64 != 0 || rows_per_sample % 64 != 0) return SCOT_ERR_UNSUPPORTED;
-  if ((dqkv == nullptr) != (Wqkv == nullptr)) return SCOT_ERR_SHAPE;
+  const TailLaunchPlan p = plan_tail_launch(&TailShape::tail_bwd, true, scot_mlp_tt_override(), C, M, rows_per_sample, hid, false,
+                               /* pro */ dqkv != nullptr, /* recomp */ dact == nullptr);
+  if (p.rc) return p.rc;
+  if (!pair_ok(dqkv, Wqkv)) return SCOT_ERR_SHAPE;
   if (dqkv && g_out != g) return SCOT_ERR_UNSUPPORTED;        // the prologue updates g in place
   if (z_dt != SCOT_F32 && z_dt != SCOT_BF16) return SCOT_ERR_DTYPE;
-  if ((dact == nullptr) && (!h16 || !b1)) return SCOT_ERR_SHAPE;       // nothing to take gelu'(u) from
-  if ((partial2 == nullptr) != (partial1 == nullptr)) return SCOT_ERR_SHAPE;
-  const bool atomics = partial2 == nullptr;
-  if (!g || !g_out || !z2 || !mean2 || !rstd2 || !gw_b2 || !W1 || !W2 || !dz2 || !z1 || !mean1 || !rstd1 || !gw_b1 || !Wo || !dz1 || !da)
+  if (p.recomp && (!h16 || !b1)) return SCOT_ERR_SHAPE;       // nothing to take gelu'(u) from
+  if (!pair_ok(partial2, partial1) || !pair_ok(gw_w1, gw_w2)) return SCOT_ERR_SHAPE;
+  if (!g || !g_out || !z2 || !mean2 || !rstd2 || !W1 || !W2 || !dz2 || !z1 || !mean1 || !rstd1 || !Wo || !dz1 || !da ||
+      !norm_bwd_ok(gw_w2, gw_b2, d_gw_w2, d_gw_b2, d_bw_w2, d_bw_b2, partial2) ||
+      !norm_bwd_ok(gw_w1, gw_b1, d_gw_w1, d_gw_b1, d_bw_w1, d_bw_b1, partial1))
     return SCOT_ERR_SHAPE;
-  if (atomics && (!d_gw_b2 || !d_bw_b2 || !d_gw_b1 || !d_bw_b1)) return SCOT_ERR_SHAPE;
-  if (atomics && ((gw_w2 == nullptr) != (d_gw_w2 == nullptr) || (d_gw_w2 == nullptr) != (d_bw_w2 == nullptr) ||
-                  (gw_w1 == nullptr) != (d_gw_w1 == nullptr) || (d_gw_w1 == nullptr) != (d_bw_w1 == nullptr)))
-    return SCOT_ERR_SHAPE;
-  if ((gw_w1 == nullptr) != (gw_w2 == nullptr)) return SCOT_ERR_SHAPE;
-  const int tt = tail_rows_per_wg(C, M, rows_per_sample) / 64;
-  TailBwdArgs a;
-  a.m.g = g; a.m.g_out = g_out; a.m.z = z2; a.m.z_dt = z_dt; a.m.mean = mean2; a.m.rstd = rstd2; a.m.time = time; a.m.gw_w = gw_w2; a.m.gw_b = gw_b2;
-  a.m.sscale = sscale2; a.m.dact = (const bf16_t*)dact; a.m.W1 = (const bf16_t*)W1; a.m.W2 = (const bf16_t*)W2; a.m.dz = (bf16_t*)dz2;
-  a.m.du = (bf16_t*)du; a.m.d_gw_w = d_gw_w2; a.m.d_gw_b = d_gw_b2; a.m.d_bw_w = d_bw_w2; a.m.d_bw_b = d_bw_b2; a.m.partial = partial2;
-  a.m.h16 = (const bf16_t*)h16; a.m.b1 = b1;
-  a.m.M = M; a.m.rows_per_sample = rows_per_sample; a.m.hid = hid; a.m.use_tr = g_scot_use_tr;
-  a.pj.W = (const bf16_t*)Wo; a.pj.da = (bf16_t*)da; a.pj.use_tr = g_scot_use_tr;
-  a.pj.b.g = g_out; a.pj.b.z = z1; a.pj.b.z_dt = z_dt; a.pj.b.mean = mean1; a.pj.b.rstd = rstd1; a.pj.b.time = time; a.pj.b.gw_w = gw_w1; a.pj.b.gw_b = gw_b1;
-  a.pj.b.sscale = sscale1; a.pj.b.dz = (bf16_t*)dz1; a.pj.b.d_gw_w = d_gw_w1; a.pj.b.d_gw_b = d_gw_b1; a.pj.b.d_bw_w = d_bw_w1;
-  a.pj.b.d_bw_b = d_bw_b1; a.pj.b.partial = partial1; a.pj.b.M = M; a.pj.b.rows_per_sample = rows_per_sample;
-  a.dqkv = (const bf16_t*)dqkv; a.Wqkv = (const bf16_t*)Wqkv;
-  if (C == 48) {
-    hipLaunchKernelGGL((tail_bwd_fused_kernel<48, 192, 1, false, false>), dim3((M + 63) / 64), dim3(256), 0, stream, a);
-    return scot_check_launch();
-  }
-  if (C == 96) return tt == 2 ? launch_tail_bwd<96, 64, 2>(a, stream) : launch_tail_bwd<96, 64, 1>(a, stream);
-  return launch_tail_bwd<192, 64, 1>(a, stream);
+  const TailBwdArgs a = {
+      .m = {.g = g, .g_out = g_out, .z = z2, .z_dt = z_dt, .mean = mean2, .rstd = rstd2, .time = time, .gw_w = gw_w2, .gw_b = gw_b2,
+            .sscale = sscale2, .dact = (const bf16_t*)dact, .W1 = (const bf16_t*)W1, .W2 = (const bf16_t*)W2, .dz = (bf16_t*)dz2,
+            .du = (bf16_t*)du, .d_gw_w = d_gw_w2, .d_gw_b = d_gw_b2, .d_bw_w = d_bw_w2, .d_bw_b = d_bw_b2, .partial = partial2,
+            .h16 = (const bf16_t*)h16, .b1 = b1, .M = M, .rows_per_sample = rows_per_sample, .hid = hid, .use_tr = g_scot_use_tr},
+      .pj = {.W = (const bf16_t*)Wo, .da = (bf16_t*)da,
+             .b = cln_rows_bwd(g_out, z1, z_dt, mean1, rstd1, time, gw_w1, gw_b1, sscale1, dz1, d_gw_w1, d_gw_b1, d_bw_w1, d_bw_b1, partial1, M,
+                               rows_per_sample),
+             .use_tr = g_scot_use_tr},
+      .dqkv = (const bf16_t*)dqkv, .Wqkv = (const bf16_t*)Wqkv};
+  return p.shape->tail_bwd(a, M, p.pro, p.recomp, stream);
 }
-
 
 // include/scot_hip.h: scot_block_tail_fwd = scot_proj_cln_fwd followed by scot_mlp_block_fwd on its output, in one launch.
 extern "C" int scot_block_tail_fwd(/* attention-output half */ const void* a, const void* Wo, const float* bo, const float* x, float* h,
@@ -1171,29 +1176,19 @@ extern "C" int scot_block_tail_fwd(/* attention-output half */ const void* a, co
                                    void* qkv,
                                    /* dtype of z1 / z2: fp32, or the 16-bit operand format (only the backward's x-hat reads them) */ int z_dt,
                                    const float* time, int M, int rows_per_sample, int C, int hid, float eps, hipStream_t stream) {
-  if (M <= 0 || rows_per_sample <= 0) return SCOT_ERR_SHAPE;
-  if (C != 96 && C != 192 && C != 48) return SCOT_ERR_UNSUPPORTED;
-  if (C == 48 && hid != 192) return SCOT_ERR_UNSUPPORTED;     // (one 192-wide hidden chunk: Poseidon-T / -S stage 0, mlp_ratio 4)
-  if (mlp_chunk(C) != 64 || hid < 64 || hid % 64 != 0) return SCOT_ERR_UNSUPPORTED;
+  const TailLaunchPlan p = plan_tail_launch(&TailShape::tail_fwd, false, scot_mlp_tt_override(), C, M, rows_per_sample, hid, /* qkv */ qkv != nullptr);
+  if (p.rc) return p.rc;
   if (z_dt != SCOT_F32 && z_dt != SCOT_BF16) return SCOT_ERR_DTYPE;
-  if (!a || !Wo || !bo || !x || !h || !h16 || !gw_b1 || !bw_b1 || !W1 || !b1 || !W2 || !b2 || !out || !gw_b2 || !bw_b2) return SCOT_ERR_SHAPE;
-  if ((act != nullptr && dact == nullptr) || (mean1 == nullptr) != (rstd1 == nullptr) || (mean2 == nullptr) != (rstd2 == nullptr) ||
-      (gw_w1 == nullptr) != (bw_w1 == nullptr) || (gw_w2 == nullptr) != (bw_w2 == nullptr) || (gw_w1 == nullptr) != (gw_w2 == nullptr))
+  if (!a || !Wo || !bo || !x || !h || !h16 || !W1 || !b1 || !W2 || !b2 || !out || (act && !dact) || !pair_ok(gw_w1, gw_w2) ||
+      !pair_ok(Wqkv, qkv) || !norm_fwd_ok(mean1, rstd1, gw_w1, gw_b1, bw_w1, bw_b1) || !norm_fwd_ok(mean2, rstd2, gw_w2, gw_b2, bw_w2, bw_b2))
     return SCOT_ERR_SHAPE;
-  TailFwdArgs t;
-  t.pj.a = (const bf16_t*)a; t.pj.W = (const bf16_t*)Wo;
-  t.pj.e.bias = bo; t.pj.e.z = z1; t.pj.e.z_dt = z_dt; t.pj.e.mean = mean1; t.pj.e.rstd = rstd1; t.pj.e.time = time; t.pj.e.gw_w = gw_w1; t.pj.e.gw_b = gw_b1;
-  t.pj.e.bw_w = bw_w1; t.pj.e.bw_b = bw_b1; t.pj.e.sscale = sscale1; t.pj.e.resid = x; t.pj.e.out = h; t.pj.e.out16 = (bf16_t*)h16;
-  t.pj.e.M = M; t.pj.e.rows_per_sample = rows_per_sample; t.pj.e.eps = eps;
-  t.m.h16 = (const bf16_t*)h16; t.m.h = h; t.m.W1 = (const bf16_t*)W1; t.m.b1 = b1; t.m.W2 = (const bf16_t*)W2; t.m.b2 = b2;
-  t.m.out = out; t.m.out16 = (bf16_t*)out16; t.m.act = (bf16_t*)act; t.m.dact = (bf16_t*)dact; t.m.z = z2; t.m.z_dt = z_dt; t.m.mean = mean2; t.m.rstd = rstd2;
-  t.m.time = time; t.m.gw_w = gw_w2; t.m.gw_b = gw_b2; t.m.bw_w = bw_w2; t.m.bw_b = bw_b2; t.m.sscale = sscale2;
-  t.m.M = M; t.m.rows_per_sample = rows_per_sample; t.m.hid = hid; t.m.eps = eps;
-  if ((Wqkv == nullptr) != (qkv == nullptr)) return SCOT_ERR_SHAPE;
-  t.Wqkv = (const bf16_t*)Wqkv; t.bqkv = bqkv; t.qkv = (bf16_t*)qkv;
-  const int tt_env = scot_mlp_tt_override();
-  const int tt = C == 96 ? (tt_env ? tt_env : (M >= 64 * 2 * 512 ? 2 : 1)) : 1;
-  if (C == 48) return launch_tail_fwd<48, 192, 1>(t, stream);       // forward only: the backward of these layers stays layer by layer
-  if (C == 96) return tt == 2 ? launch_tail_fwd<96, 64, 2>(t, stream) : launch_tail_fwd<96, 64, 1>(t, stream);
-  return launch_tail_fwd<192, 64, 1>(t, stream);
+  const TailFwdArgs t = {
+      .pj = {.a = (const bf16_t*)a, .W = (const bf16_t*)Wo,
+             .e = cln_rows_out(bo, z1, z_dt, mean1, rstd1, time, gw_w1, gw_b1, bw_w1, bw_b1, sscale1, x, h, h16, M, rows_per_sample, eps)},
+      .m = {.h16 = (const bf16_t*)h16, .h = h, .W1 = (const bf16_t*)W1, .b1 = b1, .W2 = (const bf16_t*)W2, .b2 = b2, .out = out,
+            .out16 = (bf16_t*)out16, .act = (bf16_t*)act, .dact = (bf16_t*)dact, .z = z2, .z_dt = z_dt, .mean = mean2, .rstd = rstd2,
+            .time = time, .gw_w = gw_w2, .gw_b = gw_b2, .bw_w = bw_w2, .bw_b = bw_b2, .sscale = sscale2, .M = M,
+            .rows_per_sample = rows_per_sample, .hid = hid, .eps = eps},
+      .Wqkv = (const bf16_t*)Wqkv, .bqkv = bqkv, .qkv = (bf16_t*)qkv};
+  return p.shape->tail_fwd(t, M, p.qkv, stream);
 }

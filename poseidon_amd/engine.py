@@ -74,6 +74,12 @@ class TailPlan(NamedTuple):
     bwd: str
 
 
+def _selected(entry: str, ok: bool):
+    """a fused entry point the engine's plan chose must not decline: no quiet fall-back to another path"""
+    if not ok:
+        raise RuntimeError(f"{entry} rejected a shape the engine selected it for")
+
+
 class _Token:
     """Lifetime marker of one taped forward call: alive while the caller (the autograd node) can still ask for its backward."""
     __slots__ = ("__weakref__",)
@@ -951,46 +957,41 @@ class ScOTEngine:
         hid = int(cfg.mlp_ratio * C)
         plan = self.tail_plan(blk, B, train)
         qkv_next = None
-        if plan.fwd == "tail":
-            # projection + norm + residual, then MLP + norm + residual, for the same rows in one launch
+        wo, bo = self.W(pre + ".attention.output.dense.weight"), self.P(pre + ".attention.output.dense.bias")
+        if plan.fwd in ("tail", "proj"):
+            # the fused out-projection half (projection + norm + residual) writes the same tensors alone or ahead of the MLP half
             lean = plan.bwd == "lean"
             zdt = self.adt if lean else torch.float32        # pre-norm rows: only the norm backward's x-hat reads them
             proj = self.new(B * L, C, dtype=zdt) if train else None
             st1 = (self.new(B * L), self.new(B * L)) if train else (None, None)
             h, h16 = dead("h", B * L, C), tmp("h16", B * L, C, dtype=self.adt)
+            n1 = self._norm_params(pre + ".layernorm_before")
+        if plan.fwd == "tail":
+            # ... then MLP + norm + residual, for the same rows in the same launch
             u = self.new(B * L, hid, dtype=self.adt) if (train and not lean) else None
             gp = self.new(B * L, hid, dtype=self.adt) if train else None
             y2 = self.new(B * L, C, dtype=zdt) if train else None
             st2 = (self.new(B * L), self.new(B * L)) if train else (None, None)
             out, out16 = nxt("out", B * L, C), nxt16("out16", B * L, C, dtype=self.adt)
-            n1, n2 = self._norm_params(pre + ".layernorm_before"), self._norm_params(pre + ".layernorm_after")
+            n2 = self._norm_params(pre + ".layernorm_after")
             nq = (None, None, None)
             if next_blk is not None and next_blk.dim == C and self.qkv_fusable(next_blk):
                 na = next_blk.prefix + ".attention.self."
                 qkv_next = nxt16("qkvn", B * L, 3 * C, dtype=self.adt)
                 nq = (self.Wspan(na + "qkv_weight", 3 * C * C).view(3 * C, C),
                       self.arena.span(na + "qkv_bias", 3 * C) if cfg.qkv_bias else None, qkv_next)
-            if not ops.block_tail_fwd(
-                    (attn_c, self.W(pre + ".attention.output.dense.weight"), self.P(pre + ".attention.output.dense.bias"), x, h, h16, proj,
-                     st1[0], st1[1], n1[0], n1[1], n1[2], n1[3], dp1),
-                    (self.W(pre + ".intermediate.dense.weight"), self.P(pre + ".intermediate.dense.bias"), self.W(pre + ".output.dense.weight"),
-                     self.P(pre + ".output.dense.bias"), out, out16, u, gp, y2, st2[0], st2[1], n2[0], n2[1], n2[2], n2[3], dp2),
-                    time if self.cond else None, B * L, L, C, hid, cfg.layer_norm_eps, *nq, z16=lean):
-                raise RuntimeError("scot_block_tail_fwd rejected a shape the engine selected it for")
+            _selected("scot_block_tail_fwd", ops.block_tail_fwd(
+                (attn_c, wo, bo, x, h, h16, proj, st1[0], st1[1], *n1, dp1),
+                (self.W(pre + ".intermediate.dense.weight"), self.P(pre + ".intermediate.dense.bias"), self.W(pre + ".output.dense.weight"),
+                 self.P(pre + ".output.dense.bias"), out, out16, u, gp, y2, st2[0], st2[1], *n2, dp2),
+                time if self.cond else None, B * L, L, C, hid, cfg.layer_norm_eps, *nq, z16=lean))
         else:
             if plan.fwd == "proj":
-                proj = self.new(B * L, C) if train else None
-                st1 = (self.new(B * L), self.new(B * L)) if train else (None, None)
-                h, h16 = dead("h", B * L, C), tmp("h16", B * L, C, dtype=self.adt)
-                gw_w, gw_b, bw_w, bw_b = self._norm_params(pre + ".layernorm_before")
-                if not ops.proj_cln_fwd(attn_c, self.W(pre + ".attention.output.dense.weight"), self.P(pre + ".attention.output.dense.bias"),
-                                        x, h, h16, proj, st1[0], st1[1], time if self.cond else None, gw_w, gw_b, bw_w, bw_b, dp1, B * L, L,
-                                        C, cfg.layer_norm_eps):
-                    raise RuntimeError("scot_proj_cln_fwd rejected a shape the engine selected it for")
+                _selected("scot_proj_cln_fwd", ops.proj_cln_fwd(attn_c, wo, bo, x, h, h16, proj, st1[0], st1[1], time if self.cond else None,
+                                                                *n1, dp1, B * L, L, C, cfg.layer_norm_eps))
             else:
                 proj = tmp("proj", B * L, C)
-                ops.linear_fwd(cm, attn_c, self.W(pre + ".attention.output.dense.weight"), proj,
-                               bias=self.P(pre + ".attention.output.dense.bias"))
+                ops.linear_fwd(cm, attn_c, wo, proj, bias=bo)
                 h, h16, st1 = self.norm_fwd(pre + ".layernorm_before", proj, x, L, C, cfg.layer_norm_eps, time, need_stats=train,
                                             copy=True, sample_scale=dp1, out=dead("h", B * L, C), out16=tmp("h16", B * L, C, dtype=self.adt))
             # the MLP layer by layer: the fc1 epilogue emits a = gelu(u) AND gp = gelu'(u) (one erf, fp32 registers); u itself is never stored
@@ -1032,64 +1033,50 @@ class ScOTEngine:
             g = self.dgrad_into(cm, pend[0], pend[1], g, wt=pend[2])
             pend = None
         d_attn = self.pool("d_attn", B * L, C, dtype=adt)      # read by this layer's attention backward (same stream) and by nothing else
-        if plan.bwd == "lean":
-            # the tail without 4C-wide tensors: gelu'(u) recomputed from h16, du never stored, the norms' parameter gradients as
-            # per-workgroup partial rows; on the weight-gradient stream: the partial rows' column sums, the fc1 / fc2 gradients with
-            # gelu(u) / du recomputed (scot_wgrad_mlp), the out-projection's (and, below, the qkv projection's) through the grouped GEMM
-            d_y2, d_proj = self.new(B * L, C, dtype=adt), self.new(B * L, C, dtype=adt)
+        if plan.bwd in ("lean", "tail"):
+            # both halves of the block tail in one launch: the residual-stream gradient between them stays in registers.  lean: without
+            # 4C-wide tensors — gelu'(u) recomputed from h16, du never stored, the norms' parameter gradients as per-workgroup partial rows;
+            # then on the weight-gradient stream: the partial rows' column sums, the fc1 / fc2 gradients with gelu(u) / du recomputed
+            # (scot_wgrad_mlp), the out-projection's (and, below, the qkv projection's) through the grouped GEMM
+            lean = plan.bwd == "lean"
+            d_y2 = self.new(B * L, C, dtype=adt)
+            d_u = None if lean else self.new(B * L, hid, dtype=adt)
+            d_proj = self.new(B * L, C, dtype=adt)
             n2, n1 = self._norm_params(pre + ".layernorm_after"), self._norm_params(pre + ".layernorm_before")
             g2, g1 = self._norm_grads(pre + ".layernorm_after"), self._norm_grads(pre + ".layernorm_before")
-            nwg, ncol = ops.tail_workgroups(B * L, L, C), (4 if self.cond else 2) * ((C + 63) // 64 * 64)
-            part2, part1 = self.new(nwg, ncol), self.new(nwg, ncol)
-            w1n, w2n = pre + ".intermediate.dense.weight", pre + ".output.dense.weight"
-            b1 = self.P(pre + ".intermediate.dense.bias")
+            w1n, w2n, won = pre + ".intermediate.dense.weight", pre + ".output.dense.weight", pre + ".attention.output.dense.weight"
+            form = {}
+            if lean:
+                nwg, ncol = ops.tail_workgroups(B * L, L, C), (4 if self.cond else 2) * ((C + 63) // 64 * 64)
+                part2, part1 = self.new(nwg, ncol), self.new(nwg, ncol)
+                b1 = self.P(pre + ".intermediate.dense.bias")
+                form = dict(h16=rec["h16"], b1=b1, z16=True, partial2=part2, partial1=part1)
+            ng2, ng1 = ((None,) * 4, (None,) * 4) if lean else (g2, g1)
             self.dtime(pre + ".layernorm_after", g, rec["y2"], rec["st2"], L, C, rec["dp"][1])
-            if not ops.block_tail_bwd(
-                    g, g,
-                    (rec["y2"], rec["st2"][0], rec["st2"][1], n2[0], n2[1], rec["dp"][1], rec["gp"], self.W(w1n), self.W(w2n), d_y2, None,
-                     None, None, None, None),
-                    (rec["proj"], rec["st1"][0], rec["st1"][1], n1[0], n1[1], rec["dp"][0], self.W(pre + ".attention.output.dense.weight"),
-                     d_proj, d_attn, None, None, None, None),
-                    time if self.cond else None, B * L, L, C, hid, dqkv=pend[0] if pend else None, wqkv=pend[1] if pend else None,
-                    h16=rec["h16"], b1=b1, z16=True, partial2=part2, partial1=part1):
-                raise RuntimeError("scot_block_tail_bwd rejected a shape the engine selected it for")
+            _selected("scot_block_tail_bwd", ops.block_tail_bwd(
+                g, g,
+                (rec["y2"], rec["st2"][0], rec["st2"][1], n2[0], n2[1], rec["dp"][1], rec["gp"], self.W(w1n), self.W(w2n), d_y2, d_u, *ng2),
+                (rec["proj"], rec["st1"][0], rec["st1"][1], n1[0], n1[1], rec["dp"][0], self.W(won), d_proj, d_attn, *ng1),
+                time if self.cond else None, B * L, L, C, hid, dqkv=pend[0] if pend else None, wqkv=pend[1] if pend else None, **form))
             pend = None
             self.dtime(pre + ".layernorm_before", g, rec["proj"], rec["st1"], L, C, rec["dp"][0])      # (g is g_out now)
-            first2, first1 = next(t for t in g2 if t is not None), next(t for t in g1 if t is not None)
-            h16r, w2t = rec["h16"], self.WT(w2n)
-            gW1, gb1, gW2, gb2 = self.G(w1n), self.G(pre + ".intermediate.dense.bias"), self.G(w2n), self.G(pre + ".output.dense.bias")
+            if lean:
+                first2, first1 = next(t for t in g2 if t is not None), next(t for t in g1 if t is not None)
+                h16r, w2t = rec["h16"], self.WT(w2n)
+                gW1, gb1, gW2, gb2 = self.G(w1n), self.G(pre + ".intermediate.dense.bias"), self.G(w2n), self.G(pre + ".output.dense.bias")
+                if self._pgr:
+                    self._finq += [(part2, nwg, ncol, first2), (part1, nwg, ncol, first1)]
+                mlp_mode = self.grad_mode(gW1)
+                assert mlp_mode == self.grad_mode(gW2)
 
-            if self._pgr:
-                self._finq += [(part2, nwg, ncol, first2), (part1, nwg, ncol, first1)]
-
-            mlp_mode = self.grad_mode(gW1)
-            assert mlp_mode == self.grad_mode(gW2)
-
-            def side():
-                if not ops.wgrad_mlp(h16r, d_y2, self.W(w1n), b1, w2t, gW1, gb1, gW2, gb2, mode=mlp_mode,
-                                     grad_scale=self.grad_unscale() if mlp_mode != ops.GRAD_ADD else None):
-                    raise RuntimeError("scot_wgrad_mlp rejected a shape the engine selected it for")
-            self.off_critical_path(side, h16r, d_y2)
-            self.linear_bwd_params(pre + ".attention.output.dense.weight", pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
-        elif plan.bwd == "tail":
-            # both halves of the block tail in one launch: the residual-stream gradient between them stays in registers
-            d_y2, d_u, d_proj = self.new(B * L, C, dtype=adt), self.new(B * L, hid, dtype=adt), self.new(B * L, C, dtype=adt)
-            n2, g2 = self._norm_params(pre + ".layernorm_after"), self._norm_grads(pre + ".layernorm_after")
-            n1, g1 = self._norm_params(pre + ".layernorm_before"), self._norm_grads(pre + ".layernorm_before")
-            self.dtime(pre + ".layernorm_after", g, rec["y2"], rec["st2"], L, C, rec["dp"][1])
-            if not ops.block_tail_bwd(
-                    g, g,
-                    (rec["y2"], rec["st2"][0], rec["st2"][1], n2[0], n2[1], rec["dp"][1], rec["gp"], self.W(pre + ".intermediate.dense.weight"),
-                     self.W(pre + ".output.dense.weight"), d_y2, d_u, g2[0], g2[1], g2[2], g2[3]),
-                    (rec["proj"], rec["st1"][0], rec["st1"][1], n1[0], n1[1], rec["dp"][0], self.W(pre + ".attention.output.dense.weight"),
-                     d_proj, d_attn, g1[0], g1[1], g1[2], g1[3]),
-                    time if self.cond else None, B * L, L, C, hid, dqkv=pend[0] if pend else None, wqkv=pend[1] if pend else None):
-                raise RuntimeError("scot_block_tail_bwd rejected a shape the engine selected it for")
-            pend = None
-            self.dtime(pre + ".layernorm_before", g, rec["proj"], rec["st1"], L, C, rec["dp"][0])      # (g is g_out now)
-            self.linear_bwd_params(pre + ".output.dense.weight", pre + ".output.dense.bias", d_y2, rec["u"])
-            self.linear_bwd_params(pre + ".intermediate.dense.weight", pre + ".intermediate.dense.bias", d_u, rec["h16"])
-            self.linear_bwd_params(pre + ".attention.output.dense.weight", pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
+                def side():
+                    _selected("scot_wgrad_mlp", ops.wgrad_mlp(h16r, d_y2, self.W(w1n), b1, w2t, gW1, gb1, gW2, gb2, mode=mlp_mode,
+                                                              grad_scale=self.grad_unscale() if mlp_mode != ops.GRAD_ADD else None))
+                self.off_critical_path(side, h16r, d_y2)
+            else:
+                self.linear_bwd_params(w2n, pre + ".output.dense.bias", d_y2, rec["u"])
+                self.linear_bwd_params(w1n, pre + ".intermediate.dense.bias", d_u, rec["h16"])
+            self.linear_bwd_params(won, pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
         else:
             # the MLP layer by layer — out = h + CLN_after(y2)
             d_y2 = self.norm_bwd(pre + ".layernorm_after", g, rec["y2"], rec["st2"], L, C, time, adt, sample_scale=rec["dp"][1])
@@ -1107,10 +1094,9 @@ class ScOTEngine:
                 gw_w, gw_b, _, _ = self._norm_params(pre + ".layernorm_before")
                 gg = self._norm_grads(pre + ".layernorm_before")
                 self.dtime(pre + ".layernorm_before", g, rec["proj"], rec["st1"], L, C, rec["dp"][0])
-                if not ops.proj_cln_bwd(g, rec["proj"], rec["st1"][0], rec["st1"][1], time if self.cond else None, gw_w, gw_b, rec["dp"][0],
-                                        self.W(pre + ".attention.output.dense.weight"), d_proj, d_attn, gg[0], gg[1], gg[2], gg[3], B * L,
-                                        L, C):
-                    raise RuntimeError("scot_proj_cln_bwd rejected a shape the engine selected it for")
+                _selected("scot_proj_cln_bwd", ops.proj_cln_bwd(g, rec["proj"], rec["st1"][0], rec["st1"][1], time if self.cond else None, gw_w,
+                                                                gw_b, rec["dp"][0], self.W(pre + ".attention.output.dense.weight"), d_proj, d_attn,
+                                                                *gg, B * L, L, C))
                 self.linear_bwd_params(pre + ".attention.output.dense.weight", pre + ".attention.output.dense.bias", d_proj, rec["attn_c"])
             else:
                 d_proj = self.norm_bwd(pre + ".layernorm_before", g, rec["proj"], rec["st1"], L, C, time, adt, sample_scale=rec["dp"][0])

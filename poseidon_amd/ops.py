@@ -421,7 +421,9 @@ def replay_tape(segs):
 
 
 def tail_workgroups(rows, rows_per_sample, C) -> int:
-    """workgroups of block_tail_fwd / _bwd at these dimensions = rows of the backward's partial-sum matrices (0: not covered)"""
+    """workgroups of block_tail_bwd — the BACKWARD's grid — at these dimensions = rows of its partial-sum matrices (0: not covered).
+    Not the forward's: at C = 96, rows >= 65536 and rows_per_sample % 128 != 0 block_tail_fwd runs 128-row workgroups (it needs no
+    per-workgroup conditioning time) while the backward runs 64-row ones."""
     return int(_raw().scot_block_tail_workgroups(rows, rows_per_sample, C))
 
 

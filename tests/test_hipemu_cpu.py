@@ -30,6 +30,7 @@ def emu(tmp_path_factory):
 CASES = [  # case, C, B, L, cond, train, use_tr, SCOT_MLP_TT (16-row tiles per wave)
     ("mlp_fwd", 96, 1, 128, 1, 1, 1, 2), ("mlp_fwd", 96, 1, 100, 0, 1, 1, 1), ("mlp_bwd", 96, 1, 128, 1, 1, 1, 2),
     ("mlp_bwd", 96, 1, 64, 0, 1, 0, 1), ("proj_fwd", 96, 1, 128, 0, 0, 1, 2), ("proj_bwd", 96, 1, 128, 1, 1, 1, 2),
+    ("proj_bwd", 96, 1, 192, 1, 1, 1, 3),    # a value other than 1 / 2 counts as unset: every 64-row tile of the 192 rows is processed
 ]
 
 

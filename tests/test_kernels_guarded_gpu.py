@@ -1113,6 +1113,9 @@ def test_cln_constant_row(xdt, B, L, C):
 
 # ================================================================================================================ fused layer tails
 TAIL_CASES = [(kind, C, B, L) for kind in ("bf16", "f16") for C, B, L in ((48, 3, 200), (48, 2, 1024), (96, 3, 200), (96, 2, 1024), (192, 5, 72), (192, 2, 256))]
+# C = 96 from 65536 rows on runs 128-row workgroups: M at that threshold, and M = 65664 with L % 128 != 0, where the forward runs 128-row
+# workgroups and the backward 64-row ones with partial-sum matrices sized by scot_block_tail_workgroups
+TAIL_CASES_128 = [(kind, 96, B, L) for kind in ("bf16", "f16") for B, L in ((64, 1024), (342, 192))]
 
 
 def _tail_inputs(C, B, L, cond, hd):
@@ -1135,6 +1138,7 @@ def _tail_inputs(C, B, L, cond, hd):
 # the lean form (16-bit z, no 4C-wide saves) is a training form of C = 96 / 192
 TAIL_FWD = [(*c, train, cond, nq, lean) for c in TAIL_CASES for train, cond, nq in ((True, True, True), (True, False, False), (False, True, False), (False, False, True))
             for lean in (False, True) if not (lean and (c[1] == 48 or not train))]
+TAIL_FWD += [(*c, True, True, True, lean) for c in TAIL_CASES_128 for lean in (False, True)]
 
 
 @pytest.mark.parametrize("kind,C,B,L,train,cond,next_qkv,lean", TAIL_FWD)
@@ -1185,6 +1189,7 @@ def block_tail_fwd_guarded(kind, C, B, L, train, cond, next_qkv, lean):
 # samples of whole 64-row tiles: guarded launches of the backward.  C = 48 has the stored-gelu' form only.
 TAIL_BWD = [(*c, cond, form) for c in [t for t in TAIL_CASES if t[3] % 64 == 0] + [(k, C, 3, 192) for k in ("bf16", "f16") for C in (48, 96, 192)]
             for cond in (True, False) for form in ("stored", "prologue", "lean") if not (c[1] == 48 and form != "stored")]
+TAIL_BWD += [(*c, True, form) for c in TAIL_CASES_128 for form in ("stored", "lean")]
 # ragged samples (L = 200, 72): NOT launches of the backward — the entry point must decline them (-3) and write nothing anywhere
 TAIL_BWD_DECLINED = [(*c, True, "stored") for c in TAIL_CASES if c[3] % 64]
 
