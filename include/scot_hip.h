@@ -26,8 +26,9 @@ typedef struct ihipStream_t* scot_stream_t; /* = hipStream_t */
 #define SCOT_LAYOUT_NN 1 /* C[M,N] = A[M,K] B[K,N]   : dgrad of nn.Linear; ConvTranspose2d k=s (ref:616-621)      */
 #define SCOT_LAYOUT_TN 2 /* C[M,N] += A[K,M]^T B[K,N] : wgrad of nn.Linear (autograd of the above)                 */
 
-int scot_abi_version(void);   /* 6 (round 6: 4 = scot_wgrad_group / scot_wgrad_mlp modes, scot_segments_scale, scot_gemm_splitk_config; 5 = scot_dp_init .. finalize;
-                                 6 = scot_cln_dtime, scot_zero_masked, scot_add_channels); the bindings check it at load */
+int scot_abi_version(void);   /* 7 (round 6: 4 = scot_wgrad_group / scot_wgrad_mlp modes, scot_segments_scale, scot_gemm_splitk_config; 5 = scot_dp_init .. finalize;
+                                 6 = scot_cln_dtime, scot_zero_masked, scot_add_channels; 7 = scot_gemm_route, scot_wgrad_group_route,
+                                 scot_block_tail_route, scot_route_table); the bindings check it at load */
 /* Format of dtype code 1 in THIS build of the library: 0 = bfloat16 (libscot_hip.so), 1 = IEEE binary16 (libscot_hip_f16.so, the
  * same sources compiled with -DSCOT_OPERAND_FP16).  The reference computes in fp32 (ref:1318-1509); 16-bit operands are this
  * library's choice and binary16 is the one that keeps ScOT.forward within 1e-3 of it. */
@@ -176,6 +177,55 @@ int scot_wgrad_group(int compute, int n, int K, const void* const* dY, const voi
 /* nsplit · Σ M_i N_i · 4 bytes for the K split scot_wgrad_group chooses for these shapes (0: unsplit, or shapes it does not cover).
  * With less it splits less; with none and a split wanted it returns -3. */
 size_t scot_wgrad_group_workspace_bytes(int n, int K, const int* M, const int* N);
+
+/* Route queries: which kernel a launch WOULD run.  Each takes the arguments of the entry point it mirrors (no stream), calls the same
+ * planner that entry point calls, fills route[0 .. SCOT_ROUTE_INTS) and launches nothing.  No device memory is read: a pointer matters
+ * only through being NULL or not and through its alignment.  The return value is 0 unless `route` is NULL; a call the entry point
+ * would refuse is reported in route[0] as its negative status.  For tests and tools, not on the step's path.
+ *
+ * scot_gemm_route:
+ *   [0] family (SCOT_ROUTE_PANEL / WIDE / FAST / GENERIC: csrc/gemm_panel.hip, gemm_wide.hip, gemm_fast.hip, gemm.hip) or scot_gemm's status
+ *   [1] PANEL: 16-column fragments per resident panel (3 or 6); WIDE: kernel variant (scot_gemm_wide_config); FAST: row of kFastTiles
+ *       (csrc/gemm_fast.hip); GENERIC: 0 = 16-bit MFMA, 1 = fp32 MFMA
+ *   [2] bm  [3] bn  [4] bk     the tile (PANEL: rows per wave step, panel columns, K per chunk)
+ *   [5] K slices   [6] commit: 0 = the fused epilogue stores, 1 = C += by the tile's one owner, 2 = partial tiles in the workspace + one
+ *       reduce pass, 3 = fp32 atomics   [7] WIDE: epilogue class 0 none, 1 16-bit aux, 2 fp32 residual   [8] FAST, commit 2: lanes per
+ *       8 results of the reduce pass
+ * scot_wgrad_group_route:
+ *   [0] scot_wgrad_group's status (0: it runs)   [1] kernel: 0 = 64 x 64 tiles, four waves, 1 = 64 x 64 with two K groups (eight waves),
+ *       2 = 96 x 96, 3 = 128 x 128 (csrc/wgrad_wide.hip)   [2] its variant for kernel 3, else -1   [3] K slices   [4] lanes per 8 results of
+ *       the grouped reduce pass   [5] workspace bytes written / 256   [6] tile edge   [7] output tiles of the group
+ * scot_block_tail_route (family: SCOT_TAIL_*; hid is ignored by the two projection halves; qkv / pro / recomp: scot_block_tail_fwd's
+ * next-layer qkv epilogue, scot_block_tail_bwd's qkv-dgrad prologue and gelu' recomputation, 0 elsewhere):
+ *   [0] the entry point's status from its shapes (0: it runs)   [1] C  [2] HC  [3] TT: the row of the instantiation table
+ *       (csrc/mlp_fused.hip)   [4] workgroups   [5] qkv  [6] pro  [7] recomp   ([1]-[4] are 0 when no row exists) */
+#define SCOT_ROUTE_INTS 12
+#define SCOT_ROUTE_PANEL 0
+#define SCOT_ROUTE_WIDE 1
+#define SCOT_ROUTE_FAST 2
+#define SCOT_ROUTE_GENERIC 3
+#define SCOT_TAIL_MLP_FWD 0
+#define SCOT_TAIL_MLP_BWD 1
+#define SCOT_TAIL_PROJ_FWD 2
+#define SCOT_TAIL_PROJ_BWD 3
+#define SCOT_TAIL_FWD 4
+#define SCOT_TAIL_BWD 5
+int scot_gemm_route(int layout, int compute, int M, int N, int K,
+                    const void* A, int a_dt, int lda, int a_gelu,
+                    const void* B, int b_dt, int ldb, int b_gelu,
+                    void* C, int c_dt, int ldc,
+                    const float* bias, const float* colscale,
+                    const void* aux, int aux_dt, int ldaux,
+                    const void* resid, int res_dt, int ldres,
+                    int accumulate, float* colsum_out, void* workspace, size_t ws_bytes, int aux_mul, void* C2, int* route);
+int scot_wgrad_group_route(int compute, int n, int K, const void* const* dY, const void* const* X, float* const* dW,
+                           float* const* dbias, const int* M, const int* N, void* workspace, size_t ws_bytes, const int* modes,
+                           const float* grad_scale, int* route);
+int scot_block_tail_route(int family, int C, int M, int rows_per_sample, int hid, int qkv, int pro, int recomp, int* route);
+/* The rows those routes can name, one per call: table 0 = the tile table of csrc/gemm_fast.hip ([1] bm [2] bn [3] bk [4] bit l set: a kernel
+ * exists for layout l), 1 = the instantiation table of csrc/mlp_fused.hip ([1] C [2] HC [3] TT [4] bit f set: family SCOT_TAIL_f exists),
+ * 2 = the 128 x 128 kernel variants, 3 = the grouped weight-gradient kernels.  [0] = 1, or 0 past the table's end. */
+int scot_route_table(int table, int row, int* route);
 
 /* Shifted-window cosine attention, HF:389-455 + ref:522-559 (roll/partition/mask folded into indexing).
  * qkv: [batch*Hp*Wp][3C] (q|k|v) in the compute dtype; out: [batch*Hp*Wp][C]; lse: [batch*nW][heads][ws*ws] f32;

@@ -21,6 +21,12 @@
 #define SCOT_BF16 1
 #define SCOT_BF16X3 2   /* compute mode only (never a storage dtype): fp32 operands, hi/lo bf16 split, 3 MFMAs per K-step */
 
+/* scot_*_route (include/scot_hip.h): ints per answer, and the families of scot_gemm_route */
+#define SCOT_ROUTE_INTS 12
+#define SCOT_ROUTE_PANEL 0
+#define SCOT_ROUTE_WIDE 1
+#define SCOT_ROUTE_FAST 2
+#define SCOT_ROUTE_GENERIC 3
 #define SCOT_OK 0
 #define SCOT_ERR_SHAPE (-1)
 #define SCOT_ERR_DTYPE (-2)

@@ -214,9 +214,31 @@ static int launch_layout(const GemmArgs& a, int layout, int nsplit, hipStream_t 
 
 extern "C" int scot_colsum(const void* x, int x_dt, const void* y, int y_dt, float* out, int M, int N, int ld, hipStream_t s);
 
-// The last candidate: one 64 x 64 tile shape, any alignment, mixed operand dtypes, GELU on load.
-int scot_gemm_generic(const GemmCall& c, hipStream_t stream) {
+// The last candidate: one 64 x 64 tile shape, any alignment, mixed operand dtypes, GELU on load.  Pure: SCOT_OK and the K slices, or the
+// status scot_gemm answers for a call that no family takes.
+int plan_generic(const GemmCall& c, GenericPlan& p) {
   if (c.C2 && c.layout == LAYOUT_TN) return SCOT_ERR_UNSUPPORTED;
+  p.nsplit = 1;
+  p.atomic = 0;
+  p.ksplit = ((c.K + 31) / 32) * 32;
+  if (c.layout == LAYOUT_TN) {
+    // wgrad: tiny output, huge K (= tokens) → split K so that >= ~512 workgroups exist; fp32 atomics into C.
+    if (c.c_dt != SCOT_F32) return SCOT_ERR_DTYPE;
+    const long tiles = (long)((c.M + 127) / 128) * ((c.N + 95) / 96);
+    long want = (768 + tiles - 1) / tiles;
+    long maxsplit = (c.K + 255) / 256;
+    int nsplit = (int)(want < 1 ? 1 : (want > maxsplit ? maxsplit : want));
+    int per = (c.K + nsplit - 1) / nsplit;
+    per = ((per + 31) / 32) * 32;
+    p.ksplit = per;
+    p.nsplit = (c.K + per - 1) / per;
+    p.atomic = 1;
+    if (!c.accumulate) return SCOT_ERR_UNSUPPORTED;  // caller zeroes C (gradient arena semantics: +=)
+  }
+  return SCOT_OK;
+}
+
+int scot_gemm_generic(const GemmCall& c, const GenericPlan& p, hipStream_t stream) {
   GemmArgs a;
   a.A = c.A; a.B = c.B; a.C = c.C; a.bias = c.bias; a.colscale = c.colscale; a.aux = c.aux; a.resid = c.resid;
   a.M = c.M; a.N = c.N; a.K = c.K; a.lda = c.lda; a.ldb = c.ldb; a.ldc = c.ldc; a.ldaux = c.ldaux; a.ldres = c.ldres;
@@ -225,27 +247,13 @@ int scot_gemm_generic(const GemmCall& c, hipStream_t stream) {
   a.C2 = c.C2; a.aux_mul = c.aux_mul;
   a.a_vec = aligned16(c.A) && c.lda % 8 == 0;
   a.b_vec = aligned16(c.B) && c.ldb % 8 == 0;
-  int nsplit = 1;
-  a.atomic = 0;
-  a.ksplit = ((c.K + 31) / 32) * 32;
-  if (c.layout == LAYOUT_TN) {
-    // wgrad: tiny output, huge K (= tokens) → split K so that >= ~512 workgroups exist; fp32 atomics into C.
-    if (c.c_dt != SCOT_F32) return SCOT_ERR_DTYPE;
-    const long tiles = (long)((c.M + 127) / 128) * ((c.N + 95) / 96);
-    long want = (768 + tiles - 1) / tiles;
-    long maxsplit = (c.K + 255) / 256;
-    nsplit = (int)(want < 1 ? 1 : (want > maxsplit ? maxsplit : want));
-    int per = (c.K + nsplit - 1) / nsplit;
-    per = ((per + 31) / 32) * 32;
-    a.ksplit = per;
-    nsplit = (c.K + per - 1) / per;
-    a.atomic = 1;
-    if (!c.accumulate) return SCOT_ERR_UNSUPPORTED;  // caller zeroes C (gradient arena semantics: +=)
-  } else {
+  a.atomic = p.atomic;
+  a.ksplit = p.ksplit;
+  if (c.layout != LAYOUT_TN) {
     const GemmResid r = gemm_resid(c);
     a.resid = r.p; a.res_dt = r.dt; a.ldres = r.ld;
   }
-  int rc = c.compute == SCOT_BF16 ? launch_layout<bf16_t, 64, 64>(a, c.layout, nsplit, stream) : launch_layout<float, 64, 64>(a, c.layout, nsplit, stream);
+  int rc = c.compute == SCOT_BF16 ? launch_layout<bf16_t, 64, 64>(a, c.layout, p.nsplit, stream) : launch_layout<float, 64, 64>(a, c.layout, p.nsplit, stream);
   if (rc == SCOT_OK && c.colsum_out) {   // this kernel has no column sums of its own: a second launch
     if (c.layout == LAYOUT_TN) rc = scot_colsum(c.A, c.a_dt, nullptr, 0, c.colsum_out, c.K, c.M, c.lda, stream);  // Σ_k A[k][m]
     else rc = scot_colsum(c.C, c.c_dt, nullptr, 0, c.colsum_out, c.M, c.N, c.ldc, stream);
@@ -253,26 +261,89 @@ int scot_gemm_generic(const GemmCall& c, hipStream_t stream) {
   return rc;
 }
 
-extern "C" int scot_gemm(int layout, int compute, int M, int N, int K,
-                         const void* A, int a_dt, int lda, int a_gelu,
-                         const void* B, int b_dt, int ldb, int b_gelu,
-                         void* C, int c_dt, int ldc,
-                         const float* bias, const float* colscale,
-                         const void* aux, int aux_dt, int ldaux,
-                         const void* resid, int res_dt, int ldres,
-                         int accumulate, float* colsum_out, void* workspace, size_t ws_bytes, int aux_mul, void* C2,
-                         hipStream_t stream) {
+// The arguments of scot_gemm as a GemmCall, validated: SCOT_OK, or the status the call gets before any family is asked.
+#define SCOT_GEMM_PARAMS                                                                                                        \
+  int layout, int compute, int M, int N, int K, const void *A, int a_dt, int lda, int a_gelu, const void *B, int b_dt, int ldb, \
+      int b_gelu, void *C, int c_dt, int ldc, const float *bias, const float *colscale, const void *aux, int aux_dt, int ldaux,  \
+      const void *resid, int res_dt, int ldres, int accumulate, float *colsum_out, void *workspace, size_t ws_bytes, int aux_mul, \
+      void *C2
+#define SCOT_GEMM_ARGS                                                                                                            \
+  layout, compute, M, N, K, A, a_dt, lda, a_gelu, B, b_dt, ldb, b_gelu, C, c_dt, ldc, bias, colscale, aux, aux_dt, ldaux, resid, \
+      res_dt, ldres, accumulate, colsum_out, workspace, ws_bytes, aux_mul, C2
+static int gemm_call(SCOT_GEMM_PARAMS, GemmCall& c) {
   if (M <= 0 || N <= 0 || K <= 0) return SCOT_ERR_SHAPE;
   if (layout < 0 || layout > 2 || compute < 0 || compute > SCOT_BF16X3) return SCOT_ERR_UNSUPPORTED;
   if ((a_dt | b_dt | c_dt) & ~1) return SCOT_ERR_DTYPE;
   if (compute == SCOT_BF16X3 && (a_dt != SCOT_F32 || b_dt != SCOT_F32)) return SCOT_ERR_DTYPE;   // bf16x3 splits fp32 operands
   // C += result is "the residual is C" in every NT / NN kernel (gemm_resid), so a call that names a residual as well has no kernel
   if (layout != LAYOUT_TN && accumulate && resid != nullptr) return SCOT_ERR_UNSUPPORTED;
-  const GemmCall c = {layout, compute, M, N, K, A, a_dt, lda, a_gelu, B, b_dt, ldb, b_gelu, C, c_dt, ldc, bias, colscale,
-                      aux, aux_dt, ldaux, resid, res_dt, ldres, accumulate, colsum_out, workspace, ws_bytes, aux_mul, C2};
-  int rc = scot_gemm_panel(c, stream);
-  if (rc == SCOT_ERR_UNSUPPORTED) rc = scot_gemm_wide(c, stream);
-  if (rc == SCOT_ERR_UNSUPPORTED) rc = scot_gemm_fast(c, stream);
-  if (rc == SCOT_ERR_UNSUPPORTED) rc = scot_gemm_generic(c, stream);
-  return rc;
+  c = GemmCall{SCOT_GEMM_ARGS};
+  return SCOT_OK;
+}
+
+// Which family runs a call, and its plan: the first of the four whose planner accepts.  `family` < 0: the status scot_gemm answers.
+struct GemmPlan { int family; PanelPlan panel; WidePlan wide; FastPlan fast; GenericPlan generic; };
+static GemmPlan plan_gemm(const GemmCall& c) {
+  GemmPlan g = {};
+  if (plan_panel(c, g.panel)) g.family = SCOT_ROUTE_PANEL;
+  else if (plan_wide(c, g.wide)) g.family = SCOT_ROUTE_WIDE;
+  else if (plan_fast_call(c, g.fast)) g.family = SCOT_ROUTE_FAST;
+  else { const int rc = plan_generic(c, g.generic); g.family = rc == SCOT_OK ? SCOT_ROUTE_GENERIC : rc; }
+  return g;
+}
+
+extern "C" int scot_gemm(SCOT_GEMM_PARAMS, hipStream_t stream) {
+  GemmCall c;
+  const int rc = gemm_call(SCOT_GEMM_ARGS, c);
+  if (rc != SCOT_OK) return rc;
+  const GemmPlan g = plan_gemm(c);
+  switch (g.family) {
+    case SCOT_ROUTE_PANEL: return scot_gemm_panel(c, g.panel, stream);
+    case SCOT_ROUTE_WIDE: return scot_gemm_wide(c, g.wide, stream);
+    case SCOT_ROUTE_FAST: return scot_gemm_fast(c, g.fast, stream);
+    case SCOT_ROUTE_GENERIC: return scot_gemm_generic(c, g.generic, stream);
+    default: return g.family;
+  }
+}
+
+// include/scot_hip.h: scot_gemm_route — plan_gemm's answer for the same arguments; nothing is launched, no pointer is read.
+extern "C" int scot_gemm_route(SCOT_GEMM_PARAMS, int* route) {
+  if (!route) return SCOT_ERR_SHAPE;
+  for (int i = 0; i < SCOT_ROUTE_INTS; ++i) route[i] = 0;
+  GemmCall c;
+  const int rc = gemm_call(SCOT_GEMM_ARGS, c);
+  if (rc != SCOT_OK) { route[0] = rc; return SCOT_OK; }
+  const GemmPlan g = plan_gemm(c);
+  route[0] = g.family;
+  route[5] = 1;
+  switch (g.family) {
+    case SCOT_ROUTE_PANEL:      // a wave walks 32-row groups against a resident panel of nf 16-column fragments, 96 K elements per chunk
+      route[1] = g.panel.nf; route[2] = 32; route[3] = 16 * g.panel.nf; route[4] = 96; route[6] = COMMIT_EPILOGUE; break;
+    case SCOT_ROUTE_WIDE:
+      route[1] = g.wide.variant; route[2] = 128; route[3] = 128; route[4] = 64; route[6] = COMMIT_EPILOGUE; route[7] = g.wide.epi; break;
+    case SCOT_ROUTE_FAST:
+      fast_tile_of(g.fast, &route[1], &route[2], &route[3], &route[4]);
+      route[5] = g.fast.nsplit; route[6] = g.fast.commit; route[8] = g.fast.zl; break;
+    case SCOT_ROUTE_GENERIC:    // row: 0 = the 16-bit MFMA instantiation, 1 = the fp32 one (fp32 and bf16x3 compute)
+      route[1] = c.compute == SCOT_BF16 ? 0 : 1; route[2] = 64; route[3] = 64; route[4] = BK;
+      route[5] = g.generic.nsplit; route[6] = g.generic.atomic ? COMMIT_ATOMIC : COMMIT_EPILOGUE; break;
+    default: break;
+  }
+  return SCOT_OK;
+}
+
+// include/scot_hip.h: scot_route_table — the rows a route can name, so that a test can hold every one of them to a case
+extern "C" int scot_route_table(int table, int row, int* route) {
+  if (!route) return SCOT_ERR_SHAPE;
+  for (int i = 0; i < SCOT_ROUTE_INTS; ++i) route[i] = 0;
+  bool ok = false;
+  switch (table) {
+    case 0: ok = fast_table_row(row, route); break;
+    case 1: ok = tail_table_row(row, route); break;
+    case 2: ok = row >= 0 && row < 3; break;      // gemm_wide.hip's instantiations (WIDE_V_*), also the grouped 128 x 128 kernel's
+    case 3: ok = row >= 0 && row < 4; break;      // the grouped weight-gradient kernels (GROUP_*)
+    default: break;
+  }
+  route[0] = ok ? 1 : 0;
+  return SCOT_OK;
 }

@@ -37,10 +37,32 @@ inline bool ld_vectors(const GemmCall& c, int epc) {
   return c.lda % epc == 0 && c.ldb % epc == 0 && c.ldc % 8 == 0 && !(c.aux && c.ldaux % 8) && !(c.resid && c.ldres % 8);
 }
 
-// The candidates, in the order scot_gemm asks them (gemm.hip says why).  SCOT_ERR_UNSUPPORTED = "not mine, ask the next".
-int scot_gemm_panel(const GemmCall& c, hipStream_t stream);     // gemm_panel.hip
-int scot_gemm_wide(const GemmCall& c, hipStream_t stream);      // gemm_wide.hip
-int scot_gemm_fast(const GemmCall& c, hipStream_t stream);      // gemm_fast.hip
-int scot_gemm_generic(const GemmCall& c, hipStream_t stream);   // gemm.hip
+// The candidates, in the order plan_gemm (gemm.hip) asks them.  Every family has a pure planner — shapes, dtypes, flags, which operands are
+// present and how their pointers are aligned; no pointer is read, nothing is launched — and a launcher that takes the plan.  A planner that
+// declines says "not mine, ask the next"; scot_gemm_route reports the same plan the launch would run.
+struct PanelPlan { int nf; };                      // 16-column fragments per resident panel: 3 (48 columns) or 6 (96)
+struct WidePlan { int variant, epi; };             // WIDE_V_* instantiation, WIDE_EPI_* epilogue class
+struct FastTile;
+// How a workgroup's accumulator tile meets C — EPILOGUE: NT / NN unsplit, the fused epilogue stores it; OWNER: TN unsplit, C += acc by the
+// tile's only owner; WORKSPACE: TN split, partial tiles + one reduce pass with zl lanes per 8 results; ATOMIC: split without a usable
+// workspace (TN) or by scot_gemm_splitk_config (NT), and every TN product of the generic kernel: fp32 atomics into C.
+enum { COMMIT_EPILOGUE, COMMIT_OWNER, COMMIT_WORKSPACE, COMMIT_ATOMIC };
+struct FastPlan {
+  const FastTile* tile;
+  int nsplit, ksplit, commit, zl;   // K slices; K elements per slice
+  size_t ws_used;                   // bytes of workspace the launch writes
+};
+struct GenericPlan { int nsplit, ksplit, atomic; };   // K slices (TN only), K elements per slice, fp32 atomics into C
+bool plan_panel(const GemmCall& c, PanelPlan& p);       // gemm_panel.hip
+bool plan_wide(const GemmCall& c, WidePlan& p);         // gemm_wide.hip
+bool plan_fast_call(const GemmCall& c, FastPlan& p);    // gemm_fast.hip: plan_fast with the call's own workspace and alignment
+int plan_generic(const GemmCall& c, GenericPlan& p);    // gemm.hip: SCOT_OK, or what scot_gemm answers for a call nobody takes
+void fast_tile_of(const FastPlan& p, int* row, int* bm, int* bn, int* bk);   // gemm_fast.hip: the plan's row of kFastTiles
+bool fast_table_row(int row, int* route);   // gemm_fast.hip / mlp_fused.hip: one row of kFastTiles / kTailShapes for scot_route_table
+bool tail_table_row(int row, int* route);
+int scot_gemm_panel(const GemmCall& c, const PanelPlan& p, hipStream_t stream);
+int scot_gemm_wide(const GemmCall& c, const WidePlan& p, hipStream_t stream);
+int scot_gemm_fast(const GemmCall& c, const FastPlan& p, hipStream_t stream);
+int scot_gemm_generic(const GemmCall& c, const GenericPlan& p, hipStream_t stream);
 int scot_gemm_wide_mode(int* variant);   // gemm_wide.hip: scot_gemm_wide_config's state (the grouped weight gradients' planner reads it)
 extern int g_scot_use_tr;

@@ -697,15 +697,7 @@ static int kslice_len(int K, long nsplit, int bk, bool xcd8) {
 }
 
 constexpr size_t WS_UNLIMITED = (size_t)1 << 60;   // what the workspace queries offer
-// How a workgroup's accumulator tile meets C — EPILOGUE: NT / NN unsplit, the fused epilogue stores it; OWNER: TN unsplit, C += acc by the
-// tile's only owner; WORKSPACE: TN split, partial tiles + one reduce pass with zl lanes per 8 results; ATOMIC: split without a usable
-// workspace (TN) or by scot_gemm_splitk_config (NT), fp32 atomics into C.
-enum { COMMIT_EPILOGUE, COMMIT_OWNER, COMMIT_WORKSPACE, COMMIT_ATOMIC };
-struct FastPlan {
-  const FastTile* tile;
-  int nsplit, ksplit, commit, zl;   // K slices; K elements per slice
-  size_t ws_used;                   // bytes of workspace the launch writes
-};
+// (FastPlan and the COMMIT_* modes: gemm_call.h)
 
 // Everything scot_gemm_fast decides from shapes, dtypes and flags (no pointer is read, only whether an operand is present), given
 // `ws_offer` bytes of workspace, `ws_aligned` telling whether it is on a 32-byte boundary.  false: the call is not this kernel's.
@@ -762,11 +754,24 @@ static bool plan_fast(const GemmCall& c, size_t ws_offer, bool ws_aligned, FastP
   return true;
 }
 
-// Returns SCOT_ERR_UNSUPPORTED when the call does not qualify (scot_gemm then uses the generic kernel).
-int scot_gemm_fast(const GemmCall& c, hipStream_t stream) {
-  if (!aligned16(c.A, c.B, c.C, c.aux, c.resid, c.C2)) return SCOT_ERR_UNSUPPORTED;
-  FastPlan p;
-  if (!plan_fast(c, c.workspace ? c.ws_bytes : 0, c.workspace && ((uintptr_t)c.workspace & 31) == 0, p)) return SCOT_ERR_UNSUPPORTED;
+// plan_fast for one call: its pointers' alignment, its own workspace.  false: scot_gemm uses the generic kernel.
+bool plan_fast_call(const GemmCall& c, FastPlan& p) {
+  if (!aligned16(c.A, c.B, c.C, c.aux, c.resid, c.C2)) return false;
+  return plan_fast(c, c.workspace ? c.ws_bytes : 0, c.workspace && ((uintptr_t)c.workspace & 31) == 0, p);
+}
+// row `row` of kFastTiles for scot_route_table: false past the end
+bool fast_table_row(int row, int* route) {
+  if (row < 0 || row >= (int)(sizeof(kFastTiles) / sizeof(kFastTiles[0]))) return false;
+  const FastTile& t = kFastTiles[row];
+  route[1] = t.bm; route[2] = t.bn; route[3] = t.bk;
+  for (int l = 0; l < 3; ++l) route[4] |= t.launch[l] ? 1 << l : 0;
+  return true;
+}
+void fast_tile_of(const FastPlan& p, int* row, int* bm, int* bn, int* bk) {
+  *row = (int)(p.tile - kFastTiles); *bm = p.tile->bm; *bn = p.tile->bn; *bk = p.tile->bk;
+}
+
+int scot_gemm_fast(const GemmCall& c, const FastPlan& p, hipStream_t stream) {
   // (the unsplit NT / NN epilogue is the one place that reads a residual: `accumulate` there means C itself)
   const GemmResid r = p.commit == COMMIT_EPILOGUE ? gemm_resid(c) : GemmResid{c.resid, c.res_dt, c.ldres};
   FastArgs a;
@@ -926,13 +931,37 @@ static int plan_wgrad_group(int compute, int n, int K, const int* Ms, const int*
 
 // include/scot_hip.h: scot_wgrad_group.  dY_i: [K, M_i] (16-bit operands), X_i: [K, N_i], dW_i: [M_i, N_i] fp32 (+=),
 // dbias_i: [M_i] fp32 (+= column sums of dY_i) or NULL.  All leading dimensions = the row lengths (dense).
+// plan_wgrad_group for one call: its pointers' alignment, its own workspace
+static int plan_wgrad_group_call(int compute, int n, int K, const void* const* dY, const void* const* X, float* const* dW, const int* Ms,
+                                 const int* Ns, void* workspace, size_t ws_bytes, const int* modes, WgradGroupPlan& p) {
+  unsigned unaligned = 0;
+  for (int i = 0; i < n && i < SCOT_WGRAD_GROUP_MAX; ++i) unaligned |= (aligned16(dY[i], X[i], dW[i]) ? 0u : 1u) << i;
+  return plan_wgrad_group(compute, n, K, Ms, Ns, modes, unaligned, workspace ? ws_bytes : 0, workspace && ((uintptr_t)workspace & 31) == 0, p);
+}
+
+// include/scot_hip.h: scot_wgrad_group_route — the plan of the same call; nothing is launched, no pointer is read.
+extern "C" int scot_wgrad_group_route(int compute, int n, int K, const void* const* dY, const void* const* X, float* const* dW,
+                                      float* const* dbias, const int* Ms, const int* Ns, void* workspace, size_t ws_bytes,
+                                      const int* modes, const float* grad_scale, int* route) {
+  (void)dbias; (void)grad_scale;
+  if (!route) return SCOT_ERR_SHAPE;
+  for (int i = 0; i < SCOT_ROUTE_INTS; ++i) route[i] = 0;
+  WgradGroupPlan p;
+  const int rc = plan_wgrad_group_call(compute, n, K, dY, X, dW, Ms, Ns, workspace, ws_bytes, modes, p);
+  route[0] = rc;
+  if (rc != SCOT_OK) return SCOT_OK;
+  route[1] = p.kernel; route[2] = p.wide; route[3] = p.nsplit; route[4] = p.zl;
+  route[5] = (int)(p.ws_used >> 8);      // whole 256-byte units: every M_i, N_i is a multiple of 8
+  route[6] = p.kernel == GROUP_WIDE ? 128 : p.kernel == GROUP_96x96 ? 96 : 64;
+  route[7] = p.tiles;
+  return SCOT_OK;
+}
+
 extern "C" int scot_wgrad_group(int compute, int n, int K, const void* const* dY, const void* const* X, float* const* dW,
                                 float* const* dbias, const int* Ms, const int* Ns, void* workspace, size_t ws_bytes,
                                 const int* modes, const float* grad_scale, hipStream_t stream) {
-  unsigned unaligned = 0;
-  for (int i = 0; i < n && i < SCOT_WGRAD_GROUP_MAX; ++i) unaligned |= (aligned16(dY[i], X[i], dW[i]) ? 0u : 1u) << i;
   WgradGroupPlan p;
-  int rc = plan_wgrad_group(compute, n, K, Ms, Ns, modes, unaligned, workspace ? ws_bytes : 0, workspace && ((uintptr_t)workspace & 31) == 0, p);
+  int rc = plan_wgrad_group_call(compute, n, K, dY, X, dW, Ms, Ns, workspace, ws_bytes, modes, p);
   if (rc != SCOT_OK) return rc;
   WgradGroupArgs g;
   g.n = n; g.K = K; g.use_tr = g_scot_use_tr;

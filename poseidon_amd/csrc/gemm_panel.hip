@@ -183,18 +183,23 @@ static int launch_panel(const PanelArgs& a, int layout, hipStream_t s) {
   return scot_check_launch();
 }
 
-// Returns SCOT_ERR_UNSUPPORTED when the call does not qualify (the caller then uses the tiled kernels).
-int scot_gemm_panel(const GemmCall& c, hipStream_t stream) {
-  if (c.compute != SCOT_BF16 || (c.layout != LAYOUT_NT && c.layout != LAYOUT_NN)) return SCOT_ERR_UNSUPPORTED;
-  if (c.a_dt != SCOT_BF16 || c.b_dt != SCOT_BF16 || c.a_gelu || c.b_gelu || c.colscale || c.colsum_out) return SCOT_ERR_UNSUPPORTED;
+// Pure: is the call this kernel's, and with which panel width.  false: the caller asks the tiled kernels.
+bool plan_panel(const GemmCall& c, PanelPlan& p) {
+  if (c.compute != SCOT_BF16 || (c.layout != LAYOUT_NT && c.layout != LAYOUT_NN)) return false;
+  if (c.a_dt != SCOT_BF16 || c.b_dt != SCOT_BF16 || c.a_gelu || c.b_gelu || c.colscale || c.colsum_out) return false;
   const int kmax = 192;   // measured: K = 384 (48-col panels) only ties the tiled kernel
-  if (c.K % 96 || c.K > kmax || c.N % 48 || c.M < 4096) return SCOT_ERR_UNSUPPORTED;
-  if (!aligned16(c.A, c.B, c.C, c.C2, c.aux, c.resid, c.bias) || !ld_vectors(c, 8)) return SCOT_ERR_UNSUPPORTED;
+  if (c.K % 96 || c.K > kmax || c.N % 48 || c.M < 4096) return false;
+  if (!aligned16(c.A, c.B, c.C, c.C2, c.aux, c.resid, c.bias) || !ld_vectors(c, 8)) return false;
+  const bool wide = (c.N % 96 == 0) && c.K <= 192;   // 96-column panels while the panel stays <= 40 KB (3 workgroups per CU)
+  p.nf = wide ? 6 : 3;
+  return true;
+}
+
+int scot_gemm_panel(const GemmCall& c, const PanelPlan& p, hipStream_t stream) {
   const GemmResid r = gemm_resid(c);
   PanelArgs a;
   a.A = (const bf16_t*)c.A; a.B = (const bf16_t*)c.B; a.C = c.C; a.C2 = c.C2; a.bias = c.bias; a.aux = c.aux; a.resid = r.p;
   a.M = c.M; a.N = c.N; a.K = c.K; a.lda = c.lda; a.ldb = c.ldb; a.ldc = c.ldc; a.ldaux = c.ldaux; a.ldres = r.ld;
   a.c_dt = c.c_dt; a.aux_dt = c.aux_dt; a.res_dt = r.dt; a.aux_on = c.aux != nullptr; a.aux_mul = c.aux_mul; a.use_tr = g_scot_use_tr;
-  const bool wide = (c.N % 96 == 0) && c.K <= 192;   // 96-column panels while the panel stays <= 40 KB (3 workgroups per CU)
-  return wide ? launch_panel<6>(a, c.layout, stream) : launch_panel<3>(a, c.layout, stream);
+  return p.nf == 6 ? launch_panel<6>(a, c.layout, stream) : launch_panel<3>(a, c.layout, stream);
 }

@@ -245,17 +245,21 @@ static void wide_launch(int epi, unsigned grid, const WideArgs& a, hipStream_t s
   else hipLaunchKernelGGL((gemm_wide_kernel<128, 128, WM, WN, STAGES, WIDE_EPI_NONE, PRE>), g, b, 0, stream, a);
 }
 
-// Returns SCOT_ERR_UNSUPPORTED when the call does not qualify (scot_gemm then asks gemm_fast).
-int scot_gemm_wide(const GemmCall& c, hipStream_t stream) {
-  if (c.layout != LAYOUT_NT || c.compute != SCOT_BF16 || c.a_dt != SCOT_BF16 || c.b_dt != SCOT_BF16) return SCOT_ERR_UNSUPPORTED;
-  if (c.a_gelu || c.b_gelu || c.colscale || c.colsum_out || (c.aux && c.aux_dt != SCOT_BF16)) return SCOT_ERR_UNSUPPORTED;
-  if (c.aux && (c.resid || c.accumulate)) return SCOT_ERR_UNSUPPORTED;               // (one epilogue operand per instantiation: what the engine's calls use)
-  if ((c.resid && c.res_dt != SCOT_F32) || (c.accumulate && c.c_dt != SCOT_F32)) return SCOT_ERR_UNSUPPORTED;
-  if (!aligned16(c.A, c.B, c.C, c.C2, c.aux, c.resid) || !ld_vectors(c, 8)) return SCOT_ERR_UNSUPPORTED;      // (bias is read per column: any alignment)
+// Pure: is the call this kernel's, with which instantiation and epilogue class.  false: the caller asks gemm_fast.
+bool plan_wide(const GemmCall& c, WidePlan& p) {
+  if (c.layout != LAYOUT_NT || c.compute != SCOT_BF16 || c.a_dt != SCOT_BF16 || c.b_dt != SCOT_BF16) return false;
+  if (c.a_gelu || c.b_gelu || c.colscale || c.colsum_out || (c.aux && c.aux_dt != SCOT_BF16)) return false;
+  if (c.aux && (c.resid || c.accumulate)) return false;               // (one epilogue operand per instantiation: what the engine's calls use)
+  if ((c.resid && c.res_dt != SCOT_F32) || (c.accumulate && c.c_dt != SCOT_F32)) return false;
+  if (!aligned16(c.A, c.B, c.C, c.C2, c.aux, c.resid) || !ld_vectors(c, 8)) return false;      // (bias is read per column: any alignment)
+  p.epi = c.aux ? WIDE_EPI_AUX16 : (gemm_resid(c).p ? WIDE_EPI_RES32 : WIDE_EPI_NONE);
+  p.variant = wide_variant(c.M, c.N, c.K, p.epi);
+  return p.variant >= 0;
+}
+
+int scot_gemm_wide(const GemmCall& c, const WidePlan& p, hipStream_t stream) {
   const GemmResid r = gemm_resid(c);
-  const int epi = c.aux ? WIDE_EPI_AUX16 : (r.p ? WIDE_EPI_RES32 : WIDE_EPI_NONE);
-  const int variant = wide_variant(c.M, c.N, c.K, epi);
-  if (variant < 0) return SCOT_ERR_UNSUPPORTED;
+  const int epi = p.epi, variant = p.variant;
   WideArgs a;
   a.A = (const bf16_t*)c.A; a.B = (const bf16_t*)c.B; a.C = c.C; a.C2 = c.C2; a.bias = c.bias; a.aux = c.aux; a.resid = r.p;
   a.M = c.M; a.N = c.N; a.K = c.K; a.lda = c.lda; a.ldb = c.ldb; a.ldc = c.ldc; a.ldaux = c.ldaux; a.ldres = r.ld;

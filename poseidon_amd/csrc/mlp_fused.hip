@@ -1020,6 +1020,44 @@ static TailLaunchPlan plan_tail_launch(Fn TailShape::*family, bool needs_uniform
   return p;
 }
 
+// The six launcher columns of kTailShapes by number (include/scot_hip.h: SCOT_TAIL_*), each with what its entry point asks of the plan: the
+// backward families need one conditioning time per workgroup, the projection halves have no hidden width.  Every entry point below and
+// scot_block_tail_route plan through here.
+enum { TAIL_MLP_FWD, TAIL_MLP_BWD, TAIL_PROJ_FWD, TAIL_PROJ_BWD, TAIL_FWD, TAIL_BWD, TAIL_FAMILIES };
+static TailLaunchPlan plan_tail_family(int family, int C, int M, int rows_per_sample, int hid, bool qkv = false, bool pro = false, bool recomp = false) {
+  const int tt = scot_mlp_tt_override();
+  switch (family) {
+    case TAIL_MLP_FWD: return plan_tail_launch(&TailShape::mlp_fwd, false, tt, C, M, rows_per_sample, hid);
+    case TAIL_MLP_BWD: return plan_tail_launch(&TailShape::mlp_bwd, true, tt, C, M, rows_per_sample, hid);
+    case TAIL_PROJ_FWD: return plan_tail_launch(&TailShape::proj_fwd, false, tt, C, M, rows_per_sample, kNoHidden);
+    case TAIL_PROJ_BWD: return plan_tail_launch(&TailShape::proj_bwd, true, tt, C, M, rows_per_sample, kNoHidden);
+    case TAIL_FWD: return plan_tail_launch(&TailShape::tail_fwd, false, tt, C, M, rows_per_sample, hid, qkv);
+    case TAIL_BWD: return plan_tail_launch(&TailShape::tail_bwd, true, tt, C, M, rows_per_sample, hid, false, pro, recomp);
+    default: return TailLaunchPlan{SCOT_ERR_SHAPE, nullptr, 0, false, false, false};
+  }
+}
+
+// row `row` of kTailShapes for scot_route_table (gemm.hip): false past the end
+bool tail_table_row(int row, int* route) {
+  if (row < 0 || row >= (int)(sizeof(kTailShapes) / sizeof(kTailShapes[0]))) return false;
+  const TailShape& s = kTailShapes[row];
+  route[1] = s.C; route[2] = s.HC; route[3] = s.TT;
+  route[4] = (s.mlp_fwd ? 1 << TAIL_MLP_FWD : 0) | (s.mlp_bwd ? 1 << TAIL_MLP_BWD : 0) | (s.proj_fwd ? 1 << TAIL_PROJ_FWD : 0) |
+             (s.proj_bwd ? 1 << TAIL_PROJ_BWD : 0) | (s.tail_fwd ? 1 << TAIL_FWD : 0) | (s.tail_bwd ? 1 << TAIL_BWD : 0);
+  return true;
+}
+
+// include/scot_hip.h: scot_block_tail_route — the plan of one family at these dimensions; nothing is launched.
+extern "C" int scot_block_tail_route(int family, int C, int M, int rows_per_sample, int hid, int qkv, int pro, int recomp, int* route) {
+  if (!route) return SCOT_ERR_SHAPE;
+  for (int i = 0; i < SCOT_ROUTE_INTS; ++i) route[i] = 0;
+  const TailLaunchPlan p = plan_tail_family(family, C, M, rows_per_sample, hid, qkv != 0, pro != 0, recomp != 0);
+  route[0] = p.rc;
+  if (p.shape) { route[1] = p.shape->C; route[2] = p.shape->HC; route[3] = p.shape->TT; route[4] = p.grid; }
+  route[5] = p.qkv; route[6] = p.pro; route[7] = p.recomp;
+  return SCOT_OK;
+}
+
 // The optional pointers of a conditional norm come in pairs (with per-workgroup partial rows the four gradient pointers are not read), and
 // the two row structs are filled in one place each.  Every argument struct is filled by NAME (designated initialisers, in declaration
 // order; fields left out are zero): a field that is moved or inserted is a compile error, never two silently swapped pointers.
@@ -1053,7 +1091,7 @@ extern "C" int scot_mlp_block_fwd(const void* h16, const float* h, const void* W
                                   const float* time, const float* gw_w, const float* gw_b, const float* bw_w, const float* bw_b,
                                   const float* sample_scale, int M, int rows_per_sample, int C, int hid, float eps,
                                   hipStream_t stream) {
-  const TailLaunchPlan p = plan_tail_launch(&TailShape::mlp_fwd, false, scot_mlp_tt_override(), C, M, rows_per_sample, hid);
+  const TailLaunchPlan p = plan_tail_family(TAIL_MLP_FWD, C, M, rows_per_sample, hid);
   if (p.rc) return p.rc;
   if (!h16 || !h || !W1 || !b1 || !W2 || !b2 || !out || !pair_ok(act, dact) || !norm_fwd_ok(mean, rstd, gw_w, gw_b, bw_w, bw_b))
     return SCOT_ERR_SHAPE;
@@ -1070,7 +1108,7 @@ extern "C" int scot_mlp_block_bwd(const float* g, float* g_out, const float* z, 
                                   const void* dact, const void* W1, const void* W2, void* dz, void* du, float* d_gw_w,
                                   float* d_gw_b, float* d_bw_w, float* d_bw_b, int M, int rows_per_sample, int C, int hid,
                                   hipStream_t stream) {
-  const TailLaunchPlan p = plan_tail_launch(&TailShape::mlp_bwd, true, scot_mlp_tt_override(), C, M, rows_per_sample, hid);
+  const TailLaunchPlan p = plan_tail_family(TAIL_MLP_BWD, C, M, rows_per_sample, hid);
   if (p.rc) return p.rc;
   if (!g || !g_out || !z || !mean || !rstd || !dact || !W1 || !W2 || !dz || !du ||
       !norm_bwd_ok(gw_w, gw_b, d_gw_w, d_gw_b, d_bw_w, d_bw_b, nullptr))
@@ -1087,7 +1125,7 @@ extern "C" int scot_proj_cln_fwd(const void* a, const void* W, const float* bias
                                  float* z, float* mean, float* rstd, const float* time, const float* gw_w, const float* gw_b,
                                  const float* bw_w, const float* bw_b, const float* sample_scale, int M, int rows_per_sample,
                                  int C, float eps, hipStream_t stream) {
-  const TailLaunchPlan p = plan_tail_launch(&TailShape::proj_fwd, false, scot_mlp_tt_override(), C, M, rows_per_sample, kNoHidden);
+  const TailLaunchPlan p = plan_tail_family(TAIL_PROJ_FWD, C, M, rows_per_sample, kNoHidden);
   if (p.rc) return p.rc;
   if (!a || !W || !bias || !resid || !out || !norm_fwd_ok(mean, rstd, gw_w, gw_b, bw_w, bw_b)) return SCOT_ERR_SHAPE;
   const ProjClnArgs pa = {.a = (const bf16_t*)a, .W = (const bf16_t*)W,
@@ -1101,7 +1139,7 @@ extern "C" int scot_proj_cln_bwd(const float* g, const float* z, const float* me
                                  const float* gw_w, const float* gw_b, const float* sample_scale, const void* W, void* dz, void* da,
                                  float* d_gw_w, float* d_gw_b, float* d_bw_w, float* d_bw_b, int M, int rows_per_sample, int C,
                                  hipStream_t stream) {
-  const TailLaunchPlan p = plan_tail_launch(&TailShape::proj_bwd, true, scot_mlp_tt_override(), C, M, rows_per_sample, kNoHidden);
+  const TailLaunchPlan p = plan_tail_family(TAIL_PROJ_BWD, C, M, rows_per_sample, kNoHidden);
   if (p.rc) return p.rc;
   if (!g || !z || !mean || !rstd || !W || !dz || !da || !norm_bwd_ok(gw_w, gw_b, d_gw_w, d_gw_b, d_bw_w, d_bw_b, nullptr))
     return SCOT_ERR_SHAPE;
@@ -1115,7 +1153,7 @@ extern "C" int scot_proj_cln_bwd(const float* g, const float* z, const float* me
 // include/scot_hip.h: workgroups of scot_block_tail_bwd = the grid of ITS plan (the forward's may be half of it: it does not need whole
 // tiles per sample).  The backward's partial-sum scratch is one row of 4·Cp (2·Cp without conditioning) floats per workgroup and per norm.
 extern "C" int scot_block_tail_workgroups(int M, int rows_per_sample, int C) {
-  return plan_tail_launch(&TailShape::tail_bwd, true, scot_mlp_tt_override(), C, M, rows_per_sample, kNoHidden).grid;
+  return plan_tail_family(TAIL_BWD, C, M, rows_per_sample, kNoHidden).grid;
 }
 
 // out[j] += Σ_b partial[b][j]: finishes the per-workgroup column sums of scot_block_tail_bwd / scot_cln_bwd mode 3 (norm_fast.hip)
@@ -1140,8 +1178,7 @@ extern "C" int scot_block_tail_bwd(const float* g, float* g_out,
                                    /* optional per-workgroup column sums instead of atomics: [workgroups][4C | 2C] each */ float* partial2,
                                    float* partial1,
                                    const float* time, int M, int rows_per_sample, int C, int hid, hipStream_t stream) {
-  const TailLaunchPlan p = plan_tail_launch(&TailShape::tail_bwd, true, scot_mlp_tt_override(), C, M, rows_per_sample, hid, false,
-                               /* pro */ dqkv != nullptr, /* recomp */ dact == nullptr);
+  const TailLaunchPlan p = plan_tail_family(TAIL_BWD, C, M, rows_per_sample, hid, false, /* pro */ dqkv != nullptr, /* recomp */ dact == nullptr);
   if (p.rc) return p.rc;
   if (!pair_ok(dqkv, Wqkv)) return SCOT_ERR_SHAPE;
   if (dqkv && g_out != g) return SCOT_ERR_UNSUPPORTED;        // the prologue updates g in place
@@ -1176,7 +1213,7 @@ extern "C" int scot_block_tail_fwd(/* attention-output half */ const void* a, co
                                    void* qkv,
                                    /* dtype of z1 / z2: fp32, or the 16-bit operand format (only the backward's x-hat reads them) */ int z_dt,
                                    const float* time, int M, int rows_per_sample, int C, int hid, float eps, hipStream_t stream) {
-  const TailLaunchPlan p = plan_tail_launch(&TailShape::tail_fwd, false, scot_mlp_tt_override(), C, M, rows_per_sample, hid, /* qkv */ qkv != nullptr);
+  const TailLaunchPlan p = plan_tail_family(TAIL_FWD, C, M, rows_per_sample, hid, /* qkv */ qkv != nullptr);
   if (p.rc) return p.rc;
   if (z_dt != SCOT_F32 && z_dt != SCOT_BF16) return SCOT_ERR_DTYPE;
   if (!a || !Wo || !bo || !x || !h || !h16 || !W1 || !b1 || !W2 || !b2 || !out || (act && !dact) || !pair_ok(gw_w1, gw_w2) ||

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libscot_hip.so")
 # The same sources built twice (build.py): the format of the 16-bit operand type is a compile-time property (csrc/common.h).
 LIB_PATHS = {"bf16": LIB_PATH, "f16": os.path.join(_HERE, "libscot_hip_f16.so")}
 OPERAND_FORMAT = {"bf16": 0, "f16": 1}
-ABI_VERSION = 6      # scot_abi_version() of the library these prototypes describe (checked at load)
+ABI_VERSION = 7      # scot_abi_version() of the library these prototypes describe (checked at load)
 
 P, I, F, Z = c_void_p, c_int, c_float, c_size_t
 
@@ -29,6 +29,10 @@ PROTOTYPES = {
     "scot_get_use_tr": [],
     "scot_gemm": [I, I, I, I, I, P, I, I, I, P, I, I, I, P, I, I, P, P, P, I, I, P, I, I, I, P, P, Z, I, P, P],
     "scot_wgrad_group": [I, I, I, P, P, P, P, P, P, P, Z, P, P, P],
+    "scot_gemm_route": [I, I, I, I, I, P, I, I, I, P, I, I, I, P, I, I, P, P, P, I, I, P, I, I, I, P, P, Z, I, P, P],
+    "scot_wgrad_group_route": [I, I, I, P, P, P, P, P, P, P, Z, P, P, P],
+    "scot_block_tail_route": [I, I, I, I, I, I, I, I, P],
+    "scot_route_table": [I, I, P],
     "scot_segments_scale": [P, P, I, P, P, P],
     "scot_gemm_workspace_bytes": [I, I, I, I, I],
     "scot_gemm_wide_config": [I, I],
@@ -159,6 +163,9 @@ def load(path: str = None, kind: str = "bf16"):
         lib.scot_gemm_splitk_config(int(sl), int(z or 1))
     _libs[kind] = lib
     return lib
+
+
+ROUTE_INTS = 12      # SCOT_ROUTE_INTS: the answer of scot_gemm_route / scot_wgrad_group_route / scot_block_tail_route
 
 
 _ERR = {-1: "bad shape", -2: "bad dtype", -3: "unsupported configuration", -4: "kernel launch failed"}

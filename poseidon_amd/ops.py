@@ -156,13 +156,46 @@ def gemm(layout: int, compute: int, M: int, N: int, K: int, A, lda: int, B, ldb:
                         gelu_deriv_out=gelu_deriv_out)
         finally:
             use(prev)
-    ws = _gemm_ws(layout, compute, M, N, K)
-    rc = L().scot_gemm(layout, compute, M, N, K, ptr(A), dt(A), lda, int(a_gelu), ptr(B), dt(B), ldb, int(b_gelu),
-                       ptr(C), dt(C), ldc, ptr(bias), ptr(colscale), ptr(aux), dt(aux) if aux is not None else 0, ldaux,
-                       ptr(resid), dt(resid) if resid is not None else 0, ldres, int(accumulate), ptr(colsum_out),
-                       ws.data_ptr(), ws.numel(),
-                       int(aux_mul), ptr(gelu_deriv_out), stream())
+    rc = L().scot_gemm(*_gemm_args(layout, compute, M, N, K, A, lda, B, ldb, C, ldc, bias, colscale, aux, ldaux, resid, ldres, a_gelu, b_gelu,
+                                   accumulate, colsum_out, aux_mul, gelu_deriv_out), stream())
     _lib.check(rc, "scot_gemm")
+
+
+def _gemm_args(layout, compute, M, N, K, A, lda, B, ldb, C, ldc, bias, colscale, aux, ldaux, resid, ldres, a_gelu, b_gelu, accumulate,
+               colsum_out, aux_mul, gelu_deriv_out):
+    """the arguments of scot_gemm / scot_gemm_route up to the stream / the answer"""
+    ws = _gemm_ws(layout, compute, M, N, K)
+    return (layout, compute, M, N, K, ptr(A), dt(A), lda, int(a_gelu), ptr(B), dt(B), ldb, int(b_gelu),
+            ptr(C), dt(C), ldc, ptr(bias), ptr(colscale), ptr(aux), dt(aux) if aux is not None else 0, ldaux,
+            ptr(resid), dt(resid) if resid is not None else 0, ldres, int(accumulate), ptr(colsum_out),
+            ws.data_ptr(), ws.numel(), int(aux_mul), ptr(gelu_deriv_out))
+
+
+ROUTE_PANEL, ROUTE_WIDE, ROUTE_FAST, ROUTE_GENERIC = 0, 1, 2, 3      # route[0] of gemm_route (include/scot_hip.h)
+TAIL_MLP_FWD, TAIL_MLP_BWD, TAIL_PROJ_FWD, TAIL_PROJ_BWD, TAIL_FWD, TAIL_BWD = range(6)      # families of block_tail_route
+
+
+def _route_out():
+    import ctypes
+    return (ctypes.c_int * _lib.ROUTE_INTS)()
+
+
+def gemm_route(layout: int, compute: int, M: int, N: int, K: int, A, lda: int, B, ldb: int, C, ldc: int, *, bias=None,
+               colscale=None, aux=None, ldaux: int = 0, resid=None, ldres: int = 0, a_gelu: bool = False, b_gelu: bool = False,
+               accumulate: bool = False, colsum_out=None, aux_mul: bool = False, gelu_deriv_out=None) -> list:
+    """scot_gemm_route: the kernel `gemm` would run with the same arguments, as the ints the header lists; launches nothing."""
+    if compute == X3 and _active != "bf16":
+        prev = use("bf16")
+        try:
+            return gemm_route(layout, compute, M, N, K, A, lda, B, ldb, C, ldc, bias=bias, colscale=colscale, aux=aux, ldaux=ldaux, resid=resid,
+                              ldres=ldres, a_gelu=a_gelu, b_gelu=b_gelu, accumulate=accumulate, colsum_out=colsum_out, aux_mul=aux_mul,
+                              gelu_deriv_out=gelu_deriv_out)
+        finally:
+            use(prev)
+    route = _route_out()
+    _lib.check(_raw().scot_gemm_route(*_gemm_args(layout, compute, M, N, K, A, lda, B, ldb, C, ldc, bias, colscale, aux, ldaux, resid, ldres,
+                                                  a_gelu, b_gelu, accumulate, colsum_out, aux_mul, gelu_deriv_out), route), "scot_gemm_route")
+    return list(route)
 
 
 def linear_fwd(compute, x, w, out, bias=None, a_gelu=False, gelu_deriv_out=None):
@@ -207,6 +240,18 @@ def wgrad_group(compute, problems, modes=None, grad_scale=None) -> bool:
     dy [K, M_i] / x [K, N_i] in the 16-bit operand format over the SAME K rows, dw [M_i, N_i] fp32 (+=), dbias [M_i] or None.
     modes (one GRAD_* per problem, default all GRAD_ADD) / grad_scale (1-element fp32 device tensor): see the header.
     False = not covered (the caller launches them one by one)."""
+    args = _wgrad_group_args(compute, problems, modes, grad_scale)
+    if args is None:
+        return False
+    rc = L().scot_wgrad_group(*args, stream())
+    if rc == -3:
+        return False
+    _lib.check(rc, "scot_wgrad_group")
+    return True
+
+
+def _wgrad_group_args(compute, problems, modes, grad_scale):
+    """the arguments of scot_wgrad_group / scot_wgrad_group_route up to the stream / the answer; None = operands it does not take"""
     import ctypes
     n = len(problems)
     K = problems[0][0].numel() // problems[0][0].shape[-1]
@@ -216,14 +261,42 @@ def wgrad_group(compute, problems, modes=None, grad_scale=None) -> bool:
     Ms, Ns = IA(*[p[0].shape[-1] for p in problems]), IA(*[p[1].shape[-1] for p in problems])
     for dy, x, dw, _ in problems:
         if dt(dy) != BF16 or dt(x) != BF16 or dw.dtype != torch.float32 or dy.numel() // dy.shape[-1] != K or x.numel() // x.shape[-1] != K:
-            return False
+            return None
     ws = workspace(int(_raw().scot_wgrad_group_workspace_bytes(n, K, Ms, Ns)))
     md = IA(*[int(m) for m in modes]) if modes is not None else None
-    rc = L().scot_wgrad_group(compute, n, K, dys, xs, dws, dbs, Ms, Ns, ws.data_ptr(), ws.numel(), md, ptr(grad_scale), stream())
-    if rc == -3:
-        return False
-    _lib.check(rc, "scot_wgrad_group")
-    return True
+    return (compute, n, K, dys, xs, dws, dbs, Ms, Ns, ws.data_ptr(), ws.numel(), md, ptr(grad_scale))
+
+
+def wgrad_group_route(compute, problems, modes=None, grad_scale=None):
+    """scot_wgrad_group_route: the kernel `wgrad_group` would run on the same problems (header: the ints); None where the wrapper itself
+    declines the operands.  Launches nothing."""
+    args = _wgrad_group_args(compute, problems, modes, grad_scale)
+    if args is None:
+        return None
+    route = _route_out()
+    _lib.check(_raw().scot_wgrad_group_route(*args, route), "scot_wgrad_group_route")
+    return list(route)
+
+
+def block_tail_route(family: int, C: int, rows: int, rows_per_sample: int, hid: int, qkv: bool = False, pro: bool = False,
+                     recomp: bool = False) -> list:
+    """scot_block_tail_route: status, table row (C, HC, TT), workgroups and template flags of one fused-tail family (TAIL_*) at these
+    dimensions.  Launches nothing."""
+    route = _route_out()
+    _lib.check(_raw().scot_block_tail_route(family, C, rows, rows_per_sample, hid, int(qkv), int(pro), int(recomp), route), "scot_block_tail_route")
+    return list(route)
+
+
+def route_table(table: int) -> list:
+    """scot_route_table: every row of table 0 (gemm_fast's tiles), 1 (the fused tails' instantiations), 2 (128 x 128 variants) or
+    3 (grouped weight-gradient kernels) as the ints the header lists"""
+    rows = []
+    while True:
+        route = _route_out()
+        _lib.check(_raw().scot_route_table(table, len(rows), route), "scot_route_table")
+        if not route[0]:
+            return rows
+        rows.append(list(route))
 
 
 def colsum(x, out, y=None):

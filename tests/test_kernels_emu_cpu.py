@@ -603,10 +603,10 @@ def test_guarded_gemm_split_k_bf16x3_nan_and_range(guarded_bodies):
     guarded_bodies.gemm_split_k_atomic_guarded("bf16", 96, 136, 640, 3, 8)
     guarded_bodies.gemm_bf16x3_guarded(ops.NT, 130, 72, 40, 8)
     guarded_bodies.gemm_bf16x3_guarded(ops.TN, 40, 72, 136, 0)
-    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NT, True, 65, 34, 24)
-    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NT, False, 136, 64, 40)
-    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NN, False, 136, 64, 40)
-    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NT, False, 128, 128, 64, wide=(2, 0))
+    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NT, True, 65, 34, 24, family=ops.ROUTE_GENERIC)
+    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NT, False, 136, 64, 40, family=ops.ROUTE_FAST)
+    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NN, False, 136, 64, 40, family=ops.ROUTE_FAST)
+    guarded_bodies.gemm_nan_stays_in_its_row_and_column(ops.NT, False, 128, 128, 64, wide=(2, 0), family=ops.ROUTE_WIDE)
     guarded_bodies.gemm_operands_near_binary16_maximum(65, 40, 72)
 
 

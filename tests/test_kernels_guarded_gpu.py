@@ -148,9 +148,11 @@ def test_gemm_layouts_guarded(case, pad):
 
 
 def gemm_layouts_guarded(compute, layout, mixed, M, N, K, pad):
-    """scot_gemm NT / NN / TN, operands in the compute type (gemm_panel / gemm_fast) and fp32 B beside 16-bit A (the generic kernel), fp32 and
-    16-bit results, with `lda / ldb / ldc / ldres` = width + pad.  K slices with atomics are off here (their own test below), so NT / NN are
-    deterministic; TN (split K, atomics or partial tiles) and colsum_out are order-dependent."""
+    """scot_gemm NT / NN / TN, operands in the compute type (gemm_fast; gemm_panel for the bias + residual call of the 4096-row NT / NN
+    shapes only: the calls in front of it pass colsum_out, which the panel and the 128 x 128 tiles decline) and fp32 B beside 16-bit A (the
+    generic kernel), fp32 and 16-bit results, with `lda / ldb / ldc / ldres` = width + pad.  K slices with atomics are off here (their own
+    test below), so NT / NN are deterministic; TN (split K, atomics or partial tiles) and colsum_out are order-dependent.  Which kernel a
+    shape reaches is asked, not assumed, in tests/test_kernel_routes_gpu.py: one case per route and epilogue form."""
     A, B = _operands(layout, compute, mixed, M, N, K)
     ref, ab = _product64(layout, compute, A, B)
     tn = layout == ops.TN
@@ -482,22 +484,26 @@ def gemm_bf16x3_guarded(layout, M, N, K, pad):
 
 NAN_CASES = [("generic (fp32 B beside 16-bit A)", ops.NT, True, 257, 130, 72), ("gemm_fast 64 x 64", ops.NT, False, 520, 64, 40),
              ("gemm_fast NN", ops.NN, False, 520, 64, 40), ("gemm_panel", ops.NT, False, 4096, 384, 96), ("gemm_wide", ops.NT, False, 384, 256, 192)]
+NAN_FAMILY = {"generic": ops.ROUTE_GENERIC, "gemm_fast": ops.ROUTE_FAST, "gemm_panel": ops.ROUTE_PANEL, "gemm_wide": ops.ROUTE_WIDE}
 
 
 @pytest.mark.parametrize("what,layout,mixed,M,N,K", NAN_CASES, ids=[c[0] for c in NAN_CASES])
 def test_gemm_nan_stays_in_its_row_and_column(what, layout, mixed, M, N, K):
-    gemm_nan_stays_in_its_row_and_column(layout, mixed, M, N, K, wide=(2, 0) if what == "gemm_wide" else None)
+    gemm_nan_stays_in_its_row_and_column(layout, mixed, M, N, K, wide=(2, 0) if what == "gemm_wide" else None, family=NAN_FAMILY[what.split()[0]])
 
 
-def gemm_nan_stays_in_its_row_and_column(layout, mixed, M, N, K, wide=None):
+def gemm_nan_stays_in_its_row_and_column(layout, mixed, M, N, K, wide=None, family=None):
     """A NaN inside one row of A makes exactly that row of C non-finite and leaves every other element bit-equal to the clean run; likewise
-    one column through B.  (Shapes chosen so that each kernel file of scot_gemm's dispatch takes one.)"""
+    one column through B.  (Shapes chosen so that each kernel file of scot_gemm's dispatch takes one: `family`, where given, is asserted
+    through scot_gemm_route on the very arguments of the launch.)"""
     A, B = _operands(layout, ops.BF16, mixed, M, N, K)
     with _gemm_config(wide=wide):
         def run(A_, B_):
             gd = Guards()
             C = gd.out((M, N), F32, name="C")
-            ops.gemm(layout, ops.BF16, M, N, K, gd.op(A_, name="A"), A_.shape[1], gd.op(B_, name="B"), B_.shape[1], C, N)
+            args = (layout, ops.BF16, M, N, K, gd.op(A_, name="A"), A_.shape[1], gd.op(B_, name="B"), B_.shape[1], C, N)
+            assert family is None or ops.gemm_route(*args)[0] == family, f"the case reaches kernel family {ops.gemm_route(*args)[0]}, not {family}"
+            ops.gemm(*args)
             sync()
             gd.check()
             return C
