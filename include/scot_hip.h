@@ -26,9 +26,9 @@ typedef struct ihipStream_t* scot_stream_t; /* = hipStream_t */
 #define SCOT_LAYOUT_NN 1 /* C[M,N] = A[M,K] B[K,N]   : dgrad of nn.Linear; ConvTranspose2d k=s (ref:616-621)      */
 #define SCOT_LAYOUT_TN 2 /* C[M,N] += A[K,M]^T B[K,N] : wgrad of nn.Linear (autograd of the above)                 */
 
-int scot_abi_version(void);   /* 7 (round 6: 4 = scot_wgrad_group / scot_wgrad_mlp modes, scot_segments_scale, scot_gemm_splitk_config; 5 = scot_dp_init .. finalize;
+int scot_abi_version(void);   /* 8 (round 6: 4 = scot_wgrad_group / scot_wgrad_mlp modes, scot_segments_scale, scot_gemm_splitk_config; 5 = scot_dp_init .. finalize;
                                  6 = scot_cln_dtime, scot_zero_masked, scot_add_channels; 7 = scot_gemm_route, scot_wgrad_group_route,
-                                 scot_block_tail_route, scot_route_table); the bindings check it at load */
+                                 scot_block_tail_route, scot_route_table; 8 = the model-level calls of scot_plan.h); the bindings check it at load */
 /* Format of dtype code 1 in THIS build of the library: 0 = bfloat16 (libscot_hip.so), 1 = IEEE binary16 (libscot_hip_f16.so, the
  * same sources compiled with -DSCOT_OPERAND_FP16).  The reference computes in fp32 (ref:1318-1509); 16-bit operands are this
  * library's choice and binary16 is the one that keeps ScOT.forward within 1e-3 of it. */

@@ -1,0 +1,64 @@
+/* scot_plan.h — running a trained ScOT model from C: exported inference plans (ABI 8).
+ *
+ * scot_hip.h is the kernel-level boundary: about a hundred entry points that a host program has to order itself.  This header is the
+ * model-level one.  `ScOT.export_plan` (poseidon_amd/plan.py) records one inference forward for one input signature and writes it,
+ * with the weights, as a relocatable plan image; the five calls below load such a file and run it.  A host needs nothing but the
+ * shared library and the HIP runtime: no Python, no torch.  The prediction is bit-identical to `model(...)` in Python.
+ *
+ * What a plan covers: the engine's inference forward at config.image_size on ONE stream — no training, no spectral resize, no hidden
+ * states or attention outputs, no labels (so no pixel_mask: the mask overwrites the prediction with label values).  The weights are a
+ * snapshot taken at export.  A plan recorded by the binary16 build (libscot_hip_f16.so) loads into that build only; its split-MFMA
+ * trunk products run in the bfloat16 build, which the runtime opens from the same directory (or from where the peer call points).
+ *
+ * Status codes as in scot_hip.h: 0, -1 (malformed image / bad argument), -3 (not for this library: ABI, operand format, entry point;
+ * or a host other than x86-64 System V, where the replay underneath does not exist), -4 (allocation, copy or launch failed).
+ * Runs of ONE plan share its buffers: order them (one stream, or events of the caller's).  Two plans are independent.
+ */
+#ifndef SCOT_PLAN_H
+#define SCOT_PLAN_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#ifndef SCOT_HIP_H
+typedef struct ihipStream_t* scot_stream_t; /* = hipStream_t */
+#endif
+typedef void* scot_plan_t;
+
+/* Validates the WHOLE image first (csrc/plan_image.h: section bounds, counts, every relocation inside its buffer, format version, ABI
+ * and operand format equal to this library's, every entry point by name against the library's own list), then allocates the plan's
+ * device memory and uploads the constants on `stream`, and waits for the uploads: the image may be released on return.  `image` is
+ * host memory, 8-byte aligned.  On failure *plan is NULL and nothing stays allocated. */
+int scot_plan_load(const void* image, size_t bytes, scot_plan_t* plan, scot_stream_t stream);
+/* out[16]: batch, input channels, H, W, output channels, whether time is an input, its bytes, whether pixel_mask is an input, its
+ * bytes, operand format (0 bfloat16, 1 binary16), compute mode (0 fp32, 1 fp16, 2 bf16, 3 bf16x3), bytes of device memory held,
+ * recorded calls, bytes of pixel_values, bytes of the prediction, image format version. */
+int scot_plan_describe(scot_plan_t plan, long long* out);
+/* prediction [B, Cout, H, W] <- model(pixel_values [B, Cin, H, W], time [B]); fp32 device buffers of the caller.  time / pixel_mask
+ * are NULL exactly when the plan has no such input.  Copies in, replays the recorded calls with every stream slot = `stream`, copies
+ * out; everything is asynchronous on `stream`. */
+int scot_plan_run(scot_plan_t plan, const float* pixel_values, const float* time, const void* pixel_mask, float* prediction,
+                  scot_stream_t stream);
+/* Autoregressive rollout, the integer form of the reference's (trainer.py:452-603, output_all_steps): time / steps once (rounded as torch
+ * rounds it on the GPU: time * (1.0f / steps)), then `steps`
+ * forwards; forward k's prediction goes to predictions + k * B * Cout * H * W and back over the first Cout channels of the input, the
+ * other input channels stay as given.  Needs a time input and Cout <= Cin.  Reads `time` on the host once (waits for `stream` there). */
+int scot_plan_rollout(scot_plan_t plan, const float* pixel_values, const float* time, const void* pixel_mask, float* predictions,
+                      int steps, scot_stream_t stream);
+/* Releases the plan's memory (the caller orders this after its last run).  NULL is accepted. */
+int scot_plan_free(scot_plan_t plan);
+
+/* Name i of the entry points a plan may call (NULL past the end): what can run is what is listed. */
+const char* scot_plan_entry_point(int i);
+/* Where the bfloat16 build of the library is, for a binary16 plan's trunk products, if it is not `libscot_hip.so` in this library's
+ * own directory.  -3 if the file is not that build at this ABI. */
+int scot_plan_peer_library(const char* path);
+/* Test aid: every scratch buffer and the prediction's own buffer <- byte on `stream`.  With 0xff a run that reads what it did not
+ * write first yields NaN. */
+int scot_plan_poison(scot_plan_t plan, int byte, scot_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

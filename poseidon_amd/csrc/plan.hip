@@ -1,0 +1,369 @@
+// plan — running a trained model from C: the runtime of exported inference plans (include/scot_plan.h).
+//
+// poseidon_amd/plan.py records ONE inference forward of the engine for one input signature and writes it as a relocatable image
+// (plan_image.h: the list of C-ABI calls, every device address as (buffer, offset), every stream as a placeholder, the weights and
+// tables by value).  This file owns the memory and replays the list: scot_plan_load validates the image, allocates one slab for all
+// buffers, uploads the constants and builds the program of scot_tape_replay (host_tape.hip) with the final addresses; scot_plan_run
+// copies the caller's inputs in, writes the caller's stream into the program's stream slots, replays, and copies the prediction out.
+// Nothing here launches a kernel of its own: the copies are device-to-device copies, the arithmetic is the recorded entry points'.
+//
+// A plan is one stream's worth of state: its buffers are reused by every run, so runs of ONE plan must be ordered (same stream, or
+// the caller's own events); two plans are independent.
+#include "common.h"
+#include "plan_image.h"
+#include <dlfcn.h>
+#include <stdlib.h>
+#include <string.h>
+#include <new>
+#include <string>
+#include <vector>
+
+extern "C" int scot_tape_replay(const uint64_t* prog, size_t n_words, int* fail_entry);
+extern "C" int scot_abi_version();
+extern "C" int scot_operand_format();
+
+// the listed entry points, by address (same order as scot_plan_entry_names)
+#define SCOT_PLAN_DECLARE(n) extern "C" int n(...);
+SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_DECLARE)
+#define SCOT_PLAN_ADDRESS(n) (void*)&n,
+static void* const g_entry_address[] = {SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_ADDRESS)};
+
+// ------------------------------------------------------------------ device memory and copies (plain host memory in the CPU emulation)
+namespace {
+enum CopyKind { H2D, D2H, D2D };
+#ifdef SCOT_HIPEMU
+inline void* dev_alloc(size_t n) { return malloc(n); }
+inline void dev_free(void* p) { free(p); }
+inline bool dev_copy(void* dst, const void* src, size_t n, CopyKind, hipStream_t) { memmove(dst, src, n); return true; }
+inline bool dev_fill(void* dst, int byte, size_t n, hipStream_t) { memset(dst, byte, n); return true; }
+inline bool dev_copy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipStream_t) {
+  for (size_t r = 0; r < height; ++r) memmove((char*)dst + r * dpitch, (const char*)src + r * spitch, width);
+  return true;
+}
+inline bool dev_sync(hipStream_t) { return true; }
+#else
+inline void* dev_alloc(size_t n) {
+  void* p = nullptr;
+  return hipMalloc(&p, n) == hipSuccess ? p : nullptr;
+}
+inline void dev_free(void* p) { (void)hipFree(p); }
+inline bool dev_copy(void* dst, const void* src, size_t n, CopyKind k, hipStream_t s) {
+  const hipMemcpyKind kind = k == H2D ? hipMemcpyHostToDevice : (k == D2H ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
+  return hipMemcpyAsync(dst, src, n, kind, s) == hipSuccess;
+}
+inline bool dev_fill(void* dst, int byte, size_t n, hipStream_t s) { return hipMemsetAsync(dst, byte, n, s) == hipSuccess; }
+inline bool dev_copy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipStream_t s) {
+  return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDeviceToDevice, s) == hipSuccess;
+}
+inline bool dev_sync(hipStream_t s) { return hipStreamSynchronize(s) == hipSuccess; }
+#endif
+
+const uint64_t PLAN_HANDLE_MAGIC = 0x50414c5053434f54ull;
+const size_t SLAB_ALIGN = 256, SLAB_TAIL = 64 << 10;
+
+struct Plan {
+  uint64_t magic = PLAN_HANDLE_MAGIC;
+  char* slab = nullptr;
+  size_t slab_bytes = 0;
+  std::vector<char*> buf;                          // start of every buffer inside the slab
+  std::vector<uint64_t> buf_kind, buf_bytes;
+  std::vector<uint64_t> prog;                      // scot_tape_replay's word format, final addresses
+  std::vector<size_t> stream_slot;                 // words of prog that hold the stream
+  std::vector<std::vector<uint64_t>> ptr_arrays;   // host arrays the entries pass by address
+  std::vector<std::vector<int>> int_arrays;
+  std::vector<float> host_time;                    // scot_plan_rollout: the divided time on its way back to the device
+  uint64_t io[SCOT_PLAN_IO_WORDS] = {};
+  uint64_t n_entries = 0;
+  int operand_format = 0, compute = 0;
+};
+
+inline Plan* as_plan(void* p) {
+  Plan* pl = (Plan*)p;
+  return pl && pl->magic == PLAN_HANDLE_MAGIC ? pl : nullptr;
+}
+
+// The bfloat16 build of this library, for entries recorded there (plan_image.h: library 1).  The bfloat16 build is its own peer.
+void* g_peer = nullptr;
+
+void* open_peer(const char* path) {
+  void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+  if (!h) return nullptr;
+  typedef int (*query_t)();
+  query_t fmt = (query_t)dlsym(h, "scot_operand_format"), abi = (query_t)dlsym(h, "scot_abi_version");
+  if (!fmt || !abi || fmt() != 0 || abi() != scot_abi_version()) {
+    dlclose(h);
+    return nullptr;
+  }
+  return h;
+}
+
+// the library next to this one (libscot_hip.so beside libscot_hip_f16.so), unless scot_plan_peer_library named another
+void* default_peer() {
+  Dl_info info;
+  if (!dladdr((void*)&scot_operand_format, &info) || !info.dli_fname) return nullptr;
+  std::string dir(info.dli_fname);
+  const size_t slash = dir.rfind('/');
+  dir = slash == std::string::npos ? std::string(".") : dir.substr(0, slash);
+  return open_peer((dir + "/libscot_hip.so").c_str());
+}
+
+void* resolve(int name_index, uint64_t lib) {
+  if (lib == 0 || scot_operand_format() == 0) return g_entry_address[name_index];
+  if (!g_peer) g_peer = default_peer();
+  return g_peer ? dlsym(g_peer, scot_plan_entry_names[name_index]) : nullptr;
+}
+
+// one argument pair -> the word the call receives; `slot` = stream placeholder (patched per run)
+bool materialise(Plan* pl, uint64_t tagw, uint64_t val, uint64_t* out, bool* is_stream) {
+  *is_stream = false;
+  switch (tagw & 0xff) {
+    case SCOT_PLAN_ARG_INT: *out = val; return true;
+    case SCOT_PLAN_ARG_NULL: *out = 0; return true;
+    case SCOT_PLAN_ARG_PTR: *out = (uint64_t)(uintptr_t)(pl->buf[tagw >> 8] + val); return true;
+    case SCOT_PLAN_ARG_STREAM: *out = 0; *is_stream = true; return true;
+    default: return false;
+  }
+}
+
+int replay(Plan* pl, hipStream_t stream) {
+  for (size_t s : pl->stream_slot) pl->prog[s] = (uint64_t)(uintptr_t)stream;
+  int fail = -1;
+  return scot_tape_replay(pl->prog.data(), pl->prog.size(), &fail);
+}
+
+char* io_ptr(Plan* pl, int buf_word, int off_word) { return pl->buf[pl->io[buf_word]] + pl->io[off_word]; }
+}  // namespace
+
+extern "C" const char* scot_plan_entry_point(int i) { return i >= 0 && i < SCOT_PLAN_N_ENTRY_POINTS ? scot_plan_entry_names[i] : nullptr; }
+
+extern "C" int scot_plan_peer_library(const char* path) {
+  if (!path) return SCOT_ERR_SHAPE;
+  void* h = open_peer(path);
+  if (!h) return SCOT_ERR_UNSUPPORTED;
+  g_peer = h;      // (a previous handle stays open: plans loaded through it hold its addresses)
+  return SCOT_OK;
+}
+
+extern "C" int scot_plan_free(void* plan) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return plan ? SCOT_ERR_SHAPE : SCOT_OK;
+  if (pl->slab) dev_free(pl->slab);
+  pl->magic = 0;
+  delete pl;
+  return SCOT_OK;
+}
+
+extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipStream_t stream) {
+  if (!plan) return SCOT_ERR_SHAPE;
+  *plan = nullptr;
+#if !defined(__x86_64__) || defined(_WIN32)
+  (void)image; (void)bytes; (void)stream;
+  return SCOT_ERR_UNSUPPORTED;      // where scot_tape_replay is (host_tape.hip)
+#else
+  scot_plan_view v;
+  const int rc = scot_plan_image_validate(image, bytes, scot_abi_version(), scot_operand_format(), &v);
+  if (rc != SCOT_PLAN_OK) return rc;
+  Plan* pl = new (std::nothrow) Plan;
+  if (!pl) return SCOT_ERR_LAUNCH;
+  int status = SCOT_OK;
+  try {
+    memcpy(pl->io, v.io, sizeof(pl->io));
+    pl->n_entries = v.n_entries;
+    pl->operand_format = (int)v.h[SCOT_PLAN_H_OPERAND];
+    pl->compute = (int)v.h[SCOT_PLAN_H_COMPUTE];
+    // every entry point, before anything is allocated
+    std::vector<void*> fn(v.n_entries);
+    uint64_t w = 0;
+    for (uint64_t i = 0; i < v.n_entries && status == SCOT_OK; ++i) {
+      const uint64_t name = v.entries[w], lib = v.entries[w + 1], ni = v.entries[w + 2], nf = v.entries[w + 3];
+      fn[i] = resolve(scot_plan_entry_index((const char*)(v.names + name * SCOT_PLAN_NAME_BYTES)), lib);
+      if (!fn[i]) status = SCOT_ERR_UNSUPPORTED;
+      w += 4 + 2 * ni + nf;
+    }
+    // one slab, every buffer on a 256-byte boundary
+    std::vector<size_t> off(v.n_buffers);
+    size_t total = 0;
+    for (uint64_t i = 0; i < v.n_buffers; ++i) {
+      off[i] = total;
+      total += (size_t)((v.buffers[4 * i + 1] + SLAB_ALIGN - 1) / SLAB_ALIGN * SLAB_ALIGN);
+    }
+    if (status == SCOT_OK) {
+      // (one tile of room behind the last buffer: a kernel's vector load may run a few elements past the rows it was given, as it may
+      // inside a caching allocator's block)
+      pl->slab = (char*)dev_alloc(total + SLAB_TAIL);
+      pl->slab_bytes = total;
+      if (!pl->slab) status = SCOT_ERR_LAUNCH;
+    }
+    if (status == SCOT_OK) {
+      for (uint64_t i = 0; i < v.n_buffers; ++i) {
+        pl->buf.push_back(pl->slab + off[i]);
+        pl->buf_kind.push_back(v.buffers[4 * i]);
+        pl->buf_bytes.push_back(v.buffers[4 * i + 1]);
+      }
+      // (scratch is zeroed once so that a first run never reads bytes of whoever held the memory before; scot_plan_poison overwrites it)
+      if (!dev_fill(pl->slab, 0, total, stream)) status = SCOT_ERR_LAUNCH;
+      for (uint64_t i = 0; i < v.n_buffers && status == SCOT_OK; ++i)
+        if (v.buffers[4 * i] == SCOT_PLAN_BUF_CONSTANT &&
+            !dev_copy(pl->buf[i], v.data + v.buffers[4 * i + 2], (size_t)v.buffers[4 * i + 1], H2D, stream))
+          status = SCOT_ERR_LAUNCH;
+    }
+    // host arrays, with their final contents
+    std::vector<uint64_t> array_address;
+    if (status == SCOT_OK) {
+      w = 0;
+      for (uint64_t i = 0; i < v.n_arrays; ++i) {
+        const uint64_t kind = v.arrays[w], cnt = v.arrays[w + 1];
+        if (kind == 0) {
+          std::vector<int> a(cnt ? cnt : 1);
+          for (uint64_t k = 0; k < cnt; ++k) a[k] = (int)(int64_t)v.arrays[w + 3 + 2 * k];
+          pl->int_arrays.push_back(std::move(a));
+          array_address.push_back((uint64_t)(uintptr_t)pl->int_arrays.back().data());
+        } else {
+          std::vector<uint64_t> a(cnt ? cnt : 1);
+          for (uint64_t k = 0; k < cnt; ++k) {
+            bool st;
+            if (!materialise(pl, v.arrays[w + 2 + 2 * k], v.arrays[w + 3 + 2 * k], &a[k], &st)) status = SCOT_ERR_SHAPE;
+          }
+          pl->ptr_arrays.push_back(std::move(a));
+          array_address.push_back((uint64_t)(uintptr_t)pl->ptr_arrays.back().data());
+        }
+        w += 2 + 2 * cnt;
+      }
+    }
+    // the program
+    if (status == SCOT_OK) {
+      pl->prog.reserve((size_t)(v.entries_words + v.n_entries));
+      w = 0;
+      for (uint64_t i = 0; i < v.n_entries && status == SCOT_OK; ++i) {
+        const uint64_t ni = v.entries[w + 2], nf = v.entries[w + 3];
+        pl->prog.push_back((uint64_t)(uintptr_t)fn[i]);
+        pl->prog.push_back(ni);
+        pl->prog.push_back(nf);
+        for (uint64_t k = 0; k < ni; ++k) {
+          const uint64_t tagw = v.entries[w + 4 + 2 * k], val = v.entries[w + 5 + 2 * k];
+          uint64_t word = 0;
+          bool st = false;
+          if ((tagw & 0xff) == SCOT_PLAN_ARG_ARRAY)
+            word = array_address[val];
+          else if (!materialise(pl, tagw, val, &word, &st))
+            status = SCOT_ERR_SHAPE;
+          if (st) pl->stream_slot.push_back(pl->prog.size());
+          pl->prog.push_back(word);
+        }
+        for (uint64_t k = 0; k < nf; ++k) pl->prog.push_back(v.entries[w + 4 + 2 * ni + k]);
+        w += 4 + 2 * ni + nf;
+      }
+    }
+    // the image may be released when this returns: the uploads read it
+    if (status == SCOT_OK && !dev_sync(stream)) status = SCOT_ERR_LAUNCH;
+  } catch (const std::bad_alloc&) {
+    status = SCOT_ERR_LAUNCH;
+  }
+  if (status != SCOT_OK) {
+    if (pl->slab) (void)dev_sync(stream);
+    scot_plan_free(pl);
+    return status;
+  }
+  *plan = pl;
+  return SCOT_OK;
+#endif
+}
+
+// out[16]: batch, input channels, H, W, output channels, time is an input, its bytes, pixel_mask is an input, its bytes, operand format,
+// compute mode, bytes of device memory held, recorded calls, bytes of pixel_values, bytes of the prediction, image format version
+extern "C" int scot_plan_describe(void* plan, long long* out) {
+  Plan* pl = as_plan(plan);
+  if (!pl || !out) return SCOT_ERR_SHAPE;
+  const uint64_t* io = pl->io;
+  const uint64_t hw = io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * io[SCOT_PLAN_IO_B] * 4;
+  const long long d[16] = {(long long)io[SCOT_PLAN_IO_B], (long long)io[SCOT_PLAN_IO_CIN], (long long)io[SCOT_PLAN_IO_H],
+                           (long long)io[SCOT_PLAN_IO_W], (long long)io[SCOT_PLAN_IO_COUT], (long long)io[SCOT_PLAN_IO_HAS_TIME],
+                           (long long)(io[SCOT_PLAN_IO_HAS_TIME] ? io[SCOT_PLAN_IO_TIME_BYTES] : 0), (long long)io[SCOT_PLAN_IO_HAS_MASK],
+                           (long long)(io[SCOT_PLAN_IO_HAS_MASK] ? io[SCOT_PLAN_IO_MASK_BYTES] : 0), pl->operand_format, pl->compute,
+                           (long long)pl->slab_bytes, (long long)pl->n_entries, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
+                           (long long)(hw * io[SCOT_PLAN_IO_COUT]), SCOT_PLAN_FORMAT};
+  memcpy(out, d, sizeof(d));
+  return SCOT_OK;
+}
+
+// every scratch buffer and the prediction's buffer <- byte (a test aid: with 0xff a run that reads what it did not write yields NaN)
+extern "C" int scot_plan_poison(void* plan, int byte, hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  for (size_t i = 0; i < pl->buf.size(); ++i)
+    if (pl->buf_kind[i] == SCOT_PLAN_BUF_SCRATCH || pl->buf_kind[i] == SCOT_PLAN_BUF_OUTPUT)
+      if (!dev_fill(pl->buf[i], byte, (size_t)((pl->buf_bytes[i] + SLAB_ALIGN - 1) / SLAB_ALIGN * SLAB_ALIGN), stream)) return SCOT_ERR_LAUNCH;
+  return SCOT_OK;
+}
+
+static int check_inputs(Plan* pl, const void* pixel_values, const void* time, const void* pixel_mask, const void* out) {
+  if (!pixel_values || !out) return SCOT_ERR_SHAPE;
+  if ((pl->io[SCOT_PLAN_IO_HAS_TIME] != 0) != (time != nullptr)) return SCOT_ERR_SHAPE;
+  if ((pl->io[SCOT_PLAN_IO_HAS_MASK] != 0) != (pixel_mask != nullptr)) return SCOT_ERR_SHAPE;
+  return SCOT_OK;
+}
+
+extern "C" int scot_plan_run(void* plan, const float* pixel_values, const float* time, const void* pixel_mask, float* prediction,
+                             hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  int rc = check_inputs(pl, pixel_values, time, pixel_mask, prediction);
+  if (rc != SCOT_OK) return rc;
+  const uint64_t* io = pl->io;
+  const size_t plane = (size_t)(io[SCOT_PLAN_IO_B] * io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * 4);
+  if (!dev_copy(io_ptr(pl, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF), pixel_values, plane * io[SCOT_PLAN_IO_CIN], D2D, stream)) return SCOT_ERR_LAUNCH;
+  if (time && !dev_copy(io_ptr(pl, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF), time, (size_t)io[SCOT_PLAN_IO_TIME_BYTES], D2D, stream))
+    return SCOT_ERR_LAUNCH;
+  if (pixel_mask && !dev_copy(io_ptr(pl, SCOT_PLAN_IO_MASK_BUF, SCOT_PLAN_IO_MASK_OFF), pixel_mask, (size_t)io[SCOT_PLAN_IO_MASK_BYTES], D2D, stream))
+    return SCOT_ERR_LAUNCH;
+  rc = replay(pl, stream);
+  if (rc != SCOT_OK) return rc;
+  return dev_copy(prediction, io_ptr(pl, SCOT_PLAN_IO_OUT_BUF, SCOT_PLAN_IO_OUT_OFF), plane * io[SCOT_PLAN_IO_COUT], D2D, stream) ? SCOT_OK
+                                                                                                                                  : SCOT_ERR_LAUNCH;
+}
+
+// The integer form of the autoregressive rollout (reference trainer.py:452-603 with output_all_steps): time / steps once, then `steps`
+// forwards, each prediction written to predictions[k] ([steps][B, Cout, H, W]) and copied back over the first Cout channels of the
+// plan's input; the other input channels stay as given.  The division is the host's (one read of B floats: the call waits for
+// `stream` once, before the first forward); everything after it is asynchronous.
+extern "C" int scot_plan_rollout(void* plan, const float* pixel_values, const float* time, const void* pixel_mask, float* predictions,
+                                 int steps, hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  int rc = check_inputs(pl, pixel_values, time, pixel_mask, predictions);
+  if (rc != SCOT_OK) return rc;
+  const uint64_t* io = pl->io;
+  if (steps < 1 || io[SCOT_PLAN_IO_COUT] > io[SCOT_PLAN_IO_CIN]) return SCOT_ERR_SHAPE;
+  if (!io[SCOT_PLAN_IO_HAS_TIME]) return SCOT_ERR_UNSUPPORTED;      // (without conditioning the reference's rollout is one forward)
+  const size_t B = (size_t)io[SCOT_PLAN_IO_B], hw = (size_t)(io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * 4);
+  const size_t in_row = hw * io[SCOT_PLAN_IO_CIN], out_row = hw * io[SCOT_PLAN_IO_COUT];
+  char* in = io_ptr(pl, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF);
+  char* out = io_ptr(pl, SCOT_PLAN_IO_OUT_BUF, SCOT_PLAN_IO_OUT_OFF);
+  char* t = io_ptr(pl, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF);
+  try {
+    pl->host_time.resize(B);
+  } catch (const std::bad_alloc&) {
+    return SCOT_ERR_LAUNCH;
+  }
+  if (!dev_copy(pl->host_time.data(), time, B * 4, D2H, stream) || !dev_sync(stream)) return SCOT_ERR_LAUNCH;
+  // `time / steps` with torch's own rounding, so that the rollout equals harness.rollout bit for bit: torch's GPU kernel multiplies by the
+  // reciprocal of a host scalar (one rounding more than a division); its CPU kernel, which the emulated build is compared with, divides
+#ifdef SCOT_HIPEMU
+  for (size_t b = 0; b < B; ++b) pl->host_time[b] = pl->host_time[b] / (float)steps;
+#else
+  const float inv_steps = 1.0f / (float)steps;
+  for (size_t b = 0; b < B; ++b) pl->host_time[b] = pl->host_time[b] * inv_steps;
+#endif
+  if (!dev_copy(t, pl->host_time.data(), B * 4, H2D, stream)) return SCOT_ERR_LAUNCH;
+  if (!dev_copy(in, pixel_values, B * in_row, D2D, stream)) return SCOT_ERR_LAUNCH;
+  if (pixel_mask && !dev_copy(io_ptr(pl, SCOT_PLAN_IO_MASK_BUF, SCOT_PLAN_IO_MASK_OFF), pixel_mask, (size_t)io[SCOT_PLAN_IO_MASK_BYTES], D2D, stream))
+    return SCOT_ERR_LAUNCH;
+  for (int k = 0; k < steps; ++k) {
+    rc = replay(pl, stream);
+    if (rc != SCOT_OK) return rc;
+    if (!dev_copy((char*)predictions + (size_t)k * B * out_row, out, B * out_row, D2D, stream)) return SCOT_ERR_LAUNCH;
+    if (k + 1 < steps && !dev_copy2d(in, in_row, out, out_row, out_row, B, stream)) return SCOT_ERR_LAUNCH;
+  }
+  // (host_time is pageable memory: the runtime has staged it by the time the copy call returned)
+  return SCOT_OK;
+}

@@ -1,0 +1,206 @@
+// plan_image — the format of an exported inference plan and its validator.  Header-only and HIP-free: plan.hip uses it inside the
+// library, tools/plan_image_check.cc compiles it alone (with the host sanitizers) and runs it over good and corrupt images.
+//
+// A plan image (poseidon_amd/plan.py writes it) is ONE recorded inference forward of the engine for one input signature, made
+// relocatable: the flat list of C-ABI calls with their final arguments, every device address replaced by (buffer index, byte offset)
+// and every stream argument by a placeholder.  All fields are little-endian uint64 words; the file is
+//
+//   header   SCOT_PLAN_HEADER_WORDS words (indices below)
+//   names    n_names records of SCOT_PLAN_NAME_BYTES bytes: NUL-terminated entry-point names
+//   buffers  n_buffers records of 4 words: kind, bytes, offset of the content in the data section (constants), 0
+//   entries  n_entries variable-length records: name index, library (0 = the build that loads the image, 1 = the bfloat16 build: the
+//            split-MFMA trunk GEMMs of the binary16 mode run there), n_int, n_flt, n_int argument pairs, n_flt words of raw float bits
+//   arrays   n_arrays host arrays passed by address: kind (0 = int32, 1 = pointers), count, count argument pairs
+//   io       SCOT_PLAN_IO_WORDS words: shapes and the (buffer, offset) of the inputs and of the prediction
+//   data     the constants' bytes, each piece 64-byte aligned
+//
+// An argument pair is {tag | buffer << 8, value}: SCOT_PLAN_ARG_INT (value as is), _NULL, _PTR (buffer index, byte offset), _STREAM
+// (the caller's stream at run time) or _ARRAY (value = index into `arrays`).
+#ifndef SCOT_PLAN_IMAGE_H
+#define SCOT_PLAN_IMAGE_H
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#define SCOT_PLAN_MAGIC 0x4e414c50544f4353ull /* "SCOTPLAN" */
+#define SCOT_PLAN_FORMAT 1
+#define SCOT_PLAN_HEADER_WORDS 32
+#define SCOT_PLAN_NAME_BYTES 48
+#define SCOT_PLAN_IO_WORDS 24
+#define SCOT_PLAN_MAX_INT 48 /* = SCOT_TAPE_MAX_INT of host_tape.hip: what one replayed call can carry */
+#define SCOT_PLAN_MAX_FLT 8
+
+enum { SCOT_PLAN_H_MAGIC, SCOT_PLAN_H_FORMAT, SCOT_PLAN_H_ABI, SCOT_PLAN_H_OPERAND, SCOT_PLAN_H_COMPUTE, SCOT_PLAN_H_BYTES,
+       SCOT_PLAN_H_NNAMES, SCOT_PLAN_H_NAMES_OFF, SCOT_PLAN_H_NBUFFERS, SCOT_PLAN_H_BUFFERS_OFF, SCOT_PLAN_H_NENTRIES,
+       SCOT_PLAN_H_ENTRIES_OFF, SCOT_PLAN_H_ENTRIES_WORDS, SCOT_PLAN_H_NARRAYS, SCOT_PLAN_H_ARRAYS_OFF, SCOT_PLAN_H_ARRAYS_WORDS,
+       SCOT_PLAN_H_IO_OFF, SCOT_PLAN_H_DATA_OFF, SCOT_PLAN_H_DATA_BYTES };
+enum { SCOT_PLAN_BUF_CONSTANT, SCOT_PLAN_BUF_INPUT, SCOT_PLAN_BUF_OUTPUT, SCOT_PLAN_BUF_SCRATCH };
+enum { SCOT_PLAN_ARG_INT, SCOT_PLAN_ARG_NULL, SCOT_PLAN_ARG_PTR, SCOT_PLAN_ARG_STREAM, SCOT_PLAN_ARG_ARRAY };
+enum { SCOT_PLAN_IO_B, SCOT_PLAN_IO_CIN, SCOT_PLAN_IO_H, SCOT_PLAN_IO_W, SCOT_PLAN_IO_COUT, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF,
+       SCOT_PLAN_IO_HAS_TIME, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF, SCOT_PLAN_IO_TIME_BYTES, SCOT_PLAN_IO_HAS_MASK,
+       SCOT_PLAN_IO_MASK_BUF, SCOT_PLAN_IO_MASK_OFF, SCOT_PLAN_IO_MASK_BYTES, SCOT_PLAN_IO_OUT_BUF, SCOT_PLAN_IO_OUT_OFF };
+
+// What an inference forward may call: what can run is what is listed.  (X-macro: plan.hip builds the table of addresses from it.)
+#define SCOT_PLAN_ENTRY_POINTS(X)                                                                                                     \
+  X(scot_gemm) X(scot_cpb_fwd_batched) X(scot_cln_fwd) X(scot_window_attn_fwd) X(scot_mlp_block_fwd) X(scot_block_tail_fwd)          \
+  X(scot_proj_cln_fwd) X(scot_add) X(scot_copy2d) X(scot_space_to_depth) X(scot_depth_to_space) X(scot_patchify) X(scot_unpatchify) \
+  X(scot_scale_residual) X(scot_dwconv7) X(scot_conv5) X(scot_head_finalize) X(scot_memset_async) X(scot_memcpy_async)
+
+#define SCOT_PLAN_NAME_STRING(n) #n,
+static const char* const scot_plan_entry_names[] = {SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_NAME_STRING)};
+#define SCOT_PLAN_N_ENTRY_POINTS ((int)(sizeof(scot_plan_entry_names) / sizeof(scot_plan_entry_names[0])))
+
+static inline int scot_plan_entry_index(const char* name) {
+  for (int i = 0; i < SCOT_PLAN_N_ENTRY_POINTS; ++i)
+    if (strcmp(name, scot_plan_entry_names[i]) == 0) return i;
+  return -1;
+}
+
+// status codes of the C ABI (common.h), restated so that this header needs nothing else
+#define SCOT_PLAN_OK 0
+#define SCOT_PLAN_ERR_SHAPE (-1)       /* malformed image: bounds, counts, relocations */
+#define SCOT_PLAN_ERR_UNSUPPORTED (-3) /* well formed, but not for this library: ABI, operand format, format version, entry point */
+
+typedef struct {
+  const uint8_t* base;
+  size_t bytes;
+  const uint64_t* h;       /* header */
+  const uint8_t* names;    /* n_names x SCOT_PLAN_NAME_BYTES */
+  const uint64_t* buffers; /* n_buffers x 4 */
+  const uint64_t* entries;
+  const uint64_t* arrays;
+  const uint64_t* io;
+  const uint8_t* data;
+  uint64_t n_names, n_buffers, n_entries, entries_words, n_arrays, arrays_words, data_bytes;
+} scot_plan_view;
+
+static inline uint64_t scot_plan_word(const uint8_t* p) {
+  uint64_t w;
+  memcpy(&w, p, 8);
+  return w;
+}
+
+// [off, off + n) inside [0, bytes), off 8-byte aligned, without overflow
+static inline int scot_plan_span_ok(uint64_t off, uint64_t n, uint64_t bytes) {
+  return (off & 7) == 0 && off <= bytes && n <= bytes - off;
+}
+
+// one argument pair: the tag is known, a relocation lies inside its buffer, an array index exists
+static inline int scot_plan_arg_ok(const scot_plan_view* v, uint64_t tagw, uint64_t val, int in_array) {
+  const uint64_t tag = tagw & 0xff, buf = tagw >> 8;
+  switch (tag) {
+    case SCOT_PLAN_ARG_INT:
+    case SCOT_PLAN_ARG_NULL:
+      return buf == 0;
+    case SCOT_PLAN_ARG_STREAM:
+      return buf == 0 && !in_array;
+    case SCOT_PLAN_ARG_PTR:
+      return buf < v->n_buffers && val < v->buffers[4 * buf + 1];      /* a pointer names a byte OF the buffer */
+    case SCOT_PLAN_ARG_ARRAY:
+      return buf == 0 && !in_array && val < v->n_arrays;
+    default:
+      return 0;
+  }
+}
+
+// Validates the whole image before anything is allocated: section bounds, counts, every relocation inside its buffer, every name in
+// the table above, and a format version, ABI and operand format equal to the caller's (the library's own).  Fills *v with pointers INTO
+// the image.  `image` must be 8-byte aligned.
+static inline int scot_plan_image_validate(const void* image, size_t bytes, int abi, int operand_format, scot_plan_view* v) {
+  memset(v, 0, sizeof(*v));
+  if (!image || ((uintptr_t)image & 7) || bytes < SCOT_PLAN_HEADER_WORDS * 8) return SCOT_PLAN_ERR_SHAPE;
+  const uint8_t* b = (const uint8_t*)image;
+  const uint64_t* h = (const uint64_t*)image;
+  if (h[SCOT_PLAN_H_MAGIC] != SCOT_PLAN_MAGIC) return SCOT_PLAN_ERR_SHAPE;
+  if (h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT) return SCOT_PLAN_ERR_UNSUPPORTED;
+  if (h[SCOT_PLAN_H_ABI] != (uint64_t)abi || h[SCOT_PLAN_H_OPERAND] != (uint64_t)operand_format) return SCOT_PLAN_ERR_UNSUPPORTED;
+  if (h[SCOT_PLAN_H_BYTES] != (uint64_t)bytes) return SCOT_PLAN_ERR_SHAPE;      /* a truncated (or padded) file */
+  v->base = b;
+  v->bytes = bytes;
+  v->h = h;
+  v->n_names = h[SCOT_PLAN_H_NNAMES];
+  v->n_buffers = h[SCOT_PLAN_H_NBUFFERS];
+  v->n_entries = h[SCOT_PLAN_H_NENTRIES];
+  v->entries_words = h[SCOT_PLAN_H_ENTRIES_WORDS];
+  v->n_arrays = h[SCOT_PLAN_H_NARRAYS];
+  v->arrays_words = h[SCOT_PLAN_H_ARRAYS_WORDS];
+  v->data_bytes = h[SCOT_PLAN_H_DATA_BYTES];
+  const uint64_t lim = (uint64_t)1 << 32;      /* counts that cannot overflow the products below */
+  if (v->n_names > lim || v->n_buffers > lim || v->n_entries > lim || v->entries_words > lim || v->n_arrays > lim || v->arrays_words > lim)
+    return SCOT_PLAN_ERR_SHAPE;
+  if (!scot_plan_span_ok(h[SCOT_PLAN_H_NAMES_OFF], v->n_names * SCOT_PLAN_NAME_BYTES, bytes) ||
+      !scot_plan_span_ok(h[SCOT_PLAN_H_BUFFERS_OFF], v->n_buffers * 32, bytes) ||
+      !scot_plan_span_ok(h[SCOT_PLAN_H_ENTRIES_OFF], v->entries_words * 8, bytes) ||
+      !scot_plan_span_ok(h[SCOT_PLAN_H_ARRAYS_OFF], v->arrays_words * 8, bytes) ||
+      !scot_plan_span_ok(h[SCOT_PLAN_H_IO_OFF], SCOT_PLAN_IO_WORDS * 8, bytes) ||
+      !scot_plan_span_ok(h[SCOT_PLAN_H_DATA_OFF], v->data_bytes, bytes))
+    return SCOT_PLAN_ERR_SHAPE;
+  v->names = b + h[SCOT_PLAN_H_NAMES_OFF];
+  v->buffers = (const uint64_t*)(b + h[SCOT_PLAN_H_BUFFERS_OFF]);
+  v->entries = (const uint64_t*)(b + h[SCOT_PLAN_H_ENTRIES_OFF]);
+  v->arrays = (const uint64_t*)(b + h[SCOT_PLAN_H_ARRAYS_OFF]);
+  v->io = (const uint64_t*)(b + h[SCOT_PLAN_H_IO_OFF]);
+  v->data = b + h[SCOT_PLAN_H_DATA_OFF];
+  // names: terminated, and listed
+  for (uint64_t i = 0; i < v->n_names; ++i) {
+    const char* nm = (const char*)(v->names + i * SCOT_PLAN_NAME_BYTES);
+    if (!memchr(nm, 0, SCOT_PLAN_NAME_BYTES)) return SCOT_PLAN_ERR_SHAPE;
+    if (scot_plan_entry_index(nm) < 0) return SCOT_PLAN_ERR_UNSUPPORTED;
+  }
+  // buffers: a known kind, a size, a constant's content inside the data section
+  for (uint64_t i = 0; i < v->n_buffers; ++i) {
+    const uint64_t kind = v->buffers[4 * i], n = v->buffers[4 * i + 1], off = v->buffers[4 * i + 2];
+    if (kind > SCOT_PLAN_BUF_SCRATCH || n == 0 || n > ((uint64_t)1 << 40)) return SCOT_PLAN_ERR_SHAPE;
+    if (kind == SCOT_PLAN_BUF_CONSTANT && !scot_plan_span_ok(off, n, v->data_bytes)) return SCOT_PLAN_ERR_SHAPE;
+  }
+  // arrays
+  uint64_t w = 0;
+  for (uint64_t i = 0; i < v->n_arrays; ++i) {
+    if (v->arrays_words - w < 2) return SCOT_PLAN_ERR_SHAPE;
+    const uint64_t kind = v->arrays[w], cnt = v->arrays[w + 1];
+    if (kind > 1 || cnt > (v->arrays_words - w - 2) / 2) return SCOT_PLAN_ERR_SHAPE;
+    for (uint64_t k = 0; k < cnt; ++k) {
+      const uint64_t tagw = v->arrays[w + 2 + 2 * k], val = v->arrays[w + 3 + 2 * k];
+      if (!scot_plan_arg_ok(v, tagw, val, 1)) return SCOT_PLAN_ERR_SHAPE;
+      if (kind == 0 && (tagw & 0xff) != SCOT_PLAN_ARG_INT) return SCOT_PLAN_ERR_SHAPE;
+      if (kind == 1 && (tagw & 0xff) == SCOT_PLAN_ARG_INT) return SCOT_PLAN_ERR_SHAPE;
+    }
+    w += 2 + 2 * cnt;
+  }
+  if (w != v->arrays_words) return SCOT_PLAN_ERR_SHAPE;
+  // entries
+  w = 0;
+  for (uint64_t i = 0; i < v->n_entries; ++i) {
+    if (v->entries_words - w < 4) return SCOT_PLAN_ERR_SHAPE;
+    const uint64_t name = v->entries[w], lib = v->entries[w + 1], ni = v->entries[w + 2], nf = v->entries[w + 3];
+    if (name >= v->n_names || lib > 1 || ni > SCOT_PLAN_MAX_INT || nf > SCOT_PLAN_MAX_FLT) return SCOT_PLAN_ERR_SHAPE;
+    if (2 * ni + nf > v->entries_words - w - 4) return SCOT_PLAN_ERR_SHAPE;
+    for (uint64_t k = 0; k < ni; ++k)
+      if (!scot_plan_arg_ok(v, v->entries[w + 4 + 2 * k], v->entries[w + 5 + 2 * k], 0)) return SCOT_PLAN_ERR_SHAPE;
+    for (uint64_t k = 0; k < nf; ++k)
+      if (v->entries[w + 4 + 2 * ni + k] >> 32) return SCOT_PLAN_ERR_SHAPE;      /* raw bits of ONE float */
+    w += 4 + 2 * ni + nf;
+  }
+  if (w != v->entries_words) return SCOT_PLAN_ERR_SHAPE;
+  // io: fp32 [B, Cin, H, W] in, fp32 [B, Cout, H, W] out, each whole inside a buffer of the right kind
+  const uint64_t* io = v->io;
+  const uint64_t B = io[SCOT_PLAN_IO_B], Cin = io[SCOT_PLAN_IO_CIN], H = io[SCOT_PLAN_IO_H], W = io[SCOT_PLAN_IO_W], Cout = io[SCOT_PLAN_IO_COUT];
+  if (!B || !Cin || !H || !W || !Cout || B > 65536 || Cin > 65536 || Cout > 65536 || H > 65536 || W > 65536) return SCOT_PLAN_ERR_SHAPE;
+  if (B * Cin * H * W > ((uint64_t)1 << 38) || B * Cout * H * W > ((uint64_t)1 << 38)) return SCOT_PLAN_ERR_SHAPE;
+  const uint64_t spans[4][5] = {
+      {1, io[SCOT_PLAN_IO_PV_BUF], io[SCOT_PLAN_IO_PV_OFF], B * Cin * H * W * 4, SCOT_PLAN_BUF_INPUT},
+      {io[SCOT_PLAN_IO_HAS_TIME], io[SCOT_PLAN_IO_TIME_BUF], io[SCOT_PLAN_IO_TIME_OFF], io[SCOT_PLAN_IO_TIME_BYTES], SCOT_PLAN_BUF_INPUT},
+      {io[SCOT_PLAN_IO_HAS_MASK], io[SCOT_PLAN_IO_MASK_BUF], io[SCOT_PLAN_IO_MASK_OFF], io[SCOT_PLAN_IO_MASK_BYTES], SCOT_PLAN_BUF_INPUT},
+      {1, io[SCOT_PLAN_IO_OUT_BUF], io[SCOT_PLAN_IO_OUT_OFF], B * Cout * H * W * 4, SCOT_PLAN_BUF_OUTPUT}};
+  for (int s = 0; s < 4; ++s) {
+    if (spans[s][0] > 1) return SCOT_PLAN_ERR_SHAPE;
+    if (!spans[s][0]) continue;
+    const uint64_t buf = spans[s][1], off = spans[s][2], n = spans[s][3];
+    if (buf >= v->n_buffers || n == 0) return SCOT_PLAN_ERR_SHAPE;
+    const uint64_t cap = v->buffers[4 * buf + 1];
+    if (off > cap || n > cap - off || v->buffers[4 * buf] != spans[s][4]) return SCOT_PLAN_ERR_SHAPE;
+  }
+  if (io[SCOT_PLAN_IO_HAS_TIME] && io[SCOT_PLAN_IO_TIME_BYTES] != B * 4) return SCOT_PLAN_ERR_SHAPE;
+  return SCOT_PLAN_OK;
+}
+#endif

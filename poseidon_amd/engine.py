@@ -116,6 +116,7 @@ class ScOTEngine:
         self.tape_c = __import__("platform").machine() in ("x86_64", "AMD64")     # (scot_tape_replay is System V x86-64 only)
         self._rec = None
         self._rec_keep = None
+        self._export = None         # plan.py's buffer registry while ScOT.export_plan records its forward: new / pool report to it
         self._taped = {}
         self._pending = []
         self._wgq = []                                                  # weight gradients waiting to be grouped (see wgrad)
@@ -489,6 +490,8 @@ class ScOTEngine:
             t = torch.empty(*shape, dtype=dtype, device=self.device)
         if self._rec is not None:
             self._rec_keep.append(t)   # a recorded step owns its buffers for good: replays reuse these very addresses
+        if self._export is not None:
+            self._export.scratch(t)
         return t
 
     def pool(self, tag, *shape, dtype=torch.float32):
@@ -501,6 +504,8 @@ class ScOTEngine:
             t = self._pool[key] = torch.empty(*shape, dtype=dtype, device=self.device)
         if self._rec is not None:
             self._rec_keep.append(t)      # (a recorded step names the address: it keeps the buffer alive whatever happens to the pool)
+        if self._export is not None:
+            self._export.scratch(t)
         return t
 
     def zeros(self, *shape, dtype=torch.float32):
@@ -511,7 +516,20 @@ class ScOTEngine:
     # Host-side operations between launches, as C-ABI calls on the GPU (so that they are ordinary tape entries and a recorded forward or
     # backward replays as one run inside the library); torch calls on the CPU emulation of the tests.
     def _native_host_ops(self):
-        return self.device.type == "cuda"
+        # (an export records C-ABI calls only, also on the CPU emulation, whose library implements the memset and the copy)
+        return self.device.type == "cuda" or self._export is not None
+
+    def plan_buffers(self):
+        """What an inference forward touches that exists BEFORE it, for plan.py: [(name, tensor, constant?)].  Constants are stored in a
+        plan image by value (the parameter arena, its 16-bit copy, the bias-MLP tables); the rest is written by the forward before it
+        is read (the bias tables every forward recomputes) and only needs room."""
+        out = [("arena", self.arena.data, True)]
+        if self.shadow is not None:
+            out.append(("shadow", self.shadow, True))
+        out += [("cpb_coords", self.cpb_coords, True), ("cpb_desc", self.cpb_desc, True)]
+        out += [(f"coords{ws}", t, True) for ws, t in sorted(self._coords.items())]
+        out += [("cpb_tables", self.cpb_tables, False), ("cpb_z", self.cpb_z, False)]
+        return out
 
     def h_zero(self, t):
         if self._native_host_ops() and t.is_contiguous():

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libscot_hip.so")
 # The same sources built twice (build.py): the format of the 16-bit operand type is a compile-time property (csrc/common.h).
 LIB_PATHS = {"bf16": LIB_PATH, "f16": os.path.join(_HERE, "libscot_hip_f16.so")}
 OPERAND_FORMAT = {"bf16": 0, "f16": 1}
-ABI_VERSION = 7      # scot_abi_version() of the library these prototypes describe (checked at load)
+ABI_VERSION = 8      # scot_abi_version() of the library these prototypes describe (checked at load)
 
 P, I, F, Z = c_void_p, c_int, c_float, c_size_t
 
@@ -111,13 +111,37 @@ PROTOTYPES = {
     "scot_adamw_step": [P, P, P, P, P, Z, P, P, I, F, F, F, I, P, P, P, P],
     "scot_optim_finish": [P, P, P, F, F, I, F, P],
 }
+# The model-level calls (include/scot_plan.h, csrc/plan.hip): exported inference plans.  A table of their own: they are not kernel entry
+# points (no launch of their own, queries and a free among them), so the conventions checked on PROTOTYPES do not describe them.
+PLAN_PROTOTYPES = {
+    "scot_plan_load": [P, Z, P, P],
+    "scot_plan_describe": [P, P],
+    "scot_plan_run": [P, P, P, P, P, P],
+    "scot_plan_rollout": [P, P, P, P, P, I, P],
+    "scot_plan_free": [P],
+    "scot_plan_entry_point": [I],
+    "scot_plan_peer_library": [ctypes.c_char_p],
+    "scot_plan_poison": [P, I, P],
+}
 _VOID = {"scot_set_use_tr", "scot_gemm_wide_config", "scot_gemm_splitk_config"}
 _SIZE = {"scot_gemm_workspace_bytes", "scot_wgrad_group_workspace_bytes", "scot_cln_bwd_workspace_bytes", "scot_wgrad_mlp_workspace_bytes",
          "scot_cln_dtime_workspace_bytes"}      # return size_t
 
 
 def restype(name):
+    if name == "scot_plan_entry_point":
+        return ctypes.c_char_p
     return None if name in _VOID else (c_size_t if name in _SIZE else c_int)
+
+
+def bind(lib):
+    """Type every declared symbol of a loaded build (AttributeError if one is missing): the kernel table and the plan table."""
+    for table in (PROTOTYPES, PLAN_PROTOTYPES):
+        for name, argtypes in table.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = restype(name)
+    return lib
 
 _libs = {}
 
@@ -142,10 +166,7 @@ def load(path: str = None, kind: str = "bf16"):
             f"{path} not found: the scOT hot path is HIP-only. Build it with `python -m poseidon_amd.build` "
             "(hipcc --offload-arch=gfx950).")
     lib = ctypes.CDLL(path)
-    for name, argtypes in PROTOTYPES.items():
-        fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
-        fn.argtypes = argtypes
-        fn.restype = restype(name)
+    bind(lib)  # AttributeError if a declared symbol is missing
     if lib.scot_abi_version() != ABI_VERSION:
         raise ScotLibraryError(f"{path} implements ABI version {lib.scot_abi_version()}, these bindings expect {ABI_VERSION}; "
                                "rebuild with `python -m poseidon_amd.build --force`")

@@ -1,0 +1,530 @@
+"""Exported inference plans: a trained model that runs from the C ABI alone (include/scot_plan.h, csrc/plan.hip).
+
+`export_plan` makes one dedicated recording of the engine's inference forward for exactly the given input shapes — on one stream, the
+weight-gradient stream switched off, so the list is linear and needs no events — and turns it into a relocatable image
+(csrc/plan_image.h): every argument of every recorded call is classified from its `argtypes`; a device address becomes (buffer index,
+byte offset), where the buffers are what the allocation funnels (`engine.new` / `engine.pool`, `ops.workspace`, the engine's own list
+of constants, the input copies) registered WHILE the forward was recorded; the stream becomes a placeholder.  Constants are stored by
+value.  Before the file is written the image is loaded through the runtime in this process, its scratch filled with NaN bytes, and run
+on the export inputs: the prediction has to be finite and bit-identical to the model's own.
+
+`Plan` is the ctypes wrapper of the runtime, for the tests and for a Python process that wants inference without torch (it imports
+torch only if the caller hands it tensors).
+"""
+from __future__ import annotations
+
+import ctypes
+import struct
+import sys
+
+from . import lib as _lib
+
+MAGIC = 0x4e414c50544f4353
+FORMAT = 1
+HEADER_WORDS, NAME_BYTES, IO_WORDS = 32, 48, 24
+CONSTANT, INPUT, OUTPUT, SCRATCH = range(4)
+ARG_INT, ARG_NULL, ARG_PTR, ARG_STREAM, ARG_ARRAY = range(5)
+COMPUTE_CODE = {"fp32": 0, "fp16": 1, "bf16": 2, "bf16x3": 3}
+MAX_INT, MAX_FLT = 48, 8
+(H_MAGIC, H_FORMAT, H_ABI, H_OPERAND, H_COMPUTE, H_BYTES, H_NNAMES, H_NAMES_OFF, H_NBUFFERS, H_BUFFERS_OFF, H_NENTRIES, H_ENTRIES_OFF,
+ H_ENTRIES_WORDS, H_NARRAYS, H_ARRAYS_OFF, H_ARRAYS_WORDS, H_IO_OFF, H_DATA_OFF, H_DATA_BYTES) = range(19)
+DESCRIBE = ("batch", "channels", "height", "width", "out_channels", "has_time", "time_bytes", "has_pixel_mask", "pixel_mask_bytes",
+            "operand_format", "compute", "device_bytes", "calls", "pixel_values_bytes", "prediction_bytes", "format")
+
+
+class PlanExportError(RuntimeError):
+    pass
+
+
+def bind(lib):
+    """type the plan calls of a loaded build of the library (idempotent)"""
+    for name, argtypes in _lib.PLAN_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = _lib.restype(name)
+    return lib
+
+
+def runtime_entry_points(lib):
+    """the entry points the runtime of this build lists: what a plan may call"""
+    bind(lib)
+    out, i = [], 0
+    while True:
+        n = lib.scot_plan_entry_point(i)
+        if n is None:
+            return out
+        out.append(n.decode())
+        i += 1
+
+
+# ----------------------------------------------------------------------------------------------------------------- export
+class _Registry:
+    """The allocations an export's recording touches, registered where they are made."""
+
+    def __init__(self):
+        self.bufs = {}      # address -> dict(addr, bytes, kind, name, tensor)
+
+    def add(self, t, kind, name):
+        n = t.numel() * t.element_size()
+        if n == 0:
+            return
+        if not t.is_contiguous():
+            raise PlanExportError(f"export_plan: buffer {name} is not contiguous")
+        a = t.data_ptr()
+        cur = self.bufs.get(a)
+        if cur is None or cur["bytes"] < n:
+            self.bufs[a] = dict(addr=a, bytes=n, kind=kind if cur is None else min(kind, cur["kind"]), name=name, tensor=t)
+
+    def scratch(self, t):
+        self.add(t, SCRATCH, "scratch")
+
+    def freeze(self):
+        self.order = sorted(self.bufs.values(), key=lambda b: b["addr"])
+        self.starts = [b["addr"] for b in self.order]
+        for a, b in zip(self.order, self.order[1:]):
+            if a["addr"] + a["bytes"] > b["addr"]:
+                raise PlanExportError(f"export_plan: registered buffers {a['name']} and {b['name']} overlap")
+
+    def resolve(self, addr):
+        import bisect
+        i = bisect.bisect_right(self.starts, addr) - 1
+        if i >= 0 and addr < self.order[i]["addr"] + self.order[i]["bytes"]:
+            return self.order[i], addr - self.order[i]["addr"]
+        return None, 0
+
+
+def _address(fn):
+    return ctypes.cast(fn, ctypes.c_void_p).value
+
+
+def _check_request(model, pixel_values, time, pixel_mask, labels):
+    from . import ops
+    cfg = model.config
+    if labels is not None:
+        raise PlanExportError("export_plan: labels are not part of a plan (it covers the inference forward: no loss)")
+    if pixel_mask is not None:
+        raise PlanExportError("export_plan: pixel_mask overwrites the prediction with label values (reference model.py:1411-1484) and a "
+                              "plan takes no labels: apply the mask to the plan's prediction in the host program")
+    if pixel_values is None or pixel_values.dim() != 4:
+        raise PlanExportError("export_plan: pixel_values [B, C, H, W] is required")
+    try:
+        ops.ptr(pixel_values)
+    except _lib.ScotLibraryError as e:
+        raise PlanExportError("export_plan: a CPU model cannot be exported — the forward that is recorded runs on the GPU "
+                              f"(move the model and the example inputs there first): {e}") from None
+    if pixel_values.shape[2] != cfg.image_size or pixel_values.shape[3] != cfg.image_size:
+        raise PlanExportError(f"export_plan: input size {tuple(pixel_values.shape[2:])} differs from config.image_size = {cfg.image_size}; the "
+                              "spectral resize lives outside the engine and a plan covers the engine forward only")
+    if pixel_values.shape[1] != cfg.num_channels:
+        raise PlanExportError(f"export_plan: pixel_values has {pixel_values.shape[1]} channels, the model takes {cfg.num_channels}")
+    if model.training and float(getattr(cfg, "drop_path_rate", 0.0) or 0.0) > 0.0:
+        raise PlanExportError("export_plan: the model is in training mode with stochastic depth (drop_path_rate > 0): its forward draws "
+                              "random masks on the host; call model.eval() first")
+    if cfg.use_conditioning and time is None:
+        raise PlanExportError("export_plan: time is required when use_conditioning=True")
+
+
+def _record(model, pv, t):
+    """-> (registry, recorded calls, prediction tensor, input copies): ONE dedicated, linear recording of engine._forward"""
+    from . import ops
+    eng = model._engine
+    reg = _Registry()
+    for name, ten, const in eng.plan_buffers():
+        reg.add(ten, CONSTANT if const else SCRATCH, name)
+    pv_in = pv.clone()
+    t_in = None if t is None else t.clone()
+    reg.add(pv_in, INPUT, "pixel_values")
+    if t_in is not None:
+        reg.add(t_in, INPUT, "time")
+    inner_workspace = ops.workspace
+
+    def workspace(need=0):      # the split-K scratch of the wrappers is an allocation funnel too
+        w = inner_workspace(need)
+        reg.scratch(w)
+        return w
+    saved = dict(use_side=eng.use_side, stage_timing=eng.stage_timing, stochastic=eng.stochastic, collect_attn=eng.collect_attn,
+                 last_hidden=eng.last_hidden, last_hidden_aliased=eng.last_hidden_aliased, _rec=eng._rec, _rec_keep=eng._rec_keep,
+                 _fwd_flags=eng._fwd_flags)
+    rec, keep = [], []
+    prev_lib = ops.use(eng.lib_kind)
+    try:
+        eng.refresh_weight_copies(False)      # (never part of a recording: the 16-bit copies are constants of the image)
+        ops.workspace = workspace
+        eng.use_side = eng.stage_timing = eng.stochastic = eng.collect_attn = False
+        eng._export, eng._rec, eng._rec_keep = reg, rec, keep
+        prev_rec = ops.set_recorder(rec)
+        try:
+            _, pred, _ = eng._forward(pv_in, t_in, None, None, False)
+        finally:
+            ops.set_recorder(prev_rec)
+    finally:
+        ops.workspace = inner_workspace
+        eng._export = None
+        for k, v in saved.items():
+            setattr(eng, k, v)
+        ops.use(prev_lib)
+    for name, ten, const in eng.plan_buffers():      # (tables the forward created on first use)
+        if ten.data_ptr() not in reg.bufs:
+            reg.add(ten, CONSTANT if const else SCRATCH, name)
+    return reg, rec, keep, pred, pv_in, t_in
+
+
+def _libraries(eng):
+    """(the engine's build of the library, the bfloat16 build if that is another one)"""
+    from . import ops
+    prev = ops.use(eng.lib_kind)
+    try:
+        own = ops._raw()
+        ops.use("bf16")
+        peer = ops._raw() if eng.lib_kind != "bf16" else None
+    finally:
+        ops.use(prev)
+    return own, peer
+
+
+def _bytes_of(t):
+    return t.detach().reshape(-1).cpu().contiguous().view(__import__("torch").uint8).numpy().tobytes()
+
+
+def build_image(model, reg, rec, pred, pv_in, t_in, own, peer):
+    """recorded calls + registered buffers -> the bytes of a plan image"""
+    eng = model._engine
+    listed = set(runtime_entry_points(own))
+    reg.freeze()
+    used, names, name_index = [], [], {}
+    index_of = {}
+
+    def buffer_index(b):
+        i = index_of.get(b["addr"])
+        if i is None:
+            i = index_of[b["addr"]] = len(used)
+            used.append(b)
+        return i
+
+    def pair(value, what):
+        """a device address -> argument pair"""
+        if not value:
+            return (ARG_NULL, 0)
+        b, off = reg.resolve(value)
+        if b is None:
+            raise PlanExportError(f"export_plan: {what} is a device address (0x{value:x}) inside no buffer the export registered")
+        return (ARG_PTR | (buffer_index(b) << 8), off)
+
+    entries, arrays = [], []
+    for fn, args in rec:
+        if args is None:
+            label = getattr(fn, "__qualname__", None) or getattr(fn, "__name__", None) or repr(fn)
+            raise PlanExportError(f"export_plan: the recorded forward holds a host-side Python step ({label}); a plan is C-ABI calls only")
+        name = fn.__name__
+        if name not in listed:
+            raise PlanExportError(f"export_plan: the forward calls {name}, which the plan runtime of this library does not list "
+                                  "(csrc/plan_image.h, SCOT_PLAN_ENTRY_POINTS)")
+        addr = _address(fn)
+        if addr == _address(getattr(own, name)):
+            which = 0
+        elif peer is not None and addr == _address(getattr(peer, name)):
+            which = 1
+        else:
+            raise PlanExportError(f"export_plan: {name} was recorded from a library that is neither the engine's build nor the bfloat16 build")
+        argtypes = fn.argtypes
+        if len(args) != len(argtypes):
+            raise PlanExportError(f"export_plan: {name} was recorded with {len(args)} arguments, its prototype has {len(argtypes)}")
+        ints, flts = [], []
+        last = len(args) - 1
+        for k, (a, ty) in enumerate(zip(args, argtypes)):
+            what = f"argument {k} of {name}"
+            if ty is ctypes.c_float:
+                flts.append(struct.unpack("<I", struct.pack("<f", float(a)))[0])
+            elif ty is ctypes.c_void_p and k == last:
+                ints.append((ARG_STREAM, 0))      # one stream per entry point, last: the caller's at run time
+            elif isinstance(a, ctypes.Array):
+                elem = a._type_
+                if elem is ctypes.c_int:
+                    items = [(ARG_INT, int(x) & 0xFFFFFFFFFFFFFFFF) for x in a]
+                    kind = 0
+                elif elem is ctypes.c_void_p:
+                    items = [pair(x or 0, f"element {j} of {what}") for j, x in enumerate(a)]
+                    kind = 1
+                else:
+                    raise PlanExportError(f"export_plan: {what} is a host array of {elem!r}")
+                ints.append((ARG_ARRAY, len(arrays)))
+                arrays.append((kind, items))
+            elif ty is ctypes.c_void_p:
+                v = a.value if isinstance(a, ctypes.c_void_p) else a
+                ints.append(pair(int(v or 0), what))
+            elif a is None:
+                ints.append((ARG_INT, 0))
+            elif isinstance(a, int):
+                ints.append((ARG_INT, a & 0xFFFFFFFFFFFFFFFF))
+            else:
+                raise PlanExportError(f"export_plan: {what} = {a!r} has no place in a plan image")
+        if len(ints) > MAX_INT or len(flts) > MAX_FLT:
+            raise PlanExportError(f"export_plan: {name} does not fit the replay's calling convention")
+        if name not in name_index:
+            name_index[name] = len(names)
+            names.append(name)
+        entries.append((name_index[name], which, ints, flts))
+
+    B, Cin, H, W = pv_in.shape
+    Cout = pred.shape[1]
+    io = [0] * IO_WORDS
+    io[0:5] = [B, Cin, H, W, Cout]
+
+    def whole(t, what, kind):
+        b, off = reg.resolve(t.data_ptr())
+        if b is None or off + t.numel() * t.element_size() > b["bytes"]:
+            raise PlanExportError(f"export_plan: {what} lies in no registered buffer")
+        b["kind"] = kind
+        return buffer_index(b), off
+    io[5], io[6] = whole(pv_in, "the input copy", INPUT)
+    if t_in is not None:
+        io[7] = 1
+        io[8], io[9] = whole(t_in, "the time copy", INPUT)
+        io[10] = t_in.numel() * 4
+    io[15], io[16] = whole(pred, "the prediction", OUTPUT)
+
+    # sections
+    def words(ws):
+        return struct.pack(f"<{len(ws)}Q", *ws)
+    names_b = b"".join(n.encode().ljust(NAME_BYTES, b"\0") for n in names)
+    data, buf_words = bytearray(), []
+    for b in used:
+        off = 0
+        if b["kind"] == CONSTANT:
+            data.extend(b"\0" * (-len(data) % 64))
+            off = len(data)
+            raw = _bytes_of(b["tensor"])
+            assert len(raw) == b["bytes"]
+            data.extend(raw)
+        buf_words += [b["kind"], b["bytes"], off, 0]
+    data.extend(b"\0" * (-len(data) % 8))
+    ent_words = []
+    for ni, which, ints, flts in entries:
+        ent_words += [ni, which, len(ints), len(flts)]
+        for tag, val in ints:
+            ent_words += [tag, val]
+        ent_words += flts
+    arr_words = []
+    for kind, items in arrays:
+        arr_words += [kind, len(items)]
+        for tag, val in items:
+            arr_words += [tag, val]
+    sections = [names_b, words(buf_words), words(ent_words), words(arr_words), words(io)]
+    offs, cur = [], HEADER_WORDS * 8
+    for sct in sections:
+        offs.append(cur)
+        cur += len(sct) + (-len(sct) % 8)
+    cur += -cur % 64
+    data_off = cur
+    total = data_off + len(data)
+    h = [0] * HEADER_WORDS
+    h[H_MAGIC], h[H_FORMAT], h[H_ABI], h[H_OPERAND] = MAGIC, FORMAT, own.scot_abi_version(), own.scot_operand_format()
+    h[H_COMPUTE], h[H_BYTES] = COMPUTE_CODE[model.compute], total
+    h[H_NNAMES], h[H_NAMES_OFF] = len(names), offs[0]
+    h[H_NBUFFERS], h[H_BUFFERS_OFF] = len(used), offs[1]
+    h[H_NENTRIES], h[H_ENTRIES_OFF], h[H_ENTRIES_WORDS] = len(entries), offs[2], len(ent_words)
+    h[H_NARRAYS], h[H_ARRAYS_OFF], h[H_ARRAYS_WORDS] = len(arrays), offs[3], len(arr_words)
+    h[H_IO_OFF], h[H_DATA_OFF], h[H_DATA_BYTES] = offs[4], data_off, len(data)
+    out = bytearray(words(h))
+    for sct, off in zip(sections, offs):
+        assert len(out) == off
+        out.extend(sct)
+        out.extend(b"\0" * (-len(sct) % 8))
+    out.extend(b"\0" * (data_off - len(out)))
+    out.extend(data)
+    assert len(out) == total
+    return bytes(out)
+
+
+def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labels=None):
+    """Record `model`'s inference forward for exactly these input shapes and write it as a plan image to `path` (None: only return it).
+    Returns the image's bytes.  The weights are a snapshot; see the module docstring and DESIGN.md §3 for what a plan does not cover."""
+    import torch
+    from . import ops
+    _check_request(model, pixel_values, time, pixel_mask, labels)
+    dev = pixel_values.device
+    model._ensure_arena(dev)
+    eng = model._engine
+    pv = pixel_values.detach().to(torch.float32).contiguous()
+    t = None
+    if model.config.use_conditioning:      # as ScOT.forward prepares it
+        t = torch.as_tensor(time, device=dev).detach().reshape(-1).to(torch.float32).contiguous()
+        if t.numel() == 1 and pv.shape[0] > 1:
+            t = t.expand(pv.shape[0]).contiguous()
+        if t.numel() != pv.shape[0]:
+            raise PlanExportError(f"export_plan: time has {t.numel()} values for a batch of {pv.shape[0]}")
+    own, peer = _libraries(eng)
+    bind(own)
+    with torch.no_grad():
+        _, ref, _ = eng.forward(pv, t, None, None, train=False, stochastic=False)      # the model's own prediction
+        reg, rec, keep, pred, pv_in, t_in = _record(model, pv, t)
+        image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer)
+        # load what was built through the runtime, scratch poisoned, and require the model's own bits: a constant the export missed fails
+        # here, not at a user's site
+        plan = Plan.load(image, lib=own, peer=peer)
+        try:
+            plan.poison(0xFF)
+            got = plan.run(pv, t)
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)
+            if not bool(torch.isfinite(got).all()):
+                raise PlanExportError("export_plan: the plan's prediction is not finite with poisoned scratch: the recorded forward reads "
+                                      "a buffer the image does not initialise")
+            if not torch.equal(got, ref):
+                raise PlanExportError("export_plan: the plan's prediction differs from the model's own "
+                                      f"(max |difference| {float((got - ref).abs().max()):.3e})")
+        finally:
+            plan.free()
+    del keep
+    if path is not None:
+        with open(path, "wb") as f:
+            f.write(image)
+    return image
+
+
+# ----------------------------------------------------------------------------------------------------------------- runtime wrapper
+def _load_library(kind):
+    """the build of the library for operand format `kind`: through the package's loader when torch is already in the process (its HIP
+    runtime has to be the one the library binds to), straight from the file otherwise"""
+    if "torch" in sys.modules:
+        from . import ops
+        prev = ops.use(kind)
+        try:
+            return ops._raw()
+        finally:
+            ops.use(prev)
+    import os
+    path = os.environ.get("SCOT_LIB_" + kind.upper()) or _lib.LIB_PATHS[kind]
+    if not os.path.exists(path):
+        raise _lib.ScotLibraryError(f"{path} not found: build it with `python -m poseidon_amd.build`")
+    return ctypes.CDLL(path)
+
+
+def _is_tensor(x):
+    return hasattr(x, "data_ptr")
+
+
+def _addr(x, what):
+    if x is None or isinstance(x, int):
+        return x
+    if not _is_tensor(x):
+        raise TypeError(f"{what}: a tensor or a raw device address")
+    import torch
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError(f"{what}: contiguous float32")
+    return x.data_ptr()
+
+
+class Plan:
+    """A loaded plan.  `run` / `rollout` take torch tensors (and return one) or raw device addresses (then `out` is required)."""
+
+    def __init__(self, lib, handle):
+        self._lib, self._h = lib, handle
+        self.info = self.describe()
+
+    @staticmethod
+    def header(image):
+        if len(image) < HEADER_WORDS * 8:
+            raise _lib.ScotLibraryError("not a plan image: shorter than its header")
+        h = struct.unpack(f"<{HEADER_WORDS}Q", image[:HEADER_WORDS * 8])
+        if h[H_MAGIC] != MAGIC:
+            raise _lib.ScotLibraryError("not a plan image: wrong magic")
+        return h
+
+    @classmethod
+    def load(cls, source, lib=None, peer=None, stream=None):
+        """source: a path or the image's bytes.  lib: the build to load into (default: the one the image's operand format names)."""
+        image = source if isinstance(source, (bytes, bytearray)) else open(source, "rb").read()
+        if lib is None:
+            kind = {0: "bf16", 1: "f16"}.get(cls.header(image)[H_OPERAND])
+            if kind is None:
+                raise _lib.ScotLibraryError("plan image: unknown operand format")
+            lib = _load_library(kind)
+            if kind != "bf16" and peer is None and "torch" in sys.modules:
+                peer = _load_library("bf16")
+        bind(lib)
+        if peer is not None:
+            _lib.check(lib.scot_plan_peer_library(str(peer._name).encode()), "scot_plan_peer_library")
+        handle = ctypes.c_void_p()
+        rc = load_raw(lib, image, handle, stream)
+        if rc != 0:
+            raise _lib.ScotLibraryError(f"scot_plan_load refused the image: status {rc} ({_lib._ERR.get(rc, rc)})")
+        return cls(lib, handle)
+
+    def describe(self):
+        out = (ctypes.c_longlong * 16)()
+        _lib.check(self._lib.scot_plan_describe(self._h, out), "scot_plan_describe")
+        return dict(zip(DESCRIBE, [int(x) for x in out]))
+
+    def poison(self, byte=0xFF, stream=None):
+        _lib.check(self._lib.scot_plan_poison(self._h, int(byte), self._stream(stream, None)), "scot_plan_poison")
+
+    @staticmethod
+    def _stream(stream, like):
+        if stream is not None:
+            return stream
+        if like is not None and _is_tensor(like) and like.is_cuda:
+            import torch
+            return torch.cuda.current_stream(like.device).cuda_stream
+        if "torch" in sys.modules:
+            import torch
+            if torch.cuda.is_available() and torch.cuda.is_initialized():
+                return torch.cuda.current_stream().cuda_stream
+        return None
+
+    def run(self, pixel_values, time=None, pixel_mask=None, out=None, stream=None):
+        d = self.info
+        if _is_tensor(pixel_values):
+            import torch
+            if tuple(pixel_values.shape) != (d["batch"], d["channels"], d["height"], d["width"]):
+                raise ValueError(f"this plan takes pixel_values of shape {(d['batch'], d['channels'], d['height'], d['width'])}")
+            if time is not None and _is_tensor(time):
+                time = time.reshape(-1).to(torch.float32).contiguous()
+                if time.numel() != d["batch"]:
+                    raise ValueError("time: one value per sample")
+            if out is None:
+                out = torch.empty(d["batch"], d["out_channels"], d["height"], d["width"], dtype=torch.float32, device=pixel_values.device)
+        elif out is None:
+            raise ValueError("raw addresses need `out`")
+        rc = self._lib.scot_plan_run(self._h, _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(pixel_mask, "pixel_mask"),
+                                     _addr(out, "out"), self._stream(stream, pixel_values))
+        _lib.check(rc, "scot_plan_run")
+        return out
+
+    def rollout(self, pixel_values, time, steps, pixel_mask=None, out=None, stream=None):
+        """-> [B, steps, Cout, H, W] for tensors (what harness.rollout(..., output_all_steps=True).output is); with raw addresses `out`
+        receives the C layout [steps][B, Cout, H, W]."""
+        d = self.info
+        tensors = _is_tensor(pixel_values)
+        if tensors:
+            import torch
+            if time is not None and _is_tensor(time):
+                time = time.reshape(-1).to(torch.float32).contiguous()
+            if out is None:
+                out = torch.empty(int(steps), d["batch"], d["out_channels"], d["height"], d["width"], dtype=torch.float32, device=pixel_values.device)
+        elif out is None:
+            raise ValueError("raw addresses need `out`")
+        rc = self._lib.scot_plan_rollout(self._h, _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(pixel_mask, "pixel_mask"),
+                                         _addr(out, "out"), int(steps), self._stream(stream, pixel_values))
+        _lib.check(rc, "scot_plan_rollout")
+        return out.transpose(0, 1).contiguous() if tensors and _is_tensor(out) else out
+
+    def free(self):
+        if self._h is not None and self._h.value:
+            self._lib.scot_plan_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def load_raw(lib, image, handle, stream=None):
+    """scot_plan_load on `image` (bytes) -> status; `handle` (c_void_p) receives the plan.  The image is copied to 8-byte aligned memory."""
+    bind(lib)
+    n = len(image)
+    buf = (ctypes.c_uint64 * ((n + 7) // 8 or 1))()
+    ctypes.memmove(buf, bytes(image), n)
+    return lib.scot_plan_load(ctypes.cast(buf, ctypes.c_void_p), n, ctypes.byref(handle), stream)

@@ -1,0 +1,59 @@
+// plan_image_check — the plan image validator (poseidon_amd/csrc/plan_image.h) on its own, on the CPU.
+//
+//   plan_image_check <abi> <operand format> <image file> <expected status> [<image file> <expected status> ...]
+//
+// Runs scot_plan_image_validate over every file and compares the status with the expected one; for an accepted image it also walks
+// everything the validator promised is in bounds (names, entries, arrays, constants' bytes).  Each file is read into a heap block of
+// exactly its size, so a build with -fsanitize=address,undefined turns any read past a truncated image into an error.  Exit status 0
+// when every image got the expected answer.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "plan_image.h"
+
+static uint64_t walk(const scot_plan_view* v) {
+  uint64_t sum = 0;
+  for (uint64_t i = 0; i < v->n_names; ++i) sum += strlen((const char*)(v->names + i * SCOT_PLAN_NAME_BYTES));
+  for (uint64_t i = 0; i < v->n_buffers; ++i)
+    if (v->buffers[4 * i] == SCOT_PLAN_BUF_CONSTANT)
+      for (uint64_t k = 0; k < v->buffers[4 * i + 1]; k += 64) sum += v->data[v->buffers[4 * i + 2] + k];
+  for (uint64_t w = 0; w < v->entries_words; ++w) sum += v->entries[w];
+  for (uint64_t w = 0; w < v->arrays_words; ++w) sum += v->arrays[w];
+  for (int w = 0; w < SCOT_PLAN_IO_WORDS; ++w) sum += v->io[w];
+  return sum;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 5 || (argc - 3) % 2) {
+    fprintf(stderr, "usage: %s <abi> <operand format> <image> <expected status> ...\n", argv[0]);
+    return 2;
+  }
+  const int abi = atoi(argv[1]), fmt = atoi(argv[2]);
+  int bad = 0, n = 0;
+  for (int a = 3; a + 1 < argc; a += 2, ++n) {
+    FILE* f = fopen(argv[a], "rb");
+    if (!f) {
+      fprintf(stderr, "cannot open %s\n", argv[a]);
+      return 2;
+    }
+    fseek(f, 0, SEEK_END);
+    const long size = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    void* image = malloc(size > 0 ? (size_t)size : 1);      // (malloc: 16-byte aligned, exactly `size` bytes addressable)
+    if (!image || (size > 0 && fread(image, 1, (size_t)size, f) != (size_t)size)) {
+      fprintf(stderr, "cannot read %s\n", argv[a]);
+      return 2;
+    }
+    fclose(f);
+    scot_plan_view v;
+    const int rc = scot_plan_image_validate(image, (size_t)size, abi, fmt, &v);
+    const int want = atoi(argv[a + 1]);
+    uint64_t sum = 0;
+    if (rc == SCOT_PLAN_OK) sum = walk(&v);
+    printf("%s: status %d (expected %d) checksum %llu\n", argv[a], rc, want, (unsigned long long)sum);
+    if (rc != want) ++bad;
+    free(image);
+  }
+  printf("%d images checked, %d unexpected\n", n, bad);
+  return bad ? 1 : 0;
+}
