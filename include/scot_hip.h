@@ -454,9 +454,11 @@ int scot_loss_bwd(const float* pred, const float* labels, const unsigned char* m
  * not a parameter (alignment padding, the key-bias slot of the fused qkv bias).  n = arena size in floats (multiple of 8). */
 int scot_optim_blocks(size_t n);                       /* floats of `partial` scratch scot_grad_sqnorm needs */
 int scot_grad_sqnorm(const float* grad, const unsigned char* map8, size_t n, float* partial, scot_stream_t stream);
+/* scot_clip_coef: the squares are summed in fp32, so a FINITE gradient element whose square exceeds fp32's range (|g| above 1.84e19)
+ * makes the norm infinite and the step is skipped, like one that holds Inf or NaN; elements mapped 255 never enter the norm. */
 int scot_clip_coef(const float* partial, int nblocks, float max_norm /* <= 0: no clipping */,
                    float* out3 /* {coef, total_norm, 1 if the norm is not finite else 0} */, scot_stream_t stream);
-/* clip: the three floats of scot_clip_coef (NULL: no clipping, no skip) — the update is SKIPPED when clip[2] != 0 (gradients that
+/* scot_adamw_step.  clip: the three floats of scot_clip_coef (NULL: no clipping, no skip) — the update is SKIPPED when clip[2] != 0 (gradients that
  * overflowed under the fp16 build's gradient scale; GradScaler.step semantics, decided on the device from the norm of the REDUCED
  * gradient, so every data-parallel rank decides alike).  step_state: device int[2] {steps applied, steps skipped}: Adam's step number
  * is applied + 1 (NULL: `step`).  shadow16 (optional): n elements in the library's 16-bit operand format, receives the updated

@@ -42,3 +42,15 @@ def patch_ops(monkeypatch, lib, workspace_bytes=32 << 20):
     monkeypatch.setattr(ops, "ptr", lambda t: None if t is None else t.data_ptr())
     monkeypatch.setattr(ops, "stream", lambda: None)
     monkeypatch.setattr(ops, "workspace", lambda need=0: ws)
+
+
+def fused_adamw(model, **kw):
+    """FusedAdamW over CPU tensors.  The product refuses a model that is not on the GPU (its kernels take device pointers); the emulated
+    library takes host pointers, so for the duration of the constructor every tensor answers `is_cuda` with True."""
+    from poseidon_amd.optim import FusedAdamW
+    assert "is_cuda" not in torch.Tensor.__dict__
+    torch.Tensor.is_cuda = property(lambda self: True)
+    try:
+        return FusedAdamW(model, **kw)
+    finally:
+        del torch.Tensor.is_cuda

@@ -381,3 +381,126 @@ def test_trainer_two_ranks_stay_in_lock_step(tmp_path):
     out = str(tmp_path / "ok")
     mp.spawn(_trainer_worker, args=(2, _free_port(), out), nprocs=2, join=True)
     assert open(out).read() == "ok"
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# fp16 gradient overflow on ONE rank of two: the non-finite values have to cross the wire (fp32 and bf16), so that the norm of the
+# REDUCED gradient is not finite on every rank, both skip the step, both halve the gradient scale and the replicas stay bit-equal.
+def _need_emu():
+    import shutil
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hipemu"))
+    import build_emu
+    if not (os.path.exists(build_emu.CLANG) or shutil.which(build_emu.CLANG)):
+        pytest.skip("no host clang with __bf16 vector support")
+    build_emu.build_cached()                                  # once, before the two ranks race for it
+    build_emu.build_cached(kind="f16")
+
+
+def test_wire_pack_and_unpack_keep_non_finite_values(monkeypatch):
+    """scot_dp_pack / scot_dp_unpack: +-Inf and NaN survive both ways, and a FINITE fp32 value above bfloat16's maximum (as is, or through
+    the folded-in scale) becomes Inf on the wire — round to nearest — not the format's maximum; in the 8-wide body and in the scalar tail."""
+    _need_emu()
+    import emu_session
+    from poseidon_amd import ops
+    emu_session.patch_ops(monkeypatch, emu_session.load_emu())       # (in this process: for the length of the test only)
+    n = 8 * 6 + 5
+    inf, nan, big = float("inf"), float("nan"), float(torch.finfo(torch.float32).max)
+    top = float(torch.finfo(torch.bfloat16).max)
+    src = torch.linspace(-3.0, 3.0, n)
+    plants = {1: inf, 10: -inf, 19: nan, 28: big, 37: -big, 44: top, 45: 3.0e38, n - 5: inf, n - 4: -inf, n - 3: nan, n - 2: big, n - 1: -3.397e38}
+    for i, v in plants.items():
+        src[i] = v
+    wire = torch.zeros(n, dtype=torch.bfloat16)
+    ops.dp_pack(src, wire, 1.0)
+    want = src.to(torch.bfloat16)                              # torch's conversion rounds to nearest even: the reference
+    assert torch.equal(torch.isnan(wire), torch.isnan(want)) and torch.equal(wire[~torch.isnan(want)], want[~torch.isnan(want)])
+    w = wire.float()
+    assert [float(w[i]) for i in (1, 10, 28, 37, n - 5, n - 4, n - 2, n - 1)] == [inf, -inf, inf, -inf, inf, -inf, inf, -inf]
+    assert bool(torch.isnan(w[19])) and bool(torch.isnan(w[n - 3])) and float(w[44]) == top and float(w[45]) == float(torch.tensor(3.0e38).bfloat16())
+    assert int((~torch.isfinite(w)).sum()) == 10
+    back = torch.full((n,), 7.0)
+    ops.dp_unpack(wire, back, 0.5)                             # (the scale of the unpack: Inf and NaN stay what they are)
+    assert torch.equal(torch.isnan(back), torch.isnan(w)) and torch.equal(back[~torch.isnan(w)], (w * 0.5)[~torch.isnan(w)])
+    half = torch.full((n,), 2.0e38)
+    ops.dp_pack(half, wire, 2.0)                               # overflow of the folded-in scale: Inf, not a clamp
+    assert bool(torch.isinf(wire.float()).all())
+
+
+def _overflow_worker(rank, world, port, out, wire):
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, os.path.join(here, "hipemu"))
+    sys.path.insert(0, here)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), SCOT_SIDE_STREAM="0", SCOT_TAPE="0")
+    import emu_session
+    import scOT.model as M
+    from poseidon_amd import ops
+    from poseidon_amd.synth import synth_inputs, synth_state_dict
+    lib = emu_session.load_emu()
+    ws = torch.empty(32 << 20, dtype=torch.uint8)
+    ops.L = lambda: lib if ops._active == "bf16" else emu_session.load_emu(ops._active)
+    ops.stream, ops.workspace = (lambda: None), (lambda need=0: ws)
+    ops.ptr = lambda t: None if t is None else t.data_ptr()
+    M._require_hip = lambda t: None
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    cfg = ScOTConfig(**dict(TINY, mlp_ratio=4.0, qkv_bias=True, p=1, channel_slice_list_normalized_loss=[0, 1, 3, 4], drop_path_rate=0.0))
+    model = M.ScOT(cfg, compute="fp16")
+    model.load_state_dict(synth_state_dict(param_shapes(cfg), "trained"))
+    opt = emu_session.fused_adamw(model, lr=1e-6)            # (small: an applied step moves every bit pattern, not the overflow boundary)
+    eng = model._engine
+    red = GradAllReducer(model, dist, wire=wire, chunk_mb=1)
+    red.broadcast_parameters(0)
+    pv, t, lab = synth_inputs(4, 4, 4, 32, "smooth")
+    sl = slice(2 * rank, 2 * rank + 2)
+    K = 14                                                    # the shared scale: one binade above S_auto; the shards overflow from 2^18 / 2^16 on
+
+    def gathered(x):
+        parts = [torch.empty_like(x) for _ in range(world)]
+        dist.all_gather(parts, x.contiguous())
+        return parts
+
+    def step(c):
+        """one training step of this rank's shard, pixel_values and labels multiplied by c -> (local gradients finite, flagged)"""
+        opt.zero_grad()
+        out = model(pixel_values=(pv[sl] * c).contiguous(), time=t[sl].contiguous(), labels=(lab[sl] * c).contiguous())
+        eng.scale_state.copy_(torch.tensor([2.0 ** K, 2.0 ** -K, 0.0, 0.0]))
+        out.loss.backward()
+        local = bool(torch.isfinite(model.flat_grads()).all())
+        red.allreduce()
+        opt.step()
+        return local, int(opt._clip[2]) == 1
+
+    def replicas_equal():
+        a, b = gathered(model.flat_parameters())
+        return torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+    assert step(1.0) == (True, False) and replicas_equal()                       # both shards clean: applied on both ranks
+    assert eng.grad_scale_value() == 2.0 ** K
+    p1, m1 = model.flat_parameters().clone(), opt.exp_avg.clone()
+    # the relative loss divides by the labels' magnitude: labels 2^-10 as large give a far larger d loss / d prediction, which
+    # overflows binary16 at this scale — on rank 1 only
+    local, flagged = step(2.0 ** -10 if rank == 1 else 1.0)
+    locals_ = [bool(x) for x in gathered(torch.tensor([float(local)]))]
+    assert locals_ == [True, False], locals_                                     # only rank 1's backward overflowed ...
+    assert not bool(torch.isfinite(model.flat_grads()).all())                    # ... and its Inf / NaN crossed the wire to rank 0
+    assert flagged and (opt.applied_steps(), opt.skipped_steps()) == (1, 1)      # both ranks skip
+    assert eng.grad_scale_value() == 2.0 ** (K - 1)                              # both halve the scale
+    assert torch.equal(model.flat_parameters(), p1) and torch.equal(opt.exp_avg, m1) and replicas_equal()
+    again = step(1.0)
+    assert again == (True, False), again                                         # clean again: applied on both ranks
+    assert replicas_equal() and not torch.equal(model.flat_parameters(), p1)
+    scales = [float(x) for x in gathered(eng.scale_state[0:1].clone())]
+    assert scales[0] == scales[1]
+    dist.barrier()
+    dist.destroy_process_group()
+    if rank == 0:
+        open(out, "w").write("ok")
+
+
+@pytest.mark.parametrize("wire", ["fp32", "bf16"])
+def test_overflow_on_one_rank_skips_the_step_on_both(tmp_path, wire):
+    _need_emu()
+    out = str(tmp_path / "ok")
+    mp.spawn(_overflow_worker, args=(2, _free_port(), out, wire), nprocs=2, join=True)
+    assert open(out).read() == "ok"

@@ -744,3 +744,50 @@ def test_guarded_spectral_apply(guarded_bodies, s, t, nimg):
 def test_guarded_optimizer(guarded_bodies, kind):
     """small on the emulation (one workgroup's worth of 8-element cells per member); the grid-stride case runs on the GPU"""
     guarded_bodies.optimizer_guarded(kind, guarded_bodies.OPT_SMALL)
+
+
+@pytest.mark.parametrize("kind", ["bf16", "f16"])
+def test_guarded_optimizer_verdicts(guarded_bodies, kind):
+    guarded_bodies.optimizer_verdicts(kind)
+
+
+# ---- non-finite in, non-finite out; overflow stores Inf (the section of that name in tests/test_kernels_guarded_gpu.py), a subset
+@pytest.mark.parametrize("kind,C,B,L,cond,form", [("f16", 96, 2, 64, True, "stored"), ("f16", 96, 2, 64, False, "prologue"), ("f16", 192, 2, 64, True, "lean"),
+                                                  ("bf16", 48, 2, 64, True, "stored")])
+def test_guarded_block_tail_bwd_nonfinite(guarded_bodies, kind, C, B, L, cond, form):
+    guarded_bodies.block_tail_bwd_nonfinite(kind, C, B, L, cond, form)
+
+
+def test_guarded_fused_halves_and_cln_bwd_nonfinite(guarded_bodies):
+    guarded_bodies.fused_halves_bwd_nonfinite("f16", 96, 2, 64, True)
+    guarded_bodies.cln_bwd_nonfinite("f16", True, True, 2, 72, 96)
+    guarded_bodies.cln_bwd_nonfinite("bf16", False, False, 3, 43, 20)
+
+
+@pytest.mark.parametrize("kind", ["f16", "bf16"])
+def test_guarded_gemm_16bit_result_and_device_scaled_ops_nonfinite(guarded_bodies, kind):
+    guarded_bodies.gemm_16bit_result_nonfinite(kind, ops.NT, True, 65, 34, 24, family=ops.ROUTE_GENERIC)
+    guarded_bodies.gemm_16bit_result_nonfinite(kind, ops.NT, False, 136, 64, 40, family=ops.ROUTE_FAST)
+    guarded_bodies.gemm_16bit_result_nonfinite(kind, ops.NN, False, 136, 64, 40, family=ops.ROUTE_FAST)
+    guarded_bodies.device_scaled_ops_nonfinite(kind, 130, 96)
+    guarded_bodies.device_scaled_ops_nonfinite(kind, 37, 24)
+
+
+def test_guarded_wgrad_and_dwconv7_nonfinite(guarded_bodies):
+    guarded_bodies.wgrad_group_nonfinite("f16", 200, [(40, 72), (72, 40), (48, 48)])
+    guarded_bodies.wgrad_group_nonfinite("bf16", 512, [(96, 384), (384, 96), (288, 96)])
+    guarded_bodies.wgrad_mlp_nonfinite("f16", 136, 96, ops.GRAD_STORE_SCALED)
+    guarded_bodies.wgrad_mlp_nonfinite("bf16", 72, 192, ops.GRAD_ADD)
+    guarded_bodies.wgrad_mlp_nonfinite("f16", 136, 96, ops.GRAD_ADD_SCALED)
+    guarded_bodies.dwconv7_data_gradient_nonfinite("f16", 2, 9, 11, 33, False)
+    guarded_bodies.dwconv7_data_gradient_nonfinite("bf16", 2, 12, 20, 24, True)
+
+
+@pytest.mark.parametrize("kind,case", [("f16", (2, 8, 8, 32, 2, 4, 2)), ("bf16", (1, 14, 14, 32, 1, 7, 3)), ("f16", (1, 16, 16, 32, 2, 16, 0)),
+                                       ("bf16", (1, 32, 32, 32, 1, 16, 8))], ids=lambda v: str(v).replace(" ", ""))
+def test_guarded_window_attention_bwd_nonfinite(guarded_bodies, kind, case):
+    guarded_bodies.window_attention_bwd_nonfinite(kind, case)
+
+
+def test_guarded_cpb_bwd_batched_nonfinite(guarded_bodies):
+    guarded_bodies.cpb_bwd_batched_nonfinite([(4, 3), (7, 2), (4, 6)], 0)

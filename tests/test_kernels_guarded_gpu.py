@@ -1210,7 +1210,7 @@ def test_block_tail_bwd_declines_ragged_samples(kind, C, B, L, cond, form):
     block_tail_bwd_guarded(kind, C, B, L, cond, form)
 
 
-def block_tail_bwd_guarded(kind, C, B, L, cond, form):
+def block_tail_bwd_guarded(kind, C, B, L, cond, form, upstream=None):
     """scot_block_tail_bwd: stored gelu'(u) and atomics; with the qkv data-gradient prologue in place; the lean form (gelu'(u) recomputed from
     h16 / b1, no du, 16-bit z, per-workgroup partial sums finished by scot_partial_colsum).  The norms' eight parameter gradients lie
     back to back in one guarded buffer at the arena's alignment, the partial-sum matrices are guarded to the size the header gives
@@ -1222,6 +1222,10 @@ def block_tail_bwd_guarded(kind, C, B, L, cond, form):
         lean, prologue = form == "lean", form == "prologue"
         d = _tail_inputs(C, B, L, cond, hd)
         g0 = G.rnd(M, C, seed=31)
+        if upstream is not None:      # the non-finite section below: its upstream gradient, the guarded launch only, its own checks
+            g0 = upstream(g0)
+            for s in ("s1", "s2"):        # both branches kept in every sample: a dropped one (sample scale 0) is a mask that closes the path
+                d[s] = torch.full_like(d[s], 1.0 / 0.7)
         z2, z1 = G.rnd(M, C, seed=32), G.rnd(M, C, seed=33)
         st = lambda z: (z.mean(-1).contiguous(), (1.0 / torch.sqrt(z.var(-1, unbiased=False) + 1e-5)).contiguous())
         (m2, r2), (m1, r1) = st(z2), st(z1)
@@ -1272,6 +1276,12 @@ def block_tail_bwd_guarded(kind, C, B, L, cond, form):
             gd.check()
             assert not og["ok"] and all(bool(torch.isnan(og[k].float()).all()) for k in shapes)
             return
+        if upstream is not None:
+            assert og["ok"]
+            sync()
+            gd.check()
+            og["inputs"] = d
+            return og
         op_ = run(d, False)
         assert og["ok"] and op_["ok"]
         sync()
@@ -1332,7 +1342,7 @@ def test_fused_halves_bwd_guarded(C, B, L, cond):
     fused_halves_bwd_guarded(C, B, L, cond)
 
 
-def fused_halves_bwd_guarded(C, B, L, cond):
+def fused_halves_bwd_guarded(C, B, L, cond, upstream=None):
     """scot_proj_cln_bwd and scot_mlp_block_bwd (out of place) on their own: data tensors (a), (b), (d); the norm-parameter gradients
     (atomics) back to back at the arena's alignment, at the tolerance of test_proj_cln_bwd_fused / test_mlp_block_bwd_fused."""
     hd = ops.half_dtype()
@@ -1341,6 +1351,10 @@ def fused_halves_bwd_guarded(C, B, L, cond):
     z = G.rnd(M, C, seed=2, scale=1.5) + 0.3
     d.update(g=G.rnd(M, C, seed=1), z=z, mean=z.mean(-1).contiguous(), rstd=(1.0 / torch.sqrt(z.var(-1, unbiased=False) + 1e-5)).contiguous(),
              gp=G.rnd(M, hid, seed=3, scale=0.5).to(hd))
+    if upstream is not None:
+        d["g"] = upstream(d["g"])
+        for s in ("s1", "s2"):        # both branches kept in every sample: a dropped one (sample scale 0) is a mask that closes the path
+            d[s] = torch.full_like(d[s], 1.0 / 0.7)
     gd = Guards()
     gi = {k: gd.op(v, name=k) for k, v in d.items()}
     shapes = dict(pdz=((M, C), hd), pda=((M, C), hd), mdz=((M, C), hd), mdu=((M, hid), hd), mg=((M, C), F32))
@@ -1359,6 +1373,12 @@ def fused_halves_bwd_guarded(C, B, L, cond):
                                  pm[0], pm[1], pm[2], pm[3], M, L, C, hid)
         o["grads"] = [t for t in pp + pm if t is not None]
         return o
+    if upstream is not None:
+        og = run(gi, True)
+        sync()
+        gd.check()
+        og["inputs"] = d
+        return og
     og, op_ = run(gi, True), run(d, False)
     sync()
     gd.check()
@@ -2182,7 +2202,7 @@ def test_cpb_batched_guarded(first):
     cpb_batched_guarded(CPB_LAYERS, first)
 
 
-def cpb_batched_guarded(layers, first):
+def cpb_batched_guarded(layers, first, upstream=None):
     """scot_cpb_fwd_batched over all layers, scot_cpb_bwd_batched over layers first.. of the list.  Parameters and gradients lie the way the
     arenas hold them: a layer's w0 | b0 | w2 back to back, a neighbour that is no CPB parameter (100 floats + padding to 64) behind every
     layer.  The gradients hold prior values; layers in front of `first`, every neighbour and all padding must come back bit-unchanged."""
@@ -2210,6 +2230,8 @@ def cpb_batched_guarded(layers, first):
         toff += heads * (2 * ws - 1) ** 2
     d = torch.tensor(desc, dtype=torch.int32, device=G.DEV)
     dtab = G.rnd(toff, seed=5)
+    if upstream is not None:      # the non-finite section below: its upstream gradient, one guarded launch, its own checks
+        dtab = upstream(dtab, desc)
     cg, dg, dtg = gd.op(coords, name="coords"), gd.op(d, name="desc"), gd.op(dtab, name="dtables")
     tabg, zg = gd.out((toff,), F32, name="tables"), gd.out((toff,), F32, name="z")
     pplain = torch.zeros(span, device=G.DEV)
@@ -2222,6 +2244,12 @@ def cpb_batched_guarded(layers, first):
     sync()
     gd.check()
     assert same(tabg, tabp) and same(zg, zp)
+    if upstream is not None:
+        gv = gd.group(shapes, F32, srcs=srcs_g, name="gradient arena")
+        ops.cpb_bwd_batched(pviews[0], dg, first, len(layers) - first, max_ws, max_heads, cg, zg, dtg, gv[0])
+        sync()
+        gd.check()
+        return gv, srcs_p, coords, coff
     runs = []
     for k in range(2):
         gv = gd.group(shapes, F32, srcs=srcs_g, name=f"gradient arena (launch {k})")
@@ -2428,6 +2456,818 @@ def optimizer_guarded(kind, members):
         sync()
         gd.check()
         assert state.tolist() == [5, 1]
+
+
+# (size, parameter group): 64-float spacing as in the flat arenas; 1003 is no multiple of 8, so its last 8-element chunk is shared with
+# five floats of (zero) alignment padding; the 64 floats behind the first member are a gradient-carrying non-parameter region (the key-bias
+# slot of the fused qkv bias: map8 == 255)
+VERDICT_MEMBERS = [(1000, 0), (1003, 1), (24, 2), (4104, 0)]
+VERDICT_FREE = (1024, 64)       # (offset, size) of the non-parameter region
+INF = float("inf")
+
+
+@pytest.mark.parametrize("kind", ["bf16", "f16"])
+def test_optimizer_verdicts(kind):
+    optimizer_verdicts(kind)
+
+
+def optimizer_verdicts(kind):
+    """What makes scot_clip_coef flag a step (clip[2] = 1), through the four launches of FusedAdamW.step on one guarded arena laid out like
+    the product's (64-float spacing, ZERO padding, map8 from the rule of poseidon_amd.optim.group_map8).  A flagged step changes nothing
+    but the skip counter and halves the scale; a step that is not flagged equals the clean step bit for bit (no atomics in these kernels):
+      NaN only, -Inf only, +Inf only, in a live chunk                                  -> skipped
+      the same in the last, partly padded chunk of the 1003-element member             -> skipped
+      all three in a region mapped 255 (not a parameter)                               -> applied, bit-identical to the clean step
+      one FINITE element of 2e19, whose square overflows fp32                          -> skipped (pinned; include/scot_hip.h says so)
+      one finite element of 1e19 (square 1e38)                                         -> applied: the boundary is the square's overflow"""
+    import ctypes
+    with _build(kind) as hd:
+        lib, st = ops.L(), ops.stream()
+        gd = Guards()
+        offs, o = [], 0
+        for s, _ in VERDICT_MEMBERS:
+            offs.append(o)
+            o = (o + s + 63) // 64 * 64
+            if o == VERDICT_FREE[0]:
+                o += VERDICT_FREE[1]
+        n = o
+        assert n % 8 == 0 and offs[1] == VERDICT_FREE[0] + VERDICT_FREE[1]
+        live = torch.zeros(n, dtype=torch.bool)
+        map8 = torch.full((n // 8,), 255, dtype=torch.uint8)
+        for (s, gi), o in zip(VERDICT_MEMBERS, offs):
+            live[o:o + s] = True
+            map8[o // 8:(o + s + 7) // 8] = gi
+        live = live.to(G.DEV)
+        lr32, wd32 = (ctypes.c_float * 3)(1e-2, 3e-3, 1e-3), (ctypes.c_float * 3)(0.1, 0.0, 0.05)
+        init = [G.rnd(n, seed=1) * live, G.rnd(n, seed=2, scale=0.5) * live, G.rnd(n, seed=3, scale=0.1) * live, (G.rnd(n, seed=4, scale=0.3) * live) ** 2]
+        init[1][VERDICT_FREE[0]:VERDICT_FREE[0] + VERDICT_FREE[1]] = 0.25       # the key-bias slot carries a gradient
+        P, Gr, M, V = (gd.out((n,), F32, src=t, name=nm) for t, nm in zip(init, ("params", "grads", "exp_avg", "exp_avg_sq")))
+        S = gd.out((n,), hd, src=init[0].to(hd), name="shadow16")
+        mapg = gd.op(map8.to(G.DEV), name="map8")
+        nblk = int(lib.scot_optim_blocks(n))
+        partial, clip = gd.out((nblk,), F32, name="partial"), gd.out((3,), F32, fill=0.0, name="clip")
+        state, scale = gd.out((2,), torch.int32, fill=0, name="step_state"), gd.out((4,), F32, fill=0.0, name="scale_state")
+        max_norm = 0.5 * float((init[1].double() * live).norm())       # (clipping on: the coefficient comes from the same norm)
+
+        def step(plants):
+            """from the same initial state every time -> (flagged, [p, m, v, shadow16, clip, step_state, scale_state])"""
+            for t, src in zip((P, Gr, M, V), init):
+                t.copy_(src)
+            S.copy_(init[0].to(hd))
+            for i, v in plants:
+                Gr[i] = v
+            clip.copy_(torch.tensor([1.0, 0.0, 0.0]))
+            state.copy_(torch.tensor([4, 7], dtype=torch.int32))
+            scale.copy_(torch.tensor([1024.0, 1.0 / 1024.0, 0.0, 0.0]))
+            assert lib.scot_grad_sqnorm(ops.ptr(Gr), ops.ptr(mapg), n, ops.ptr(partial), st) == 0
+            assert lib.scot_clip_coef(ops.ptr(partial), nblk, max_norm, ops.ptr(clip), st) == 0
+            assert lib.scot_adamw_step(ops.ptr(P), ops.ptr(Gr), ops.ptr(M), ops.ptr(V), ops.ptr(mapg), n, ctypes.cast(lr32, ctypes.c_void_p),
+                                       ctypes.cast(wd32, ctypes.c_void_p), 3, 0.9, 0.999, 1e-8, 1, ops.ptr(clip), ops.ptr(state), ops.ptr(S), st) == 0
+            assert lib.scot_optim_finish(ops.ptr(state), ops.ptr(clip), ops.ptr(scale), 2.0, 0.5, 2000, float(2 ** 30), st) == 0
+            sync()
+            gd.check()
+            assert float(clip[2]) in (0.0, 1.0)
+            return float(clip[2]) == 1.0, [t.clone() for t in (P, M, V, S, clip, state, scale)]
+
+        def skipped(res, what):
+            flagged, (p, m, v, s16, c, stt, sc) = res
+            assert flagged, f"{what}: not flagged"
+            for nm, a, b in zip(("params", "exp_avg", "exp_avg_sq"), (p, m, v), (init[0], init[2], init[3])):
+                assert same(a, b), f"{what}: a flagged step changed {nm}"
+            assert same(s16, init[0].to(hd)), f"{what}: a flagged step changed the 16-bit copy"
+            assert stt.tolist() == [4, 8] and sc.tolist() == [512.0, 1.0 / 512.0, 0.0, 0.0], (what, stt.tolist(), sc.tolist())
+
+        clean = step([])
+        assert not clean[0] and clean[1][5].tolist() == [5, 7] and clean[1][6].tolist() == [1024.0, 1.0 / 1024.0, 1.0, 0.0]
+        assert finite(clean[1][0]) and not same(clean[1][0], init[0]) and 0.0 < float(clean[1][4][0]) < 1.0
+        mid, last = offs[0] + 500, offs[1] + VERDICT_MEMBERS[1][0] - 1           # (the last live element of the partly padded chunk)
+        assert last % 8 == 2 and int(map8[last // 8]) == 1 and not bool(live[last + 1])
+        for name, v in (("NaN", NAN), ("-Inf", -INF), ("+Inf", INF)):
+            skipped(step([(mid, v)]), f"{name} only, in a live chunk")
+            skipped(step([(last, v)]), f"{name} only, in the last, partly padded chunk of a {VERDICT_MEMBERS[1][0]}-element tensor")
+        f0 = VERDICT_FREE[0]
+        free = step([(f0, NAN), (f0 + 9, INF), (f0 + VERDICT_FREE[1] - 1, -INF)])
+        assert not free[0], "a non-finite value outside every parameter (map8 == 255) flagged the step"
+        for nm, a, b in zip(("params", "exp_avg", "exp_avg_sq", "shadow16", "clip", "step_state", "scale_state"), free[1], clean[1]):
+            assert same(a, b), f"non-finite values where map8 == 255 changed {nm}"
+        skipped(step([(mid, 2e19)]), "a finite gradient whose square overflows fp32 (2e19)")
+        skipped(step([(last, -2e19)]), "a finite gradient whose square overflows fp32 (-2e19)")
+        edge = step([(mid, 1e19)])
+        assert not edge[0] and float(edge[1][4][1]) >= float(torch.tensor(1e19, dtype=F32)) and finite(edge[1][0]) and finite(edge[1][1]) and finite(edge[1][2])
+
+
+# ====================================================================================== non-finite in, non-finite out; overflow stores Inf
+# The fp16 backward runs under a gradient scale that grows until something overflows, and training is right only if that overflow is SEEN:
+# an Inf or NaN in a kernel's upstream gradient has to come out of it as Inf / NaN (a clamping convert, a max / med3 that drops a NaN or
+# a "safe" epilogue would hide it from scot_clip_coef), and a result beyond binary16's range has to be stored as Inf.  Per kernel:
+#   arrival     +Inf, NaN and -Inf, one element each, in row 0, a row of an inner tile and the last row of the upstream gradient: every
+#               data-gradient output is non-finite in EVERY element of those rows (all of these kernels contract over, or normalise, the
+#               row), and every reduction over rows (parameter gradients, partial sums, column sums) holds a non-finite element;
+#   locality    all other rows are bit-identical to the clean launch, where the header documents the output as deterministic;
+#   saturation  (f16 build, 16-bit outputs) three upstream rows scaled so that the fp64 reference leaves binary16's range: beyond
+#               65520 (1 + b) the stored value is +-Inf with the reference's sign, below 65504 (1 - b) it is finite and within the bound.
+#               In a fused chain this is claimed for the FIRST 16-bit store; what contracts over that row afterwards meets Inf of both
+#               signs, so there the claim is non-finite in every element (Inf - Inf = NaN is legitimate), stated per output;
+# and the guard bands are checked after every launch, as everywhere in this file.
+def plant_rows(M):
+    return (0, 64 + 5 if M > 128 else M // 2, M - 1)
+
+
+def plant(g):
+    """+Inf, NaN, -Inf in three rows of a [M, W] upstream gradient (columns 1, W // 2, W - 1)"""
+    g = g.clone()
+    M, W = g.shape
+    for r, c, v in zip(plant_rows(M), (1, W // 2, W - 1), (INF, NAN, -INF)):
+        g[r, c] = v
+    return g
+
+
+def bits(t):
+    return t.contiguous().view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def arrived(what, clean, dirty, M, rows=None, deterministic=True):
+    """arrival and locality of one row-local output (rows of `dirty` that hold a planted upstream element: all of it non-finite)"""
+    rows = plant_rows(M) if rows is None else rows
+    c, d = clean.reshape(M, -1), dirty.reshape(M, -1)
+    assert finite(c), what
+    nf = ~torch.isfinite(d.float())
+    for r in rows:
+        assert bool(nf[r].all()), f"{what}: row {r} holds a planted non-finite upstream element, yet {int((~nf[r]).sum())} of {nf.shape[1]} elements are finite"
+    keep = torch.ones(M, dtype=torch.bool, device=d.device)
+    keep[list(rows)] = False
+    assert not bool(nf[keep].any()), f"{what}: non-finite values in {int(nf[keep].any(-1).sum())} row(s) that depend on no planted element"
+    if deterministic:
+        assert torch.equal(bits(d[keep]), bits(c[keep])), f"{what}: rows that depend on no planted element differ from the clean launch"
+
+
+def reduced(what, clean, dirty):
+    """a reduction over rows: finite in the clean launch, non-finite somewhere once a row holds a planted element"""
+    assert finite(clean), what
+    assert bool((~torch.isfinite(dirty.float())).any()), f"{what}: a sum over rows with planted Inf / NaN is finite everywhere"
+
+
+def scale_rows(k, rows=None):
+    """the upstream gradient with three rows (default: plant_rows) times 2^k (exact: a power of two on fp32 or fp64 data)"""
+    def up(g):
+        g = g.clone()
+        g[list(plant_rows(g.shape[0]) if rows is None else rows)] *= 2.0 ** k
+        return g
+    return up
+
+
+def saturated(what, got, ref, room, rows, b, row_band=None):
+    """saturation of one 16-bit [M, n] output whose `rows` were scaled out of binary16's range; ref in fp64, room: the absolute part of the
+    bound (roundoff of cancelling sums), b its relative part.  On the reference ALONE: at least 90 % of the scaled rows' elements lie
+    beyond 65520 (1 + b), at most 1 % between the two classes, every other row is in range.  Then: beyond 65520 (1 + b) the stored value
+    is Inf of the reference's sign; below 65504 (1 - b) it is finite and, in the scaled rows, within b |ref| + room (the other rows are
+    held to locality by the caller)."""
+    M = ref.shape[0]
+    got = got.reshape(M, -1)
+    big = torch.zeros(M, dtype=torch.bool, device=ref.device)
+    big[list(rows)] = True
+    if row_band is None:
+        must_inf, must_fin = ref.abs() > 65520.0 * (1 + b), ref.abs() < 65504.0 * (1 - b)
+    else:       # a case whose existing bound is one absolute figure per row (a bound on the row's error norm bounds each element's)
+        must_inf, must_fin = ref.abs() > 65520.0 + row_band, ref.abs() < 65504.0 - row_band
+    share_inf, share_band = float(must_inf[big].float().mean()), float((~must_inf & ~must_fin)[big].float().mean())
+    print(f"saturation {what}: {share_inf:.3f} of the scaled rows' elements must be Inf, {share_band:.4f} undecided")
+    assert bool(must_fin[~big].all()), what
+    if row_band is None:
+        assert share_inf >= 0.9 and share_band <= 0.01, (what, share_inf, share_band)      # (the reference alone)
+    else:
+        assert share_inf > 0.5, (what, share_inf)             # (see the caller: the shares above are out of reach of a per-row bound)
+    g64 = got.double()
+    assert bool((torch.isinf(g64) & (torch.sign(g64) == torch.sign(ref)))[must_inf].all()), \
+        f"{what}: {int((~(torch.isinf(g64) & (torch.sign(g64) == torch.sign(ref))))[must_inf].sum())} element(s) beyond binary16's range were not stored as Inf of the reference's sign"
+    assert bool(torch.isfinite(g64)[must_fin].all()), f"{what}: Inf / NaN stored for a reference inside binary16's range"
+    inside = must_fin & big.unsqueeze(1)
+    bad = inside & ~((g64 - ref).abs() <= b * ref.abs() + room)
+    assert not bool(bad.any()), f"{what}: {int(bad.sum())} in-range element(s) of the scaled rows beyond the bound; first at {bad.nonzero()[0].tolist()}"
+
+
+def all_nonfinite(what, got, M, rows):
+    """an output BEHIND a 16-bit tensor that overflowed: a contraction over a row that holds +Inf and -Inf is Inf - Inf = NaN, legitimately,
+    so the claim for the scaled rows is non-finite in every element, and finite everywhere else"""
+    nf = ~torch.isfinite(got.reshape(M, -1).float())
+    keep = torch.ones(M, dtype=torch.bool, device=nf.device)
+    keep[list(rows)] = False
+    assert bool(nf[~keep].all()), f"{what}: {int((~nf[~keep]).sum())} finite element(s) in rows whose 16-bit upstream overflowed"
+    assert not bool(nf[keep].any()), f"{what}: non-finite values in rows that were not scaled"
+
+
+def _ln_bwd64(g, z, mean, rstd, t, gw_w, gw_b, sc, L, cond):
+    """(dz, the same expression over absolute values) in fp64 of the conditional layer norm's data gradient from SAVED statistics, as
+    test_mlp_block_bwd_fused restates it: dz = rstd (d - mean(d) - xhat mean(d xhat)), d = g s gamma"""
+    M = g.shape[0]
+    per_row = lambda v: v.double().repeat_interleave(L).view(M, 1)
+    gam = (per_row(t) * gw_w.double() + gw_b.double()) if cond else gw_b.double()
+    xh = (z.double() - mean.double().view(M, 1)) * rstd.double().view(M, 1)
+    d = g.double() * per_row(sc) * gam
+    r = rstd.double().view(M, 1)
+    dz = r * (d - d.mean(-1, keepdim=True) - xh * (d * xh).mean(-1, keepdim=True))
+    mag = r * (d.abs() + d.abs().mean(-1, keepdim=True) + xh.abs() * (d * xh).abs().mean(-1, keepdim=True))
+    return dz, mag
+
+
+B_LN16 = 2.0 ** -9       # a 16-bit layer-norm gradient: the store's 2^-11 and the fp32 arithmetic of two C-term means (the absolute term
+                         # (C + 8) 2^-24 mag covers their cancellation; next to 65504 in a row scaled to ~2^21 it is below 2^-11 |ref| too)
+K_SAT = 22               # g ~ N(0, 1) times 2^22 against 65504 < 2^16: |dz| / 65520 > 1 for all but the few per cent of |N(0, 1)| below 2^-5
+
+
+NF_TAIL = [(kind, C, 2, 64, cond, form) for kind, cond in (("f16", True), ("bf16", False)) for C, form in ((96, "stored"), (96, "prologue"), (96, "lean"), (192, "lean"), (48, "stored"))]
+
+
+@pytest.mark.parametrize("kind,C,B,L,cond,form", NF_TAIL)
+def test_block_tail_bwd_nonfinite(kind, C, B, L, cond, form):
+    block_tail_bwd_nonfinite(kind, C, B, L, cond, form)
+
+
+def block_tail_bwd_nonfinite(kind, C, B, L, cond, form):
+    """scot_block_tail_bwd in its three forms: g (upstream) -> dz2, du, dz1, da and the gradient handed to the layer below, row by row;
+    the norms' parameter gradients (atomics) or the lean form's partial-sum matrices over rows."""
+    M = B * L
+    clean = block_tail_bwd_guarded(kind, C, B, L, cond, form, upstream=lambda g: g)
+    dirty = block_tail_bwd_guarded(kind, C, B, L, cond, form, upstream=plant)
+    for k in ("dz2", "dz1", "da", "g") + (() if form == "lean" else ("du",)):
+        arrived(f"block_tail_bwd {form} C {C}: {k}", clean[k], dirty[k], M)
+    if form == "lean":
+        for k in ("part2", "part1"):
+            reduced(f"block_tail_bwd lean C {C}: {k}", clean[k].view(clean[k].shape[0], -1, (C + 63) // 64 * 64)[:, :, :C],
+                    dirty[k].view(dirty[k].shape[0], -1, (C + 63) // 64 * 64)[:, :, :C])
+    else:
+        for k in ("p2", "p1"):
+            for i, (a, b) in enumerate(zip(clean[k], dirty[k])):
+                if a is not None:
+                    reduced(f"block_tail_bwd {form} C {C}: {k}[{i}]", a, b)
+    if kind != "f16":
+        return
+    # saturation.  dz2 is the chain's first 16-bit store: beyond binary16's range it holds Inf of the reference's sign.  Everything behind it
+    # (du, the gradient handed on, dz1, da) contracts over a row of dz2 that now holds Inf of both signs: NaN is legitimate there.
+    sat = block_tail_bwd_guarded(kind, C, B, L, cond, form, upstream=scale_rows(K_SAT))
+    i, rows = sat["inputs"], plant_rows(M)
+    gin = i["g0"].double() + (i["dqkv"].double() @ i["wqkv"].double() if form == "prologue" else 0.0)
+    ref, mag = _ln_bwd64(gin, i["z2"], i["m2"], i["r2"], i["t"], i["n2_0"], i["n2_1"], i["s2"], L, cond)
+    saturated(f"block_tail_bwd {form} C {C}: dz2", sat["dz2"], ref, (C + 8) * kc.U32 * mag, rows, B_LN16)
+    keep = [r for r in range(M) if r not in rows]
+    assert torch.equal(bits(sat["dz2"][keep]), bits(clean["dz2"][keep])), "dz2: rows that were not scaled differ from the clean launch"
+    for k in ("dz1", "da", "g") + (() if form == "lean" else ("du",)):
+        all_nonfinite(f"block_tail_bwd {form} C {C} behind an overflowed dz2: {k}", sat[k], M, rows)
+        assert torch.equal(bits(sat[k].reshape(M, -1)[keep]), bits(clean[k].reshape(M, -1)[keep])), f"{k}: rows that were not scaled differ from the clean launch"
+
+
+@pytest.mark.parametrize("kind,C,cond", [("f16", 96, True), ("bf16", 192, False)])
+def test_fused_halves_bwd_nonfinite(kind, C, cond):
+    fused_halves_bwd_nonfinite(kind, C, 2, 64, cond)
+
+
+def fused_halves_bwd_nonfinite(kind, C, B, L, cond):
+    """scot_proj_cln_bwd and scot_mlp_block_bwd on their own"""
+    with _build(kind):
+        M = B * L
+        clean = fused_halves_bwd_guarded(C, B, L, cond, upstream=lambda g: g)
+        dirty = fused_halves_bwd_guarded(C, B, L, cond, upstream=plant)
+        for k in ("pdz", "pda", "mdz", "mdu", "mg"):
+            arrived(f"fused halves bwd C {C}: {k}", clean[k], dirty[k], M)
+        for i, (a, b) in enumerate(zip(clean["grads"], dirty["grads"])):
+            reduced(f"fused halves bwd C {C}: parameter gradient {i}", a, b)
+        if kind != "f16":
+            return
+        # saturation: each kernel's first 16-bit store (its layer-norm gradient) holds Inf of the reference's sign; what contracts over
+        # that row (proj_cln_bwd's da; mlp_block_bwd's du and the gradient handed on) sees Inf of both signs: NaN is legitimate there
+        sat = fused_halves_bwd_guarded(C, B, L, cond, upstream=scale_rows(K_SAT))
+        i, rows = sat["inputs"], plant_rows(M)
+        keep = [r for r in range(M) if r not in rows]
+        for out, n, s, behind in (("pdz", "n1", "s1", ("pda",)), ("mdz", "n2", "s2", ("mdu", "mg"))):
+            ref, mag = _ln_bwd64(i["g"], i["z"], i["mean"], i["rstd"], i["t"], i[n + "_0"], i[n + "_1"], i[s], L, cond)
+            saturated(f"fused halves bwd C {C}: {out}", sat[out], ref, (C + 8) * kc.U32 * mag, rows, B_LN16)
+            for k in behind:
+                all_nonfinite(f"fused halves bwd C {C} behind an overflowed {out}: {k}", sat[k], M, rows)
+            for k in (out,) + behind:
+                assert torch.equal(bits(sat[k].reshape(M, -1)[keep]), bits(clean[k].reshape(M, -1)[keep])), f"{k}: rows that were not scaled differ from the clean launch"
+
+
+@pytest.mark.parametrize("kind,cond,x16,B,L,C", [("f16", True, True, 2, 72, 96), ("f16", False, False, 3, 43, 20), ("f16", True, True, 2, 1024, 192),
+                                                 ("f16", False, True, 3, 43, 20), ("bf16", True, True, 2, 72, 96)])
+def test_cln_bwd_nonfinite(kind, cond, x16, B, L, C):
+    cln_bwd_nonfinite(kind, cond, x16, B, L, C)
+
+
+def cln_bwd_nonfinite(kind, cond, x16, B, L, C):
+    """scot_cln_bwd (atomics) and its mode 3 with scot_cln_bwd_finish: dout -> dx row by row, parameter gradients and d_xbias over rows.
+    x16: x and dx in the build's 16-bit type.  Saturation (f16 build, 16-bit dx): three rows of dout times 2^22 against cln_model's fp64 dx;
+    dx is the kernel's only 16-bit store, so Inf of the reference's sign is the claim for both entry points."""
+    with _build(kind) as hd:
+        _cln_bwd_nonfinite(kind, cond, hd if x16 else F32, B, L, C)
+
+
+def _cln_bwd_nonfinite(kind, cond, xdt, B, L, C):
+    x, res, t, ps, dout = _cln_inputs(xdt, B, L, C)
+    M = B * L
+    tt = t if cond else None
+    out = {}
+    ups = [("clean", dout), ("dirty", plant(dout.reshape(M, C)).reshape(dout.shape))]
+    if kind == "f16" and xdt != F32:
+        ups.append(("scaled", scale_rows(K_SAT)(dout.reshape(M, C)).reshape(dout.shape)))
+    for name, up in ups:
+        gd = Guards()
+        xg, rg, tg, dog = gd.op(x, name="x"), gd.op(res, name="resid"), gd.op(tt, name="time"), gd.op(up, name="dout")
+        pg = [gd.op(p, name=f"param{i}") if (cond or i in (1, 3)) else None for i, p in enumerate(ps)]
+        og, mg, sg = gd.out((B, L, C), F32, name="out"), gd.out((M,), F32, name="mean"), gd.out((M,), F32, name="rstd")
+        ops.cln_fwd(xg, rg, og, mg, sg, tg, pg[0], pg[1], pg[2], pg[3], M, L, C, 1e-5)
+        dxg = gd.out((B, L, C), xdt, name="dx")
+        gr = gd.group([(C,)] * 5, F32, fills=[0.0] * 5, name="d_gw_w|d_gw_b|d_bw_w|d_bw_b|d_xbias")
+        ops.cln_bwd(dog, xg, mg, sg, tg, pg[0], pg[1], dxg, gr[0], gr[1], gr[2], gr[3], M, L, C, d_xbias=gr[4])
+        o = dict(dx=dxg, grads=[gr[i] for i in ([0, 1, 2, 3] if cond else [1, 3])] + [gr[4]])
+        nf = ops.cln_bwd_partial_floats(M, L, C, cond)
+        if nf:
+            part, dx3 = gd.out((nf,), F32, name="mode-3 partial sums"), gd.out((B, L, C), xdt, name="dx (mode 3)")
+            g3 = gd.group([(C,)] * 4, F32, fills=[0.0] * 4, name="mode-3 gradients")
+            sel = g3 if cond else [None, g3[0], None, g3[1]]
+            ops.cln_bwd(dog, xg, mg, sg, tg, pg[0], pg[1], dx3, None, None, None, None, M, L, C, sample_scale=None, mode=3, partial=part)
+            ops.cln_bwd_finish(part, M, L, C, sel[0], sel[1], sel[2], sel[3])
+            o.update(dx3=dx3, grads3=[g_ for g_ in sel if g_ is not None])
+        sync()
+        gd.check()
+        out[name] = o
+    c, d = out["clean"], out["dirty"]
+    arrived(f"cln_bwd {(B, L, C)}: dx", c["dx"], d["dx"], M)
+    for i, (a, b) in enumerate(zip(c["grads"], d["grads"])):
+        reduced(f"cln_bwd {(B, L, C)}: gradient {i}", a, b)
+    if "dx3" in c:
+        arrived(f"cln_bwd mode 3 {(B, L, C)}: dx", c["dx3"], d["dx3"], M)
+        for i, (a, b) in enumerate(zip(c["grads3"], d["grads3"])):
+            reduced(f"cln_bwd_finish {(B, L, C)}: gradient {i}", a, b)
+    if "scaled" not in out:
+        return
+    s, rows = out["scaled"], plant_rows(M)
+    ref = cln_model(x, res, t, ps[0], ps[1], ps[2], ps[3], None, ups[2][1], cond, xdt, exact=True)[1].reshape(M, C)
+    # the same expression over absolute values, from fp64 statistics (biased variance, eps = 1e-5)
+    x64 = x.double().reshape(M, C)
+    xc = x64 - x64.mean(-1, keepdim=True)
+    rs = 1.0 / torch.sqrt((xc * xc).mean(-1, keepdim=True) + 1e-5)
+    gam = (t.double().repeat_interleave(L).view(M, 1) * ps[0].double() + ps[1].double()) if cond else ps[1].double()
+    dd, xh = ups[2][1].double().reshape(M, C) * gam, xc * rs
+    mag = rs * (dd.abs() + dd.abs().mean(-1, keepdim=True) + xh.abs() * (dd * xh).abs().mean(-1, keepdim=True))
+    keep = [r for r in range(M) if r not in rows]
+    for k in ("dx", "dx3") if "dx3" in s else ("dx",):
+        saturated(f"cln_bwd {(B, L, C)}: {k}", s[k], ref, (C + 8) * kc.U32 * mag, rows, B_LN16)
+        assert torch.equal(bits(s[k].reshape(M, C)[keep]), bits(c[k].reshape(M, C)[keep])), f"{k}: rows that were not scaled differ from the clean launch"
+
+
+@pytest.mark.parametrize("kind", ["f16", "bf16"])
+@pytest.mark.parametrize("what,layout,mixed,M,N,K", NAN_CASES, ids=[c[0] for c in NAN_CASES])
+def test_gemm_16bit_result_nonfinite(kind, what, layout, mixed, M, N, K):
+    gemm_16bit_result_nonfinite(kind, layout, mixed, M, N, K, wide=(2, 0) if what == "gemm_wide" else None, family=NAN_FAMILY[what.split()[0]])
+
+
+def gemm_16bit_result_nonfinite(kind, layout, mixed, M, N, K, wide=None, family=None):
+    """scot_gemm with a 16-bit C (the data gradients dX = dY W of the backward), one case per kernel family: arrival and locality for
+    planted rows of A, and — f16 build — saturation: three rows of A times 2^12 and B times 2^8 put the fp64 reference of those rows
+    around 2^20, all else stays in range.  b = 2e-3, this file's bound for 16-bit products."""
+    with _build(kind) as hd:
+        with _gemm_config(wide=wide):
+            A, B = _operands(layout, ops.BF16, mixed, M, N, K)
+            rows = plant_rows(M)
+
+            def launch(A_, B_):
+                gd = Guards()
+                Ag, Bg, Cg = gd.op(A_, 8, "A"), gd.op(B_, 8, "B"), gd.out((M, N), hd, 8, name="C")
+                args = (layout, ops.BF16, M, N, K, Ag, A_.shape[1] + 8, Bg, B_.shape[1] + 8, Cg, N + 8)
+                assert family is None or ops.gemm_route(*args)[0] == family, f"the case reaches kernel family {ops.gemm_route(*args)[0]}, not {family}"
+                ops.gemm(*args)
+                sync()
+                gd.check()
+                return Cg
+            clean = launch(A, B)
+            arrived(f"gemm layout {layout} {M}x{N}x{K} -> 16-bit C", clean, launch(plant(A), B), M)
+            if kind != "f16":
+                return
+            b = 2e-3
+            As, Bs = A.clone(), (B.float() * 256.0).to(B.dtype)
+            As[list(rows)] = (As[list(rows)].float() * 4096.0).to(A.dtype)
+            assert finite(As) and finite(Bs)
+            ref, ab = _product64(layout, ops.BF16, As, Bs)
+            big = torch.zeros(M, dtype=torch.bool, device=ref.device)
+            big[list(rows)] = True
+            must_inf, must_fin = ref.abs() > 65520.0 * (1 + b), ref.abs() < 65504.0 * (1 - b)
+            share_inf = float(must_inf[big].float().mean())
+            share_band = float((~must_inf & ~must_fin)[big].float().mean())
+            print(f"saturation {M}x{N}x{K}: {share_inf:.3f} of the scaled rows' elements must be Inf, {share_band:.4f} undecided")
+            assert share_inf >= 0.9 and share_band <= 0.01 and bool(must_fin[~big].all())          # (a condition on the reference alone)
+            got = launch(As, Bs)
+            g64 = got.double()
+            assert bool((torch.isinf(g64) & (torch.sign(g64) == torch.sign(ref)))[must_inf].all()), \
+                f"{int((~torch.isinf(g64))[must_inf].sum())} element(s) beyond binary16's range were not stored as Inf of the reference's sign"
+            assert bool(torch.isfinite(g64)[must_fin].all()), "Inf / NaN stored for a reference inside binary16's range"
+            zero = torch.zeros_like(got)
+            assert_excess(f"gemm saturation {M}x{N}x{K}: the elements in range", torch.where(must_fin, got, zero), torch.where(must_fin, ref, zero.double()),
+                          torch.where(must_fin, ab, torch.ones_like(ab)), K, U_MFMA16)
+            base = launch(A, Bs)                       # the unscaled rows obey locality: identical to the launch without scaled rows
+            keep = ~big
+            assert torch.equal(bits(got[keep]), bits(base[keep]))
+
+
+@pytest.mark.parametrize("kind", ["f16", "bf16"])
+@pytest.mark.parametrize("rows,C", [(130, 96), (37, 24)])
+def test_device_scaled_ops_nonfinite(kind, rows, C):
+    device_scaled_ops_nonfinite(kind, rows, C)
+
+
+def device_scaled_ops_nonfinite(kind, rows, C):
+    """scot_colscale_dev (16-bit out: the ConvNeXt branch's upstream gradient under its extra power of two) and scot_axpy_dev (the way the
+    branch's scratch gradients — where an overflow of that branch happens — reach the arena); scot_partial_colsum(_batch) and
+    scot_replica_reduce (the sums that finish partial matrices and attention's replicas).  Elementwise kernels: the planted ELEMENT is
+    non-finite, every other element is bit-identical (the column sums of 64 and more partial rows meet in atomics: those columns agree
+    to the roundoff of the sum instead).  Saturation of colscale_dev (f16): the three rows of g times 2^22, every other row as in the clean launch."""
+    with _build(kind) as hd:
+        g, gamma = G.rnd(rows, C, seed=1), 1.0 + G.rnd(C, seed=2, scale=0.1)
+        spots = list(zip(plant_rows(rows), (1, C // 2, C - 1)))
+
+        def elementwise(what, clean, dirty, shape):
+            c, d = clean.reshape(shape), dirty.reshape(shape)
+            assert finite(c)
+            hit = torch.zeros(shape, dtype=torch.bool, device=c.device)
+            for r, col in spots:
+                hit[r, col] = True
+            nf = ~torch.isfinite(d.float())
+            assert torch.equal(nf, hit), f"{what}: non-finite exactly where planted expected, found {int(nf.sum())} element(s)"
+            assert torch.equal(bits(d[~hit]), bits(c[~hit])), what
+
+        def colscale(g_, mul):
+            gd = Guards()
+            o = gd.out((rows, C), hd, name="colscale out")
+            ops.colscale_dev(gd.op(g_, name="g"), gd.op(gamma, name="gamma"), gd.op(torch.tensor([mul], device=G.DEV), name="mul"), o, rows, C)
+            sync()
+            gd.check()
+            return o
+        elementwise("colscale_dev", colscale(g, 4.0), colscale(plant(g), 4.0), (rows, C))
+        if kind == "f16":
+            b = 2.0 ** -10              # three fp32 roundings and the store's
+            gs = scale_rows(K_SAT)(g)                   # the three rows times 2^22, mul = 4 as in the clean launch: all other rows stay in range
+            ref = gs.double() * gamma.double() * 4.0
+            sat = colscale(gs, 4.0)
+            saturated("colscale_dev", sat, ref, 0.0, plant_rows(rows), b)
+            keep = [r for r in range(rows) if r not in plant_rows(rows)]
+            assert torch.equal(bits(sat[keep]), bits(colscale(g, 4.0)[keep])), "colscale_dev: rows that were not scaled differ from the clean launch"
+
+        def axpy(src_, clear):
+            gd = Guards()
+            dst, src = gd.out((rows * C,), F32, src=G.rnd(rows * C, seed=3), name="dst"), gd.out((rows * C,), F32, src=src_.reshape(-1), name="src")
+            ops.axpy_dev(dst, src, gd.op(torch.tensor([0.25], device=G.DEV), name="alpha"), clear_src=clear)
+            sync()
+            gd.check()
+            if clear:
+                assert float(src.abs().max()) == 0.0
+            return dst
+        for clear in (False, True):
+            elementwise(f"axpy_dev clear_src {clear}", axpy(g, clear), axpy(plant(g), clear), (rows, C))
+
+        def colsums(part_):
+            gd = Guards()
+            pg = gd.op(part_, name="partial")
+            o1 = gd.out((C,), F32, fill=0.5, name="partial_colsum out")
+            o2 = gd.out((C,), F32, fill=0.5, name="partial_colsum_batch out")
+            o3 = gd.out((C,), F32, fill=0.5, name="partial_colsum_batch out (2)")
+            ops.partial_colsum(pg, rows, C, o1)
+            ops.partial_colsum_batch([(pg, rows, C, o2), (pg, rows - 1, C, o3)])
+            rep = gd.out((3, 2 * C), F32, src=torch.stack([part_[r, :C].repeat(2) for r in plant_rows(rows)]), name="replicas")
+            desc = gd.op(torch.tensor([[0, 0, C], [C, C, C - 3]], dtype=torch.int32, device=G.DEV), name="desc")
+            o4 = gd.out((2 * C,), F32, fill=0.5, name="replica_reduce dst")
+            ops.replica_reduce(rep, 0, 3, 2 * C, desc, 2, C, o4)
+            sync()
+            gd.check()
+            return o1, o2, o3, o4
+        cols = [c for _, c in spots]
+        cl, di = colsums(g), colsums(plant(g))
+        for what, c_, d_, planted_cols in (("partial_colsum", cl[0], di[0], cols), ("partial_colsum_batch", cl[1], di[1], cols),
+                                           ("partial_colsum_batch (all but the last row)", cl[2], di[2], cols[:2]),
+                                           ("replica_reduce", cl[3][:C], di[3][:C], cols), ("replica_reduce (second entry)", cl[3][C:2 * C - 3], di[3][C:2 * C - 3], cols[:2])):
+            assert finite(c_), what
+            nf = ~torch.isfinite(d_)
+            want = torch.zeros_like(nf)
+            want[planted_cols] = True
+            assert torch.equal(nf, want), f"{what}: non-finite columns {nf.nonzero().flatten().tolist()}, planted {planted_cols}"
+            if what.startswith("partial_colsum") and rows >= 64:      # from 64 rows on the sum runs in slices that meet in `out` through atomics
+                room = 8 * kc.U32 * (g.double().abs().sum(0) + 0.5)[:d_.numel()]
+                assert bool(((d_.double() - c_.double()).abs() <= room)[~want].all()), what
+            else:
+                assert torch.equal(bits(d_[~want]), bits(c_[~want])), what
+        assert float(di[3][2 * C - 3:].min()) == 0.5 and float(di[3][2 * C - 3:].max()) == 0.5      # beyond the entry's count: untouched
+
+
+@pytest.mark.parametrize("kind", ["f16", "bf16"])
+@pytest.mark.parametrize("K,dims", [(200, [(40, 72), (72, 40), (48, 48)]), (2048, [(96, 384), (384, 96), (288, 96)])], ids=["ragged", "C96"])
+def test_wgrad_group_nonfinite(kind, K, dims):
+    wgrad_group_nonfinite(kind, K, dims)
+
+
+def wgrad_group_nonfinite(kind, K, dims):
+    """scot_wgrad_group (or, for shapes it declines, the per-problem path) in every grad mode — GRAD_STORE_SCALED, GRAD_ADD_SCALED, GRAD_ADD,
+    one problem each: dW = dY^T X is a reduction over the tokens, so a planted element of dY in column c makes ROW c of dW non-finite in
+    every element and db[c] non-finite; every other row of dW is bit-identical to the clean launch (deterministic), every other bias
+    gradient (atomics) stays finite."""
+    with _build(kind) as hd:
+        modes = [ops.GRAD_STORE_SCALED, ops.GRAD_ADD_SCALED, ops.GRAD_ADD][:len(dims)]
+        s = torch.tensor([2.0 ** -7], device=G.DEV)
+        dys = [G.rnd(K, m, dtype=hd, scale=0.5, seed=10 + i) for i, (m, _) in enumerate(dims)]
+        xs = [G.rnd(K, nn, dtype=hd, seed=20 + i) for i, (_, nn) in enumerate(dims)]
+        dws0 = [G.rnd(m, nn, seed=30 + i) for i, (m, nn) in enumerate(dims)]
+        dbs0 = [G.rnd(m, seed=40 + i) for i, (m, _) in enumerate(dims)]
+        covered = all(m % 8 == 0 and nn % 8 == 0 for m, nn in dims) and K % 8 == 0
+
+        def launch(dys_):
+            with _gemm_config(splitk=(0, 1)):
+                gd = Guards()
+                dyg, xg = [gd.op(t, name=f"dY{i}") for i, t in enumerate(dys_)], [gd.op(t, name=f"X{i}") for i, t in enumerate(xs)]
+                dwg = gd.group([tuple(t.shape) for t in dws0], F32, srcs=[None if md == ops.GRAD_STORE_SCALED else t for t, md in zip(dws0, modes)], name="dW arena")
+                dbg = gd.group([tuple(t.shape) for t in dbs0], F32, srcs=dbs0, name="dbias arena")
+                ok = ops.wgrad_group(ops.BF16, list(zip(dyg, xg, dwg, dbg)), modes, gd.op(s, name="grad_scale"))
+                assert ok == covered
+                if not ok:
+                    for dy, x, dw, db in zip(dyg, xg, dwg, dbg):
+                        dw.copy_(dws0[dwg.index(dw)])
+                        ops.linear_wgrad(ops.BF16, dy, x, dw, dbias=db)
+                sync()
+                gd.check()
+                return dwg, dbg
+        cw, cb = launch(dys)
+        dw_, db_ = launch([plant(t.float()).to(hd) for t in dys])
+        for i, (m, _) in enumerate(dims):
+            cols = (1, m // 2, m - 1)
+            arrived(f"wgrad_group K {K} dW{i} mode {modes[i]}", cw[i], dw_[i], m, rows=cols)
+            nf = ~torch.isfinite(db_[i])
+            want = torch.zeros_like(nf)
+            want[list(cols)] = True
+            assert finite(cb[i]) and torch.equal(nf, want), f"wgrad_group K {K} db{i}: non-finite at {nf.nonzero().flatten().tolist()}, planted columns {cols}"
+
+
+@pytest.mark.parametrize("kind,M,C,mode", [("f16", 136, 96, ops.GRAD_ADD), ("f16", 136, 96, ops.GRAD_STORE_SCALED), ("f16", 136, 96, ops.GRAD_ADD_SCALED),
+                                           ("bf16", 72, 192, ops.GRAD_STORE_SCALED), ("f16", 1000, 96, ops.GRAD_ADD_SCALED)])
+def test_wgrad_mlp_nonfinite(kind, M, C, mode):
+    wgrad_mlp_nonfinite(kind, M, C, mode)
+
+
+def wgrad_mlp_nonfinite(kind, M, C, mode):
+    """scot_wgrad_mlp in every grad mode.  dz (upstream) planted at (r, c):  dW2 = dz^T gelu(u): row c non-finite in every element, the other
+    rows bit-identical (deterministic), db2[c] non-finite alone;  D = dz W2 is non-finite in all of row r, so du = D gelu'(u) is, and
+    dW1 = du^T h16 and db1 = sum du, reductions over the rows, are non-finite in EVERY element."""
+    with _build(kind) as hd:
+        hid = 4 * C
+        h16, dz = G.rnd(M, C, dtype=hd, seed=1), G.rnd(M, C, dtype=hd, scale=0.5, seed=2)
+        w1, b1 = G.rnd(hid, C, scale=C ** -0.5, seed=3).to(hd), G.rnd(hid, seed=4, scale=0.2)
+        w2t = G.rnd(C, hid, scale=hid ** -0.5, seed=5).to(hd).t().contiguous()
+        sizes = [hid * C, hid, C * hid, C]
+        s = torch.tensor([2.0 ** -7], device=G.DEV) if mode != ops.GRAD_ADD else None
+        flat0 = G.rnd(sum(sizes), seed=6)
+
+        def launch(dz_):
+            gd = Guards()
+            fg = gd.out((sum(sizes),), F32, src=flat0, name="dW1|db1|dW2|db2")
+            o = torch.split(fg, sizes)
+            dW1, db1, dW2, db2 = o[0].view(hid, C), o[1], o[2].view(C, hid), o[3]
+            if mode == ops.GRAD_STORE_SCALED:
+                dW1.fill_(NAN)
+                dW2.fill_(NAN)
+            assert ops.wgrad_mlp(gd.op(h16, name="h16"), gd.op(dz_, name="dz"), gd.op(w1, name="w1"), gd.op(b1, name="b1"), gd.op(w2t, name="w2t"),
+                                 dW1, db1, dW2, db2, mode=mode, grad_scale=gd.op(s, name="grad_scale"))
+            sync()
+            gd.check()
+            return dW1, db1, dW2, db2
+        c, d = launch(dz), launch(plant(dz.float()).to(hd))
+        cols = (1, C // 2, C - 1)
+        assert all(finite(t) for t in c)
+        arrived(f"wgrad_mlp M {M} C {C} mode {mode}: dW2", c[2], d[2], C, rows=cols)
+        nf = ~torch.isfinite(d[3])
+        want = torch.zeros_like(nf)
+        want[list(cols)] = True
+        assert torch.equal(nf, want) and torch.equal(bits(d[3][~want]), bits(c[3][~want])), "wgrad_mlp: db2"
+        assert not bool(torch.isfinite(d[0]).any()), f"wgrad_mlp dW1: {int(torch.isfinite(d[0]).sum())} finite element(s) below rows of du that are not finite"
+        assert not bool(torch.isfinite(d[1]).any()), "wgrad_mlp db1"
+
+
+@pytest.mark.parametrize("kind", ["f16", "bf16"])
+@pytest.mark.parametrize("shape", [(2, 9, 11, 33), (2, 12, 20, 24), (1, 17, 16, 96)], ids=DW_IDS)
+@pytest.mark.parametrize("x16", [False, True], ids=["x_f32", "x_16"])
+def test_dwconv7_data_gradient_nonfinite(kind, shape, x16):
+    dwconv7_data_gradient_nonfinite(kind, *shape, x16)
+
+
+def dwconv7_data_gradient_nonfinite(kind, B, H, W, C, x16):
+    """scot_dwconv7 with flip = 1 and a 16-bit result (the ConvNeXt block's data gradient).  A pixel of the result depends on the 7 x 7
+    pixels around it in its own image and channel, cropped at the border (zero padding): the dependency mask is the stencil applied to the
+    indicator of the planted elements.  Saturation (f16, fp32 upstream): image row H // 2 of sample 0 times 2^22; b = 2^-10 (50 fp32
+    additions and the store's rounding)."""
+    with _build(kind) as hd:
+        xdt = hd if x16 else F32
+        dy = G.rnd(B, H, W, C, seed=3, dtype=xdt)
+        w = G.rnd(C, 1, 7, 7, seed=1, scale=0.2)
+
+        def launch(dy_):
+            gd = Guards()
+            y = gd.out((B, H, W, C), hd, name="dx")
+            ops.dwconv7(gd.op(dy_, name="dy"), gd.op(w, name="w"), None, y, B, H, W, C, flip=True)
+            sync()
+            gd.check()
+            return y
+        clean = launch(dy)
+        assert finite(clean)
+        hit = torch.zeros(B, H, W, C, dtype=torch.float64, device=G.DEV)
+        dirty_in = dy.clone()
+        for (b_, h_, w_, c_), v in zip(((0, 0, 1, 1), (B - 1, H // 2, W // 2, C // 2), (B - 1, H - 1, W - 1, C - 1)), (INF, NAN, -INF)):
+            dirty_in[b_, h_, w_, c_] = v
+            hit[b_, h_, w_, c_] = 1.0
+        dep = _dwconv64(hit, torch.ones_like(w, dtype=torch.float64), None, True) > 0
+        assert int(dep.sum()) in range(3 * 16, 3 * 49 + 1)
+        got = launch(dirty_in)
+        nf = ~torch.isfinite(got.float())
+        assert torch.equal(nf, dep), f"dwconv7 flip: {int((nf & ~dep).sum())} non-finite element(s) outside the stencil of a planted one, {int((dep & ~nf).sum())} finite inside"
+        assert torch.equal(bits(got[~dep]), bits(clean[~dep]))
+        if kind != "f16" or x16:
+            return
+        b = 2.0 ** -10
+        big_in = dy.clone()
+        big_in[0, H // 2] *= 2.0 ** 22
+        ref = _dwconv64(big_in.double(), w.double(), None, True)
+        mag = _dwconv64(big_in.double().abs(), w.double().abs(), None, True)
+        rows = torch.zeros(B, H, W, C, dtype=torch.bool, device=G.DEV)
+        rows[0, H // 2] = True
+        near = _dwconv64(rows.double(), torch.ones_like(w, dtype=torch.float64), None, True) > 0
+        must_inf, must_fin = ref.abs() > 65520.0 * (1 + b), ref.abs() < 65504.0 * (1 - b)
+        share_inf, share_band = float(must_inf[rows].float().mean()), float((~must_inf & ~must_fin)[rows].float().mean())
+        print(f"dwconv7 saturation {(B, H, W, C)}: {share_inf:.3f} of the scaled row's elements must be Inf, {share_band:.4f} undecided")
+        assert share_inf >= 0.9 and share_band <= 0.01 and bool(must_fin[~near].all())
+        got = launch(big_in)
+        g64 = got.double()
+        assert bool((torch.isinf(g64) & (torch.sign(g64) == torch.sign(ref)))[must_inf].all()), \
+            f"{int((~torch.isinf(g64))[must_inf].sum())} element(s) beyond binary16's range were not stored as Inf of the reference's sign"
+        assert bool(torch.isfinite(g64)[must_fin].all())
+        zero = torch.zeros_like(got)
+        assert_excess(f"dwconv7 saturation {(B, H, W, C)}: the elements in range", torch.where(must_fin, got, zero), torch.where(must_fin, ref, zero.double()),
+                      torch.where(must_fin, mag, torch.ones_like(mag)), 50, kc.U32)
+        assert torch.equal(bits(got[~near]), bits(clean[~near]))
+
+
+NF_ATTN = [("f16", (2, 8, 8, 32, 2, 4, 2)), ("bf16", (1, 14, 14, 32, 1, 7, 3)), ("f16", (1, 32, 32, 96, 3, 16, 8)), ("bf16", (1, 16, 16, 32, 2, 16, 0))]
+
+
+@pytest.mark.parametrize("kind,case", NF_ATTN, ids=lambda v: str(v).replace(" ", ""))
+def test_window_attention_bwd_nonfinite(kind, case):
+    window_attention_bwd_nonfinite(kind, case)
+
+
+def window_attention_bwd_nonfinite(kind, case):
+    """scot_window_attn_bwd (generic and 16 x 16 windows) and scot_window_attn_bwd_rep with 16-bit operands.  dout planted at token r, channel
+    ch of head h; within r's (shifted) window W:
+      dV = P^T dO     column ch of the value block is non-finite for EVERY token of W (a masked pair has P = 0 and 0 * Inf = NaN);
+      dP = dO V^T     row r, so dS row r, so dQ of token r in all of head h's channels, and dK = dS^T Q in all of head h's channels for
+                      every token of W (the cosine normalisation's backward keeps NaN);
+      dbias_table and dlogit_scale (sums over windows, atomics / replicas) hold a non-finite element for head h.
+    Locality: tokens of every other window are bit-identical to the clean launch, and so are, inside W, the columns of the other heads.
+    (Inside head h's blocks of W the untouched columns may or may not be identical: not asserted.)"""
+    with _build(kind) as half:
+        B, Hp, Wp, C, heads, ws, shift = case
+        L, TS, N, d = Hp * Wp, (2 * ws - 1) ** 2, ws * ws, C // heads
+        nW = (Hp // ws) * (Wp // ws)
+        qkv, table, ls, dout = _attn_inputs(case, half)
+        R, pad = 3, 5
+        st, sl = heads * TS + pad, heads + pad
+
+        def launch(dout_, qkv_=None):
+            gd = Guards()
+            qg, tg, lg, dg = gd.op(qkv if qkv_ is None else qkv_, name="qkv"), gd.op(table, name="bias_table"), gd.op(ls, name="logit_scale"), gd.op(dout_, name="dout")
+            og, lseg = gd.out((B, L, C), half, name="out"), gd.out((B * nW, heads, N), F32, name="lse")
+            dqg, dtg, dlg = gd.out((B, L, 3 * C), half, name="dqkv"), gd.out((heads, TS), F32, fill=0.0, name="dbias_table"), \
+                gd.out((heads,), F32, fill=0.0, name="dlogit_scale")
+            ops.window_attn_fwd(ops.BF16, qg, og, lseg, tg, lg, B, Hp, Wp, C, heads, ws, shift)
+            ops.window_attn_bwd(ops.BF16, qg, og, dg, lseg, tg, lg, dqg, dtg, dlg, B, Hp, Wp, C, heads, ws, shift)
+            rtg, rlg = gd.out((R * st,), F32, fill=0.0, name="table replicas"), gd.out((R * sl,), F32, fill=0.0, name="logit-scale replicas")
+            dq2g = gd.out((B, L, 3 * C), half, name="dqkv (replica entry)")
+            ops.window_attn_bwd_rep(ops.BF16, qg, og, dg, lseg, tg, lg, dq2g, rtg, rlg, B, Hp, Wp, C, heads, ws, shift, R, st, sl)
+            sync()
+            gd.check()
+            rt = rtg.view(R, st)[:, :heads * TS].reshape(R, heads, TS)
+            return dict(dqkv=dqg, dqkv_rep=dq2g, dtable=dtg, dls=dlg, rt=rt, rl=rlg.view(R, sl)[:, :heads])
+        clean = launch(dout)
+        assert all(finite(v) for v in clean.values())
+        M = B * L
+        spots = list(zip(plant_rows(M), (1, C // 2, C - 1)))
+        dirty = launch(plant(dout.reshape(M, C).float()).to(half).reshape(B, L, C))
+        tok = torch.arange(M, device=G.DEV)
+        b_, y_, x_ = tok // L, (tok % L) // Wp, tok % Wp
+        win = (b_ * (Hp // ws) + ((y_ - shift) % Hp) // ws) * (Wp // ws) + ((x_ - shift) % Wp) // ws       # window of every token (torch.roll by -shift)
+        must = torch.zeros(M, 3 * C, dtype=torch.bool, device=G.DEV)       # has to be non-finite
+        free = torch.zeros(M, 3 * C, dtype=torch.bool, device=G.DEV)       # may be either
+        hit_heads = set()
+        for r, ch in spots:
+            h = ch // d
+            hit_heads.add(h)
+            inw = win == win[r]
+            assert int(inw.sum()) == N
+            must[inw, 2 * C + ch] = True
+            must[inw, C + h * d:C + (h + 1) * d] = True
+            must[r, h * d:(h + 1) * d] = True
+            for blk in range(3):
+                free[inw, blk * C + h * d:blk * C + (h + 1) * d] = True
+        for name in ("dqkv", "dqkv_rep"):
+            got, ref = dirty[name].reshape(M, 3 * C), clean[name].reshape(M, 3 * C)
+            nf = ~torch.isfinite(got.float())
+            assert bool(nf[must].all()), f"{name}: {int((~nf)[must].sum())} of {int(must.sum())} elements that depend on a planted dout element are finite"
+            assert not bool(nf[~free].any()), f"{name}: {int(nf[~free].sum())} non-finite element(s) in other windows or other heads"
+            assert torch.equal(bits(got[~free]), bits(ref[~free])), f"{name}: other windows / other heads differ from the clean launch"
+        for h in range(heads):
+            for name in ("dtable", "dls", "rt", "rl"):
+                t = dirty[name]
+                part = t[..., h, :] if name in ("dtable", "rt") else t[..., h]
+                if h in hit_heads:
+                    assert bool((~torch.isfinite(part)).any()), f"{name}: head {h} saw a planted element, its sum is finite everywhere"
+                else:
+                    assert bool(torch.isfinite(part).all()), f"{name}: head {h} saw no planted element"
+        if kind != "f16":
+            return
+        # saturation.  dout is a 16-bit OPERAND here, so a scaled row has to stay below 65504 itself: three tokens' rows times 2^A_SAT.
+        #   dV = P^T dO is a convex combination of rows of dO: it cannot leave the range, and is asserted finite everywhere.
+        #   dq = (dq^ - q^ (q^ . dq^)) / |q| grows with 1 / |q| (cosine attention: the forward does not depend on |q|), so q and k of every
+        #   token are given at 2^-Q_SAT of their size; dS = P (dP - delta), the 16-bit operand in between, stays in range (the logit
+        #   scale is applied in fp32 behind it), so the q block of the three tokens is a FINAL 16-bit store: Inf of the reference's sign.
+        # The bound: this kernel's existing bound is window_attention_guarded's, per ROW: |got - exact| <= MARGIN max(e_model, median) |exact|
+        # in the row's 2-norm, e_model the rounding model's relative error (dominated by delta taken from the rounded O).  A bound on the
+        # row's error norm bounds each element's, so every element of row r gets the absolute band t_r = that figure, from the model at
+        # the unscaled dout (dq of a token is linear in its row of dout; the model itself rounds its scaled result to Inf): beyond
+        # 65520 + t_r Inf of the reference's sign, below 65504 - t_r finite and within t_r.  t_r is a fixed fraction of the row's norm, so
+        # NO scale brings 90 % of a row beyond it with 1 % in between: on the reference alone the shares are 0.875 / 0.125 ((2,8,8,32,2,4,2))
+        # and 0.875 / 0.087 ((1,32,32,96,3,16,8)) here and 0.906 / 0.094, 0.917 / 0.083 at four times the scale.  Asserted instead: more
+        # than half of the scaled rows' elements are in the must-be-Inf class.
+        A_SAT, Q_SAT = 13, 9
+        small = qkv.clone()
+        small[..., :2 * C] = (small[..., :2 * C].float() * 2.0 ** -Q_SAT).to(half)
+        rows = plant_rows(M)
+        dsc = scale_rows(A_SAT)(dout.reshape(M, C).float()).to(half).reshape(B, L, C)
+        assert finite(dsc)
+        ex = attn_model(small, table, ls, dout, case, "16", half, exact=True)[1].reshape(M, 3 * C)[:, :C]
+        mo = attn_model(small, table, ls, dout, case, "16", half)[1].reshape(M, 3 * C)[:, :C]
+        e_model = kc.row_errors(mo, ex)
+        factor = torch.ones(M, 1, dtype=torch.float64, device=ex.device)
+        factor[list(rows)] = 2.0 ** A_SAT
+        ref = ex * factor
+        band = (MARGIN["attn16"] * torch.maximum(e_model, e_model.median()) * ex.norm(dim=-1)).unsqueeze(1) * factor
+        base, sat = launch(dout, small), launch(dsc, small)
+        scaled_windows = torch.zeros(M, dtype=torch.bool, device=G.DEV)
+        for r in rows:
+            scaled_windows |= win == win[r]
+        for name in ("dqkv", "dqkv_rep"):
+            got = sat[name].reshape(M, 3 * C)
+            saturated(f"window attention {case}: the q block of {name}", got[:, :C], ref[:, :C], band, rows, 0.0, row_band=band)
+            assert finite(got[:, 2 * C:]), f"{name}: dV, a convex combination of in-range rows of dO, is not finite"
+            assert torch.equal(bits(got[~scaled_windows]), bits(base[name].reshape(M, 3 * C)[~scaled_windows])), f"{name}: windows without a scaled token differ from the unscaled launch"
+
+
+def test_cpb_bwd_batched_nonfinite():
+    cpb_bwd_batched_nonfinite(CPB_LAYERS, 1)
+
+
+def cpb_bwd_batched_nonfinite(layers, first):
+    """scot_cpb_bwd_batched: dtable (what the attention backward accumulated) planted at (head h, table entry t) of three layers of the
+    range.  The bias MLP is table = 16 sigmoid(w2 relu(w0 c + b0)): the ReLU is a documented mask, so the element is planted where it is
+    open and the claim is made for the hidden units that are open at entry t (pre-activation beyond 1e-3 in fp64): dw2[h, unit], dw0[unit, :]
+    and db0[unit] are non-finite.  Locality: the other heads' rows of dw2, every other layer, every neighbour in the arena are
+    bit-identical to the clean launch (this kernel sums without atomics: asserted by the guarded case above through two launches)."""
+    picks = {}
+
+    def planted(dtab, desc):
+        dtab = dtab.clone()
+        inside = [li for li in range(first, len(layers))]
+        for li, v in zip((inside[0], inside[len(inside) // 2], inside[-1]), (INF, NAN, -INF)):
+            ws, heads = layers[li]
+            ts, t0 = (2 * ws - 1) ** 2, desc[8 * li + 6]
+            h, t = heads - 1, ts // 3
+            dtab[t0 + h * ts + t] = v
+            picks[li] = (h, t)
+        return dtab
+    clean = cpb_batched_guarded(layers, first, upstream=lambda dtab, desc: dtab)[0]
+    dirty, srcs_p, coords, coff = cpb_batched_guarded(layers, first, upstream=planted)
+    assert len(picks) == 3
+    for li, (ws, heads) in enumerate(layers):
+        gc, gdirty = clean[2 * li], dirty[2 * li]
+        assert finite(gc) and torch.equal(bits(clean[2 * li + 1]), bits(dirty[2 * li + 1])), f"the neighbour behind layer {li}"
+        if li not in picks:
+            assert torch.equal(bits(gc), bits(gdirty)), f"layer {li} holds no planted element"
+            continue
+        h, t = picks[li]
+        ts = (2 * ws - 1) ** 2
+        lp = srcs_p[2 * li].double()
+        w0, b0 = lp[:1024].view(512, 2), lp[1024:1536]
+        c = coords[coff[ws]:coff[ws] + 2 * ts].view(ts, 2).double()[t]
+        pre = w0 @ c + b0
+        opened = pre > 1e-3
+        assert int(opened.sum()) > 32
+        cut = lambda g: (g[:1024].view(512, 2), g[1024:1536], g[1536:].view(heads, 512))
+        (dw0, db0, dw2), (cw0, cb0, cw2) = cut(gdirty), cut(gc)
+        nf = lambda x: ~torch.isfinite(x)
+        assert bool(nf(dw2[h])[opened].all()), f"layer {li}: dw2[{h}] is finite at {int((~nf(dw2[h]))[opened].sum())} open unit(s)"
+        assert bool(nf(dw0)[opened].all()) and bool(nf(db0)[opened].all()), f"layer {li}: dw0 / db0 are finite at open units"
+        others = [i for i in range(heads) if i != h]
+        assert torch.equal(bits(dw2[others]), bits(cw2[others])), f"layer {li}: rows of dw2 of other heads differ from the clean launch"
 
 
 def measure_margins():

@@ -473,3 +473,53 @@ def test_output_attentions_match_reference(emu, monkeypatch):
     o2 = model(pixel_values=pv, time=t, labels=lab, output_attentions=True)
     o2.loss.backward()
     assert len(o2.attentions) == 4 and float((o2.attentions[1] - out.attentions[1]).abs().max()) < 1e-6
+
+
+# the exponents bracket the boundaries a full sweep of the emulation measured (tiny_trained: finite up to 2^16, flagged from 2^18;
+# tiny_hf: finite up to 2^28, flagged from 2^30).  If a boundary moves, the sweep's bracketed / monotone assertions say so.
+@pytest.mark.parametrize("name,ks,bound", [("tiny_trained", (13, 16, 18, 20, 40), 5e-2), ("tiny_hf", (13, 28, 30, 40), 2 * 5.34e-5)])
+def test_at_every_gradient_scale_a_step_is_flagged_or_right(emu, monkeypatch, name, ks, bound):
+    """The small version of tests/test_model_gpu.py's sweep (rule: tests/overflow_sweep.py), through ScOT.forward / loss.backward() and
+    the fused AdamW's own launches on the emulated kernels.  e(S_auto) bounds: tiny_trained 5e-2 (test_engine_reduced_precision_modes');
+    tiny_hf twice the 5.34e-5 measured on the MI355X (tests/test_model_gpu.py: E_AUTO)."""
+    import emu_session
+    import overflow_sweep as osw
+    import scOT.model as M
+    monkeypatch.setattr(M, "_require_hip", lambda t: None)
+    f, meta = load_fixture(name)
+    cfg = ScOTConfig(**meta["cfg"])
+    pv, t, lab, pm = fixture_inputs(meta, cfg)
+    assert pm is None
+    kw = dict(pixel_values=pv, time=t, labels=lab)
+    sd = synth_state_dict(param_shapes(cfg), meta["regime"])
+    models = {}
+    for compute in ("fp32", "fp16"):
+        models[compute] = m = M.ScOT(cfg, compute=compute)
+        m.load_state_dict(sd)
+    g32 = osw.fp32_arena_grads(models["fp32"], kw)
+    assert grads_global(models["fp32"], f) < 1e-4                # the reference of the sweep is the real reference's gradient
+    model = models["fp16"]
+    res = osw.sweep(model, kw, g32, bound, ks=ks, tag=name + " (emulation)", opt=emu_session.fused_adamw(model, lr=0.0))
+    if name == "tiny_hf":
+        assert model._engine._ls                               # the ConvNeXt branches ran under the extra device-side power of two
+    assert res["k_auto"] == 13
+
+
+def test_fused_adamw_recovers_through_real_overflow(emu, monkeypatch):
+    """tests/overflow_sweep.py `recovery` on the emulated kernels: fp16 tiny_trained from a gradient scale of 2^30."""
+    import emu_session
+    import overflow_sweep as osw
+    import scOT.model as M
+    monkeypatch.setattr(M, "_require_hip", lambda t: None)
+    f, meta = load_fixture("tiny_trained")
+    cfg = ScOTConfig(**meta["cfg"])
+    pv, t, lab, pm = fixture_inputs(meta, cfg)
+    kw = dict(pixel_values=pv, time=t, labels=lab)
+    sd = synth_state_dict(param_shapes(cfg), meta["regime"])
+    m32, model = M.ScOT(cfg, compute="fp32"), M.ScOT(cfg, compute="fp16")
+    m32.load_state_dict(sd)
+    model.load_state_dict(sd)
+    g32 = osw.fp32_arena_grads(m32, kw)
+    opt = emu_session.fused_adamw(model, lr=1e-6)
+    opt.growth_interval = 2
+    osw.recovery(model, kw, g32, opt, 5e-2)

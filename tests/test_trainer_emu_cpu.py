@@ -326,3 +326,68 @@ def test_resumed_run_equals_the_uninterrupted_one(emu, tmp_path):
     assert n4 == 6 and np.allclose(lr4[-4:], lr0[-4:], rtol=1e-6, atol=1e-12)
     worst = max(float((mid[k].double() - straight[k].double()).abs().max() / (straight[k].double().abs().max() + 1e-12)) for k in straight)
     assert worst < 1e-5, worst
+
+
+def _fp16_trainer(cfg, meta, tmp_path, scale_log2, sched=None, steps=8):
+    """an fp16-mode model under the trainer with the fused AdamW (on the GPU the trainer builds it itself; on the emulation it is handed
+    in) and a gradient scale that is too large by a few binades, as the growth rule leaves it"""
+    import emu_session
+    from scOT.model import ScOT
+    from scOT.trainer import Trainer, TrainingArguments
+    model = ScOT(cfg, compute="fp16")
+    model.load_state_dict(synth_state_dict(param_shapes(cfg), meta["regime"]))
+    args = TrainingArguments(output_dir=str(tmp_path), per_device_train_batch_size=2, num_train_epochs=4, max_steps=steps, learning_rate=1e-4,
+                             lr_scheduler_type="linear", warmup_ratio=0.25, logging_steps=1, max_grad_norm=5.0, save_strategy="no")
+    opt = emu_session.fused_adamw(model, lr=args.learning_rate, max_grad_norm=5.0)
+    eng = model._engine
+    eng.scale_state.copy_(torch.tensor([2.0 ** scale_log2, 2.0 ** -scale_log2, 0.0, 0.0]))
+    eng._scale_ready = True                         # (as a restored checkpoint does: the first forward keeps this scale)
+    lr_used = []
+
+    from scOT.trainer import TrainerCallback
+
+    class Spy(TrainerCallback):
+        def on_step_begin(self, args, state, control, optimizer=None, **kw):
+            lr_used.append((optimizer.applied_steps(), optimizer.param_groups[0]["lr"]))
+
+    made = sched(opt) if sched is not None else None
+    tr = Trainer(model=model, args=args, train_dataset=Samples(8, cfg, 0), optimizers=(opt, made), callbacks=[Spy()])
+    return tr, opt, lr_used
+
+
+def test_trainer_accounts_for_steps_skipped_after_fp16_overflow(emu, monkeypatch, tmp_path):
+    """A short fp16 run whose initial gradient scale (2^20) forces skips through real overflow in the backward.  The trainer's bookkeeping:
+    state["skipped_steps"] and the log entry carry the optimizer's count, the warning is emitted, and the learning rate every step RUNS
+    with is the schedule's value at the number of steps applied so far — a skipped step does not advance the schedule (HF / GradScaler)."""
+    from scOT.trainer import lr_lambda
+    monkeypatch.setenv("SCOT_SIDE_STREAM", "0")
+    f, meta = load_fixture("tiny_trained")
+    cfg = ScOTConfig(**meta["cfg"])
+    tr, opt, lr_used = _fp16_trainer(cfg, meta, tmp_path, 20)
+    with pytest.warns(UserWarning, match=r"optimizer step\(s\) skipped: fp16 gradients overflowed under the loss scale"):
+        out = tr.train()
+    skipped, applied = opt.skipped_steps(), opt.applied_steps()
+    print(f"\n[trainer] {applied} applied, {skipped} skipped, scale now 2^{math.log2(opt.loss_scale_value()):.0f}; lr in use {lr_used}")
+    assert out.global_step == 8 and skipped + applied == 8 and skipped >= 2 and applied >= 2
+    assert tr.state["skipped_steps"] == skipped
+    logged = [h["skipped_steps"] for h in tr.state["log_history"] if "skipped_steps" in h]
+    assert logged == list(range(1, skipped + 1))                    # logging_steps = 1: every skip is seen at its own step
+    assert opt.loss_scale_value() == 2.0 ** (20 - skipped)          # (fewer than growth_interval applied steps: no growth)
+    lam = lr_lambda("linear", 2, 8)
+    assert len(lr_used) == 8 and [n for n, _ in lr_used] == sorted(n for n, _ in lr_used) and lr_used[-1][0] == applied - 1
+    for n_applied, lr in lr_used:
+        assert lr == pytest.approx(1e-4 * lam(n_applied), rel=1e-6, abs=1e-15), (n_applied, lr, lr_used)
+    assert tr.lr_scheduler.last_epoch == applied and tr.lr_scheduler.get_last_lr()[0] == pytest.approx(1e-4 * lam(applied), rel=1e-6, abs=1e-15)
+
+
+def test_trainer_warns_that_a_foreign_scheduler_cannot_be_rewound(emu, monkeypatch, tmp_path):
+    monkeypatch.setenv("SCOT_SIDE_STREAM", "0")
+    f, meta = load_fixture("tiny_trained")
+    cfg = ScOTConfig(**meta["cfg"])
+    tr, opt, _ = _fp16_trainer(cfg, meta, tmp_path, 19, sched=lambda o: torch.optim.lr_scheduler.StepLR(o, step_size=1, gamma=0.5), steps=2)
+    with pytest.warns(UserWarning) as rec:
+        tr.train()
+    msgs = [str(w.message) for w in rec]
+    assert opt.skipped_steps() == 2 and tr.state["skipped_steps"] == 2
+    assert sum("StepLR cannot be rewound: the LR schedule is 1 step(s) ahead of the applied optimizer steps" in m for m in msgs) == 2, msgs
+    assert tr.lr_scheduler.last_epoch == 2 and opt.applied_steps() == 0       # its state is its own: it ran ahead
