@@ -1,14 +1,21 @@
-/* scot_plan.h — running a trained ScOT model from C: exported inference plans (ABI 8).
+/* scot_plan.h — running a trained ScOT model from C: exported inference plans and their adjoints (ABI 8).
  *
  * scot_hip.h is the kernel-level boundary: about a hundred entry points that a host program has to order itself.  This header is the
  * model-level one.  `ScOT.export_plan` (poseidon_amd/plan.py) records one inference forward for one input signature and writes it,
- * with the weights, as a relocatable plan image; the five calls below load such a file and run it.  A host needs nothing but the
+ * with the weights, as a relocatable plan image; the calls below load such a file and run it.  A host needs nothing but the
  * shared library and the HIP runtime: no Python, no torch.  The prediction is bit-identical to `model(...)` in Python.
  *
  * What a plan covers: the engine's inference forward at config.image_size on ONE stream — no training, no spectral resize, no hidden
  * states or attention outputs, no labels (so no pixel_mask: the mask overwrites the prediction with label values).  The weights are a
  * snapshot taken at export.  A plan recorded by the binary16 build (libscot_hip_f16.so) loads into that build only; its split-MFMA
  * trunk products run in the bfloat16 build, which the runtime opens from the same directory (or from where the peer call points).
+ *
+ * An ADJOINT plan (`export_plan(..., adjoint=("pixel_values", "time"))`, image format 2) also covers the frozen model's backward from
+ * a cotangent of the prediction to the gradients of these two inputs — what `torch.autograd.grad(output, (pixel_values, time),
+ * grad_outputs=g)` returns with every parameter frozen, bit for bit: no labels, no loss, no parameter gradient, no training.  Its
+ * forward is the one a differentiable call runs, so beyond an inference plan it holds the saved activations of one forward, the
+ * transposed 16-bit weight copy the data gradients read, and room in the gradient arena where a fused layer tail leaves by-products
+ * nobody reads.  One vjp per run (the backward reuses saved rows); a rollout leaves nothing to differentiate.
  *
  * Status codes as in scot_hip.h: 0, -1 (malformed image / bad argument), -3 (not for this library: ABI, operand format, entry point;
  * or a host other than x86-64 System V, where the replay underneath does not exist), -4 (allocation, copy or launch failed).
@@ -57,6 +64,26 @@ int scot_plan_peer_library(const char* path);
 /* Test aid: every scratch buffer and the prediction's own buffer <- byte on `stream`.  With 0xff a run that reads what it did not
  * write first yields NaN. */
 int scot_plan_poison(scot_plan_t plan, int byte, scot_stream_t stream);
+
+/* ---- adjoint plans ---- */
+/* out[8]: has adjoint, d_pixel_values available, d_time available, recorded backward calls, bytes kept between run and vjp,
+ * default gradient scale (export-time value, as an integer power-of-two exponent), 0, 0.  Format-1 plan: all zeros, status 0. */
+int scot_plan_describe_adjoint(scot_plan_t plan, long long* out);
+/* (d_pixel_values [B, Cin, H, W], d_time [B]) <- J^T d_prediction at the inputs of the LAST scot_plan_run of this plan.  fp32 device
+ * buffers of the caller; an output pointer may be NULL (not copied out); asking for one the plan was not exported with: -1.
+ * grad_scale: power of two the 16-bit backward runs under (fp16 plans), 0 = the export-time value; must be 0 or 1 for plans whose
+ * backward runs unscaled (fp32, bf16, bf16x3).  Needs a completed scot_plan_run since load / poison / rollout / the previous vjp:
+ * otherwise -1 and nothing is launched.  On a plan without an adjoint (format 1): -3.  Copies the cotangent in, writes {S, 1/S} into the
+ * plan's scale state on `stream`, replays the recorded backward, copies the gradients out; asynchronous on `stream`. */
+int scot_plan_vjp(scot_plan_t plan, const float* d_prediction, float* d_pixel_values, float* d_time, float grad_scale,
+                  scot_stream_t stream);
+/* out[2]: non-finite values the un-scale passes have counted since load (a gradient that overflowed binary16 under the scale arrives
+ * as inf / NaN and is counted here, never clipped: run + vjp again under a smaller grad_scale), the scale of the last vjp as an
+ * exponent.  Waits for `stream`. */
+int scot_plan_grad_status(scot_plan_t plan, long long* out, scot_stream_t stream);
+/* Name i of the entry points the BACKWARD of an adjoint plan may call (NULL past the end): the data-gradient chain only — no
+ * weight-gradient kernel and no optimizer step is in either list. */
+const char* scot_plan_adjoint_entry_point(int i);
 
 #ifdef __cplusplus
 }

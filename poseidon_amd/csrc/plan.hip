@@ -7,11 +7,17 @@
 // copies the caller's inputs in, writes the caller's stream into the program's stream slots, replays, and copies the prediction out.
 // Nothing here launches a kernel of its own: the copies are device-to-device copies, the arithmetic is the recorded entry points'.
 //
+// An ADJOINT plan (image format 2) also holds the recorded frozen-model backward: scot_plan_run replays the differentiable forward,
+// which leaves its saved activations in the plan's buffers, and scot_plan_vjp copies a cotangent of the prediction in, writes the
+// gradient scale {S, 1/S} into the plan's state buffer on the stream, replays the backward list and copies the input gradients out.
+// One vjp per run: the backward reuses saved rows.
+//
 // A plan is one stream's worth of state: its buffers are reused by every run, so runs of ONE plan must be ordered (same stream, or
 // the caller's own events); two plans are independent.
 #include "common.h"
 #include "plan_image.h"
 #include <dlfcn.h>
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <new>
@@ -27,16 +33,22 @@ extern "C" int scot_operand_format();
 SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_DECLARE)
 #define SCOT_PLAN_ADDRESS(n) (void*)&n,
 static void* const g_entry_address[] = {SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_ADDRESS)};
+SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_DECLARE)
+static void* const g_adjoint_entry_address[] = {SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_ADDRESS)};
 
 // ------------------------------------------------------------------ device memory and copies (plain host memory in the CPU emulation)
 namespace {
 enum CopyKind { H2D, D2H, D2D };
 #ifdef SCOT_HIPEMU
+// the emulated build's launch log: everything the plan runtime has put on a stream — copies, fills and replayed calls — is counted,
+// so that a test can see that a refused call issued nothing (scot_plan_emu_issued below; not part of the C ABI)
+long long g_emu_issued = 0;
 inline void* dev_alloc(size_t n) { return malloc(n); }
 inline void dev_free(void* p) { free(p); }
-inline bool dev_copy(void* dst, const void* src, size_t n, CopyKind, hipStream_t) { memmove(dst, src, n); return true; }
-inline bool dev_fill(void* dst, int byte, size_t n, hipStream_t) { memset(dst, byte, n); return true; }
+inline bool dev_copy(void* dst, const void* src, size_t n, CopyKind, hipStream_t) { ++g_emu_issued; memmove(dst, src, n); return true; }
+inline bool dev_fill(void* dst, int byte, size_t n, hipStream_t) { ++g_emu_issued; memset(dst, byte, n); return true; }
 inline bool dev_copy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipStream_t) {
+  ++g_emu_issued;
   for (size_t r = 0; r < height; ++r) memmove((char*)dst + r * dpitch, (const char*)src + r * spitch, width);
   return true;
 }
@@ -69,12 +81,18 @@ struct Plan {
   std::vector<uint64_t> buf_kind, buf_bytes;
   std::vector<uint64_t> prog;                      // scot_tape_replay's word format, final addresses
   std::vector<size_t> stream_slot;                 // words of prog that hold the stream
+  std::vector<uint64_t> prog_bwd;                  // adjoint plans: the backward list, same format
+  std::vector<size_t> stream_slot_bwd;
   std::vector<std::vector<uint64_t>> ptr_arrays;   // host arrays the entries pass by address
   std::vector<std::vector<int>> int_arrays;
   std::vector<float> host_time;                    // scot_plan_rollout: the divided time on its way back to the device
   uint64_t io[SCOT_PLAN_IO_WORDS] = {};
-  uint64_t n_entries = 0;
-  int operand_format = 0, compute = 0;
+  uint64_t adj[SCOT_PLAN_ADJ_WORDS] = {};
+  uint64_t n_entries = 0, n_backward = 0;
+  int operand_format = 0, compute = 0, format = SCOT_PLAN_FORMAT;
+  bool ran = false;                                // a completed scot_plan_run whose saved activations no vjp / poison / rollout has used up
+  float host_scale[4] = {1.0f, 1.0f, 0.0f, 0.0f};  // {S, 1/S, 0, 0} on its way to the state buffer
+  int last_exponent = 0;                           // log2 S of the last vjp
 };
 
 inline Plan* as_plan(void* p) {
@@ -107,10 +125,12 @@ void* default_peer() {
   return open_peer((dir + "/libscot_hip.so").c_str());
 }
 
-void* resolve(int name_index, uint64_t lib) {
-  if (lib == 0 || scot_operand_format() == 0) return g_entry_address[name_index];
+void* resolve(const char* name, uint64_t lib, bool backward) {
+  const int index = backward ? scot_plan_adjoint_entry_index(name) : scot_plan_entry_index(name);
+  if (index < 0) return nullptr;
+  if (lib == 0 || scot_operand_format() == 0) return backward ? g_adjoint_entry_address[index] : g_entry_address[index];
   if (!g_peer) g_peer = default_peer();
-  return g_peer ? dlsym(g_peer, scot_plan_entry_names[name_index]) : nullptr;
+  return g_peer ? dlsym(g_peer, name) : nullptr;
 }
 
 // one argument pair -> the word the call receives; `slot` = stream placeholder (patched per run)
@@ -125,16 +145,68 @@ bool materialise(Plan* pl, uint64_t tagw, uint64_t val, uint64_t* out, bool* is_
   }
 }
 
-int replay(Plan* pl, hipStream_t stream) {
-  for (size_t s : pl->stream_slot) pl->prog[s] = (uint64_t)(uintptr_t)stream;
+int replay(Plan* pl, hipStream_t stream, bool backward = false) {
+  std::vector<uint64_t>& prog = backward ? pl->prog_bwd : pl->prog;
+  for (size_t s : backward ? pl->stream_slot_bwd : pl->stream_slot) prog[s] = (uint64_t)(uintptr_t)stream;
+#ifdef SCOT_HIPEMU
+  g_emu_issued += (long long)(backward ? pl->n_backward : pl->n_entries);
+#endif
   int fail = -1;
-  return scot_tape_replay(pl->prog.data(), pl->prog.size(), &fail);
+  return scot_tape_replay(prog.data(), prog.size(), &fail);
 }
+
+// one entries section -> the entry points' addresses (false: one is missing)
+bool resolve_section(const scot_plan_view& v, const uint64_t* e, uint64_t n, bool backward, std::vector<void*>* fn) {
+  fn->resize(n);
+  uint64_t w = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t name = e[w], lib = e[w + 1], ni = e[w + 2], nf = e[w + 3];
+    (*fn)[i] = resolve((const char*)(v.names + name * SCOT_PLAN_NAME_BYTES), lib, backward);
+    if (!(*fn)[i]) return false;
+    w += 4 + 2 * ni + nf;
+  }
+  return true;
+}
+
+// one entries section -> scot_tape_replay's program with the final addresses
+bool build_program(Plan* pl, const uint64_t* e, uint64_t n, uint64_t words, const std::vector<void*>& fn,
+                   const std::vector<uint64_t>& array_address, std::vector<uint64_t>* prog, std::vector<size_t>* slots) {
+  prog->reserve((size_t)(words + n));
+  uint64_t w = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t ni = e[w + 2], nf = e[w + 3];
+    prog->push_back((uint64_t)(uintptr_t)fn[i]);
+    prog->push_back(ni);
+    prog->push_back(nf);
+    for (uint64_t k = 0; k < ni; ++k) {
+      const uint64_t tagw = e[w + 4 + 2 * k], val = e[w + 5 + 2 * k];
+      uint64_t word = 0;
+      bool st = false;
+      if ((tagw & 0xff) == SCOT_PLAN_ARG_ARRAY)
+        word = array_address[val];
+      else if (!materialise(pl, tagw, val, &word, &st))
+        return false;
+      if (st) slots->push_back(prog->size());
+      prog->push_back(word);
+    }
+    for (uint64_t k = 0; k < nf; ++k) prog->push_back(e[w + 4 + 2 * ni + k]);
+    w += 4 + 2 * ni + nf;
+  }
+  return true;
+}
+
+char* adj_ptr(Plan* pl, int span) { return pl->buf[pl->adj[span]] + pl->adj[span + 1]; }
 
 char* io_ptr(Plan* pl, int buf_word, int off_word) { return pl->buf[pl->io[buf_word]] + pl->io[off_word]; }
 }  // namespace
 
 extern "C" const char* scot_plan_entry_point(int i) { return i >= 0 && i < SCOT_PLAN_N_ENTRY_POINTS ? scot_plan_entry_names[i] : nullptr; }
+extern "C" const char* scot_plan_adjoint_entry_point(int i) {
+  return i >= 0 && i < SCOT_PLAN_N_ADJOINT_ENTRY_POINTS ? scot_plan_adjoint_entry_names[i] : nullptr;
+}
+#ifdef SCOT_HIPEMU
+extern "C" long long scot_plan_emu_issued() { return g_emu_issued; }
+#endif
 
 extern "C" int scot_plan_peer_library(const char* path) {
   if (!path) return SCOT_ERR_SHAPE;
@@ -169,17 +241,16 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
   try {
     memcpy(pl->io, v.io, sizeof(pl->io));
     pl->n_entries = v.n_entries;
+    pl->format = (int)v.format;
+    pl->n_backward = v.n_backward;
+    if (v.adj) memcpy(pl->adj, v.adj, sizeof(pl->adj));
     pl->operand_format = (int)v.h[SCOT_PLAN_H_OPERAND];
     pl->compute = (int)v.h[SCOT_PLAN_H_COMPUTE];
     // every entry point, before anything is allocated
-    std::vector<void*> fn(v.n_entries);
+    std::vector<void*> fn, fn_bwd;
     uint64_t w = 0;
-    for (uint64_t i = 0; i < v.n_entries && status == SCOT_OK; ++i) {
-      const uint64_t name = v.entries[w], lib = v.entries[w + 1], ni = v.entries[w + 2], nf = v.entries[w + 3];
-      fn[i] = resolve(scot_plan_entry_index((const char*)(v.names + name * SCOT_PLAN_NAME_BYTES)), lib);
-      if (!fn[i]) status = SCOT_ERR_UNSUPPORTED;
-      w += 4 + 2 * ni + nf;
-    }
+    if (!resolve_section(v, v.entries, v.n_entries, false, &fn) || !resolve_section(v, v.backward, v.n_backward, true, &fn_bwd))
+      status = SCOT_ERR_UNSUPPORTED;
     // one slab, every buffer on a 256-byte boundary
     std::vector<size_t> off(v.n_buffers);
     size_t total = 0;
@@ -230,30 +301,11 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
         w += 2 + 2 * cnt;
       }
     }
-    // the program
-    if (status == SCOT_OK) {
-      pl->prog.reserve((size_t)(v.entries_words + v.n_entries));
-      w = 0;
-      for (uint64_t i = 0; i < v.n_entries && status == SCOT_OK; ++i) {
-        const uint64_t ni = v.entries[w + 2], nf = v.entries[w + 3];
-        pl->prog.push_back((uint64_t)(uintptr_t)fn[i]);
-        pl->prog.push_back(ni);
-        pl->prog.push_back(nf);
-        for (uint64_t k = 0; k < ni; ++k) {
-          const uint64_t tagw = v.entries[w + 4 + 2 * k], val = v.entries[w + 5 + 2 * k];
-          uint64_t word = 0;
-          bool st = false;
-          if ((tagw & 0xff) == SCOT_PLAN_ARG_ARRAY)
-            word = array_address[val];
-          else if (!materialise(pl, tagw, val, &word, &st))
-            status = SCOT_ERR_SHAPE;
-          if (st) pl->stream_slot.push_back(pl->prog.size());
-          pl->prog.push_back(word);
-        }
-        for (uint64_t k = 0; k < nf; ++k) pl->prog.push_back(v.entries[w + 4 + 2 * ni + k]);
-        w += 4 + 2 * ni + nf;
-      }
-    }
+    // the program(s)
+    if (status == SCOT_OK &&
+        (!build_program(pl, v.entries, v.n_entries, v.entries_words, fn, array_address, &pl->prog, &pl->stream_slot) ||
+         !build_program(pl, v.backward, v.n_backward, v.backward_words, fn_bwd, array_address, &pl->prog_bwd, &pl->stream_slot_bwd)))
+      status = SCOT_ERR_SHAPE;
     // the image may be released when this returns: the uploads read it
     if (status == SCOT_OK && !dev_sync(stream)) status = SCOT_ERR_LAUNCH;
   } catch (const std::bad_alloc&) {
@@ -281,7 +333,7 @@ extern "C" int scot_plan_describe(void* plan, long long* out) {
                            (long long)(io[SCOT_PLAN_IO_HAS_TIME] ? io[SCOT_PLAN_IO_TIME_BYTES] : 0), (long long)io[SCOT_PLAN_IO_HAS_MASK],
                            (long long)(io[SCOT_PLAN_IO_HAS_MASK] ? io[SCOT_PLAN_IO_MASK_BYTES] : 0), pl->operand_format, pl->compute,
                            (long long)pl->slab_bytes, (long long)pl->n_entries, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
-                           (long long)(hw * io[SCOT_PLAN_IO_COUT]), SCOT_PLAN_FORMAT};
+                           (long long)(hw * io[SCOT_PLAN_IO_COUT]), pl->format};
   memcpy(out, d, sizeof(d));
   return SCOT_OK;
 }
@@ -290,6 +342,7 @@ extern "C" int scot_plan_describe(void* plan, long long* out) {
 extern "C" int scot_plan_poison(void* plan, int byte, hipStream_t stream) {
   Plan* pl = as_plan(plan);
   if (!pl) return SCOT_ERR_SHAPE;
+  pl->ran = false;      // (the saved activations are scratch)
   for (size_t i = 0; i < pl->buf.size(); ++i)
     if (pl->buf_kind[i] == SCOT_PLAN_BUF_SCRATCH || pl->buf_kind[i] == SCOT_PLAN_BUF_OUTPUT)
       if (!dev_fill(pl->buf[i], byte, (size_t)((pl->buf_bytes[i] + SLAB_ALIGN - 1) / SLAB_ALIGN * SLAB_ALIGN), stream)) return SCOT_ERR_LAUNCH;
@@ -309,6 +362,7 @@ extern "C" int scot_plan_run(void* plan, const float* pixel_values, const float*
   if (!pl) return SCOT_ERR_SHAPE;
   int rc = check_inputs(pl, pixel_values, time, pixel_mask, prediction);
   if (rc != SCOT_OK) return rc;
+  pl->ran = false;
   const uint64_t* io = pl->io;
   const size_t plane = (size_t)(io[SCOT_PLAN_IO_B] * io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * 4);
   if (!dev_copy(io_ptr(pl, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF), pixel_values, plane * io[SCOT_PLAN_IO_CIN], D2D, stream)) return SCOT_ERR_LAUNCH;
@@ -318,8 +372,75 @@ extern "C" int scot_plan_run(void* plan, const float* pixel_values, const float*
     return SCOT_ERR_LAUNCH;
   rc = replay(pl, stream);
   if (rc != SCOT_OK) return rc;
-  return dev_copy(prediction, io_ptr(pl, SCOT_PLAN_IO_OUT_BUF, SCOT_PLAN_IO_OUT_OFF), plane * io[SCOT_PLAN_IO_COUT], D2D, stream) ? SCOT_OK
-                                                                                                                                  : SCOT_ERR_LAUNCH;
+  if (!dev_copy(prediction, io_ptr(pl, SCOT_PLAN_IO_OUT_BUF, SCOT_PLAN_IO_OUT_OFF), plane * io[SCOT_PLAN_IO_COUT], D2D, stream)) return SCOT_ERR_LAUNCH;
+  pl->ran = pl->n_backward != 0;
+  return SCOT_OK;
+}
+
+// out[8]: has adjoint, d_pixel_values available, d_time available, recorded backward calls, bytes kept between run and vjp, default
+// gradient scale (export-time value, as an integer power-of-two exponent), 0, 0.  Format-1 plan: all zeros, status 0.
+extern "C" int scot_plan_describe_adjoint(void* plan, long long* out) {
+  Plan* pl = as_plan(plan);
+  if (!pl || !out) return SCOT_ERR_SHAPE;
+  memset(out, 0, 8 * sizeof(long long));
+  if (pl->format != SCOT_PLAN_FORMAT_ADJOINT) return SCOT_OK;
+  out[0] = 1;
+  out[1] = (long long)(pl->adj[SCOT_PLAN_ADJ_FLAGS] & 1);
+  out[2] = (long long)((pl->adj[SCOT_PLAN_ADJ_FLAGS] >> 1) & 1);
+  out[3] = (long long)pl->n_backward;
+  out[4] = (long long)pl->adj[SCOT_PLAN_ADJ_KEPT_BYTES];
+  out[5] = (long long)(int64_t)pl->adj[SCOT_PLAN_ADJ_SCALE_EXP];
+  return SCOT_OK;
+}
+
+// (d_pixel_values, d_time) <- J^T d_prediction at the inputs of the last scot_plan_run (include/scot_plan.h).  Every refusal comes before
+// the first copy: a refused call launches nothing and leaves the state as it was.
+extern "C" int scot_plan_vjp(void* plan, const float* d_prediction, float* d_pixel_values, float* d_time, float grad_scale, hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  if (pl->format != SCOT_PLAN_FORMAT_ADJOINT) return SCOT_ERR_UNSUPPORTED;
+  const uint64_t* a = pl->adj;
+  if (!d_prediction) return SCOT_ERR_SHAPE;
+  if ((d_pixel_values && !(a[SCOT_PLAN_ADJ_FLAGS] & 1)) || (d_time && !(a[SCOT_PLAN_ADJ_FLAGS] & 2))) return SCOT_ERR_SHAPE;
+  const bool scaled = a[SCOT_PLAN_ADJ_STATE + 2] != 0;
+  int exponent = (int)(int64_t)a[SCOT_PLAN_ADJ_SCALE_EXP];
+  if (grad_scale != 0.0f) {
+    int e = 0;
+    if (!(grad_scale > 0.0f) || !__builtin_isfinite(grad_scale) || frexpf(grad_scale, &e) != 0.5f) return SCOT_ERR_SHAPE;      // a power of two
+    if (!scaled && grad_scale != 1.0f) return SCOT_ERR_SHAPE;      // (fp32 / bf16 / bf16x3: the backward runs unscaled)
+    if (e - 1 < -120 || e - 1 > 120) return SCOT_ERR_SHAPE;        // (1 / S has to be a normal float too)
+    exponent = e - 1;
+  }
+  if (!pl->ran) return SCOT_ERR_SHAPE;
+  pl->ran = false;      // one vjp per run: the backward reuses saved rows
+  if (!dev_copy(adj_ptr(pl, SCOT_PLAN_ADJ_COT), d_prediction, (size_t)a[SCOT_PLAN_ADJ_COT + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
+  if (scaled) {
+    pl->host_scale[0] = ldexpf(1.0f, exponent);
+    pl->host_scale[1] = ldexpf(1.0f, -exponent);
+    pl->host_scale[2] = pl->host_scale[3] = 0.0f;
+    // (host_scale is pageable memory: the runtime has staged it by the time the copy call returned)
+    if (!dev_copy(adj_ptr(pl, SCOT_PLAN_ADJ_STATE), pl->host_scale, sizeof(pl->host_scale), H2D, stream)) return SCOT_ERR_LAUNCH;
+  }
+  pl->last_exponent = exponent;
+  const int rc = replay(pl, stream, true);
+  if (rc != SCOT_OK) return rc;
+  if (d_pixel_values && !dev_copy(d_pixel_values, adj_ptr(pl, SCOT_PLAN_ADJ_DPV), (size_t)a[SCOT_PLAN_ADJ_DPV + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
+  if (d_time && !dev_copy(d_time, adj_ptr(pl, SCOT_PLAN_ADJ_DTIME), (size_t)a[SCOT_PLAN_ADJ_DTIME + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
+  return SCOT_OK;
+}
+
+// out[2]: non-finite values the un-scale passes have counted since load, the scale of the last vjp as an exponent.  Waits for `stream`.
+extern "C" int scot_plan_grad_status(void* plan, long long* out, hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl || !out) return SCOT_ERR_SHAPE;
+  out[0] = out[1] = 0;
+  if (pl->format != SCOT_PLAN_FORMAT_ADJOINT) return SCOT_ERR_UNSUPPORTED;
+  int count = 0;
+  if (pl->adj[SCOT_PLAN_ADJ_STATE + 2] && !dev_copy(&count, adj_ptr(pl, SCOT_PLAN_ADJ_COUNTER), sizeof(count), D2H, stream)) return SCOT_ERR_LAUNCH;
+  if (!dev_sync(stream)) return SCOT_ERR_LAUNCH;      // (also without a counter: the caller's gradients are complete on return)
+  out[0] = count;
+  out[1] = pl->last_exponent;
+  return SCOT_OK;
 }
 
 // The integer form of the autoregressive rollout (reference trainer.py:452-603 with output_all_steps): time / steps once, then `steps`
@@ -335,6 +456,7 @@ extern "C" int scot_plan_rollout(void* plan, const float* pixel_values, const fl
   const uint64_t* io = pl->io;
   if (steps < 1 || io[SCOT_PLAN_IO_COUT] > io[SCOT_PLAN_IO_CIN]) return SCOT_ERR_SHAPE;
   if (!io[SCOT_PLAN_IO_HAS_TIME]) return SCOT_ERR_UNSUPPORTED;      // (without conditioning the reference's rollout is one forward)
+  pl->ran = false;      // (a rollout leaves nothing to differentiate: its forwards overwrite each other's saved rows)
   const size_t B = (size_t)io[SCOT_PLAN_IO_B], hw = (size_t)(io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * 4);
   const size_t in_row = hw * io[SCOT_PLAN_IO_CIN], out_row = hw * io[SCOT_PLAN_IO_COUT];
   char* in = io_ptr(pl, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF);

@@ -1,4 +1,4 @@
-// plan_image — the format of an exported inference plan and its validator.  Header-only and HIP-free: plan.hip uses it inside the
+// plan_image — the format of an exported plan (inference, or inference + adjoint) and its validator.  Header-only and HIP-free: plan.hip uses it inside the
 // library, tools/plan_image_check.cc compiles it alone (with the host sanitizers) and runs it over good and corrupt images.
 //
 // A plan image (poseidon_amd/plan.py writes it) is ONE recorded inference forward of the engine for one input signature, made
@@ -16,6 +16,17 @@
 //
 // An argument pair is {tag | buffer << 8, value}: SCOT_PLAN_ARG_INT (value as is), _NULL, _PTR (buffer index, byte offset), _STREAM
 // (the caller's stream at run time) or _ARRAY (value = index into `arrays`).
+//
+// Format 2 (an ADJOINT plan, `export_plan(..., adjoint=...)`) is format 1 plus, named by header words format 1 leaves zero:
+//
+//   backward a second entries section, same record layout: the recorded vjp (cotangent of the prediction -> input gradients).  Its
+//            calls are checked against a list of their own, SCOT_PLAN_ADJOINT_ENTRY_POINTS: the data-gradient chain only
+//   adjoint  SCOT_PLAN_ADJ_WORDS words: which gradients exist, the (buffer, offset, bytes) of the cotangent's copy, of d_pixel_values,
+//            of d_time, of the 16-byte gradient-scale state {S, 1/S, -, -} and of the non-finite counter of the un-scale passes, the
+//            export-time scale as a power-of-two exponent, the bytes a run leaves for the vjp
+//   buffers  may have kind SCOT_PLAN_BUF_STATE: device memory the RUNTIME writes (zeroed at load, never poisoned)
+//
+// The `entries` section of a format-2 image is the DIFFERENTIABLE forward (it saves what the backward reads).
 #ifndef SCOT_PLAN_IMAGE_H
 #define SCOT_PLAN_IMAGE_H
 #include <stddef.h>
@@ -24,35 +35,58 @@
 
 #define SCOT_PLAN_MAGIC 0x4e414c50544f4353ull /* "SCOTPLAN" */
 #define SCOT_PLAN_FORMAT 1
+#define SCOT_PLAN_FORMAT_ADJOINT 2
 #define SCOT_PLAN_HEADER_WORDS 32
 #define SCOT_PLAN_NAME_BYTES 48
 #define SCOT_PLAN_IO_WORDS 24
+#define SCOT_PLAN_ADJ_WORDS 24
 #define SCOT_PLAN_MAX_INT 48 /* = SCOT_TAPE_MAX_INT of host_tape.hip: what one replayed call can carry */
 #define SCOT_PLAN_MAX_FLT 8
 
 enum { SCOT_PLAN_H_MAGIC, SCOT_PLAN_H_FORMAT, SCOT_PLAN_H_ABI, SCOT_PLAN_H_OPERAND, SCOT_PLAN_H_COMPUTE, SCOT_PLAN_H_BYTES,
        SCOT_PLAN_H_NNAMES, SCOT_PLAN_H_NAMES_OFF, SCOT_PLAN_H_NBUFFERS, SCOT_PLAN_H_BUFFERS_OFF, SCOT_PLAN_H_NENTRIES,
        SCOT_PLAN_H_ENTRIES_OFF, SCOT_PLAN_H_ENTRIES_WORDS, SCOT_PLAN_H_NARRAYS, SCOT_PLAN_H_ARRAYS_OFF, SCOT_PLAN_H_ARRAYS_WORDS,
-       SCOT_PLAN_H_IO_OFF, SCOT_PLAN_H_DATA_OFF, SCOT_PLAN_H_DATA_BYTES };
-enum { SCOT_PLAN_BUF_CONSTANT, SCOT_PLAN_BUF_INPUT, SCOT_PLAN_BUF_OUTPUT, SCOT_PLAN_BUF_SCRATCH };
+       SCOT_PLAN_H_IO_OFF, SCOT_PLAN_H_DATA_OFF, SCOT_PLAN_H_DATA_BYTES,
+       /* format 2 */ SCOT_PLAN_H_NBACKWARD, SCOT_PLAN_H_BACKWARD_OFF, SCOT_PLAN_H_BACKWARD_WORDS, SCOT_PLAN_H_ADJ_OFF };
+enum { SCOT_PLAN_BUF_CONSTANT, SCOT_PLAN_BUF_INPUT, SCOT_PLAN_BUF_OUTPUT, SCOT_PLAN_BUF_SCRATCH, SCOT_PLAN_BUF_STATE };
 enum { SCOT_PLAN_ARG_INT, SCOT_PLAN_ARG_NULL, SCOT_PLAN_ARG_PTR, SCOT_PLAN_ARG_STREAM, SCOT_PLAN_ARG_ARRAY };
 enum { SCOT_PLAN_IO_B, SCOT_PLAN_IO_CIN, SCOT_PLAN_IO_H, SCOT_PLAN_IO_W, SCOT_PLAN_IO_COUT, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF,
        SCOT_PLAN_IO_HAS_TIME, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF, SCOT_PLAN_IO_TIME_BYTES, SCOT_PLAN_IO_HAS_MASK,
        SCOT_PLAN_IO_MASK_BUF, SCOT_PLAN_IO_MASK_OFF, SCOT_PLAN_IO_MASK_BYTES, SCOT_PLAN_IO_OUT_BUF, SCOT_PLAN_IO_OUT_OFF };
+/* the adjoint section: FLAGS bit 0 = d_pixel_values, bit 1 = d_time; a span is (buffer, offset, bytes), bytes 0 = absent */
+enum { SCOT_PLAN_ADJ_FLAGS, SCOT_PLAN_ADJ_COT, SCOT_PLAN_ADJ_DPV = SCOT_PLAN_ADJ_COT + 3, SCOT_PLAN_ADJ_DTIME = SCOT_PLAN_ADJ_DPV + 3,
+       SCOT_PLAN_ADJ_STATE = SCOT_PLAN_ADJ_DTIME + 3, SCOT_PLAN_ADJ_COUNTER = SCOT_PLAN_ADJ_STATE + 3,
+       SCOT_PLAN_ADJ_SCALE_EXP = SCOT_PLAN_ADJ_COUNTER + 3, SCOT_PLAN_ADJ_KEPT_BYTES };
 
-// What an inference forward may call: what can run is what is listed.  (X-macro: plan.hip builds the table of addresses from it.)
+// What a forward may call: what can run is what is listed.  (X-macro: plan.hip builds the table of addresses from it.)
 #define SCOT_PLAN_ENTRY_POINTS(X)                                                                                                     \
   X(scot_gemm) X(scot_cpb_fwd_batched) X(scot_cln_fwd) X(scot_window_attn_fwd) X(scot_mlp_block_fwd) X(scot_block_tail_fwd)          \
   X(scot_proj_cln_fwd) X(scot_add) X(scot_copy2d) X(scot_space_to_depth) X(scot_depth_to_space) X(scot_patchify) X(scot_unpatchify) \
   X(scot_scale_residual) X(scot_dwconv7) X(scot_conv5) X(scot_head_finalize) X(scot_memset_async) X(scot_memcpy_async)
 
+// What the backward section of an adjoint plan may call: the data-gradient chain of the frozen model and nothing else — no
+// weight-gradient kernel, no column sum into a parameter gradient, no optimizer step is listed in either table.
+#define SCOT_PLAN_ADJOINT_ENTRY_POINTS(X)                                                                                            \
+  X(scot_gemm) X(scot_cln_bwd) X(scot_cln_dtime) X(scot_window_attn_bwd_rep) X(scot_block_tail_bwd) X(scot_proj_cln_bwd) X(scot_add)  \
+  X(scot_add_channels) X(scot_copy2d) X(scot_space_to_depth) X(scot_depth_to_space) X(scot_patchify) X(scot_unpatchify)              \
+  X(scot_scale_residual) X(scot_dwconv7) X(scot_conv5) X(scot_scale_inplace_dev) X(scot_pow2_rescale) X(scot_colscale_dev)           \
+  X(scot_axpy_dev) X(scot_memset_async) X(scot_memcpy_async)
+
 #define SCOT_PLAN_NAME_STRING(n) #n,
 static const char* const scot_plan_entry_names[] = {SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_NAME_STRING)};
 #define SCOT_PLAN_N_ENTRY_POINTS ((int)(sizeof(scot_plan_entry_names) / sizeof(scot_plan_entry_names[0])))
+static const char* const scot_plan_adjoint_entry_names[] = {SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_NAME_STRING)};
+#define SCOT_PLAN_N_ADJOINT_ENTRY_POINTS ((int)(sizeof(scot_plan_adjoint_entry_names) / sizeof(scot_plan_adjoint_entry_names[0])))
 
 static inline int scot_plan_entry_index(const char* name) {
   for (int i = 0; i < SCOT_PLAN_N_ENTRY_POINTS; ++i)
     if (strcmp(name, scot_plan_entry_names[i]) == 0) return i;
+  return -1;
+}
+
+static inline int scot_plan_adjoint_entry_index(const char* name) {
+  for (int i = 0; i < SCOT_PLAN_N_ADJOINT_ENTRY_POINTS; ++i)
+    if (strcmp(name, scot_plan_adjoint_entry_names[i]) == 0) return i;
   return -1;
 }
 
@@ -72,6 +106,10 @@ typedef struct {
   const uint64_t* io;
   const uint8_t* data;
   uint64_t n_names, n_buffers, n_entries, entries_words, n_arrays, arrays_words, data_bytes;
+  /* format 2 (zero / NULL otherwise) */
+  uint64_t format, n_backward, backward_words;
+  const uint64_t* backward;
+  const uint64_t* adj;
 } scot_plan_view;
 
 static inline uint64_t scot_plan_word(const uint8_t* p) {
@@ -103,6 +141,32 @@ static inline int scot_plan_arg_ok(const scot_plan_view* v, uint64_t tagw, uint6
   }
 }
 
+// one entries section: record bounds, n_int / n_flt, every argument pair, every name in the section's OWN list
+static inline int scot_plan_entries_ok(const scot_plan_view* v, const uint64_t* e, uint64_t n, uint64_t words, int backward) {
+  uint64_t w = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (words - w < 4) return SCOT_PLAN_ERR_SHAPE;
+    const uint64_t name = e[w], lib = e[w + 1], ni = e[w + 2], nf = e[w + 3];
+    if (name >= v->n_names || lib > 1 || ni > SCOT_PLAN_MAX_INT || nf > SCOT_PLAN_MAX_FLT) return SCOT_PLAN_ERR_SHAPE;
+    if (2 * ni + nf > words - w - 4) return SCOT_PLAN_ERR_SHAPE;
+    for (uint64_t k = 0; k < ni; ++k)
+      if (!scot_plan_arg_ok(v, e[w + 4 + 2 * k], e[w + 5 + 2 * k], 0)) return SCOT_PLAN_ERR_SHAPE;
+    for (uint64_t k = 0; k < nf; ++k)
+      if (e[w + 4 + 2 * ni + k] >> 32) return SCOT_PLAN_ERR_SHAPE;      /* raw bits of ONE float */
+    const char* nm = (const char*)(v->names + name * SCOT_PLAN_NAME_BYTES);
+    if ((backward ? scot_plan_adjoint_entry_index(nm) : scot_plan_entry_index(nm)) < 0) return SCOT_PLAN_ERR_UNSUPPORTED;
+    w += 4 + 2 * ni + nf;
+  }
+  return w == words ? SCOT_PLAN_OK : SCOT_PLAN_ERR_SHAPE;
+}
+
+// a (buffer, offset, bytes) span of the io / adjoint words: whole inside a buffer of kind `kind`
+static inline int scot_plan_io_span_ok(const scot_plan_view* v, uint64_t buf, uint64_t off, uint64_t n, uint64_t kind) {
+  if (buf >= v->n_buffers || n == 0) return 0;
+  const uint64_t cap = v->buffers[4 * buf + 1];
+  return off <= cap && n <= cap - off && v->buffers[4 * buf] == kind;
+}
+
 // Validates the whole image before anything is allocated: section bounds, counts, every relocation inside its buffer, every name in
 // the table above, and a format version, ABI and operand format equal to the caller's (the library's own).  Fills *v with pointers INTO
 // the image.  `image` must be 8-byte aligned.
@@ -112,7 +176,8 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
   const uint8_t* b = (const uint8_t*)image;
   const uint64_t* h = (const uint64_t*)image;
   if (h[SCOT_PLAN_H_MAGIC] != SCOT_PLAN_MAGIC) return SCOT_PLAN_ERR_SHAPE;
-  if (h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT) return SCOT_PLAN_ERR_UNSUPPORTED;
+  if (h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT && h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT_ADJOINT) return SCOT_PLAN_ERR_UNSUPPORTED;
+  const int adjoint = h[SCOT_PLAN_H_FORMAT] == SCOT_PLAN_FORMAT_ADJOINT;
   if (h[SCOT_PLAN_H_ABI] != (uint64_t)abi || h[SCOT_PLAN_H_OPERAND] != (uint64_t)operand_format) return SCOT_PLAN_ERR_UNSUPPORTED;
   if (h[SCOT_PLAN_H_BYTES] != (uint64_t)bytes) return SCOT_PLAN_ERR_SHAPE;      /* a truncated (or padded) file */
   v->base = b;
@@ -125,8 +190,12 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
   v->n_arrays = h[SCOT_PLAN_H_NARRAYS];
   v->arrays_words = h[SCOT_PLAN_H_ARRAYS_WORDS];
   v->data_bytes = h[SCOT_PLAN_H_DATA_BYTES];
+  v->format = h[SCOT_PLAN_H_FORMAT];
+  v->n_backward = adjoint ? h[SCOT_PLAN_H_NBACKWARD] : 0;
+  v->backward_words = adjoint ? h[SCOT_PLAN_H_BACKWARD_WORDS] : 0;
   const uint64_t lim = (uint64_t)1 << 32;      /* counts that cannot overflow the products below */
-  if (v->n_names > lim || v->n_buffers > lim || v->n_entries > lim || v->entries_words > lim || v->n_arrays > lim || v->arrays_words > lim)
+  if (v->n_names > lim || v->n_buffers > lim || v->n_entries > lim || v->entries_words > lim || v->n_arrays > lim || v->arrays_words > lim ||
+      v->n_backward > lim || v->backward_words > lim)
     return SCOT_PLAN_ERR_SHAPE;
   if (!scot_plan_span_ok(h[SCOT_PLAN_H_NAMES_OFF], v->n_names * SCOT_PLAN_NAME_BYTES, bytes) ||
       !scot_plan_span_ok(h[SCOT_PLAN_H_BUFFERS_OFF], v->n_buffers * 32, bytes) ||
@@ -135,22 +204,29 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
       !scot_plan_span_ok(h[SCOT_PLAN_H_IO_OFF], SCOT_PLAN_IO_WORDS * 8, bytes) ||
       !scot_plan_span_ok(h[SCOT_PLAN_H_DATA_OFF], v->data_bytes, bytes))
     return SCOT_PLAN_ERR_SHAPE;
+  if (adjoint && (!scot_plan_span_ok(h[SCOT_PLAN_H_BACKWARD_OFF], v->backward_words * 8, bytes) ||
+                  !scot_plan_span_ok(h[SCOT_PLAN_H_ADJ_OFF], SCOT_PLAN_ADJ_WORDS * 8, bytes)))
+    return SCOT_PLAN_ERR_SHAPE;
   v->names = b + h[SCOT_PLAN_H_NAMES_OFF];
   v->buffers = (const uint64_t*)(b + h[SCOT_PLAN_H_BUFFERS_OFF]);
   v->entries = (const uint64_t*)(b + h[SCOT_PLAN_H_ENTRIES_OFF]);
   v->arrays = (const uint64_t*)(b + h[SCOT_PLAN_H_ARRAYS_OFF]);
   v->io = (const uint64_t*)(b + h[SCOT_PLAN_H_IO_OFF]);
   v->data = b + h[SCOT_PLAN_H_DATA_OFF];
-  // names: terminated, and listed
+  if (adjoint) {
+    v->backward = (const uint64_t*)(b + h[SCOT_PLAN_H_BACKWARD_OFF]);
+    v->adj = (const uint64_t*)(b + h[SCOT_PLAN_H_ADJ_OFF]);
+  }
+  // names: terminated, and listed (format 2: in either table; each entry is then held to its own section's)
   for (uint64_t i = 0; i < v->n_names; ++i) {
     const char* nm = (const char*)(v->names + i * SCOT_PLAN_NAME_BYTES);
     if (!memchr(nm, 0, SCOT_PLAN_NAME_BYTES)) return SCOT_PLAN_ERR_SHAPE;
-    if (scot_plan_entry_index(nm) < 0) return SCOT_PLAN_ERR_UNSUPPORTED;
+    if (scot_plan_entry_index(nm) < 0 && !(adjoint && scot_plan_adjoint_entry_index(nm) >= 0)) return SCOT_PLAN_ERR_UNSUPPORTED;
   }
   // buffers: a known kind, a size, a constant's content inside the data section
   for (uint64_t i = 0; i < v->n_buffers; ++i) {
     const uint64_t kind = v->buffers[4 * i], n = v->buffers[4 * i + 1], off = v->buffers[4 * i + 2];
-    if (kind > SCOT_PLAN_BUF_SCRATCH || n == 0 || n > ((uint64_t)1 << 40)) return SCOT_PLAN_ERR_SHAPE;
+    if (kind > (uint64_t)(adjoint ? SCOT_PLAN_BUF_STATE : SCOT_PLAN_BUF_SCRATCH) || n == 0 || n > ((uint64_t)1 << 40)) return SCOT_PLAN_ERR_SHAPE;
     if (kind == SCOT_PLAN_BUF_CONSTANT && !scot_plan_span_ok(off, n, v->data_bytes)) return SCOT_PLAN_ERR_SHAPE;
   }
   // arrays
@@ -168,20 +244,10 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
     w += 2 + 2 * cnt;
   }
   if (w != v->arrays_words) return SCOT_PLAN_ERR_SHAPE;
-  // entries
-  w = 0;
-  for (uint64_t i = 0; i < v->n_entries; ++i) {
-    if (v->entries_words - w < 4) return SCOT_PLAN_ERR_SHAPE;
-    const uint64_t name = v->entries[w], lib = v->entries[w + 1], ni = v->entries[w + 2], nf = v->entries[w + 3];
-    if (name >= v->n_names || lib > 1 || ni > SCOT_PLAN_MAX_INT || nf > SCOT_PLAN_MAX_FLT) return SCOT_PLAN_ERR_SHAPE;
-    if (2 * ni + nf > v->entries_words - w - 4) return SCOT_PLAN_ERR_SHAPE;
-    for (uint64_t k = 0; k < ni; ++k)
-      if (!scot_plan_arg_ok(v, v->entries[w + 4 + 2 * k], v->entries[w + 5 + 2 * k], 0)) return SCOT_PLAN_ERR_SHAPE;
-    for (uint64_t k = 0; k < nf; ++k)
-      if (v->entries[w + 4 + 2 * ni + k] >> 32) return SCOT_PLAN_ERR_SHAPE;      /* raw bits of ONE float */
-    w += 4 + 2 * ni + nf;
-  }
-  if (w != v->entries_words) return SCOT_PLAN_ERR_SHAPE;
+  // entries: the forward against its list, the backward of an adjoint plan against the other one, by the same rules
+  int erc = scot_plan_entries_ok(v, v->entries, v->n_entries, v->entries_words, 0);
+  if (erc != SCOT_PLAN_OK) return erc;
+  if (adjoint && (erc = scot_plan_entries_ok(v, v->backward, v->n_backward, v->backward_words, 1)) != SCOT_PLAN_OK) return erc;
   // io: fp32 [B, Cin, H, W] in, fp32 [B, Cout, H, W] out, each whole inside a buffer of the right kind
   const uint64_t* io = v->io;
   const uint64_t B = io[SCOT_PLAN_IO_B], Cin = io[SCOT_PLAN_IO_CIN], H = io[SCOT_PLAN_IO_H], W = io[SCOT_PLAN_IO_W], Cout = io[SCOT_PLAN_IO_COUT];
@@ -201,6 +267,27 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
     if (off > cap || n > cap - off || v->buffers[4 * buf] != spans[s][4]) return SCOT_PLAN_ERR_SHAPE;
   }
   if (io[SCOT_PLAN_IO_HAS_TIME] && io[SCOT_PLAN_IO_TIME_BYTES] != B * 4) return SCOT_PLAN_ERR_SHAPE;
+  if (adjoint) {
+    // the cotangent's copy is an input, the gradients are outputs, the scale and its counter are the runtime's own
+    const uint64_t* a = v->adj;
+    const uint64_t flags = a[SCOT_PLAN_ADJ_FLAGS];
+    if (flags > 3 || (flags && !v->n_backward)) return SCOT_PLAN_ERR_SHAPE;
+    if ((flags & 2) && !io[SCOT_PLAN_IO_HAS_TIME]) return SCOT_PLAN_ERR_SHAPE;
+    if (a[SCOT_PLAN_ADJ_COT + 2] != B * Cout * H * W * 4 ||
+        !scot_plan_io_span_ok(v, a[SCOT_PLAN_ADJ_COT], a[SCOT_PLAN_ADJ_COT + 1], a[SCOT_PLAN_ADJ_COT + 2], SCOT_PLAN_BUF_INPUT))
+      return SCOT_PLAN_ERR_SHAPE;
+    const uint64_t want[4][3] = {{SCOT_PLAN_ADJ_DPV, (flags & 1) ? B * Cin * H * W * 4 : 0, SCOT_PLAN_BUF_OUTPUT},
+                                 {SCOT_PLAN_ADJ_DTIME, (flags & 2) ? B * 4 : 0, SCOT_PLAN_BUF_OUTPUT},
+                                 {SCOT_PLAN_ADJ_STATE, (uint64_t)(a[SCOT_PLAN_ADJ_STATE + 2] ? 16 : 0), SCOT_PLAN_BUF_STATE},
+                                 {SCOT_PLAN_ADJ_COUNTER, (uint64_t)(a[SCOT_PLAN_ADJ_STATE + 2] ? 4 : 0), SCOT_PLAN_BUF_STATE}};
+    for (int s = 0; s < 4; ++s) {
+      const uint64_t* sp = a + want[s][0];
+      if (sp[2] != want[s][1]) return SCOT_PLAN_ERR_SHAPE;
+      if (sp[2] && !scot_plan_io_span_ok(v, sp[0], sp[1], sp[2], want[s][2])) return SCOT_PLAN_ERR_SHAPE;
+    }
+    const int64_t e = (int64_t)a[SCOT_PLAN_ADJ_SCALE_EXP];
+    if (e < -120 || e > 120 || (e != 0 && !a[SCOT_PLAN_ADJ_STATE + 2])) return SCOT_PLAN_ERR_SHAPE;
+  }
   return SCOT_PLAN_OK;
 }
 #endif

@@ -117,6 +117,11 @@ class ScOTEngine:
         self._rec = None
         self._rec_keep = None
         self._export = None         # plan.py's buffer registry while ScOT.export_plan records its forward: new / pool report to it
+        # ... and, for an adjoint export, whether this engine's own backward forks the skips' ConvNeXt blocks to the side stream: the
+        # (one-stream) recording then adds their share of the time gradient in the side stream's row and order, so that the sum has the
+        # engine's own association and the plan's d_time its bits
+        self._export_side_rows = False
+        self._dt_side = False
         self._taped = {}
         self._pending = []
         self._wgq = []                                                  # weight gradients waiting to be grouped (see wgrad)
@@ -519,16 +524,29 @@ class ScOTEngine:
         # (an export records C-ABI calls only, also on the CPU emulation, whose library implements the memset and the copy)
         return self.device.type == "cuda" or self._export is not None
 
-    def plan_buffers(self):
+    def plan_buffers(self, adjoint=False):
         """What an inference forward touches that exists BEFORE it, for plan.py: [(name, tensor, constant?)].  Constants are stored in a
         plan image by value (the parameter arena, its 16-bit copy, the bias-MLP tables); the rest is written by the forward before it
-        is read (the bias tables every forward recomputes) and only needs room."""
+        is read (the bias tables every forward recomputes) and only needs room.
+        adjoint: also what the frozen-model backward touches — the transposed 16-bit copy (a constant), the bias-table gradient scratch,
+        the ConvNeXt blocks' power-of-two pairs and the gradient arena, where the stored form of the fused tails leaves by-products
+        (room only: nothing reads them); and, third element "state", what the plan RUNTIME writes: the gradient scale and the
+        non-finite counter of the un-scale passes."""
         out = [("arena", self.arena.data, True)]
         if self.shadow is not None:
             out.append(("shadow", self.shadow, True))
         out += [("cpb_coords", self.cpb_coords, True), ("cpb_desc", self.cpb_desc, True)]
         out += [(f"coords{ws}", t, True) for ws, t in sorted(self._coords.items())]
         out += [("cpb_tables", self.cpb_tables, False), ("cpb_z", self.cpb_z, False)]
+        if adjoint:
+            if self.shadow_t is not None:
+                out.append(("shadow_t", self.shadow_t, True))
+            if self.scale_grads:
+                out += [("scale_state", self.scale_state, "state"), ("grad_overflow", self.grad_overflow, "state")]
+            out += [("cpb_dtables", self.cpb_dtables, False), ("cpb_dls", self.cpb_dls, False)]
+            out += [(f"ls_pair:{pre}", ls["cs"], False) for pre, ls in sorted(self._ls.items())]
+            if self.arena.grad is not None:
+                out.append(("grad_arena", self.arena.grad, False))
         return out
 
     def h_zero(self, t):
@@ -681,7 +699,7 @@ class ScOTEngine:
         dout = gradient of the norm's output branch, x = its pre-norm rows, stats = the forward's (mean, rstd)"""
         if self._dt is None:
             return
-        acc = self._dt_to if self._dt_to is not None else self._dt[1 if self._in_side is not None else 0]
+        acc = self._dt_to if self._dt_to is not None else self._dt[1 if (self._in_side is not None or self._dt_side) else 0]
         ops.cln_dtime(dout, x, stats[0], stats[1], self.P(prefix + ".weight.weight"), self.P(prefix + ".bias.weight"), acc,
                       x.numel() // C, rows_per_sample, C, sample_scale=sample_scale)
 
@@ -1242,7 +1260,7 @@ class ScOTEngine:
         try:
             g = self._convnext_bwd_chain(pre, rec, g, d_y2, B, H, W, C, time, ls)
             if self._dt_to is not None:
-                ops.axpy_dev(self._dt[1 if self._in_side is not None else 0], self._dt_to, ls["cs"][1:2])
+                ops.axpy_dev(self._dt[1 if (self._in_side is not None or self._dt_side) else 0], self._dt_to, ls["cs"][1:2])
             return g
         finally:
             self._gredirect, self._dt_to = None, None
@@ -1729,7 +1747,8 @@ class ScOTEngine:
             ev, self.grad_fill_event = self.grad_fill_event, None
             if ev is not None:
                 torch.cuda.current_stream().wait_event(ev)
-        self.tdo_dynamic(fill_done)
+        if self._export is None:      # (a plan's backward is C-ABI calls only, and it writes no parameter gradient: nothing to wait for)
+            self.tdo_dynamic(fill_done)
         self.h_zero(self.cpb_dtables)
         self.h_zero(self.cpb_dls)
         self.mark("bwd head")
@@ -1745,7 +1764,7 @@ class ScOTEngine:
             def prescale():
                 if not self.grads_are_zero:
                     self.scale_grad_range(S_dev)
-            if pgr:      # (no trainable parameter: whatever the fused kernels leave in the arena is never read — ScOT clears it before use)
+            if pgr and self._export is None:      # (no trainable parameter: whatever the fused kernels leave in the arena is never read — ScOT clears it before use)
                 self.tdo_dynamic(prescale)
             if dpred is not None:
                 dpred = self.clone(dpred.contiguous())
@@ -1855,6 +1874,7 @@ class ScOTEngine:
         nl = len(self.dec)
         g_skips: List[Optional[torch.Tensor]] = [None] * nl  # gradient wrt the (ConvNeXt-processed) skips
         skip_ev = [None] * nl
+        inline_done = set()
         side_skips = self.use_side and not self.stage_timing
 
         def skip_bwd(i, gi):
@@ -1878,12 +1898,20 @@ class ScOTEngine:
                     # this skip's gradient is only needed when the backward reaches encoder stage i: its ConvNeXt blocks go to
                     # the side stream now, beside the deeper decoder / encoder stages
                     g_skips[i], skip_ev[i] = self.fork_task(lambda i=i, gi=g_skips[i]: skip_bwd(i, gi))
+                elif self._export is not None and self._export_side_rows and tape["res"][i]:
+                    # a plan's recording of an engine that forks here: in line, at the same place, into the side stream's row
+                    self._dt_side = True
+                    try:
+                        g_skips[i] = skip_bwd(i, g_skips[i])
+                    finally:
+                        self._dt_side = False
+                    inline_done.add(i)
         g_skips[nl - 1] = g  # decoder input = skips[-1]
 
         # ConvNeXt blocks (in line: the deepest skip, and every skip when the side stream is off)
         self.mark("bwd convnext")
         for i in reversed(range(nl)):
-            if skip_ev[i] is None:
+            if skip_ev[i] is None and i not in inline_done:
                 g_skips[i] = skip_bwd(i, g_skips[i])
 
         if not side_skips:

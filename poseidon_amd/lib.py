@@ -122,6 +122,11 @@ PLAN_PROTOTYPES = {
     "scot_plan_entry_point": [I],
     "scot_plan_peer_library": [ctypes.c_char_p],
     "scot_plan_poison": [P, I, P],
+    # adjoint plans (image format 2): the vjp of the last run, its gradient-scale status, what its backward may call
+    "scot_plan_describe_adjoint": [P, P],
+    "scot_plan_vjp": [P, P, P, P, F, P],
+    "scot_plan_grad_status": [P, P, P],
+    "scot_plan_adjoint_entry_point": [I],
 }
 _VOID = {"scot_set_use_tr", "scot_gemm_wide_config", "scot_gemm_splitk_config"}
 _SIZE = {"scot_gemm_workspace_bytes", "scot_wgrad_group_workspace_bytes", "scot_cln_bwd_workspace_bytes", "scot_wgrad_mlp_workspace_bytes",
@@ -129,7 +134,7 @@ _SIZE = {"scot_gemm_workspace_bytes", "scot_wgrad_group_workspace_bytes", "scot_
 
 
 def restype(name):
-    if name == "scot_plan_entry_point":
+    if name in ("scot_plan_entry_point", "scot_plan_adjoint_entry_point"):
         return ctypes.c_char_p
     return None if name in _VOID else (c_size_t if name in _SIZE else c_int)
 

@@ -8,6 +8,10 @@ of constants, the input copies) registered WHILE the forward was recorded; the s
 value.  Before the file is written the image is loaded through the runtime in this process, its scratch filled with NaN bytes, and run
 on the export inputs: the prediction has to be finite and bit-identical to the model's own.
 
+`export_plan(..., adjoint=("pixel_values", "time"))` records two lists instead — the forward a differentiable call runs and the frozen-model
+backward from a cotangent of the prediction — and writes a format-2 image whose second entries section `scot_plan_vjp` replays; the
+self-check then also requires the engine's own bits for both input gradients.
+
 `Plan` is the ctypes wrapper of the runtime, for the tests and for a Python process that wants inference without torch (it imports
 torch only if the caller hands it tensors).
 """
@@ -21,13 +25,17 @@ from . import lib as _lib
 
 MAGIC = 0x4e414c50544f4353
 FORMAT = 1
-HEADER_WORDS, NAME_BYTES, IO_WORDS = 32, 48, 24
-CONSTANT, INPUT, OUTPUT, SCRATCH = range(4)
+FORMAT_ADJOINT = 2      # + a backward entries section and the adjoint words (csrc/plan_image.h)
+HEADER_WORDS, NAME_BYTES, IO_WORDS, ADJ_WORDS = 32, 48, 24, 24
+CONSTANT, INPUT, OUTPUT, SCRATCH, STATE = range(5)
 ARG_INT, ARG_NULL, ARG_PTR, ARG_STREAM, ARG_ARRAY = range(5)
 COMPUTE_CODE = {"fp32": 0, "fp16": 1, "bf16": 2, "bf16x3": 3}
 MAX_INT, MAX_FLT = 48, 8
 (H_MAGIC, H_FORMAT, H_ABI, H_OPERAND, H_COMPUTE, H_BYTES, H_NNAMES, H_NAMES_OFF, H_NBUFFERS, H_BUFFERS_OFF, H_NENTRIES, H_ENTRIES_OFF,
- H_ENTRIES_WORDS, H_NARRAYS, H_ARRAYS_OFF, H_ARRAYS_WORDS, H_IO_OFF, H_DATA_OFF, H_DATA_BYTES) = range(19)
+ H_ENTRIES_WORDS, H_NARRAYS, H_ARRAYS_OFF, H_ARRAYS_WORDS, H_IO_OFF, H_DATA_OFF, H_DATA_BYTES, H_NBACKWARD, H_BACKWARD_OFF,
+ H_BACKWARD_WORDS, H_ADJ_OFF) = range(23)
+ADJ_FLAGS, ADJ_COT, ADJ_DPV, ADJ_DTIME, ADJ_STATE, ADJ_COUNTER, ADJ_SCALE_EXP, ADJ_KEPT_BYTES = 0, 1, 4, 7, 10, 13, 16, 17
+DESCRIBE_ADJOINT = ("has_adjoint", "d_pixel_values", "d_time", "backward_calls", "kept_bytes", "grad_scale_exponent")
 DESCRIBE = ("batch", "channels", "height", "width", "out_channels", "has_time", "time_bytes", "has_pixel_mask", "pixel_mask_bytes",
             "operand_format", "compute", "device_bytes", "calls", "pixel_values_bytes", "prediction_bytes", "format")
 
@@ -45,12 +53,13 @@ def bind(lib):
     return lib
 
 
-def runtime_entry_points(lib):
-    """the entry points the runtime of this build lists: what a plan may call"""
+def runtime_entry_points(lib, adjoint=False):
+    """the entry points the runtime of this build lists: what a plan's forward (adjoint: its backward) may call"""
     bind(lib)
+    query = lib.scot_plan_adjoint_entry_point if adjoint else lib.scot_plan_entry_point
     out, i = [], 0
     while True:
-        n = lib.scot_plan_entry_point(i)
+        n = query(i)
         if n is None:
             return out
         out.append(n.decode())
@@ -124,23 +133,45 @@ def _check_request(model, pixel_values, time, pixel_mask, labels):
         raise PlanExportError("export_plan: time is required when use_conditioning=True")
 
 
-def _record(model, pv, t):
-    """-> (registry, recorded calls, prediction tensor, input copies): ONE dedicated, linear recording of engine._forward"""
+def _check_adjoint(model, adjoint):
+    adjoint = tuple(sorted(set(adjoint or ())))
+    if not set(adjoint) <= {"pixel_values", "time"}:
+        raise PlanExportError(f"export_plan: adjoint names unknown input(s) {sorted(set(adjoint) - {'pixel_values', 'time'})}; a plan "
+                              "differentiates with respect to pixel_values and time")
+    if "time" in adjoint and not model.config.use_conditioning:
+        raise PlanExportError("export_plan: adjoint=('time',) needs use_conditioning=True: this model's prediction does not depend on time")
+    return adjoint
+
+
+def _kind(const):
+    return STATE if const == "state" else (CONSTANT if const else SCRATCH)
+
+
+def _record(model, pv, t, adjoint=()):
+    """-> (registry, recorded calls, kept tensors, prediction tensor, input copies, adjoint record or None): ONE dedicated, linear
+    recording of engine._forward — with `adjoint`, of the forward a differentiable call runs (train=True without stochastic depth,
+    these input gradients, no parameter gradient) followed by engine._backward from a cotangent of the prediction alone; the adjoint
+    record holds where the second list starts and the cotangent / gradient tensors"""
+    import torch
     from . import ops
     eng = model._engine
     reg = _Registry()
-    for name, ten, const in eng.plan_buffers():
-        reg.add(ten, CONSTANT if const else SCRATCH, name)
+    for name, ten, const in eng.plan_buffers(adjoint=bool(adjoint)):
+        reg.add(ten, _kind(const), name)
     pv_in = pv.clone()
     t_in = None if t is None else t.clone()
     reg.add(pv_in, INPUT, "pixel_values")
     if t_in is not None:
         reg.add(t_in, INPUT, "time")
+    adj = None
+    if adjoint:
+        cot = torch.zeros(pv.shape[0], model.config.num_out_channels, pv.shape[2], pv.shape[3], dtype=torch.float32, device=pv.device)
+        reg.add(cot, INPUT, "d_prediction")
     inner_workspace = ops.workspace
 
     def workspace(need=0):      # the split-K scratch of the wrappers is an allocation funnel too
         w = inner_workspace(need)
-        reg.scratch(w)
+        reg.add(w, SCRATCH, "workspace")
         return w
     saved = dict(use_side=eng.use_side, stage_timing=eng.stage_timing, stochastic=eng.stochastic, collect_attn=eng.collect_attn,
                  last_hidden=eng.last_hidden, last_hidden_aliased=eng.last_hidden_aliased, _rec=eng._rec, _rec_keep=eng._rec_keep,
@@ -148,13 +179,26 @@ def _record(model, pv, t):
     rec, keep = [], []
     prev_lib = ops.use(eng.lib_kind)
     try:
-        eng.refresh_weight_copies(False)      # (never part of a recording: the 16-bit copies are constants of the image)
+        eng.refresh_weight_copies(bool(adjoint))      # (never part of a recording: the 16-bit copies are constants of the image)
         ops.workspace = workspace
         eng.use_side = eng.stage_timing = eng.stochastic = eng.collect_attn = False
         eng._export, eng._rec, eng._rec_keep = reg, rec, keep
+        eng._export_side_rows = bool(saved["use_side"] and not saved["stage_timing"])
         prev_rec = ops.set_recorder(rec)
         try:
-            _, pred, _ = eng._forward(pv_in, t_in, None, None, False)
+            if adjoint:      # forced for the export, whatever the caller's tensors require
+                eng._fwd_flags = (adjoint, False)
+                _, pred, tape = eng._forward(pv_in, t_in, None, None, True)
+                n_fwd = len(rec)
+                cot.copy_(pred / float(pred.numel()))      # (a value for the recording run; a vjp copies the caller's in)
+                counted = None if eng.grad_overflow is None else eng.grad_overflow.clone()
+                d_pv, d_t = eng._backward(tape, None, cot)
+                if counted is not None:      # (the recording run is not a step of the model's: its un-scale passes do not count)
+                    eng.grad_overflow.copy_(counted)
+                keep.append(tape)
+                adj = dict(n_fwd=n_fwd, cot=cot, d_pv=d_pv, d_t=d_t)
+            else:
+                _, pred, _ = eng._forward(pv_in, t_in, None, None, False)
         finally:
             ops.set_recorder(prev_rec)
     finally:
@@ -163,10 +207,10 @@ def _record(model, pv, t):
         for k, v in saved.items():
             setattr(eng, k, v)
         ops.use(prev_lib)
-    for name, ten, const in eng.plan_buffers():      # (tables the forward created on first use)
+    for name, ten, const in eng.plan_buffers(adjoint=bool(adjoint)):      # (tables the forward created on first use)
         if ten.data_ptr() not in reg.bufs:
-            reg.add(ten, CONSTANT if const else SCRATCH, name)
-    return reg, rec, keep, pred, pv_in, t_in
+            reg.add(ten, _kind(const), name)
+    return reg, rec, keep, pred, pv_in, t_in, adj
 
 
 def _libraries(eng):
@@ -186,10 +230,9 @@ def _bytes_of(t):
     return t.detach().reshape(-1).cpu().contiguous().view(__import__("torch").uint8).numpy().tobytes()
 
 
-def build_image(model, reg, rec, pred, pv_in, t_in, own, peer):
-    """recorded calls + registered buffers -> the bytes of a plan image"""
+def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None):
+    """recorded calls + registered buffers -> the bytes of a plan image (adj: the adjoint record of _record -> a format-2 image)"""
     eng = model._engine
-    listed = set(runtime_entry_points(own))
     reg.freeze()
     used, names, name_index = [], [], {}
     index_of = {}
@@ -208,17 +251,24 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer):
         b, off = reg.resolve(value)
         if b is None:
             raise PlanExportError(f"export_plan: {what} is a device address (0x{value:x}) inside no buffer the export registered")
+        if touching is not None:
+            touching.add(b["addr"])
         return (ARG_PTR | (buffer_index(b) << 8), off)
 
-    entries, arrays = [], []
-    for fn, args in rec:
+    arrays, touching = [], None
+    n_fwd = len(rec) if adj is None else adj["n_fwd"]
+    listed_fwd = set(runtime_entry_points(own))
+    listed_bwd = set(runtime_entry_points(own, adjoint=True)) if adj is not None else set()
+    sections = [("forward", "SCOT_PLAN_ENTRY_POINTS", listed_fwd, [], set()), ("backward", "SCOT_PLAN_ADJOINT_ENTRY_POINTS", listed_bwd, [], set())]
+    for pos, (fn, args) in enumerate(rec):
+        what_list, macro, listed, entries, touching = sections[0 if pos < n_fwd else 1]
         if args is None:
             label = getattr(fn, "__qualname__", None) or getattr(fn, "__name__", None) or repr(fn)
-            raise PlanExportError(f"export_plan: the recorded forward holds a host-side Python step ({label}); a plan is C-ABI calls only")
+            raise PlanExportError(f"export_plan: the recorded {what_list} holds a host-side Python step ({label}); a plan is C-ABI calls only")
         name = fn.__name__
         if name not in listed:
-            raise PlanExportError(f"export_plan: the forward calls {name}, which the plan runtime of this library does not list "
-                                  "(csrc/plan_image.h, SCOT_PLAN_ENTRY_POINTS)")
+            raise PlanExportError(f"export_plan: the {what_list} calls {name}, which the plan runtime of this library does not list "
+                                  f"(csrc/plan_image.h, {macro})")
         addr = _address(fn)
         if addr == _address(getattr(own, name)):
             which = 0
@@ -264,6 +314,8 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer):
             name_index[name] = len(names)
             names.append(name)
         entries.append((name_index[name], which, ints, flts))
+    touching = None
+    entries, backward = sections[0][3], sections[1][3]
 
     B, Cin, H, W = pv_in.shape
     Cout = pred.shape[1]
@@ -282,6 +334,31 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer):
         io[8], io[9] = whole(t_in, "the time copy", INPUT)
         io[10] = t_in.numel() * 4
     io[15], io[16] = whole(pred, "the prediction", OUTPUT)
+    adj_words = [0] * ADJ_WORDS
+    if adj is not None:
+        def span(slot, t, what, kind):
+            adj_words[slot], adj_words[slot + 1] = whole(t, what, kind)
+            adj_words[slot + 2] = t.numel() * t.element_size()
+        span(ADJ_COT, adj["cot"], "the cotangent copy", INPUT)
+        if adj["d_pv"] is not None:
+            adj_words[ADJ_FLAGS] |= 1
+            span(ADJ_DPV, adj["d_pv"], "d_pixel_values", OUTPUT)
+        if adj["d_t"] is not None:
+            adj_words[ADJ_FLAGS] |= 2
+            span(ADJ_DTIME, adj["d_t"], "d_time", OUTPUT)
+        S = 1.0
+        if eng.scale_grads:
+            import math
+            span(ADJ_STATE, eng.scale_state, "the gradient-scale state", STATE)
+            span(ADJ_COUNTER, eng.grad_overflow, "the non-finite counter", STATE)
+            S = eng.grad_scale_value()
+            m, e = math.frexp(S)
+            if m != 0.5:
+                raise PlanExportError(f"export_plan: the engine's gradient scale {S} is not a power of two")
+            adj_words[ADJ_SCALE_EXP] = (e - 1) & 0xFFFFFFFFFFFFFFFF
+        # what a run leaves for the vjp: the forward's buffers the backward names too (saved activations, the prediction aside)
+        both = sections[0][4] & sections[1][4]
+        adj_words[ADJ_KEPT_BYTES] = sum(b["bytes"] for b in used if b["addr"] in both and b["kind"] == SCRATCH and b["name"] != "workspace")
 
     # sections
     def words(ws):
@@ -298,18 +375,23 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer):
             data.extend(raw)
         buf_words += [b["kind"], b["bytes"], off, 0]
     data.extend(b"\0" * (-len(data) % 8))
-    ent_words = []
-    for ni, which, ints, flts in entries:
-        ent_words += [ni, which, len(ints), len(flts)]
-        for tag, val in ints:
-            ent_words += [tag, val]
-        ent_words += flts
     arr_words = []
     for kind, items in arrays:
         arr_words += [kind, len(items)]
         for tag, val in items:
             arr_words += [tag, val]
+    def entry_words(es):
+        ws = []
+        for ni, which, ints, flts in es:
+            ws += [ni, which, len(ints), len(flts)]
+            for tag, val in ints:
+                ws += [tag, val]
+            ws += flts
+        return ws
+    ent_words, bwd_words = entry_words(entries), entry_words(backward)
     sections = [names_b, words(buf_words), words(ent_words), words(arr_words), words(io)]
+    if adj is not None:
+        sections += [words(bwd_words), words(adj_words)]
     offs, cur = [], HEADER_WORDS * 8
     for sct in sections:
         offs.append(cur)
@@ -319,6 +401,9 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer):
     total = data_off + len(data)
     h = [0] * HEADER_WORDS
     h[H_MAGIC], h[H_FORMAT], h[H_ABI], h[H_OPERAND] = MAGIC, FORMAT, own.scot_abi_version(), own.scot_operand_format()
+    if adj is not None:
+        h[H_FORMAT] = FORMAT_ADJOINT
+        h[H_NBACKWARD], h[H_BACKWARD_OFF], h[H_BACKWARD_WORDS], h[H_ADJ_OFF] = len(backward), offs[5], len(bwd_words), offs[6]
     h[H_COMPUTE], h[H_BYTES] = COMPUTE_CODE[model.compute], total
     h[H_NNAMES], h[H_NAMES_OFF] = len(names), offs[0]
     h[H_NBUFFERS], h[H_BUFFERS_OFF] = len(used), offs[1]
@@ -336,12 +421,15 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer):
     return bytes(out)
 
 
-def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labels=None):
+def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labels=None, *, adjoint=()):
     """Record `model`'s inference forward for exactly these input shapes and write it as a plan image to `path` (None: only return it).
-    Returns the image's bytes.  The weights are a snapshot; see the module docstring and DESIGN.md §3 for what a plan does not cover."""
+    Returns the image's bytes.  The weights are a snapshot; see the module docstring and DESIGN.md §3 for what a plan does not cover.
+    adjoint: () or some of ("pixel_values", "time") — the image (format 2) then also holds the frozen-model backward from a cotangent of
+    the prediction to these inputs' gradients (scot_plan_vjp), and its forward is the one a differentiable call runs."""
     import torch
     from . import ops
     _check_request(model, pixel_values, time, pixel_mask, labels)
+    adjoint = _check_adjoint(model, adjoint)
     dev = pixel_values.device
     model._ensure_arena(dev)
     eng = model._engine
@@ -356,9 +444,23 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
     own, peer = _libraries(eng)
     bind(own)
     with torch.no_grad():
-        _, ref, _ = eng.forward(pv, t, None, None, train=False, stochastic=False)      # the model's own prediction
-        reg, rec, keep, pred, pv_in, t_in = _record(model, pv, t)
-        image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer)
+        ref_g = None
+        if adjoint:      # the engine's own bits of the differentiable call: its prediction, and a vjp
+            _, ref, tape = eng.forward(pv, t, None, None, train=True, stochastic=False, input_grads=adjoint, param_grads=False)
+            ref = ref.clone()
+            # (the cotangent of the self-check: the prediction brought to at most 1 / its element count — the magnitude a mean loss
+            # hands back and the fp16 gradient scale is chosen for)
+            cot = ref / (float(ref.numel()) * max(1.0, float(ref.abs().max())))
+            counted = 0 if eng.grad_overflow is None else int(eng.grad_overflow)
+            ref_g = eng.backward(tape, None, cot.clone())
+            counted = 0 if eng.grad_overflow is None else int(eng.grad_overflow) - counted
+            del tape
+            for p in model._params:      # (as after any frozen backward: by-products of the fused tails may sit in the gradient arena)
+                p.grad = None
+        else:
+            _, ref, _ = eng.forward(pv, t, None, None, train=False, stochastic=False)      # the model's own prediction
+        reg, rec, keep, pred, pv_in, t_in, adj = _record(model, pv, t, adjoint)
+        image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj)
         # load what was built through the runtime, scratch poisoned, and require the model's own bits: a constant the export missed fails
         # here, not at a user's site
         plan = Plan.load(image, lib=own, peer=peer)
@@ -373,6 +475,21 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
             if not torch.equal(got, ref):
                 raise PlanExportError("export_plan: the plan's prediction differs from the model's own "
                                       f"(max |difference| {float((got - ref).abs().max()):.3e})")
+            if adjoint:
+                got_g = plan.vjp(cot.clone())
+                if dev.type == "cuda":
+                    torch.cuda.synchronize(dev)
+                for name, a, b in zip(("d_pixel_values", "d_time"), got_g, ref_g):
+                    # the engine's own bits; where its fp16 backward overflowed, the same elements are non-finite (never clipped)
+                    same = (a is None) == (b is None)
+                    if same and a is not None:
+                        fin = torch.isfinite(b)
+                        same = torch.equal(torch.isfinite(a), fin) and torch.equal(a[fin], b[fin])
+                    if not same:
+                        raise PlanExportError(f"export_plan: the plan's {name} differs from the engine's own for the export inputs")
+                if plan.grad_status()[0] != counted:
+                    raise PlanExportError(f"export_plan: the plan's un-scale passes counted {plan.grad_status()[0]} non-finite values, the "
+                                          f"engine's {counted}")
         finally:
             plan.free()
     del keep
@@ -508,6 +625,36 @@ class Plan:
                                          _addr(out, "out"), int(steps), self._stream(stream, pixel_values))
         _lib.check(rc, "scot_plan_rollout")
         return out.transpose(0, 1).contiguous() if tensors and _is_tensor(out) else out
+
+    def describe_adjoint(self):
+        out = (ctypes.c_longlong * 8)()
+        _lib.check(self._lib.scot_plan_describe_adjoint(self._h, out), "scot_plan_describe_adjoint")
+        return dict(zip(DESCRIBE_ADJOINT, [int(x) for x in out]))
+
+    def vjp(self, d_prediction, grad_scale=0, out=None, stream=None):
+        """-> (d_pixel_values, d_time) = J^T d_prediction at the inputs of the last `run` (None for a gradient the plan was not exported
+        with).  out: (buffer or None, buffer or None) to receive them; required with raw addresses.  grad_scale: scot_plan.h."""
+        d, a = self.info, self.describe_adjoint()
+        if _is_tensor(d_prediction):
+            import torch
+            if tuple(d_prediction.shape) != (d["batch"], d["out_channels"], d["height"], d["width"]):
+                raise ValueError(f"this plan takes a cotangent of shape {(d['batch'], d['out_channels'], d['height'], d['width'])}")
+            if out is None:
+                dev = d_prediction.device
+                out = (torch.empty(d["batch"], d["channels"], d["height"], d["width"], dtype=torch.float32, device=dev) if a["d_pixel_values"] else None,
+                       torch.empty(d["batch"], dtype=torch.float32, device=dev) if a["d_time"] else None)
+        elif out is None:
+            raise ValueError("raw addresses need `out`")
+        rc = self._lib.scot_plan_vjp(self._h, _addr(d_prediction, "d_prediction"), _addr(out[0], "d_pixel_values"), _addr(out[1], "d_time"),
+                                     float(grad_scale), self._stream(stream, d_prediction))
+        _lib.check(rc, "scot_plan_vjp")
+        return out
+
+    def grad_status(self, stream=None):
+        """-> (non-finite values the un-scale passes have counted since load, the last vjp's scale as a power-of-two exponent)"""
+        out = (ctypes.c_longlong * 2)()
+        _lib.check(self._lib.scot_plan_grad_status(self._h, out, self._stream(stream, None)), "scot_plan_grad_status")
+        return int(out[0]), int(out[1])
 
     def free(self):
         if self._h is not None and self._h.value:

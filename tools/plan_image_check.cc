@@ -20,6 +20,10 @@ static uint64_t walk(const scot_plan_view* v) {
   for (uint64_t w = 0; w < v->entries_words; ++w) sum += v->entries[w];
   for (uint64_t w = 0; w < v->arrays_words; ++w) sum += v->arrays[w];
   for (int w = 0; w < SCOT_PLAN_IO_WORDS; ++w) sum += v->io[w];
+  if (v->format == SCOT_PLAN_FORMAT_ADJOINT) {      // the backward section and the adjoint words of a format-2 image
+    for (uint64_t w = 0; w < v->backward_words; ++w) sum += v->backward[w];
+    for (int w = 0; w < SCOT_PLAN_ADJ_WORDS; ++w) sum += v->adj[w];
+  }
   return sum;
 }
 
