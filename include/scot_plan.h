@@ -15,7 +15,8 @@
  * grad_outputs=g)` returns with every parameter frozen, bit for bit: no labels, no loss, no parameter gradient, no training.  Its
  * forward is the one a differentiable call runs, so beyond an inference plan it holds the saved activations of one forward, the
  * transposed 16-bit weight copy the data gradients read, and room in the gradient arena where a fused layer tail leaves by-products
- * nobody reads.  One vjp per run (the backward reuses saved rows); a rollout leaves nothing to differentiate.
+ * nobody reads.  One vjp per run (the backward reuses saved rows); a rollout leaves nothing to differentiate afterwards, so the
+ * adjoint of a whole rollout is a call of its own, scot_plan_rollout_vjp: it recomputes each step from the rollout's predictions.
  *
  * Status codes as in scot_hip.h: 0, -1 (malformed image / bad argument), -3 (not for this library: ABI, operand format, entry point;
  * or a host other than x86-64 System V, where the replay underneath does not exist), -4 (allocation, copy or launch failed).
@@ -72,11 +73,34 @@ int scot_plan_describe_adjoint(scot_plan_t plan, long long* out);
 /* (d_pixel_values [B, Cin, H, W], d_time [B]) <- J^T d_prediction at the inputs of the LAST scot_plan_run of this plan.  fp32 device
  * buffers of the caller; an output pointer may be NULL (not copied out); asking for one the plan was not exported with: -1.
  * grad_scale: power of two the 16-bit backward runs under (fp16 plans), 0 = the export-time value; must be 0 or 1 for plans whose
- * backward runs unscaled (fp32, bf16, bf16x3).  Needs a completed scot_plan_run since load / poison / rollout / the previous vjp:
+ * backward runs unscaled (fp32, bf16, bf16x3).  Needs a completed scot_plan_run since load / poison / rollout / rollout_vjp / the previous vjp:
  * otherwise -1 and nothing is launched.  On a plan without an adjoint (format 1): -3.  Copies the cotangent in, writes {S, 1/S} into the
  * plan's scale state on `stream`, replays the recorded backward, copies the gradients out; asynchronous on `stream`. */
 int scot_plan_vjp(scot_plan_t plan, const float* d_prediction, float* d_pixel_values, float* d_time, float grad_scale,
                   scot_stream_t stream);
+/* The adjoint of scot_plan_rollout with NO detach between the steps: (d_pixel_values [B, Cin, H, W], d_time [B]) <- the gradient of
+ * sum_k <d_predictions[k], predictions[k]> with respect to pixel_values and time, through the chain the rollout runs: t_step = time /
+ * steps (rounded as the rollout rounds it), step k >= 1 reads cat(predictions[k-1], pixel_values[:, Cout:]).
+ *   predictions   [steps][B, Cout, H, W]: what scot_plan_rollout wrote for these pixel_values and time (the step inputs; read only)
+ *   d_predictions [steps][B, Cout, H, W]: the cotangent of every step's prediction (zeros where a step is not observed)
+ * A checkpointed sweep: nothing but the step inputs is kept, and those are the caller's `predictions`.  For k = steps-1 .. 0 the call
+ * writes step k's input, replays the forward (which recomputes the saved activations), forms the cotangent d_predictions[k] + the first
+ * Cout channels of step k+1's input gradient, writes {S, 1/S} and replays the backward.  COST: `steps` forwards + `steps` backwards per
+ * call, on top of the forward rollout that produced `predictions`.  With g_k the input gradient and tau_k the time gradient of step k,
+ * in plain fp32 adds in exactly this order (bit for bit what the same chain of single-step gradients gives in Python):
+ *   d_pixel_values[:, :Cout] = g_0[:, :Cout]
+ *   d_pixel_values[:, Cout:] = ((g_{K-1} + g_{K-2}) + ...) + g_0
+ *   d_time                   = (((tau_{K-1} + tau_{K-2}) + ...) + tau_0) * (1 / steps), rounded as the rollout rounds time / steps
+ * The sums are formed in the caller's d_pixel_values / d_time; either may be NULL (without a d_pixel_values and with steps > 1 the runtime
+ * allocates a carry buffer of that size at the first such call, held until the plan is freed and counted in the described device bytes;
+ * -4 if that fails).  Needs no preceding run and leaves none behind: a vjp right after it returns -1.  grad_scale as for the vjp;
+ * non-finite values of every step are counted in the grad status.  Reads `time` on the host once (waits for `stream` there).
+ * Refused before anything is copied or launched: a plan without an adjoint or without a time input: -3; steps < 1, Cout > Cin, a NULL
+ * pixel_values / time / predictions / d_predictions, a grad_scale the vjp refuses, steps > 1 or a d_pixel_values on a plan exported
+ * without the pixel_values adjoint, a d_time on a plan exported without the time adjoint: -1. */
+int scot_plan_rollout_vjp(scot_plan_t plan, const float* pixel_values, const float* time, const float* predictions,
+                          const float* d_predictions, int steps, float* d_pixel_values, float* d_time, float grad_scale,
+                          scot_stream_t stream);
 /* out[2]: non-finite values the un-scale passes have counted since load (a gradient that overflowed binary16 under the scale arrives
  * as inf / NaN and is counted here, never clipped: run + vjp again under a smaller grad_scale), the scale of the last vjp as an
  * exponent.  Waits for `stream`. */

@@ -5,12 +5,15 @@
 // tables by value).  This file owns the memory and replays the list: scot_plan_load validates the image, allocates one slab for all
 // buffers, uploads the constants and builds the program of scot_tape_replay (host_tape.hip) with the final addresses; scot_plan_run
 // copies the caller's inputs in, writes the caller's stream into the program's stream slots, replays, and copies the prediction out.
-// Nothing here launches a kernel of its own: the copies are device-to-device copies, the arithmetic is the recorded entry points'.
+// The copies are device-to-device copies and the model's arithmetic is the recorded entry points'; the only kernels of this file's own
+// are the two that carry a gradient from one step of scot_plan_rollout_vjp to the next (below).
 //
 // An ADJOINT plan (image format 2) also holds the recorded frozen-model backward: scot_plan_run replays the differentiable forward,
 // which leaves its saved activations in the plan's buffers, and scot_plan_vjp copies a cotangent of the prediction in, writes the
 // gradient scale {S, 1/S} into the plan's state buffer on the stream, replays the backward list and copies the input gradients out.
-// One vjp per run: the backward reuses saved rows.
+// One vjp per run: the backward reuses saved rows.  scot_plan_rollout_vjp is the adjoint of the whole rollout: it keeps no activations
+// beyond the caller's predictions (every step's input) and, from the last step to the first, replays the forward to recompute the
+// saved rows, forms the step's cotangent, replays the backward and carries the input gradient on.
 //
 // A plan is one stream's worth of state: its buffers are reused by every run, so runs of ONE plan must be ordered (same stream, or
 // the caller's own events); two plans are independent.
@@ -53,6 +56,25 @@ inline bool dev_copy2d(void* dst, size_t dpitch, const void* src, size_t spitch,
   return true;
 }
 inline bool dev_sync(hipStream_t) { return true; }
+// the carry of scot_plan_rollout_vjp as host loops (the kernels further down, element for element)
+inline bool dev_carry(float* hold, const float* g, float* hold_t, const float* g_t, size_t B, size_t cin, size_t cout, size_t hw, bool first,
+                      bool last, int steps, hipStream_t) {
+  ++g_emu_issued;
+  if (hold)
+    for (size_t i = 0; i < B * cin * hw; ++i) hold[i] = (first || (i / hw) % cin < cout) ? g[i] : hold[i] + g[i];
+  if (hold_t)
+    for (size_t b = 0; b < B; ++b) {
+      const float v = first ? g_t[b] : hold_t[b] + g_t[b];
+      hold_t[b] = last ? v / (float)steps : v;      // (torch's CPU kernel divides: scot_plan_rollout)
+    }
+  return true;
+}
+inline bool dev_cotangent(float* cot, const float* d_pred, const float* hold, size_t B, size_t cin, size_t cout, size_t hw, hipStream_t) {
+  ++g_emu_issued;
+  for (size_t b = 0; b < B; ++b)
+    for (size_t i = 0; i < cout * hw; ++i) cot[b * cout * hw + i] = d_pred[b * cout * hw + i] + hold[b * cin * hw + i];
+  return true;
+}
 #else
 inline void* dev_alloc(size_t n) {
   void* p = nullptr;
@@ -68,6 +90,69 @@ inline bool dev_copy2d(void* dst, size_t dpitch, const void* src, size_t spitch,
   return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDeviceToDevice, s) == hipSuccess;
 }
 inline bool dev_sync(hipStream_t s) { return hipStreamSynchronize(s) == hipSuccess; }
+
+// ---- the carry of scot_plan_rollout_vjp: the only kernels the plan runtime launches itself.  Internal (no entry points of scot_hip.h);
+// T = float4 where every (sample, channel) plane is a whole number of 16-byte aligned vectors, float otherwise.  Plain fp32 adds in the
+// order scot_plan.h fixes; plain vector stores.
+__device__ __forceinline__ float vadd(float a, float b) { return a + b; }
+__device__ __forceinline__ float4 vadd(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// after one backward: hold [B, Cin, plane] <- the step's input gradient g — moved on the first Cout channels (the next cotangent's
+// carry), accumulated on the pass-through channels (hold + g; moved by the first backward of the sweep); hold_t [B] <- hold_t + g_t
+// (moved by the first backward), times 1 / steps in the last one.  hold / hold_t may be NULL.  n, plane in units of T.
+template <typename T>
+__global__ __launch_bounds__(256) void plan_carry_kernel(T* __restrict__ hold, const T* __restrict__ g, float* __restrict__ hold_t,
+                                                         const float* __restrict__ g_t, size_t n, size_t plane, unsigned cin, unsigned cout,
+                                                         unsigned B, int first, int last, float inv_steps) {
+  const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  if (hold_t)
+    for (size_t b = t0; b < B; b += stride) {
+      const float v = first ? g_t[b] : hold_t[b] + g_t[b];
+      hold_t[b] = last ? v * inv_steps : v;      // (torch's GPU kernel multiplies by the reciprocal: scot_plan_rollout)
+    }
+  if (hold)
+    for (size_t i = t0; i < n; i += stride) {
+      const T v = g[i];
+      hold[i] = (first || (i / plane) % cin < cout) ? v : vadd(hold[i], v);
+    }
+}
+// after the next forward: cot [B, Cout, plane] <- d_pred [B, Cout, plane] + hold[:, :Cout] (hold's sample pitch is Cin planes)
+template <typename T>
+__global__ __launch_bounds__(256) void plan_cotangent_kernel(T* __restrict__ cot, const T* __restrict__ d_pred, const T* __restrict__ hold,
+                                                             size_t n, size_t out_row, size_t in_row) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / out_row;
+    cot[i] = vadd(d_pred[i], hold[b * in_row + (i - b * out_row)]);
+  }
+}
+inline unsigned carry_blocks(size_t n) {
+  const size_t blocks = (n + 255) / 256;
+  return (unsigned)(blocks > 4096 ? 4096 : (blocks ? blocks : 1));
+}
+inline bool vec4_ok(size_t hw, const void* a, const void* b, const void* c) {
+  return hw % 4 == 0 && ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0);
+}
+inline bool dev_carry(float* hold, const float* g, float* hold_t, const float* g_t, size_t B, size_t cin, size_t cout, size_t hw, bool first,
+                      bool last, int steps, hipStream_t s) {
+  const float inv_steps = 1.0f / (float)steps;
+  const size_t n = hold ? B * cin * hw : B;
+  if (vec4_ok(hw, hold, g, nullptr))
+    hipLaunchKernelGGL(plan_carry_kernel<float4>, dim3(carry_blocks(n / 4)), dim3(256), 0, s, (float4*)hold, (const float4*)g, hold_t, g_t, n / 4,
+                       hw / 4, (unsigned)cin, (unsigned)cout, (unsigned)B, (int)first, (int)last, inv_steps);
+  else
+    hipLaunchKernelGGL(plan_carry_kernel<float>, dim3(carry_blocks(n)), dim3(256), 0, s, hold, g, hold_t, g_t, n, hw, (unsigned)cin,
+                       (unsigned)cout, (unsigned)B, (int)first, (int)last, inv_steps);
+  return scot_check_launch() == SCOT_OK;
+}
+inline bool dev_cotangent(float* cot, const float* d_pred, const float* hold, size_t B, size_t cin, size_t cout, size_t hw, hipStream_t s) {
+  const size_t n = B * cout * hw;
+  if (vec4_ok(hw, cot, d_pred, hold))
+    hipLaunchKernelGGL(plan_cotangent_kernel<float4>, dim3(carry_blocks(n / 4)), dim3(256), 0, s, (float4*)cot, (const float4*)d_pred,
+                       (const float4*)hold, n / 4, cout * hw / 4, cin * hw / 4);
+  else
+    hipLaunchKernelGGL(plan_cotangent_kernel<float>, dim3(carry_blocks(n)), dim3(256), 0, s, cot, d_pred, hold, n, cout * hw, cin * hw);
+  return scot_check_launch() == SCOT_OK;
+}
 #endif
 
 const uint64_t PLAN_HANDLE_MAGIC = 0x50414c5053434f54ull;
@@ -93,6 +178,8 @@ struct Plan {
   bool ran = false;                                // a completed scot_plan_run whose saved activations no vjp / poison / rollout has used up
   float host_scale[4] = {1.0f, 1.0f, 0.0f, 0.0f};  // {S, 1/S, 0, 0} on its way to the state buffer
   int last_exponent = 0;                           // log2 S of the last vjp
+  float* holder = nullptr;                         // scot_plan_rollout_vjp without a d_pixel_values of the caller's: the carry's [B, Cin, H, W]
+  size_t holder_bytes = 0;
 };
 
 inline Plan* as_plan(void* p) {
@@ -220,6 +307,7 @@ extern "C" int scot_plan_free(void* plan) {
   Plan* pl = as_plan(plan);
   if (!pl) return plan ? SCOT_ERR_SHAPE : SCOT_OK;
   if (pl->slab) dev_free(pl->slab);
+  if (pl->holder) dev_free(pl->holder);
   pl->magic = 0;
   delete pl;
   return SCOT_OK;
@@ -332,7 +420,7 @@ extern "C" int scot_plan_describe(void* plan, long long* out) {
                            (long long)io[SCOT_PLAN_IO_W], (long long)io[SCOT_PLAN_IO_COUT], (long long)io[SCOT_PLAN_IO_HAS_TIME],
                            (long long)(io[SCOT_PLAN_IO_HAS_TIME] ? io[SCOT_PLAN_IO_TIME_BYTES] : 0), (long long)io[SCOT_PLAN_IO_HAS_MASK],
                            (long long)(io[SCOT_PLAN_IO_HAS_MASK] ? io[SCOT_PLAN_IO_MASK_BYTES] : 0), pl->operand_format, pl->compute,
-                           (long long)pl->slab_bytes, (long long)pl->n_entries, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
+                           (long long)(pl->slab_bytes + pl->holder_bytes), (long long)pl->n_entries, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
                            (long long)(hw * io[SCOT_PLAN_IO_COUT]), pl->format};
   memcpy(out, d, sizeof(d));
   return SCOT_OK;
@@ -393,6 +481,30 @@ extern "C" int scot_plan_describe_adjoint(void* plan, long long* out) {
   return SCOT_OK;
 }
 
+// grad_scale of a vjp -> log2 S: 0 = the export-time value, otherwise a power of two whose reciprocal is a normal float too, and 1 on a
+// plan whose backward runs unscaled (fp32 / bf16 / bf16x3).  false: refused.
+static bool scale_exponent(const Plan* pl, float grad_scale, int* exponent) {
+  *exponent = (int)(int64_t)pl->adj[SCOT_PLAN_ADJ_SCALE_EXP];
+  if (grad_scale == 0.0f) return true;
+  int e = 0;
+  if (!(grad_scale > 0.0f) || !__builtin_isfinite(grad_scale) || frexpf(grad_scale, &e) != 0.5f) return false;
+  if (!pl->adj[SCOT_PLAN_ADJ_STATE + 2] && grad_scale != 1.0f) return false;
+  if (e - 1 < -120 || e - 1 > 120) return false;
+  *exponent = e - 1;
+  return true;
+}
+
+// {S, 1/S, 0, 0} -> the plan's scale state on `stream` (plans whose backward runs under a scale)
+static bool write_scale(Plan* pl, int exponent, hipStream_t stream) {
+  pl->last_exponent = exponent;
+  if (!pl->adj[SCOT_PLAN_ADJ_STATE + 2]) return true;
+  pl->host_scale[0] = ldexpf(1.0f, exponent);
+  pl->host_scale[1] = ldexpf(1.0f, -exponent);
+  pl->host_scale[2] = pl->host_scale[3] = 0.0f;
+  // (host_scale is pageable memory: the runtime has staged it by the time the copy call returned)
+  return dev_copy(adj_ptr(pl, SCOT_PLAN_ADJ_STATE), pl->host_scale, sizeof(pl->host_scale), H2D, stream);
+}
+
 // (d_pixel_values, d_time) <- J^T d_prediction at the inputs of the last scot_plan_run (include/scot_plan.h).  Every refusal comes before
 // the first copy: a refused call launches nothing and leaves the state as it was.
 extern "C" int scot_plan_vjp(void* plan, const float* d_prediction, float* d_pixel_values, float* d_time, float grad_scale, hipStream_t stream) {
@@ -402,26 +514,12 @@ extern "C" int scot_plan_vjp(void* plan, const float* d_prediction, float* d_pix
   const uint64_t* a = pl->adj;
   if (!d_prediction) return SCOT_ERR_SHAPE;
   if ((d_pixel_values && !(a[SCOT_PLAN_ADJ_FLAGS] & 1)) || (d_time && !(a[SCOT_PLAN_ADJ_FLAGS] & 2))) return SCOT_ERR_SHAPE;
-  const bool scaled = a[SCOT_PLAN_ADJ_STATE + 2] != 0;
-  int exponent = (int)(int64_t)a[SCOT_PLAN_ADJ_SCALE_EXP];
-  if (grad_scale != 0.0f) {
-    int e = 0;
-    if (!(grad_scale > 0.0f) || !__builtin_isfinite(grad_scale) || frexpf(grad_scale, &e) != 0.5f) return SCOT_ERR_SHAPE;      // a power of two
-    if (!scaled && grad_scale != 1.0f) return SCOT_ERR_SHAPE;      // (fp32 / bf16 / bf16x3: the backward runs unscaled)
-    if (e - 1 < -120 || e - 1 > 120) return SCOT_ERR_SHAPE;        // (1 / S has to be a normal float too)
-    exponent = e - 1;
-  }
+  int exponent = 0;
+  if (!scale_exponent(pl, grad_scale, &exponent)) return SCOT_ERR_SHAPE;
   if (!pl->ran) return SCOT_ERR_SHAPE;
   pl->ran = false;      // one vjp per run: the backward reuses saved rows
   if (!dev_copy(adj_ptr(pl, SCOT_PLAN_ADJ_COT), d_prediction, (size_t)a[SCOT_PLAN_ADJ_COT + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
-  if (scaled) {
-    pl->host_scale[0] = ldexpf(1.0f, exponent);
-    pl->host_scale[1] = ldexpf(1.0f, -exponent);
-    pl->host_scale[2] = pl->host_scale[3] = 0.0f;
-    // (host_scale is pageable memory: the runtime has staged it by the time the copy call returned)
-    if (!dev_copy(adj_ptr(pl, SCOT_PLAN_ADJ_STATE), pl->host_scale, sizeof(pl->host_scale), H2D, stream)) return SCOT_ERR_LAUNCH;
-  }
-  pl->last_exponent = exponent;
+  if (!write_scale(pl, exponent, stream)) return SCOT_ERR_LAUNCH;
   const int rc = replay(pl, stream, true);
   if (rc != SCOT_OK) return rc;
   if (d_pixel_values && !dev_copy(d_pixel_values, adj_ptr(pl, SCOT_PLAN_ADJ_DPV), (size_t)a[SCOT_PLAN_ADJ_DPV + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
@@ -443,6 +541,26 @@ extern "C" int scot_plan_grad_status(void* plan, long long* out, hipStream_t str
   return SCOT_OK;
 }
 
+// pl->host_time <- time / steps, read on the host (waits for `stream`).  torch's own rounding, so that the rollout equals harness.rollout
+// bit for bit: torch's GPU kernel multiplies by the reciprocal of a host scalar (one rounding more than a division); its CPU kernel, which
+// the emulated build is compared with, divides
+static bool read_step_time(Plan* pl, const float* time, int steps, hipStream_t stream) {
+  const size_t B = (size_t)pl->io[SCOT_PLAN_IO_B];
+  try {
+    pl->host_time.resize(B);
+  } catch (const std::bad_alloc&) {
+    return false;
+  }
+  if (!dev_copy(pl->host_time.data(), time, B * 4, D2H, stream) || !dev_sync(stream)) return false;
+#ifdef SCOT_HIPEMU
+  for (size_t b = 0; b < B; ++b) pl->host_time[b] = pl->host_time[b] / (float)steps;
+#else
+  const float inv_steps = 1.0f / (float)steps;
+  for (size_t b = 0; b < B; ++b) pl->host_time[b] = pl->host_time[b] * inv_steps;
+#endif
+  return true;
+}
+
 // The integer form of the autoregressive rollout (reference trainer.py:452-603 with output_all_steps): time / steps once, then `steps`
 // forwards, each prediction written to predictions[k] ([steps][B, Cout, H, W]) and copied back over the first Cout channels of the
 // plan's input; the other input channels stay as given.  The division is the host's (one read of B floats: the call waits for
@@ -462,20 +580,7 @@ extern "C" int scot_plan_rollout(void* plan, const float* pixel_values, const fl
   char* in = io_ptr(pl, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF);
   char* out = io_ptr(pl, SCOT_PLAN_IO_OUT_BUF, SCOT_PLAN_IO_OUT_OFF);
   char* t = io_ptr(pl, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF);
-  try {
-    pl->host_time.resize(B);
-  } catch (const std::bad_alloc&) {
-    return SCOT_ERR_LAUNCH;
-  }
-  if (!dev_copy(pl->host_time.data(), time, B * 4, D2H, stream) || !dev_sync(stream)) return SCOT_ERR_LAUNCH;
-  // `time / steps` with torch's own rounding, so that the rollout equals harness.rollout bit for bit: torch's GPU kernel multiplies by the
-  // reciprocal of a host scalar (one rounding more than a division); its CPU kernel, which the emulated build is compared with, divides
-#ifdef SCOT_HIPEMU
-  for (size_t b = 0; b < B; ++b) pl->host_time[b] = pl->host_time[b] / (float)steps;
-#else
-  const float inv_steps = 1.0f / (float)steps;
-  for (size_t b = 0; b < B; ++b) pl->host_time[b] = pl->host_time[b] * inv_steps;
-#endif
+  if (!read_step_time(pl, time, steps, stream)) return SCOT_ERR_LAUNCH;
   if (!dev_copy(t, pl->host_time.data(), B * 4, H2D, stream)) return SCOT_ERR_LAUNCH;
   if (!dev_copy(in, pixel_values, B * in_row, D2D, stream)) return SCOT_ERR_LAUNCH;
   if (pixel_mask && !dev_copy(io_ptr(pl, SCOT_PLAN_IO_MASK_BUF, SCOT_PLAN_IO_MASK_OFF), pixel_mask, (size_t)io[SCOT_PLAN_IO_MASK_BYTES], D2D, stream))
@@ -487,5 +592,74 @@ extern "C" int scot_plan_rollout(void* plan, const float* pixel_values, const fl
     if (k + 1 < steps && !dev_copy2d(in, in_row, out, out_row, out_row, B, stream)) return SCOT_ERR_LAUNCH;
   }
   // (host_time is pageable memory: the runtime has staged it by the time the copy call returned)
+  return SCOT_OK;
+}
+
+// The adjoint of that rollout with no detach between the steps (include/scot_plan.h): the gradient of sum_k <d_predictions[k],
+// predictions[k]> with respect to pixel_values and time.  A checkpointed sweep: the step inputs are the caller's predictions, nothing
+// else is kept.  For k = steps-1 .. 0: the whole input of step k is written again (the plan's input buffers are not assumed to outlive a
+// backward), the forward list recomputes the saved activations, the cotangent d_predictions[k] + carry is formed AFTER that forward and
+// the gradients are moved to the holder right after the backward (the plan's cotangent / gradient buffers are not assumed to outlive a
+// forward).  The holder is the caller's d_pixel_values / d_time, so the sums are formed in place, in the order the header fixes.
+// Every refusal, the holder's allocation included, comes before the first copy.
+extern "C" int scot_plan_rollout_vjp(void* plan, const float* pixel_values, const float* time, const float* predictions,
+                                     const float* d_predictions, int steps, float* d_pixel_values, float* d_time, float grad_scale,
+                                     hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  if (pl->format != SCOT_PLAN_FORMAT_ADJOINT) return SCOT_ERR_UNSUPPORTED;
+  const uint64_t* io = pl->io;
+  const uint64_t* a = pl->adj;
+  if (!io[SCOT_PLAN_IO_HAS_TIME] || io[SCOT_PLAN_IO_HAS_MASK]) return SCOT_ERR_UNSUPPORTED;
+  if (steps < 1 || io[SCOT_PLAN_IO_COUT] > io[SCOT_PLAN_IO_CIN]) return SCOT_ERR_SHAPE;
+  if (!pixel_values || !time || !predictions || !d_predictions) return SCOT_ERR_SHAPE;
+  const bool has_dpv = (a[SCOT_PLAN_ADJ_FLAGS] & 1) != 0, has_dt = (a[SCOT_PLAN_ADJ_FLAGS] & 2) != 0;
+  if ((!has_dpv && (steps > 1 || d_pixel_values)) || (!has_dt && d_time)) return SCOT_ERR_SHAPE;
+  int exponent = 0;
+  if (!scale_exponent(pl, grad_scale, &exponent)) return SCOT_ERR_SHAPE;
+  const size_t B = (size_t)io[SCOT_PLAN_IO_B], hw = (size_t)(io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W]);
+  const size_t cin = (size_t)io[SCOT_PLAN_IO_CIN], cout = (size_t)io[SCOT_PLAN_IO_COUT];
+  const size_t in_row = hw * cin * 4, out_row = hw * cout * 4;      // bytes of one sample
+  // the carry's holder: the caller's d_pixel_values, or (more than one step and none given) a buffer of the runtime's own
+  float* hold = d_pixel_values;
+  if (!hold && steps > 1) {
+    if (!pl->holder) {
+      pl->holder = (float*)dev_alloc(B * in_row);
+      if (!pl->holder) return SCOT_ERR_LAUNCH;
+      pl->holder_bytes = B * in_row;
+    }
+    hold = pl->holder;
+  }
+  pl->ran = false;      // (the sweep's forwards overwrite the saved rows of any earlier run, and its backwards use their own up)
+  char* in = io_ptr(pl, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF);
+  char* t = io_ptr(pl, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF);
+  float* cot = (float*)adj_ptr(pl, SCOT_PLAN_ADJ_COT);
+  const float* g_pv = has_dpv ? (const float*)adj_ptr(pl, SCOT_PLAN_ADJ_DPV) : nullptr;
+  const float* g_t = has_dt ? (const float*)adj_ptr(pl, SCOT_PLAN_ADJ_DTIME) : nullptr;
+  if (!read_step_time(pl, time, steps, stream)) return SCOT_ERR_LAUNCH;
+  for (int k = steps - 1; k >= 0; --k) {
+    // step k's input: cat(predictions[k-1], pixel_values[:, Cout:]) — pixel_values itself for step 0 — and time / steps
+    if (k == 0) {
+      if (!dev_copy(in, pixel_values, B * in_row, D2D, stream)) return SCOT_ERR_LAUNCH;
+    } else {
+      if (!dev_copy2d(in, in_row, (const char*)predictions + (size_t)(k - 1) * B * out_row, out_row, out_row, B, stream)) return SCOT_ERR_LAUNCH;
+      if (cin > cout && !dev_copy2d(in + out_row, in_row, (const char*)pixel_values + out_row, in_row, in_row - out_row, B, stream))
+        return SCOT_ERR_LAUNCH;
+    }
+    if (!dev_copy(t, pl->host_time.data(), B * 4, H2D, stream)) return SCOT_ERR_LAUNCH;
+    int rc = replay(pl, stream);
+    if (rc != SCOT_OK) return rc;
+    const float* d_pred = (const float*)((const char*)d_predictions + (size_t)k * B * out_row);
+    if (k == steps - 1) {
+      if (!dev_copy(cot, d_pred, B * out_row, D2D, stream)) return SCOT_ERR_LAUNCH;
+    } else if (!dev_cotangent(cot, d_pred, hold, B, cin, cout, hw, stream)) {
+      return SCOT_ERR_LAUNCH;
+    }
+    if (!write_scale(pl, exponent, stream)) return SCOT_ERR_LAUNCH;
+    rc = replay(pl, stream, true);
+    if (rc != SCOT_OK) return rc;
+    if ((hold || d_time) && !dev_carry(hold, g_pv, d_time, g_t, B, cin, cout, hw, k == steps - 1, k == 0, steps, stream)) return SCOT_ERR_LAUNCH;
+  }
+  // (host_time and host_scale are pageable memory: the runtime has staged them by the time the copy calls returned)
   return SCOT_OK;
 }

@@ -94,9 +94,13 @@ def compute_loss(model, inputs: Dict[str, torch.Tensor], return_outputs: bool = 
 
 
 def rollout(model, inputs: Dict[str, torch.Tensor], ar_steps: Union[int, Sequence[int], None] = None,
-            output_all_steps: bool = False):
+            output_all_steps: bool = False, detach: bool = True):
     """reference Trainer._model_forward (trainer.py:452-603).  Returns the model's ScOTOutput of the last step with
-    `.output` / `.loss` replaced as the reference does."""
+    `.output` / `.loss` replaced as the reference does.
+
+    detach=False (integer `ar_steps` only; not in the reference, which always detaches): every step's output is fed back, and stacked
+    under `output_all_steps`, ATTACHED, so the result carries the graph of the whole rollout — the back-propagated roll-out whose
+    input gradients `Plan.rollout_vjp` / scot_plan_rollout_vjp give for an exported model."""
     cfg = model.config
     if ar_steps is None or not cfg.use_conditioning:
         return model(**inputs)
@@ -110,6 +114,9 @@ def rollout(model, inputs: Dict[str, torch.Tensor], ar_steps: Union[int, Sequenc
         lead = inputs["time"]
     else:
         raise ValueError("num_ar_steps must be an integer or a list of integers.")
+    if not detach and lead is not None:
+        raise ValueError("detach=False is the integer form's: a list of lead times feeds every step its own time")
+    keep = (lambda x: x.detach()) if detach else (lambda x: x)
     outs, losses, loss = [], [], 0
     hidden, reshaped, attn = [], [], []
     outputs = None
@@ -118,7 +125,7 @@ def rollout(model, inputs: Dict[str, torch.Tensor], ar_steps: Union[int, Sequenc
             inputs = {**inputs, "time": lead * i}
         outputs = model(**inputs)
         if output_all_steps:
-            outs.append(outputs.output.detach())
+            outs.append(keep(outputs.output))
             if lead is not None:
                 outs.append(outputs.output.detach())  # duplicated append of the reference's list branch (trainer.py:540-543)
             # per-step hidden states / attentions, stacked over the steps below (trainer.py:472-479, 509-520, 544-551, 584-595)
@@ -132,7 +139,7 @@ def rollout(model, inputs: Dict[str, torch.Tensor], ar_steps: Union[int, Sequenc
                 losses.append(outputs.loss)
         elif outputs.loss is not None:
             loss = loss + outputs.loss
-        nxt = outputs.output.detach()
+        nxt = keep(outputs.output)
         if channel_difference:
             nxt = torch.cat([nxt, inputs["pixel_values"][:, cfg.num_out_channels:]], dim=1)
         inputs = {**inputs, "pixel_values": nxt}

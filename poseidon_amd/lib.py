@@ -125,6 +125,7 @@ PLAN_PROTOTYPES = {
     # adjoint plans (image format 2): the vjp of the last run, its gradient-scale status, what its backward may call
     "scot_plan_describe_adjoint": [P, P],
     "scot_plan_vjp": [P, P, P, P, F, P],
+    "scot_plan_rollout_vjp": [P, P, P, P, P, I, P, P, F, P],      # the adjoint of the whole rollout (recomputes every step)
     "scot_plan_grad_status": [P, P, P],
     "scot_plan_adjoint_entry_point": [I],
 }

@@ -10,7 +10,8 @@ on the export inputs: the prediction has to be finite and bit-identical to the m
 
 `export_plan(..., adjoint=("pixel_values", "time"))` records two lists instead — the forward a differentiable call runs and the frozen-model
 backward from a cotangent of the prediction — and writes a format-2 image whose second entries section `scot_plan_vjp` replays; the
-self-check then also requires the engine's own bits for both input gradients.
+self-check then also requires the engine's own bits for both input gradients.  The same image differentiates a whole rollout:
+`Plan.rollout_vjp` (scot_plan_rollout_vjp) recomputes every step from the rollout's predictions, from the last to the first.
 
 `Plan` is the ctypes wrapper of the runtime, for the tests and for a Python process that wants inference without torch (it imports
 torch only if the caller hands it tensors).
@@ -533,7 +534,8 @@ def _addr(x, what):
 
 
 class Plan:
-    """A loaded plan.  `run` / `rollout` take torch tensors (and return one) or raw device addresses (then `out` is required)."""
+    """A loaded plan.  `run` / `rollout` / `vjp` / `rollout_vjp` take torch tensors (and return them) or raw device addresses (then `out`
+    is required)."""
 
     def __init__(self, lib, handle):
         self._lib, self._h = lib, handle
@@ -648,6 +650,38 @@ class Plan:
         rc = self._lib.scot_plan_vjp(self._h, _addr(d_prediction, "d_prediction"), _addr(out[0], "d_pixel_values"), _addr(out[1], "d_time"),
                                      float(grad_scale), self._stream(stream, d_prediction))
         _lib.check(rc, "scot_plan_vjp")
+        return out
+
+    def rollout_vjp(self, pixel_values, time, predictions, d_predictions, grad_scale=0, out=None, stream=None, steps=None):
+        """-> (d_pixel_values, d_time): the gradient of sum_k <d_predictions[:, k], predictions[:, k]> through the rollout with no detach
+        between the steps (scot_plan_rollout_vjp: recomputes every step, `steps` forwards + `steps` backwards).  Tensors come in the
+        layout `rollout` returns, [B, steps, Cout, H, W], `predictions` being what `rollout(pixel_values, time, steps)` gave.  None for
+        a gradient the plan was not exported with.  out: (buffer or None, buffer or None) to receive them.  With raw addresses
+        `predictions` / `d_predictions` are in the C layout [steps][B, Cout, H, W], and `out` and `steps=` are required."""
+        d, a = self.info, self.describe_adjoint()
+        if _is_tensor(pixel_values):
+            import torch
+            if not (_is_tensor(predictions) and _is_tensor(d_predictions)) or predictions.dim() != 5 or predictions.shape != d_predictions.shape:
+                raise ValueError("predictions and d_predictions: tensors of one shape [B, steps, Cout, H, W]")
+            if tuple(predictions.shape[:1] + predictions.shape[2:]) != (d["batch"], d["out_channels"], d["height"], d["width"]):
+                raise ValueError(f"this plan's rollout is of shape {(d['batch'], 'steps', d['out_channels'], d['height'], d['width'])}")
+            if steps is not None and int(steps) != predictions.shape[1]:
+                raise ValueError(f"steps={steps}, predictions hold {predictions.shape[1]} steps")
+            steps = predictions.shape[1]
+            predictions = predictions.to(torch.float32).transpose(0, 1).contiguous()
+            d_predictions = d_predictions.to(torch.float32).transpose(0, 1).contiguous()
+            if time is not None and _is_tensor(time):
+                time = time.reshape(-1).to(torch.float32).contiguous()
+            if out is None:
+                dev = pixel_values.device
+                out = (torch.empty(d["batch"], d["channels"], d["height"], d["width"], dtype=torch.float32, device=dev) if a["d_pixel_values"] else None,
+                       torch.empty(d["batch"], dtype=torch.float32, device=dev) if a["d_time"] else None)
+        elif out is None or steps is None:
+            raise ValueError("raw addresses need `out` and `steps`")
+        rc = self._lib.scot_plan_rollout_vjp(self._h, _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(predictions, "predictions"),
+                                             _addr(d_predictions, "d_predictions"), int(steps), _addr(out[0], "d_pixel_values"),
+                                             _addr(out[1], "d_time"), float(grad_scale), self._stream(stream, pixel_values))
+        _lib.check(rc, "scot_plan_rollout_vjp")
         return out
 
     def grad_status(self, stream=None):

@@ -4,10 +4,12 @@ cotangent of the prediction: two streams; a call without labels is issued throug
 steps only) against `scot_plan_run` + `scot_plan_vjp` of an adjoint
 plan (one stream, no Python between launches).
 
-usage: python tools/bench_plan_adjoint.py [--batches 64,1] [--python-only] [--root CHECKOUT] [--repeat N]
+usage: python tools/bench_plan_adjoint.py [--batches 64,1] [--python-only] [--root CHECKOUT] [--repeat N] [--rollout-steps N]
   --python-only  only the Python frozen step (what a checkout without adjoint plans can run)
   --root         import the package from another checkout (the parent commit, built there) to time ITS frozen step in the same visit
   --repeat       time the Python step N times (the spread of repeated runs is what two trees are compared against)
+  --rollout-steps N  also time the adjoint of an N-step rollout of the same plan in the same process (`Plan.rollout_vjp`: N recomputed
+                 forwards + N backwards, the forward rollout that produced the predictions not included), next to N x plan_ms
 Prints one JSON line per batch size.  Numbers: profiles/plan_adjoint/README.md."""
 import argparse
 import json
@@ -22,6 +24,7 @@ ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspat
 ap.add_argument("--calls", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--repeat", type=int, default=1)
+ap.add_argument("--rollout-steps", type=int, default=0)
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
 
@@ -79,6 +82,19 @@ for B in [int(b) for b in args.batches.split(",")]:
         res["plan_kept_MB"] = round(info["kept_bytes"] / 1e6, 1)
         res["calls_per_run"], res["calls_per_vjp"] = plan.info["calls"], info["backward_calls"]
         res["identical"] = bool(torch.equal(grads[0], ref[0]) and torch.equal(grads[1], ref[1]))
+        if args.rollout_steps > 0:
+            N = args.rollout_steps
+            preds = torch.empty(N, B, 4, 128, 128, device="cuda")      # the C layout, as scot_plan_rollout writes it
+            plan.rollout(pv.data_ptr(), t.data_ptr(), N, out=preds.data_ptr(), stream=stream)
+            gs = (torch.randn(N, B, 4, 128, 128, device="cuda") / (B * 4 * 128 * 128)).contiguous()
+
+            def rollout_vjp():
+                plan.rollout_vjp(pv.data_ptr(), t.data_ptr(), preds.data_ptr(), gs.data_ptr(), grad_scale=S, out=grads, steps=N, stream=stream)
+            res["rollout_steps"] = N
+            res["rollout_vjp_ms"] = round(timed(rollout_vjp), 3)
+            res["steps_x_plan_ms"] = round(N * res["plan_ms"], 3)
+            res["rollout_vjp_over_steps_x_plan"] = round(res["rollout_vjp_ms"] / res["steps_x_plan_ms"], 4)
+            res["rollout_finite"] = bool(torch.isfinite(grads[0]).all() and torch.isfinite(grads[1]).all())
         res["nonfinite_counted"] = plan.grad_status()[0]
         plan.free()
     model._engine.reset_tapes()
