@@ -453,6 +453,9 @@ __global__ __launch_bounds__(256) void colsum_vec8_kernel(const void* x, int x_d
     atomicAdd(&out[c], sum);
   }
 }
+// (Which of the two kernels runs depends on the ADDRESS of x and y — 32-byte alignment — and they add in different orders: the same
+// values at another alignment give sums a few ulp apart.  Whoever replays a recorded call at relocated addresses, as the plan runtime
+// does, has to keep the alignment of the original buffers to keep the bits; device allocations are 256-byte aligned.)
 extern "C" int scot_colsum(const void* x, int x_dt, const void* y, int y_dt, float* out, int M, int N, int ld, hipStream_t s) {
   if (M <= 0 || N <= 0) return SCOT_ERR_SHAPE;
   if (N % 8 == 0 && ld % 8 == 0 && N <= 2048 && N >= 8 && (((uintptr_t)x | (uintptr_t)y) & 31) == 0) {

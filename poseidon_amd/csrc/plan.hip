@@ -15,6 +15,12 @@
 // beyond the caller's predictions (every step's input) and, from the last step to the first, replays the forward to recompute the
 // saved rows, forms the step's cotangent, replays the backward and carries the input gradient on.
 //
+// A TRAINING plan (image format 4) holds, beside the inference forward, one optimizer step as three more lists — the forward through the
+// loss, the backward with the weight gradients, the optimizer update — and everything a step changes as STATE buffers the image stores
+// by value: scot_plan_train_step copies a batch in, writes the caller's learning rates into the host array the recorded
+// scot_adamw_step call reads at issue time, and replays the three lists; scot_plan_snapshot reads the state back into the image.
+// No arithmetic of its own: clipping, the skip decision and the fp16 gradient scale are the recorded kernels', on the device.
+//
 // A plan is one stream's worth of state: its buffers are reused by every run, so runs of ONE plan must be ordered (same stream, or
 // the caller's own events); two plans are independent.
 #include "common.h"
@@ -38,6 +44,8 @@ SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_DECLARE)
 static void* const g_entry_address[] = {SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_ADDRESS)};
 SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_DECLARE)
 static void* const g_adjoint_entry_address[] = {SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_ADDRESS)};
+SCOT_PLAN_TRAINING_ENTRY_POINTS(SCOT_PLAN_DECLARE)
+static void* const g_training_entry_address[] = {SCOT_PLAN_TRAINING_ENTRY_POINTS(SCOT_PLAN_ADDRESS)};
 
 // ------------------------------------------------------------------ device memory and copies (plain host memory in the CPU emulation)
 namespace {
@@ -46,7 +54,8 @@ enum CopyKind { H2D, D2H, D2D };
 // the emulated build's launch log: everything the plan runtime has put on a stream — copies, fills and replayed calls — is counted,
 // so that a test can see that a refused call issued nothing (scot_plan_emu_issued below; not part of the C ABI)
 long long g_emu_issued = 0;
-inline void* dev_alloc(size_t n) { return malloc(n); }
+// (as aligned as hipMalloc's memory: kernels choose their vector paths by address, and a plan must take the engine's)
+inline void* dev_alloc(size_t n) { return aligned_alloc(256, (n + 255) / 256 * 256); }
 inline void dev_free(void* p) { free(p); }
 inline bool dev_copy(void* dst, const void* src, size_t n, CopyKind, hipStream_t) { ++g_emu_issued; memmove(dst, src, n); return true; }
 inline bool dev_fill(void* dst, int byte, size_t n, hipStream_t) { ++g_emu_issued; memset(dst, byte, n); return true; }
@@ -170,6 +179,16 @@ struct Plan {
   std::vector<size_t> stream_slot_bwd;
   std::vector<std::vector<uint64_t>> ptr_arrays;   // host arrays the entries pass by address
   std::vector<std::vector<int>> int_arrays;
+  std::vector<std::vector<float>> flt_arrays;
+  // training plans: the three step lists (forward, backward, update), the training words, where the update reads lr[groups], and what
+  // scot_plan_snapshot compares a target image with and writes into (the header, the buffer table, each stored buffer's place)
+  std::vector<uint64_t> prog_step[3];
+  std::vector<size_t> stream_slot_step[3];
+  uint64_t n_step[3] = {0, 0, 0};
+  uint64_t train[SCOT_PLAN_TRAIN_WORDS] = {};
+  float* lr = nullptr;
+  uint64_t header[SCOT_PLAN_HEADER_WORDS] = {};
+  std::vector<uint64_t> buffer_table;
   std::vector<float> host_time;                    // scot_plan_rollout: the divided time on its way back to the device
   uint64_t io[SCOT_PLAN_IO_WORDS] = {};
   uint64_t adj[SCOT_PLAN_ADJ_WORDS] = {};
@@ -212,10 +231,12 @@ void* default_peer() {
   return open_peer((dir + "/libscot_hip.so").c_str());
 }
 
-void* resolve(const char* name, uint64_t lib, bool backward) {
-  const int index = backward ? scot_plan_adjoint_entry_index(name) : scot_plan_entry_index(name);
+void* resolve(const char* name, uint64_t lib, int list) {
+  const int index = scot_plan_list_index(name, list);
   if (index < 0) return nullptr;
-  if (lib == 0 || scot_operand_format() == 0) return backward ? g_adjoint_entry_address[index] : g_entry_address[index];
+  if (lib == 0 || scot_operand_format() == 0)
+    return list == SCOT_PLAN_LIST_TRAINING ? g_training_entry_address[index]
+                                           : (list == SCOT_PLAN_LIST_ADJOINT ? g_adjoint_entry_address[index] : g_entry_address[index]);
   if (!g_peer) g_peer = default_peer();
   return g_peer ? dlsym(g_peer, name) : nullptr;
 }
@@ -232,23 +253,32 @@ bool materialise(Plan* pl, uint64_t tagw, uint64_t val, uint64_t* out, bool* is_
   }
 }
 
-int replay(Plan* pl, hipStream_t stream, bool backward = false) {
-  std::vector<uint64_t>& prog = backward ? pl->prog_bwd : pl->prog;
-  for (size_t s : backward ? pl->stream_slot_bwd : pl->stream_slot) prog[s] = (uint64_t)(uintptr_t)stream;
+int replay_list(std::vector<uint64_t>& prog, const std::vector<size_t>& slots, uint64_t calls, hipStream_t stream) {
+  for (size_t s : slots) prog[s] = (uint64_t)(uintptr_t)stream;
 #ifdef SCOT_HIPEMU
-  g_emu_issued += (long long)(backward ? pl->n_backward : pl->n_entries);
+  g_emu_issued += (long long)calls;
+#else
+  (void)calls;
 #endif
   int fail = -1;
   return scot_tape_replay(prog.data(), prog.size(), &fail);
 }
 
+int replay(Plan* pl, hipStream_t stream, bool backward = false) {
+  return backward ? replay_list(pl->prog_bwd, pl->stream_slot_bwd, pl->n_backward, stream)
+                  : replay_list(pl->prog, pl->stream_slot, pl->n_entries, stream);
+}
+
+// list s of a training plan's step: 0 forward through the loss, 1 backward, 2 update
+int replay_step(Plan* pl, int s, hipStream_t stream) { return replay_list(pl->prog_step[s], pl->stream_slot_step[s], pl->n_step[s], stream); }
+
 // one entries section -> the entry points' addresses (false: one is missing)
-bool resolve_section(const scot_plan_view& v, const uint64_t* e, uint64_t n, bool backward, std::vector<void*>* fn) {
+bool resolve_section(const scot_plan_view& v, const uint64_t* e, uint64_t n, int list, std::vector<void*>* fn) {
   fn->resize(n);
   uint64_t w = 0;
   for (uint64_t i = 0; i < n; ++i) {
     const uint64_t name = e[w], lib = e[w + 1], ni = e[w + 2], nf = e[w + 3];
-    (*fn)[i] = resolve((const char*)(v.names + name * SCOT_PLAN_NAME_BYTES), lib, backward);
+    (*fn)[i] = resolve((const char*)(v.names + name * SCOT_PLAN_NAME_BYTES), lib, list);
     if (!(*fn)[i]) return false;
     w += 4 + 2 * ni + nf;
   }
@@ -284,12 +314,17 @@ bool build_program(Plan* pl, const uint64_t* e, uint64_t n, uint64_t words, cons
 
 char* adj_ptr(Plan* pl, int span) { return pl->buf[pl->adj[span]] + pl->adj[span + 1]; }
 
+char* train_ptr(Plan* pl, int span) { return pl->buf[pl->train[span]] + pl->train[span + 1]; }
+
 char* io_ptr(Plan* pl, int buf_word, int off_word) { return pl->buf[pl->io[buf_word]] + pl->io[off_word]; }
 }  // namespace
 
 extern "C" const char* scot_plan_entry_point(int i) { return i >= 0 && i < SCOT_PLAN_N_ENTRY_POINTS ? scot_plan_entry_names[i] : nullptr; }
 extern "C" const char* scot_plan_adjoint_entry_point(int i) {
   return i >= 0 && i < SCOT_PLAN_N_ADJOINT_ENTRY_POINTS ? scot_plan_adjoint_entry_names[i] : nullptr;
+}
+extern "C" const char* scot_plan_training_entry_point(int i) {
+  return i >= 0 && i < SCOT_PLAN_N_TRAINING_ENTRY_POINTS ? scot_plan_training_entry_names[i] : nullptr;
 }
 #ifdef SCOT_HIPEMU
 extern "C" long long scot_plan_emu_issued() { return g_emu_issued; }
@@ -332,13 +367,21 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
     pl->format = (int)v.format;
     pl->n_backward = v.n_backward;
     if (v.adj) memcpy(pl->adj, v.adj, sizeof(pl->adj));
+    if (v.train) memcpy(pl->train, v.train, sizeof(pl->train));
+    memcpy(pl->header, v.h, sizeof(pl->header));
+    pl->buffer_table.assign(v.buffers, v.buffers + 4 * v.n_buffers);
     pl->operand_format = (int)v.h[SCOT_PLAN_H_OPERAND];
     pl->compute = (int)v.h[SCOT_PLAN_H_COMPUTE];
     // every entry point, before anything is allocated
-    std::vector<void*> fn, fn_bwd;
+    std::vector<void*> fn, fn_bwd, fn_step[3];
     uint64_t w = 0;
-    if (!resolve_section(v, v.entries, v.n_entries, false, &fn) || !resolve_section(v, v.backward, v.n_backward, true, &fn_bwd))
+    if (!resolve_section(v, v.entries, v.n_entries, SCOT_PLAN_LIST_FORWARD, &fn) ||
+        !resolve_section(v, v.backward, v.n_backward, SCOT_PLAN_LIST_ADJOINT, &fn_bwd))
       status = SCOT_ERR_UNSUPPORTED;
+    for (int s = 0; s < 3; ++s) {
+      pl->n_step[s] = v.n_step[s];
+      if (!resolve_section(v, v.step[s], v.n_step[s], SCOT_PLAN_LIST_TRAINING, &fn_step[s])) status = SCOT_ERR_UNSUPPORTED;
+    }
     // one slab, every buffer on a 256-byte boundary
     std::vector<size_t> off(v.n_buffers);
     size_t total = 0;
@@ -362,7 +405,7 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
       // (scratch is zeroed once so that a first run never reads bytes of whoever held the memory before; scot_plan_poison overwrites it)
       if (!dev_fill(pl->slab, 0, total, stream)) status = SCOT_ERR_LAUNCH;
       for (uint64_t i = 0; i < v.n_buffers && status == SCOT_OK; ++i)
-        if (v.buffers[4 * i] == SCOT_PLAN_BUF_CONSTANT &&
+        if ((v.buffers[4 * i] == SCOT_PLAN_BUF_CONSTANT || (v.buffers[4 * i] == SCOT_PLAN_BUF_STATE && v.train && v.buffers[4 * i + 3] == 1)) &&
             !dev_copy(pl->buf[i], v.data + v.buffers[4 * i + 2], (size_t)v.buffers[4 * i + 1], H2D, stream))
           status = SCOT_ERR_LAUNCH;
     }
@@ -372,7 +415,15 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
       w = 0;
       for (uint64_t i = 0; i < v.n_arrays; ++i) {
         const uint64_t kind = v.arrays[w], cnt = v.arrays[w + 1];
-        if (kind == 0) {
+        if (kind == 2) {
+          std::vector<float> a(cnt ? cnt : 1);
+          for (uint64_t k = 0; k < cnt; ++k) {
+            const uint32_t bits = (uint32_t)v.arrays[w + 3 + 2 * k];
+            memcpy(&a[k], &bits, 4);
+          }
+          pl->flt_arrays.push_back(std::move(a));
+          array_address.push_back((uint64_t)(uintptr_t)pl->flt_arrays.back().data());
+        } else if (kind == 0) {
           std::vector<int> a(cnt ? cnt : 1);
           for (uint64_t k = 0; k < cnt; ++k) a[k] = (int)(int64_t)v.arrays[w + 3 + 2 * k];
           pl->int_arrays.push_back(std::move(a));
@@ -394,6 +445,15 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
         (!build_program(pl, v.entries, v.n_entries, v.entries_words, fn, array_address, &pl->prog, &pl->stream_slot) ||
          !build_program(pl, v.backward, v.n_backward, v.backward_words, fn_bwd, array_address, &pl->prog_bwd, &pl->stream_slot_bwd)))
       status = SCOT_ERR_SHAPE;
+    for (int s = 0; s < 3 && status == SCOT_OK; ++s)
+      if (!build_program(pl, v.step[s], v.n_step[s], v.step_words[s], fn_step[s], array_address, &pl->prog_step[s], &pl->stream_slot_step[s]))
+        status = SCOT_ERR_SHAPE;
+    if (status == SCOT_OK && v.train) {      // where the recorded scot_adamw_step reads lr[groups] (validated: an array of that many floats)
+      const uint64_t* e = v.step[2];
+      uint64_t at = 0;
+      for (uint64_t i = 0; i < v.train[SCOT_PLAN_TR_LR_ENTRY]; ++i) at += 4 + 2 * e[at + 2] + e[at + 3];
+      pl->lr = (float*)(uintptr_t)array_address[e[at + 5 + 2 * v.train[SCOT_PLAN_TR_LR_ARG]]];
+    }
     // the image may be released when this returns: the uploads read it
     if (status == SCOT_OK && !dev_sync(stream)) status = SCOT_ERR_LAUNCH;
   } catch (const std::bad_alloc&) {
@@ -662,4 +722,117 @@ extern "C" int scot_plan_rollout_vjp(void* plan, const float* pixel_values, cons
   }
   // (host_time and host_scale are pageable memory: the runtime has staged them by the time the copy calls returned)
   return SCOT_OK;
+}
+
+// ------------------------------------------------------------------ training plans (image format 4)
+// out[8]: has training, parameter groups, floats in the arena, calls of one step, bytes of labels, bytes kept between the step's forward
+// and its backward, whether the gradient scale is dynamic, 0.  Format-1/2 plan: all zeros, status 0.
+extern "C" int scot_plan_describe_training(void* plan, long long* out) {
+  Plan* pl = as_plan(plan);
+  if (!pl || !out) return SCOT_ERR_SHAPE;
+  memset(out, 0, 8 * sizeof(long long));
+  if (pl->format != SCOT_PLAN_FORMAT_TRAINING) return SCOT_OK;
+  const uint64_t* t = pl->train;
+  out[0] = 1;
+  out[1] = (long long)t[SCOT_PLAN_TR_GROUPS];
+  out[2] = (long long)t[SCOT_PLAN_TR_ARENA_FLOATS];
+  out[3] = (long long)(pl->n_step[0] + pl->n_step[1] + pl->n_step[2]);
+  out[4] = (long long)t[SCOT_PLAN_TR_LABELS + 2];
+  out[5] = (long long)t[SCOT_PLAN_TR_KEPT_BYTES];
+  out[6] = (long long)(t[SCOT_PLAN_TR_FLAGS] & 1);
+  return SCOT_OK;
+}
+
+// the batch -> the plan's input copies (the caller has checked the pointers)
+static bool copy_batch_in(Plan* pl, const float* pixel_values, const float* time, const float* labels, hipStream_t stream) {
+  const uint64_t* io = pl->io;
+  const size_t plane = (size_t)(io[SCOT_PLAN_IO_B] * io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * 4);
+  if (!dev_copy(io_ptr(pl, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF), pixel_values, plane * io[SCOT_PLAN_IO_CIN], D2D, stream)) return false;
+  if (time && !dev_copy(io_ptr(pl, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF), time, (size_t)io[SCOT_PLAN_IO_TIME_BYTES], D2D, stream)) return false;
+  return dev_copy(train_ptr(pl, SCOT_PLAN_TR_LABELS), labels, (size_t)pl->train[SCOT_PLAN_TR_LABELS + 2], D2D, stream);
+}
+
+static int check_batch(Plan* pl, const void* pixel_values, const void* time, const void* labels) {
+  if (pl->format != SCOT_PLAN_FORMAT_TRAINING) return SCOT_ERR_UNSUPPORTED;
+  if (!pixel_values || !labels) return SCOT_ERR_SHAPE;
+  if ((pl->io[SCOT_PLAN_IO_HAS_TIME] != 0) != (time != nullptr)) return SCOT_ERR_SHAPE;
+  return SCOT_OK;
+}
+
+// loss [1] <- what model(pixel_values, time, labels=labels).loss returns, prediction (may be NULL) <- its output: the step's forward
+// alone.  No state buffer is written.
+extern "C" int scot_plan_loss(void* plan, const float* pixel_values, const float* time, const float* labels, float* loss, float* prediction,
+                              hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  int rc = check_batch(pl, pixel_values, time, labels);
+  if (rc != SCOT_OK) return rc;
+  if (!loss) return SCOT_ERR_SHAPE;
+  if (!copy_batch_in(pl, pixel_values, time, labels, stream)) return SCOT_ERR_LAUNCH;
+  rc = replay_step(pl, 0, stream);
+  if (rc != SCOT_OK) return rc;
+  if (!dev_copy(loss, train_ptr(pl, SCOT_PLAN_TR_LOSS), 4, D2D, stream)) return SCOT_ERR_LAUNCH;
+  if (prediction && !dev_copy(prediction, train_ptr(pl, SCOT_PLAN_TR_PRED), (size_t)pl->train[SCOT_PLAN_TR_PRED + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
+  return SCOT_OK;
+}
+
+// One optimizer step on the batch: forward, loss, backward, update (include/scot_plan.h).  lr is HOST memory, read before the call
+// returns: it goes into the plan's own array, which the recorded scot_adamw_step call reads when it is issued.
+extern "C" int scot_plan_train_step(void* plan, const float* pixel_values, const float* time, const float* labels, const float* lr, float* loss,
+                                    hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  int rc = check_batch(pl, pixel_values, time, labels);
+  if (rc != SCOT_OK) return rc;
+  if (!lr || !pl->lr) return SCOT_ERR_SHAPE;
+  if (!copy_batch_in(pl, pixel_values, time, labels, stream)) return SCOT_ERR_LAUNCH;
+  memcpy(pl->lr, lr, (size_t)pl->train[SCOT_PLAN_TR_GROUPS] * sizeof(float));
+  for (int s = 0; s < 3; ++s)
+    if ((rc = replay_step(pl, s, stream)) != SCOT_OK) return rc;
+  if (loss && !dev_copy(loss, train_ptr(pl, SCOT_PLAN_TR_LOSS), 4, D2D, stream)) return SCOT_ERR_LAUNCH;
+  return SCOT_OK;
+}
+
+// out[6]: steps applied, steps skipped, gradient scale (1 where it is not dynamic), last gradient norm before clipping, last clip
+// coefficient, non-finite values the un-scale passes have counted.  Waits for `stream`.
+extern "C" int scot_plan_train_status(void* plan, double* out, hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl || !out) return SCOT_ERR_SHAPE;
+  memset(out, 0, 6 * sizeof(double));
+  if (pl->format != SCOT_PLAN_FORMAT_TRAINING) return SCOT_ERR_UNSUPPORTED;
+  int steps[2] = {0, 0}, counted = 0;
+  float clip[3] = {0.0f, 0.0f, 0.0f}, scale[4] = {1.0f, 1.0f, 0.0f, 0.0f};
+  const bool dyn = (pl->train[SCOT_PLAN_TR_FLAGS] & 1) != 0;
+  if (!dev_copy(steps, train_ptr(pl, SCOT_PLAN_TR_STEP_STATE), sizeof(steps), D2H, stream)) return SCOT_ERR_LAUNCH;
+  if (!dev_copy(clip, train_ptr(pl, SCOT_PLAN_TR_CLIP), sizeof(clip), D2H, stream)) return SCOT_ERR_LAUNCH;
+  if (dyn && (!dev_copy(scale, train_ptr(pl, SCOT_PLAN_TR_SCALE_STATE), sizeof(scale), D2H, stream) ||
+              !dev_copy(&counted, train_ptr(pl, SCOT_PLAN_TR_COUNTER), sizeof(counted), D2H, stream)))
+    return SCOT_ERR_LAUNCH;
+  if (!dev_sync(stream)) return SCOT_ERR_LAUNCH;
+  out[0] = steps[0];
+  out[1] = steps[1];
+  out[2] = scale[0];
+  out[3] = clip[1];
+  out[4] = clip[0];
+  out[5] = counted;
+  return SCOT_OK;
+}
+
+// image <- the current value of every stored STATE buffer.  `image` is a host copy of the image this plan was loaded from: same size,
+// header, buffer table and training words (anything else: -1, nothing copied).  Waits for `stream`.
+extern "C" int scot_plan_snapshot(void* plan, void* image, size_t bytes, hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  if (pl->format != SCOT_PLAN_FORMAT_TRAINING) return SCOT_ERR_UNSUPPORTED;
+  const uint64_t* h = pl->header;
+  if (!image || bytes != (size_t)h[SCOT_PLAN_H_BYTES] || memcmp(image, h, sizeof(pl->header)) != 0) return SCOT_ERR_SHAPE;
+  char* b = (char*)image;      // (the header is the loaded one's: every offset below was validated at load against this size)
+  if (memcmp(b + h[SCOT_PLAN_H_BUFFERS_OFF], pl->buffer_table.data(), pl->buffer_table.size() * 8) != 0 ||
+      memcmp(b + h[SCOT_PLAN_H_TRAIN_OFF], pl->train, sizeof(pl->train)) != 0)
+    return SCOT_ERR_SHAPE;
+  for (size_t i = 0; i < pl->buf.size(); ++i)
+    if (pl->buf_kind[i] == SCOT_PLAN_BUF_STATE && pl->buffer_table[4 * i + 3] == 1 &&
+        !dev_copy(b + h[SCOT_PLAN_H_DATA_OFF] + pl->buffer_table[4 * i + 2], pl->buf[i], (size_t)pl->buf_bytes[i], D2H, stream))
+      return SCOT_ERR_LAUNCH;
+  return dev_sync(stream) ? SCOT_OK : SCOT_ERR_LAUNCH;
 }

@@ -1,4 +1,4 @@
-// plan_image — the format of an exported plan (inference, or inference + adjoint) and its validator.  Header-only and HIP-free: plan.hip uses it inside the
+// plan_image — the format of an exported plan (inference, inference + adjoint, or training) and its validator.  Header-only and HIP-free: plan.hip uses it inside the
 // library, tools/plan_image_check.cc compiles it alone (with the host sanitizers) and runs it over good and corrupt images.
 //
 // A plan image (poseidon_amd/plan.py writes it) is ONE recorded inference forward of the engine for one input signature, made
@@ -7,7 +7,7 @@
 //
 //   header   SCOT_PLAN_HEADER_WORDS words (indices below)
 //   names    n_names records of SCOT_PLAN_NAME_BYTES bytes: NUL-terminated entry-point names
-//   buffers  n_buffers records of 4 words: kind, bytes, offset of the content in the data section (constants), 0
+//   buffers  n_buffers records of 4 words: kind, bytes, offset of the content in the data section (constants), 0 (format 4: 1 = stored state)
 //   entries  n_entries variable-length records: name index, library (0 = the build that loads the image, 1 = the bfloat16 build: the
 //            split-MFMA trunk GEMMs of the binary16 mode run there), n_int, n_flt, n_int argument pairs, n_flt words of raw float bits
 //   arrays   n_arrays host arrays passed by address: kind (0 = int32, 1 = pointers), count, count argument pairs
@@ -27,6 +27,22 @@
 //   buffers  may have kind SCOT_PLAN_BUF_STATE: device memory the RUNTIME writes (zeroed at load, never poisoned)
 //
 // The `entries` section of a format-2 image is the DIFFERENTIABLE forward (it saves what the backward reads).
+//
+// Format 4 (a TRAINING plan, `export_plan(..., labels=..., train=optimizer)`; format 3 is unassigned) is format 1 plus ONE header word,
+// the offset of a training section; everything else is named from there:
+//
+//   training SCOT_PLAN_TRAIN_WORDS words: the (count, offset, words) of three more entries sections — the step's forward through the
+//            loss, its backward with the weight gradients (the zero fill of the accumulated gradients first, the un-scale passes last)
+//            and the optimizer update — each checked against a THIRD list, SCOT_PLAN_TRAINING_ENTRY_POINTS; the (buffer, offset,
+//            bytes) of the labels' copy, the loss and the step forward's prediction; the state spans (fp32 parameter arena, both
+//            moments, the 16-bit copies, the step counters, the three clip floats, the gradient-scale state and its non-finite
+//            counter); the number of parameter groups and the lr patch point: which argument of which update entry is the host array
+//            lr[groups] that scot_plan_train_step overwrites
+//   buffers  a STATE buffer whose fourth word is 1 is stored in the data section by value (its third word is the offset, as for a
+//            constant): uploaded at load, written by the steps, read back by scot_plan_snapshot
+//   arrays   kind 2 = floats (raw bits as SCOT_PLAN_ARG_INT pairs): the optimizer's per-group learning rates and weight decays
+//
+// The `entries` section of a format-4 image is the plain inference forward; it reads the 16-bit copies the update keeps current.
 #ifndef SCOT_PLAN_IMAGE_H
 #define SCOT_PLAN_IMAGE_H
 #include <stddef.h>
@@ -36,10 +52,13 @@
 #define SCOT_PLAN_MAGIC 0x4e414c50544f4353ull /* "SCOTPLAN" */
 #define SCOT_PLAN_FORMAT 1
 #define SCOT_PLAN_FORMAT_ADJOINT 2
+#define SCOT_PLAN_FORMAT_TRAINING 4 /* (3 is unassigned) */
 #define SCOT_PLAN_HEADER_WORDS 32
 #define SCOT_PLAN_NAME_BYTES 48
 #define SCOT_PLAN_IO_WORDS 24
 #define SCOT_PLAN_ADJ_WORDS 24
+#define SCOT_PLAN_TRAIN_WORDS 64
+#define SCOT_PLAN_ADAMW_LR_ARG 6 /* scot_adamw_step(params, grads, exp_avg, exp_avg_sq, map8, n, LR, wd, ...): the patch point */
 #define SCOT_PLAN_MAX_INT 48 /* = SCOT_TAPE_MAX_INT of host_tape.hip: what one replayed call can carry */
 #define SCOT_PLAN_MAX_FLT 8
 
@@ -47,7 +66,8 @@ enum { SCOT_PLAN_H_MAGIC, SCOT_PLAN_H_FORMAT, SCOT_PLAN_H_ABI, SCOT_PLAN_H_OPERA
        SCOT_PLAN_H_NNAMES, SCOT_PLAN_H_NAMES_OFF, SCOT_PLAN_H_NBUFFERS, SCOT_PLAN_H_BUFFERS_OFF, SCOT_PLAN_H_NENTRIES,
        SCOT_PLAN_H_ENTRIES_OFF, SCOT_PLAN_H_ENTRIES_WORDS, SCOT_PLAN_H_NARRAYS, SCOT_PLAN_H_ARRAYS_OFF, SCOT_PLAN_H_ARRAYS_WORDS,
        SCOT_PLAN_H_IO_OFF, SCOT_PLAN_H_DATA_OFF, SCOT_PLAN_H_DATA_BYTES,
-       /* format 2 */ SCOT_PLAN_H_NBACKWARD, SCOT_PLAN_H_BACKWARD_OFF, SCOT_PLAN_H_BACKWARD_WORDS, SCOT_PLAN_H_ADJ_OFF };
+       /* format 2 */ SCOT_PLAN_H_NBACKWARD, SCOT_PLAN_H_BACKWARD_OFF, SCOT_PLAN_H_BACKWARD_WORDS, SCOT_PLAN_H_ADJ_OFF,
+       /* format 4 */ SCOT_PLAN_H_TRAIN_OFF };
 enum { SCOT_PLAN_BUF_CONSTANT, SCOT_PLAN_BUF_INPUT, SCOT_PLAN_BUF_OUTPUT, SCOT_PLAN_BUF_SCRATCH, SCOT_PLAN_BUF_STATE };
 enum { SCOT_PLAN_ARG_INT, SCOT_PLAN_ARG_NULL, SCOT_PLAN_ARG_PTR, SCOT_PLAN_ARG_STREAM, SCOT_PLAN_ARG_ARRAY };
 enum { SCOT_PLAN_IO_B, SCOT_PLAN_IO_CIN, SCOT_PLAN_IO_H, SCOT_PLAN_IO_W, SCOT_PLAN_IO_COUT, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF,
@@ -57,6 +77,16 @@ enum { SCOT_PLAN_IO_B, SCOT_PLAN_IO_CIN, SCOT_PLAN_IO_H, SCOT_PLAN_IO_W, SCOT_PL
 enum { SCOT_PLAN_ADJ_FLAGS, SCOT_PLAN_ADJ_COT, SCOT_PLAN_ADJ_DPV = SCOT_PLAN_ADJ_COT + 3, SCOT_PLAN_ADJ_DTIME = SCOT_PLAN_ADJ_DPV + 3,
        SCOT_PLAN_ADJ_STATE = SCOT_PLAN_ADJ_DTIME + 3, SCOT_PLAN_ADJ_COUNTER = SCOT_PLAN_ADJ_STATE + 3,
        SCOT_PLAN_ADJ_SCALE_EXP = SCOT_PLAN_ADJ_COUNTER + 3, SCOT_PLAN_ADJ_KEPT_BYTES };
+/* the training section: FLAGS bit 0 = the gradient scale is dynamic (fp16); a list is (count, offset in the image, words); a span is
+ * (buffer, offset, bytes), bytes 0 = absent */
+enum { SCOT_PLAN_TR_FLAGS, SCOT_PLAN_TR_GROUPS, SCOT_PLAN_TR_ARENA_FLOATS, SCOT_PLAN_TR_FWD, SCOT_PLAN_TR_BWD = SCOT_PLAN_TR_FWD + 3,
+       SCOT_PLAN_TR_UPD = SCOT_PLAN_TR_BWD + 3, SCOT_PLAN_TR_LR_ENTRY = SCOT_PLAN_TR_UPD + 3, SCOT_PLAN_TR_LR_ARG, SCOT_PLAN_TR_KEPT_BYTES,
+       SCOT_PLAN_TR_LABELS, SCOT_PLAN_TR_LOSS = SCOT_PLAN_TR_LABELS + 3, SCOT_PLAN_TR_PRED = SCOT_PLAN_TR_LOSS + 3,
+       SCOT_PLAN_TR_ARENA = SCOT_PLAN_TR_PRED + 3, SCOT_PLAN_TR_EXP_AVG = SCOT_PLAN_TR_ARENA + 3,
+       SCOT_PLAN_TR_EXP_AVG_SQ = SCOT_PLAN_TR_EXP_AVG + 3, SCOT_PLAN_TR_SHADOW = SCOT_PLAN_TR_EXP_AVG_SQ + 3,
+       SCOT_PLAN_TR_SHADOW_T = SCOT_PLAN_TR_SHADOW + 3, SCOT_PLAN_TR_STEP_STATE = SCOT_PLAN_TR_SHADOW_T + 3,
+       SCOT_PLAN_TR_CLIP = SCOT_PLAN_TR_STEP_STATE + 3, SCOT_PLAN_TR_SCALE_STATE = SCOT_PLAN_TR_CLIP + 3,
+       SCOT_PLAN_TR_COUNTER = SCOT_PLAN_TR_SCALE_STATE + 3, SCOT_PLAN_TR_END = SCOT_PLAN_TR_COUNTER + 3 };
 
 // What a forward may call: what can run is what is listed.  (X-macro: plan.hip builds the table of addresses from it.)
 #define SCOT_PLAN_ENTRY_POINTS(X)                                                                                                     \
@@ -72,11 +102,25 @@ enum { SCOT_PLAN_ADJ_FLAGS, SCOT_PLAN_ADJ_COT, SCOT_PLAN_ADJ_DPV = SCOT_PLAN_ADJ
   X(scot_scale_residual) X(scot_dwconv7) X(scot_conv5) X(scot_scale_inplace_dev) X(scot_pow2_rescale) X(scot_colscale_dev)           \
   X(scot_axpy_dev) X(scot_memset_async) X(scot_memcpy_async)
 
+// What the three step lists of a training plan may call: the differentiable forward with the loss, the whole backward — data AND
+// weight gradients —, the gradient arena's fill and un-scale, and the optimizer update.  A list of its own: none of the weight-gradient
+// or optimizer names enters the two lists above, so an inference or adjoint image still cannot name them.
+#define SCOT_PLAN_TRAINING_ENTRY_POINTS(X)                                                                                          \
+  SCOT_PLAN_ENTRY_POINTS(X)                                                                                                          \
+  X(scot_loss_finish) X(scot_loss_bwd) X(scot_cln_bwd) X(scot_window_attn_bwd_rep) X(scot_block_tail_bwd) X(scot_proj_cln_bwd)      \
+  X(scot_scale_inplace_dev) X(scot_pow2_rescale) X(scot_colscale_dev) X(scot_axpy_dev) X(scot_wgrad_group) X(scot_wgrad_mlp)        \
+  X(scot_colsum) X(scot_conv5_wgrad) X(scot_dwconv7_wgrad) X(scot_nchw_channel_sum) X(scot_partial_colsum_batch)                    \
+  X(scot_replica_reduce) X(scot_cpb_bwd_batched) X(scot_batch_sum) X(scot_segments_scale) X(scot_grad_sqnorm) X(scot_clip_coef)     \
+  X(scot_adamw_step) X(scot_optim_finish) X(scot_transpose_cast)
+
 #define SCOT_PLAN_NAME_STRING(n) #n,
 static const char* const scot_plan_entry_names[] = {SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_NAME_STRING)};
 #define SCOT_PLAN_N_ENTRY_POINTS ((int)(sizeof(scot_plan_entry_names) / sizeof(scot_plan_entry_names[0])))
 static const char* const scot_plan_adjoint_entry_names[] = {SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_NAME_STRING)};
 #define SCOT_PLAN_N_ADJOINT_ENTRY_POINTS ((int)(sizeof(scot_plan_adjoint_entry_names) / sizeof(scot_plan_adjoint_entry_names[0])))
+static const char* const scot_plan_training_entry_names[] = {SCOT_PLAN_TRAINING_ENTRY_POINTS(SCOT_PLAN_NAME_STRING)};
+#define SCOT_PLAN_N_TRAINING_ENTRY_POINTS ((int)(sizeof(scot_plan_training_entry_names) / sizeof(scot_plan_training_entry_names[0])))
+enum { SCOT_PLAN_LIST_FORWARD, SCOT_PLAN_LIST_ADJOINT, SCOT_PLAN_LIST_TRAINING };
 
 static inline int scot_plan_entry_index(const char* name) {
   for (int i = 0; i < SCOT_PLAN_N_ENTRY_POINTS; ++i)
@@ -88,6 +132,18 @@ static inline int scot_plan_adjoint_entry_index(const char* name) {
   for (int i = 0; i < SCOT_PLAN_N_ADJOINT_ENTRY_POINTS; ++i)
     if (strcmp(name, scot_plan_adjoint_entry_names[i]) == 0) return i;
   return -1;
+}
+
+static inline int scot_plan_training_entry_index(const char* name) {
+  for (int i = 0; i < SCOT_PLAN_N_TRAINING_ENTRY_POINTS; ++i)
+    if (strcmp(name, scot_plan_training_entry_names[i]) == 0) return i;
+  return -1;
+}
+
+// the index of `name` in one of the three lists (SCOT_PLAN_LIST_*), -1: not listed there
+static inline int scot_plan_list_index(const char* name, int list) {
+  return list == SCOT_PLAN_LIST_TRAINING ? scot_plan_training_entry_index(name)
+                                         : (list == SCOT_PLAN_LIST_ADJOINT ? scot_plan_adjoint_entry_index(name) : scot_plan_entry_index(name));
 }
 
 // status codes of the C ABI (common.h), restated so that this header needs nothing else
@@ -110,6 +166,10 @@ typedef struct {
   uint64_t format, n_backward, backward_words;
   const uint64_t* backward;
   const uint64_t* adj;
+  /* format 4 (zero / NULL otherwise): the training words and the three step lists (forward, backward, update) they name */
+  const uint64_t* train;
+  const uint64_t* step[3];
+  uint64_t n_step[3], step_words[3];
 } scot_plan_view;
 
 static inline uint64_t scot_plan_word(const uint8_t* p) {
@@ -142,7 +202,7 @@ static inline int scot_plan_arg_ok(const scot_plan_view* v, uint64_t tagw, uint6
 }
 
 // one entries section: record bounds, n_int / n_flt, every argument pair, every name in the section's OWN list
-static inline int scot_plan_entries_ok(const scot_plan_view* v, const uint64_t* e, uint64_t n, uint64_t words, int backward) {
+static inline int scot_plan_entries_ok(const scot_plan_view* v, const uint64_t* e, uint64_t n, uint64_t words, int list) {
   uint64_t w = 0;
   for (uint64_t i = 0; i < n; ++i) {
     if (words - w < 4) return SCOT_PLAN_ERR_SHAPE;
@@ -154,7 +214,7 @@ static inline int scot_plan_entries_ok(const scot_plan_view* v, const uint64_t* 
     for (uint64_t k = 0; k < nf; ++k)
       if (e[w + 4 + 2 * ni + k] >> 32) return SCOT_PLAN_ERR_SHAPE;      /* raw bits of ONE float */
     const char* nm = (const char*)(v->names + name * SCOT_PLAN_NAME_BYTES);
-    if ((backward ? scot_plan_adjoint_entry_index(nm) : scot_plan_entry_index(nm)) < 0) return SCOT_PLAN_ERR_UNSUPPORTED;
+    if (scot_plan_list_index(nm, list) < 0) return SCOT_PLAN_ERR_UNSUPPORTED;
     w += 4 + 2 * ni + nf;
   }
   return w == words ? SCOT_PLAN_OK : SCOT_PLAN_ERR_SHAPE;
@@ -167,6 +227,65 @@ static inline int scot_plan_io_span_ok(const scot_plan_view* v, uint64_t buf, ui
   return off <= cap && n <= cap - off && v->buffers[4 * buf] == kind;
 }
 
+// array `index` of the arrays section -> its kind and count (the section has been validated)
+static inline void scot_plan_array_at(const scot_plan_view* v, uint64_t index, uint64_t* kind, uint64_t* count) {
+  uint64_t w = 0;
+  for (uint64_t i = 0; i < index; ++i) w += 2 + 2 * v->arrays[w + 1];
+  *kind = v->arrays[w];
+  *count = v->arrays[w + 1];
+}
+
+// the training words of a format-4 image, after everything else has been validated: the lr patch point names an array of exactly
+// `groups` floats of an update entry called scot_adamw_step; labels in an input buffer, loss and prediction in output buffers, every
+// state span whole inside a STATE buffer that the image initialises (so none can touch a constant)
+static inline int scot_plan_training_ok(const scot_plan_view* v) {
+  const uint64_t* t = v->train;
+  const uint64_t* io = v->io;
+  const uint64_t groups = t[SCOT_PLAN_TR_GROUPS], floats = t[SCOT_PLAN_TR_ARENA_FLOATS];
+  if (t[SCOT_PLAN_TR_FLAGS] > 1 || groups < 1 || groups > 8 || floats == 0 || floats % 8 || floats > ((uint64_t)1 << 36)) return SCOT_PLAN_ERR_SHAPE;
+  if (!v->n_step[0] || !v->n_step[1] || !v->n_step[2] || t[SCOT_PLAN_TR_LR_ENTRY] >= v->n_step[2]) return SCOT_PLAN_ERR_SHAPE;
+  const uint64_t* e = v->step[2];
+  uint64_t w = 0;
+  for (uint64_t i = 0; i < t[SCOT_PLAN_TR_LR_ENTRY]; ++i) w += 4 + 2 * e[w + 2] + e[w + 3];
+  if (strcmp((const char*)(v->names + e[w] * SCOT_PLAN_NAME_BYTES), "scot_adamw_step") != 0) return SCOT_PLAN_ERR_SHAPE;
+  /* (the weight-decay array behind it has the same kind and length: only lr's own position is a patch point) */
+  if (t[SCOT_PLAN_TR_LR_ARG] != SCOT_PLAN_ADAMW_LR_ARG || t[SCOT_PLAN_TR_LR_ARG] >= e[w + 2] ||
+      (e[w + 4 + 2 * t[SCOT_PLAN_TR_LR_ARG]] & 0xff) != SCOT_PLAN_ARG_ARRAY)
+    return SCOT_PLAN_ERR_SHAPE;
+  uint64_t kind = 0, count = 0;
+  scot_plan_array_at(v, e[w + 5 + 2 * t[SCOT_PLAN_TR_LR_ARG]], &kind, &count);
+  if (kind != 2 || count != groups) return SCOT_PLAN_ERR_SHAPE;
+  const uint64_t out_bytes = io[SCOT_PLAN_IO_B] * io[SCOT_PLAN_IO_COUT] * io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * 4;
+  const uint64_t dyn = t[SCOT_PLAN_TR_FLAGS] & 1, half = t[SCOT_PLAN_TR_SHADOW + 2] ? floats * 2 : 0;
+  const uint64_t want[12][3] = {{SCOT_PLAN_TR_LABELS, out_bytes, SCOT_PLAN_BUF_INPUT},
+                                {SCOT_PLAN_TR_LOSS, 4, SCOT_PLAN_BUF_OUTPUT},
+                                {SCOT_PLAN_TR_PRED, out_bytes, SCOT_PLAN_BUF_OUTPUT},
+                                {SCOT_PLAN_TR_ARENA, floats * 4, SCOT_PLAN_BUF_STATE},
+                                {SCOT_PLAN_TR_EXP_AVG, floats * 4, SCOT_PLAN_BUF_STATE},
+                                {SCOT_PLAN_TR_EXP_AVG_SQ, floats * 4, SCOT_PLAN_BUF_STATE},
+                                {SCOT_PLAN_TR_SHADOW, half, SCOT_PLAN_BUF_STATE},
+                                {SCOT_PLAN_TR_SHADOW_T, (uint64_t)(t[SCOT_PLAN_TR_SHADOW_T + 2] ? half : 0), SCOT_PLAN_BUF_STATE},
+                                {SCOT_PLAN_TR_STEP_STATE, 8, SCOT_PLAN_BUF_STATE},
+                                {SCOT_PLAN_TR_CLIP, 12, SCOT_PLAN_BUF_STATE},
+                                {SCOT_PLAN_TR_SCALE_STATE, (uint64_t)(dyn ? 16 : 0), SCOT_PLAN_BUF_STATE},
+                                {SCOT_PLAN_TR_COUNTER, (uint64_t)(dyn ? 4 : 0), SCOT_PLAN_BUF_STATE}};
+  for (int s = 0; s < 12; ++s) {
+    const uint64_t* sp = t + want[s][0];
+    if (sp[2] != want[s][1]) return SCOT_PLAN_ERR_SHAPE;
+    if (!sp[2]) continue;
+    if (!scot_plan_io_span_ok(v, sp[0], sp[1], sp[2], want[s][2])) return SCOT_PLAN_ERR_SHAPE;
+    if (want[s][2] == SCOT_PLAN_BUF_STATE && v->buffers[4 * sp[0] + 3] != 1) return SCOT_PLAN_ERR_SHAPE;
+  }
+  if (t[SCOT_PLAN_TR_SHADOW_T + 2] && !t[SCOT_PLAN_TR_SHADOW + 2]) return SCOT_PLAN_ERR_SHAPE;
+  for (int a = 0; a < 12; ++a)      /* no two spans share a byte: labels, loss, prediction and every piece of state are distinct memory */
+    for (int b = a + 1; b < 12; ++b) {
+      const uint64_t* x = t + want[a][0];
+      const uint64_t* y = t + want[b][0];
+      if (x[2] && y[2] && x[0] == y[0] && x[1] < y[1] + y[2] && y[1] < x[1] + x[2]) return SCOT_PLAN_ERR_SHAPE;
+    }
+  return SCOT_PLAN_OK;
+}
+
 // Validates the whole image before anything is allocated: section bounds, counts, every relocation inside its buffer, every name in
 // the table above, and a format version, ABI and operand format equal to the caller's (the library's own).  Fills *v with pointers INTO
 // the image.  `image` must be 8-byte aligned.
@@ -176,8 +295,10 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
   const uint8_t* b = (const uint8_t*)image;
   const uint64_t* h = (const uint64_t*)image;
   if (h[SCOT_PLAN_H_MAGIC] != SCOT_PLAN_MAGIC) return SCOT_PLAN_ERR_SHAPE;
-  if (h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT && h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT_ADJOINT) return SCOT_PLAN_ERR_UNSUPPORTED;
-  const int adjoint = h[SCOT_PLAN_H_FORMAT] == SCOT_PLAN_FORMAT_ADJOINT;
+  if (h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT && h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT_ADJOINT &&
+      h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT_TRAINING)
+    return SCOT_PLAN_ERR_UNSUPPORTED;
+  const int adjoint = h[SCOT_PLAN_H_FORMAT] == SCOT_PLAN_FORMAT_ADJOINT, training = h[SCOT_PLAN_H_FORMAT] == SCOT_PLAN_FORMAT_TRAINING;
   if (h[SCOT_PLAN_H_ABI] != (uint64_t)abi || h[SCOT_PLAN_H_OPERAND] != (uint64_t)operand_format) return SCOT_PLAN_ERR_UNSUPPORTED;
   if (h[SCOT_PLAN_H_BYTES] != (uint64_t)bytes) return SCOT_PLAN_ERR_SHAPE;      /* a truncated (or padded) file */
   v->base = b;
@@ -207,6 +328,17 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
   if (adjoint && (!scot_plan_span_ok(h[SCOT_PLAN_H_BACKWARD_OFF], v->backward_words * 8, bytes) ||
                   !scot_plan_span_ok(h[SCOT_PLAN_H_ADJ_OFF], SCOT_PLAN_ADJ_WORDS * 8, bytes)))
     return SCOT_PLAN_ERR_SHAPE;
+  if (training) {      // the training words, then the three lists they name
+    if (!scot_plan_span_ok(h[SCOT_PLAN_H_TRAIN_OFF], SCOT_PLAN_TRAIN_WORDS * 8, bytes)) return SCOT_PLAN_ERR_SHAPE;
+    v->train = (const uint64_t*)(b + h[SCOT_PLAN_H_TRAIN_OFF]);
+    for (int s = 0; s < 3; ++s) {
+      const uint64_t* l = v->train + SCOT_PLAN_TR_FWD + 3 * s;
+      if (l[0] > lim || l[2] > lim || !scot_plan_span_ok(l[1], l[2] * 8, bytes)) return SCOT_PLAN_ERR_SHAPE;
+      v->n_step[s] = l[0];
+      v->step[s] = (const uint64_t*)(b + l[1]);
+      v->step_words[s] = l[2];
+    }
+  }
   v->names = b + h[SCOT_PLAN_H_NAMES_OFF];
   v->buffers = (const uint64_t*)(b + h[SCOT_PLAN_H_BUFFERS_OFF]);
   v->entries = (const uint64_t*)(b + h[SCOT_PLAN_H_ENTRIES_OFF]);
@@ -221,33 +353,42 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
   for (uint64_t i = 0; i < v->n_names; ++i) {
     const char* nm = (const char*)(v->names + i * SCOT_PLAN_NAME_BYTES);
     if (!memchr(nm, 0, SCOT_PLAN_NAME_BYTES)) return SCOT_PLAN_ERR_SHAPE;
-    if (scot_plan_entry_index(nm) < 0 && !(adjoint && scot_plan_adjoint_entry_index(nm) >= 0)) return SCOT_PLAN_ERR_UNSUPPORTED;
+    if (scot_plan_entry_index(nm) < 0 && !(adjoint && scot_plan_adjoint_entry_index(nm) >= 0) &&
+        !(training && scot_plan_training_entry_index(nm) >= 0))
+      return SCOT_PLAN_ERR_UNSUPPORTED;
   }
   // buffers: a known kind, a size, a constant's content inside the data section
   for (uint64_t i = 0; i < v->n_buffers; ++i) {
     const uint64_t kind = v->buffers[4 * i], n = v->buffers[4 * i + 1], off = v->buffers[4 * i + 2];
-    if (kind > (uint64_t)(adjoint ? SCOT_PLAN_BUF_STATE : SCOT_PLAN_BUF_SCRATCH) || n == 0 || n > ((uint64_t)1 << 40)) return SCOT_PLAN_ERR_SHAPE;
+    if (kind > (uint64_t)(adjoint || training ? SCOT_PLAN_BUF_STATE : SCOT_PLAN_BUF_SCRATCH) || n == 0 || n > ((uint64_t)1 << 40)) return SCOT_PLAN_ERR_SHAPE;
     if (kind == SCOT_PLAN_BUF_CONSTANT && !scot_plan_span_ok(off, n, v->data_bytes)) return SCOT_PLAN_ERR_SHAPE;
+    if (training && kind == SCOT_PLAN_BUF_STATE) {      // stored by value (1) or zeroed at load (0)
+      const uint64_t init = v->buffers[4 * i + 3];
+      if (init > 1 || (init && !scot_plan_span_ok(off, n, v->data_bytes))) return SCOT_PLAN_ERR_SHAPE;
+    }
   }
   // arrays
   uint64_t w = 0;
   for (uint64_t i = 0; i < v->n_arrays; ++i) {
     if (v->arrays_words - w < 2) return SCOT_PLAN_ERR_SHAPE;
     const uint64_t kind = v->arrays[w], cnt = v->arrays[w + 1];
-    if (kind > 1 || cnt > (v->arrays_words - w - 2) / 2) return SCOT_PLAN_ERR_SHAPE;
+    if (kind > (uint64_t)(training ? 2 : 1) || cnt > (v->arrays_words - w - 2) / 2) return SCOT_PLAN_ERR_SHAPE;
     for (uint64_t k = 0; k < cnt; ++k) {
       const uint64_t tagw = v->arrays[w + 2 + 2 * k], val = v->arrays[w + 3 + 2 * k];
       if (!scot_plan_arg_ok(v, tagw, val, 1)) return SCOT_PLAN_ERR_SHAPE;
-      if (kind == 0 && (tagw & 0xff) != SCOT_PLAN_ARG_INT) return SCOT_PLAN_ERR_SHAPE;
+      if (kind != 1 && (tagw & 0xff) != SCOT_PLAN_ARG_INT) return SCOT_PLAN_ERR_SHAPE;
+      if (kind == 2 && (val >> 32)) return SCOT_PLAN_ERR_SHAPE;      /* raw bits of ONE float */
       if (kind == 1 && (tagw & 0xff) == SCOT_PLAN_ARG_INT) return SCOT_PLAN_ERR_SHAPE;
     }
     w += 2 + 2 * cnt;
   }
   if (w != v->arrays_words) return SCOT_PLAN_ERR_SHAPE;
   // entries: the forward against its list, the backward of an adjoint plan against the other one, by the same rules
-  int erc = scot_plan_entries_ok(v, v->entries, v->n_entries, v->entries_words, 0);
+  int erc = scot_plan_entries_ok(v, v->entries, v->n_entries, v->entries_words, SCOT_PLAN_LIST_FORWARD);
   if (erc != SCOT_PLAN_OK) return erc;
-  if (adjoint && (erc = scot_plan_entries_ok(v, v->backward, v->n_backward, v->backward_words, 1)) != SCOT_PLAN_OK) return erc;
+  if (adjoint && (erc = scot_plan_entries_ok(v, v->backward, v->n_backward, v->backward_words, SCOT_PLAN_LIST_ADJOINT)) != SCOT_PLAN_OK) return erc;
+  for (int s = 0; training && s < 3; ++s)
+    if ((erc = scot_plan_entries_ok(v, v->step[s], v->n_step[s], v->step_words[s], SCOT_PLAN_LIST_TRAINING)) != SCOT_PLAN_OK) return erc;
   // io: fp32 [B, Cin, H, W] in, fp32 [B, Cout, H, W] out, each whole inside a buffer of the right kind
   const uint64_t* io = v->io;
   const uint64_t B = io[SCOT_PLAN_IO_B], Cin = io[SCOT_PLAN_IO_CIN], H = io[SCOT_PLAN_IO_H], W = io[SCOT_PLAN_IO_W], Cout = io[SCOT_PLAN_IO_COUT];
@@ -288,6 +429,7 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
     const int64_t e = (int64_t)a[SCOT_PLAN_ADJ_SCALE_EXP];
     if (e < -120 || e > 120 || (e != 0 && !a[SCOT_PLAN_ADJ_STATE + 2])) return SCOT_PLAN_ERR_SHAPE;
   }
+  if (training) return scot_plan_training_ok(v);
   return SCOT_PLAN_OK;
 }
 #endif

@@ -524,14 +524,21 @@ class ScOTEngine:
         # (an export records C-ABI calls only, also on the CPU emulation, whose library implements the memset and the copy)
         return self.device.type == "cuda" or self._export is not None
 
-    def plan_buffers(self, adjoint=False):
+    def plan_buffers(self, adjoint=False, train=None):
         """What an inference forward touches that exists BEFORE it, for plan.py: [(name, tensor, constant?)].  Constants are stored in a
         plan image by value (the parameter arena, its 16-bit copy, the bias-MLP tables); the rest is written by the forward before it
         is read (the bias tables every forward recomputes) and only needs room.
         adjoint: also what the frozen-model backward touches — the transposed 16-bit copy (a constant), the bias-table gradient scratch,
         the ConvNeXt blocks' power-of-two pairs and the gradient arena, where the stored form of the fused tails leaves by-products
         (room only: nothing reads them); and, third element "state", what the plan RUNTIME writes: the gradient scale and the
-        non-finite counter of the un-scale passes."""
+        non-finite counter of the un-scale passes.
+        train (a FusedAdamW of this model): what one whole training step touches.  Everything the step CHANGES is "stored" — state the
+        image holds by value and the runtime owns afterwards: the parameter arena, both 16-bit copies, the moments, the step counters,
+        the clip floats, the gradient scale and its counter.  The ConvNeXt blocks' gradient scratch is state too (zero between steps,
+        never poisoned); the descriptor tables of the weight-gradient and optimizer launches are constants; the gradient arena and the
+        norm partials are room only."""
+        if train is not None:
+            return self._train_plan_buffers(train)
         out = [("arena", self.arena.data, True)]
         if self.shadow is not None:
             out.append(("shadow", self.shadow, True))
@@ -547,6 +554,31 @@ class ScOTEngine:
             out += [(f"ls_pair:{pre}", ls["cs"], False) for pre, ls in sorted(self._ls.items())]
             if self.arena.grad is not None:
                 out.append(("grad_arena", self.arena.grad, False))
+        return out
+
+    def _train_plan_buffers(self, opt):
+        out = [("arena", self.arena.data, "stored")]
+        if self.shadow is not None:
+            out.append(("shadow", self.shadow, "stored"))
+        if self.shadow_t is not None:
+            out += [("shadow_t", self.shadow_t, "stored"), ("wt_desc", self._wt_desc, True)]
+        out += [("cpb_coords", self.cpb_coords, True), ("cpb_desc", self.cpb_desc, True)]
+        out += [(f"coords{ws}", t, True) for ws, t in sorted(self._coords.items())]
+        out += [("cpb_tables", self.cpb_tables, False), ("cpb_z", self.cpb_z, False)]
+        if self.scale_grads:
+            out += [("scale_state", self.scale_state, "stored"), ("grad_overflow", self.grad_overflow, "stored")]
+        out += [("cpb_dtables", self.cpb_dtables, False), ("cpb_dls", self.cpb_dls, False)]
+        for pre, ls in sorted(self._ls.items()):
+            out += [(f"ls_pair:{pre}", ls["cs"], False), (f"ls_scratch:{pre}", ls["scratch"], "state")]
+        for key, (td, sd, _, _) in sorted(self._rep_desc.items()):
+            out += [(f"replica_tables:{key}", td, True), (f"replica_scales:{key}", sd, True)]
+        if self._small_chunks is not None and self._small_chunks[1]:
+            out.append(("small_chunks", self._small_chunks[0], True))
+        if self._loss_meta is not None:
+            out += [("loss_groups", self._loss_meta[1]["goc"], True), ("loss_counts", self._loss_meta[1]["counts"], True)]
+        out.append(("grad_arena", self.arena.grad, False))
+        out += [("exp_avg", opt.exp_avg, "stored"), ("exp_avg_sq", opt.exp_avg_sq, "stored"), ("step_state", opt._step_state, "stored"),
+                ("clip", opt._clip, "stored"), ("group_map", opt._map, True), ("norm_partials", opt._partial, False)]
         return out
 
     def h_zero(self, t):

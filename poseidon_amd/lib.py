@@ -128,6 +128,13 @@ PLAN_PROTOTYPES = {
     "scot_plan_rollout_vjp": [P, P, P, P, P, I, P, P, F, P],      # the adjoint of the whole rollout (recomputes every step)
     "scot_plan_grad_status": [P, P, P],
     "scot_plan_adjoint_entry_point": [I],
+    # training plans (image format 4): one optimizer step per call, the state read back into the image
+    "scot_plan_describe_training": [P, P],
+    "scot_plan_loss": [P, P, P, P, P, P, P],
+    "scot_plan_train_step": [P, P, P, P, P, P, P],      # lr: a HOST array, one float per parameter group
+    "scot_plan_train_status": [P, P, P],
+    "scot_plan_snapshot": [P, P, Z, P],
+    "scot_plan_training_entry_point": [I],
 }
 _VOID = {"scot_set_use_tr", "scot_gemm_wide_config", "scot_gemm_splitk_config"}
 _SIZE = {"scot_gemm_workspace_bytes", "scot_wgrad_group_workspace_bytes", "scot_cln_bwd_workspace_bytes", "scot_wgrad_mlp_workspace_bytes",
@@ -135,7 +142,7 @@ _SIZE = {"scot_gemm_workspace_bytes", "scot_wgrad_group_workspace_bytes", "scot_
 
 
 def restype(name):
-    if name in ("scot_plan_entry_point", "scot_plan_adjoint_entry_point"):
+    if name in ("scot_plan_entry_point", "scot_plan_adjoint_entry_point", "scot_plan_training_entry_point"):
         return ctypes.c_char_p
     return None if name in _VOID else (c_size_t if name in _SIZE else c_int)
 

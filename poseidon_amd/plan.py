@@ -13,6 +13,13 @@ backward from a cotangent of the prediction — and writes a format-2 image whos
 self-check then also requires the engine's own bits for both input gradients.  The same image differentiates a whole rollout:
 `Plan.rollout_vjp` (scot_plan_rollout_vjp) recomputes every step from the rollout's predictions, from the last to the first.
 
+`export_plan(..., labels=y, train=optimizer)` (a `FusedAdamW` over this model) writes a TRAINING image, format 4: beside the inference
+forward it holds one optimizer step as three lists — the forward through the loss, the backward with the weight gradients (behind the
+zero fill of the accumulated gradients, before the un-scale passes), and what `FusedAdamW.step` issues — and, by value, everything a
+step changes: the fp32 parameters, both 16-bit copies, both moments, the step counters, the clip floats, the gradient scale.
+`Plan.train_step` runs one step from C (scot_plan_train_step), `Plan.snapshot` reads the state back into the image, and
+`load_training_state` brings such an image's state back into a `ScOT` and its optimizer.
+
 `Plan` is the ctypes wrapper of the runtime, for the tests and for a Python process that wants inference without torch (it imports
 torch only if the caller hands it tensors).
 """
@@ -27,15 +34,24 @@ from . import lib as _lib
 MAGIC = 0x4e414c50544f4353
 FORMAT = 1
 FORMAT_ADJOINT = 2      # + a backward entries section and the adjoint words (csrc/plan_image.h)
-HEADER_WORDS, NAME_BYTES, IO_WORDS, ADJ_WORDS = 32, 48, 24, 24
+FORMAT_TRAINING = 4     # + the training words, which name three step lists and the state spans (3 is unassigned)
+HEADER_WORDS, NAME_BYTES, IO_WORDS, ADJ_WORDS, TRAIN_WORDS = 32, 48, 24, 24, 64
 CONSTANT, INPUT, OUTPUT, SCRATCH, STATE = range(5)
 ARG_INT, ARG_NULL, ARG_PTR, ARG_STREAM, ARG_ARRAY = range(5)
 COMPUTE_CODE = {"fp32": 0, "fp16": 1, "bf16": 2, "bf16x3": 3}
 MAX_INT, MAX_FLT = 48, 8
 (H_MAGIC, H_FORMAT, H_ABI, H_OPERAND, H_COMPUTE, H_BYTES, H_NNAMES, H_NAMES_OFF, H_NBUFFERS, H_BUFFERS_OFF, H_NENTRIES, H_ENTRIES_OFF,
  H_ENTRIES_WORDS, H_NARRAYS, H_ARRAYS_OFF, H_ARRAYS_WORDS, H_IO_OFF, H_DATA_OFF, H_DATA_BYTES, H_NBACKWARD, H_BACKWARD_OFF,
- H_BACKWARD_WORDS, H_ADJ_OFF) = range(23)
+ H_BACKWARD_WORDS, H_ADJ_OFF, H_TRAIN_OFF) = range(24)
 ADJ_FLAGS, ADJ_COT, ADJ_DPV, ADJ_DTIME, ADJ_STATE, ADJ_COUNTER, ADJ_SCALE_EXP, ADJ_KEPT_BYTES = 0, 1, 4, 7, 10, 13, 16, 17
+(TR_FLAGS, TR_GROUPS, TR_ARENA_FLOATS, TR_FWD, TR_BWD, TR_UPD, TR_LR_ENTRY, TR_LR_ARG, TR_KEPT_BYTES, TR_LABELS, TR_LOSS, TR_PRED, TR_ARENA,
+ TR_EXP_AVG, TR_EXP_AVG_SQ, TR_SHADOW, TR_SHADOW_T, TR_STEP_STATE, TR_CLIP, TR_SCALE_STATE, TR_COUNTER) = (0, 1, 2, 3, 6, 9, 12, 13, 14, 15, 18, 21,
+                                                                                                     24, 27, 30, 33, 36, 39, 42, 45, 48)
+DESCRIBE_TRAINING = ("has_training", "groups", "arena_floats", "step_calls", "labels_bytes", "kept_bytes", "dynamic_scale")
+TRAIN_STATUS = ("applied", "skipped", "grad_scale", "grad_norm", "clip_coef", "nonfinite")
+# host arrays of floats among the recorded arguments: {entry point: {argument index: index of the argument that holds the count}}
+HOST_FLOAT_ARRAYS = {"scot_adamw_step": {6: 8, 7: 8}}
+LR_ARGUMENT = ("scot_adamw_step", 6)
 DESCRIBE_ADJOINT = ("has_adjoint", "d_pixel_values", "d_time", "backward_calls", "kept_bytes", "grad_scale_exponent")
 DESCRIBE = ("batch", "channels", "height", "width", "out_channels", "has_time", "time_bytes", "has_pixel_mask", "pixel_mask_bytes",
             "operand_format", "compute", "device_bytes", "calls", "pixel_values_bytes", "prediction_bytes", "format")
@@ -54,10 +70,11 @@ def bind(lib):
     return lib
 
 
-def runtime_entry_points(lib, adjoint=False):
-    """the entry points the runtime of this build lists: what a plan's forward (adjoint: its backward) may call"""
+def runtime_entry_points(lib, adjoint=False, training=False):
+    """the entry points the runtime of this build lists: what a plan's forward (adjoint: its backward; training: the three step lists
+    of a training plan) may call"""
     bind(lib)
-    query = lib.scot_plan_adjoint_entry_point if adjoint else lib.scot_plan_entry_point
+    query = lib.scot_plan_training_entry_point if training else (lib.scot_plan_adjoint_entry_point if adjoint else lib.scot_plan_entry_point)
     out, i = [], 0
     while True:
         n = query(i)
@@ -74,7 +91,8 @@ class _Registry:
     def __init__(self):
         self.bufs = {}      # address -> dict(addr, bytes, kind, name, tensor)
 
-    def add(self, t, kind, name):
+    def add(self, t, kind, name, stored=False):
+        """stored: a STATE buffer the image holds by value (a training plan's; otherwise the runtime zeroes it at load)"""
         n = t.numel() * t.element_size()
         if n == 0:
             return
@@ -83,7 +101,8 @@ class _Registry:
         a = t.data_ptr()
         cur = self.bufs.get(a)
         if cur is None or cur["bytes"] < n:
-            self.bufs[a] = dict(addr=a, bytes=n, kind=kind if cur is None else min(kind, cur["kind"]), name=name, tensor=t)
+            self.bufs[a] = dict(addr=a, bytes=n, kind=kind if cur is None else min(kind, cur["kind"]), name=name, tensor=t,
+                                stored=bool(stored or (cur is not None and cur["stored"])))
 
     def scratch(self, t):
         self.add(t, SCRATCH, "scratch")
@@ -107,11 +126,14 @@ def _address(fn):
     return ctypes.cast(fn, ctypes.c_void_p).value
 
 
-def _check_request(model, pixel_values, time, pixel_mask, labels):
+def _check_request(model, pixel_values, time, pixel_mask, labels, train=None):
     from . import ops
     cfg = model.config
-    if labels is not None:
+    if labels is not None and train is None:
         raise PlanExportError("export_plan: labels are not part of a plan (it covers the inference forward: no loss)")
+    if train is not None and pixel_mask is not None:
+        raise PlanExportError("export_plan: pixel_mask is not part of a training plan: the mask is one more per-batch input and the "
+                              "recorded loss has no mask argument")
     if pixel_mask is not None:
         raise PlanExportError("export_plan: pixel_mask overwrites the prediction with label values (reference model.py:1411-1484) and a "
                               "plan takes no labels: apply the mask to the plan's prediction in the host program")
@@ -127,6 +149,9 @@ def _check_request(model, pixel_values, time, pixel_mask, labels):
                               "spectral resize lives outside the engine and a plan covers the engine forward only")
     if pixel_values.shape[1] != cfg.num_channels:
         raise PlanExportError(f"export_plan: pixel_values has {pixel_values.shape[1]} channels, the model takes {cfg.num_channels}")
+    if train is not None and float(getattr(cfg, "drop_path_rate", 0.0) or 0.0) > 0.0:
+        raise PlanExportError("export_plan: a training plan cannot hold stochastic depth (drop_path_rate > 0): the training-mode masks "
+                              "are host draws")
     if model.training and float(getattr(cfg, "drop_path_rate", 0.0) or 0.0) > 0.0:
         raise PlanExportError("export_plan: the model is in training mode with stochastic depth (drop_path_rate > 0): its forward draws "
                               "random masks on the host; call model.eval() first")
@@ -144,8 +169,42 @@ def _check_adjoint(model, adjoint):
     return adjoint
 
 
+def _check_training(model, pixel_values, labels, train, adjoint):
+    """the refusals of a training export that need more than the request's shapes; nothing has been recorded yet"""
+    from .optim import FusedAdamW
+    if adjoint:
+        raise PlanExportError("export_plan: adjoint= together with train=: a training plan differentiates with respect to the "
+                              "parameters; export the input adjoint as an image of its own")
+    if labels is None:
+        raise PlanExportError("export_plan: train= without labels: a training plan records the loss, so it needs example labels "
+                              "[B, num_out_channels, H, W]")
+    if not isinstance(train, FusedAdamW) or train.model is not model:
+        raise PlanExportError("export_plan: train= takes the optimizer whose step is recorded: a poseidon_amd.optim.FusedAdamW built "
+                              "over this very model")
+    frozen = [n for n, p in model.named_parameters() if not p.requires_grad]
+    if frozen:
+        raise PlanExportError(f"export_plan: {len(frozen)} parameter(s) have requires_grad=False ({frozen[0]}, ...): a partially frozen "
+                              "model cannot be exported for training (the recorded backward is all-or-nothing)")
+    eng = model._engine
+    if eng.on_grads_final is not None or model._grad_hooks:
+        raise PlanExportError("export_plan: a data-parallel reducer is attached to this model: a training plan is one device's step "
+                              "(detach the reducer first)")
+    want = (pixel_values.shape[0], model.config.num_out_channels, pixel_values.shape[2], pixel_values.shape[3])
+    if tuple(labels.shape) != want:
+        raise PlanExportError(f"export_plan: labels have shape {tuple(labels.shape)}, the model's output has {want}")
+
+
 def _kind(const):
-    return STATE if const == "state" else (CONSTANT if const else SCRATCH)
+    return STATE if const in ("state", "stored") else (CONSTANT if const else SCRATCH)
+
+
+def _register(reg, buffers, only_new=False):
+    for name, ten, const in buffers:
+        if not (only_new and ten.data_ptr() in reg.bufs):
+            if const == "stored":
+                reg.add(ten, STATE, name, stored=True)
+            else:
+                reg.add(ten, _kind(const), name)
 
 
 def _record(model, pv, t, adjoint=()):
@@ -157,8 +216,7 @@ def _record(model, pv, t, adjoint=()):
     from . import ops
     eng = model._engine
     reg = _Registry()
-    for name, ten, const in eng.plan_buffers(adjoint=bool(adjoint)):
-        reg.add(ten, _kind(const), name)
+    _register(reg, eng.plan_buffers(adjoint=bool(adjoint)))
     pv_in = pv.clone()
     t_in = None if t is None else t.clone()
     reg.add(pv_in, INPUT, "pixel_values")
@@ -208,10 +266,99 @@ def _record(model, pv, t, adjoint=()):
         for k, v in saved.items():
             setattr(eng, k, v)
         ops.use(prev_lib)
-    for name, ten, const in eng.plan_buffers(adjoint=bool(adjoint)):      # (tables the forward created on first use)
-        if ten.data_ptr() not in reg.bufs:
-            reg.add(ten, _kind(const), name)
+    _register(reg, eng.plan_buffers(adjoint=bool(adjoint)), only_new=True)      # (tables the forward created on first use)
     return reg, rec, keep, pred, pv_in, t_in, adj
+
+
+def _training_state(model, opt):
+    """every tensor a training step changes, in a fixed order"""
+    eng = model._engine
+    ts = [eng.arena.data, opt.exp_avg, opt.exp_avg_sq, opt._step_state, opt._clip]
+    ts += [x for x in (eng.shadow, eng.shadow_t, eng.scale_state, eng.grad_overflow) if x is not None]
+    ts += [ls["scratch"] for _, ls in sorted(eng._ls.items())]
+    return ts
+
+
+def _record_training(model, opt, pv, t, labels):
+    """-> (registry, recorded calls, kept tensors, inference prediction, input copies, training record): ONE linear recording of four
+    lists on one stream — the inference forward; the step's forward through the loss; the fill of the accumulated gradients, the
+    backward from d loss = 1 with the store-form weight gradients and the un-scale passes; what FusedAdamW.step issues.  The recording
+    run IS a step on the model's own tensors, so everything it changes is saved before and put back afterwards."""
+    import torch
+    from . import ops
+    eng = model._engine
+    reg = _Registry()
+    _register(reg, eng.plan_buffers(train=opt))
+    pv_in, lab_in = pv.clone(), labels.clone()
+    t_in = None if t is None else t.clone()
+    reg.add(pv_in, INPUT, "pixel_values")
+    if t_in is not None:
+        reg.add(t_in, INPUT, "time")
+    reg.add(lab_in, INPUT, "labels")
+    one = None
+    if not eng.scale_grads:      # d loss = 1 as a constant of the image (under a gradient scale the backward copies S from the state)
+        one = torch.ones(1, dtype=torch.float32, device=pv.device)
+        reg.add(one, CONSTANT, "one")
+    inner_workspace = ops.workspace
+
+    def workspace(need=0):
+        w = inner_workspace(need)
+        reg.add(w, SCRATCH, "workspace")
+        return w
+    saved = dict(use_side=eng.use_side, stage_timing=eng.stage_timing, stochastic=eng.stochastic, collect_attn=eng.collect_attn,
+                 last_hidden=eng.last_hidden, last_hidden_aliased=eng.last_hidden_aliased, _rec=eng._rec, _rec_keep=eng._rec_keep,
+                 _fwd_flags=eng._fwd_flags, grad_fill_event=eng.grad_fill_event)
+    rec, keep = [], []
+    prev_lib = ops.use(eng.lib_kind)
+    state = _training_state(model, opt)
+    try:
+        eng.refresh_weight_copies(True)      # (both 16-bit copies current BEFORE they are saved: the image stores them by value)
+        before, step_count = [x.clone() for x in state], opt.step_count
+        grads_before = (eng.arena.grad.clone(), eng.grads_are_zero, eng.lazy_grads)      # (what the caller has accumulated so far)
+        ops.workspace = workspace
+        eng.use_side = eng.stage_timing = eng.stochastic = eng.collect_attn = False
+        eng.grad_fill_event = None
+        eng._export, eng._rec, eng._rec_keep = reg, rec, keep
+        eng._export_side_rows = False
+        prev_rec = ops.set_recorder(rec)
+        try:
+            eng._fwd_flags = ((), True)
+            _, pred, _ = eng._forward(pv_in, t_in, None, None, False)
+            n_inf = len(rec)
+            loss, pred_step, tape = eng._forward(pv_in, t_in, lab_in, None, True)
+            n_fwd = len(rec)
+            _register(reg, eng.plan_buffers(train=opt), only_new=True)
+            lazy = eng._small_chunks is not None      # ScOT.zero_grad(overlap=True): only what is accumulated into is filled
+            if lazy:
+                eng.fill_small_grads()
+            else:
+                ops.memset_async(eng.arena.grad, 0)
+            eng.grads_are_zero, eng.lazy_grads = True, lazy
+            eng._backward(tape, one, None)
+            eng.grads_are_zero = eng.lazy_grads = False
+            n_bwd = len(rec)
+            opt.step()
+            keep.append(tape)
+        finally:
+            ops.set_recorder(prev_rec)
+            with torch.no_grad():
+                for x, b in zip(state, before):
+                    x.copy_(b)
+                eng.arena.grad.copy_(grads_before[0])
+            opt.step_count = step_count
+            eng.grads_are_zero, eng.lazy_grads = grads_before[1], grads_before[2]
+            model.mark_weights_dirty()
+            if eng.shadow is not None:      # (put back with the master weights: current again)
+                eng._shadow_v = eng._shadow_t_v = model._weights_version()
+    finally:
+        ops.workspace = inner_workspace
+        eng._export = None
+        for k, v in saved.items():
+            setattr(eng, k, v)
+        ops.use(prev_lib)
+    _register(reg, eng.plan_buffers(train=opt), only_new=True)      # (tables the step created on first use)
+    tr = dict(n_inf=n_inf, n_fwd=n_fwd, n_bwd=n_bwd, labels=lab_in, loss=loss, pred=pred_step, opt=opt)
+    return reg, rec, keep, pred, pv_in, t_in, tr
 
 
 def _libraries(eng):
@@ -231,8 +378,9 @@ def _bytes_of(t):
     return t.detach().reshape(-1).cpu().contiguous().view(__import__("torch").uint8).numpy().tobytes()
 
 
-def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None):
-    """recorded calls + registered buffers -> the bytes of a plan image (adj: the adjoint record of _record -> a format-2 image)"""
+def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=None):
+    """recorded calls + registered buffers -> the bytes of a plan image (adj: the adjoint record of _record -> a format-2 image; train:
+    the training record of _record_training -> a format-4 image)"""
     eng = model._engine
     reg.freeze()
     used, names, name_index = [], [], {}
@@ -261,8 +409,15 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None):
     listed_fwd = set(runtime_entry_points(own))
     listed_bwd = set(runtime_entry_points(own, adjoint=True)) if adj is not None else set()
     sections = [("forward", "SCOT_PLAN_ENTRY_POINTS", listed_fwd, [], set()), ("backward", "SCOT_PLAN_ADJOINT_ENTRY_POINTS", listed_bwd, [], set())]
+    bounds = [n_fwd, len(rec)]
+    lr_point = None
+    if train is not None:
+        listed_tr = set(runtime_entry_points(own, training=True))
+        sections = [sections[0]] + [(what, "SCOT_PLAN_TRAINING_ENTRY_POINTS", listed_tr, [], set())
+                                    for what in ("step forward", "step backward", "update")]
+        bounds = [train["n_inf"], train["n_fwd"], train["n_bwd"], len(rec)]
     for pos, (fn, args) in enumerate(rec):
-        what_list, macro, listed, entries, touching = sections[0 if pos < n_fwd else 1]
+        what_list, macro, listed, entries, touching = sections[next(i for i, hi in enumerate(bounds) if pos < hi)]
         if args is None:
             label = getattr(fn, "__qualname__", None) or getattr(fn, "__name__", None) or repr(fn)
             raise PlanExportError(f"export_plan: the recorded {what_list} holds a host-side Python step ({label}); a plan is C-ABI calls only")
@@ -286,6 +441,15 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None):
             what = f"argument {k} of {name}"
             if ty is ctypes.c_float:
                 flts.append(struct.unpack("<I", struct.pack("<f", float(a)))[0])
+            elif train is not None and k in HOST_FLOAT_ARRAYS.get(name, ()):      # a host array of floats, passed by address
+                count = int(args[HOST_FLOAT_ARRAYS[name][k]])
+                values = (ctypes.c_float * count).from_address(a.value if isinstance(a, ctypes.c_void_p) else int(a))
+                if (name, k) == LR_ARGUMENT:
+                    if lr_point is not None:
+                        raise PlanExportError(f"export_plan: the update calls {name} more than once")
+                    lr_point = (len(entries), len(ints), count)
+                ints.append((ARG_ARRAY, len(arrays)))
+                arrays.append((2, [(ARG_INT, struct.unpack("<I", struct.pack("<f", float(x)))[0]) for x in values]))
             elif ty is ctypes.c_void_p and k == last:
                 ints.append((ARG_STREAM, 0))      # one stream per entry point, last: the caller's at run time
             elif isinstance(a, ctypes.Array):
@@ -316,7 +480,8 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None):
             names.append(name)
         entries.append((name_index[name], which, ints, flts))
     touching = None
-    entries, backward = sections[0][3], sections[1][3]
+    step_lists = sections[1:] if train is not None else []
+    entries, backward = sections[0][3], (sections[1][3] if train is None else [])
 
     B, Cin, H, W = pv_in.shape
     Cout = pred.shape[1]
@@ -361,6 +526,33 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None):
         both = sections[0][4] & sections[1][4]
         adj_words[ADJ_KEPT_BYTES] = sum(b["bytes"] for b in used if b["addr"] in both and b["kind"] == SCRATCH and b["name"] != "workspace")
 
+    tr_words = [0] * TRAIN_WORDS
+    if train is not None:
+        opt = train["opt"]
+        if lr_point is None or sections[3][3][lr_point[0]][0] != name_index.get(LR_ARGUMENT[0]):
+            raise PlanExportError("export_plan: the recorded update holds no scot_adamw_step call")
+
+        def tspan(slot, t, what, kind):
+            tr_words[slot], tr_words[slot + 1] = whole(t, what, kind)
+            tr_words[slot + 2] = t.numel() * t.element_size()
+        tspan(TR_LABELS, train["labels"], "the labels' copy", INPUT)
+        tspan(TR_LOSS, train["loss"], "the loss", OUTPUT)
+        tspan(TR_PRED, train["pred"], "the step forward's prediction", OUTPUT)
+        for slot, t, what in ((TR_ARENA, eng.arena.data, "the parameter arena"), (TR_EXP_AVG, opt.exp_avg, "exp_avg"),
+                              (TR_EXP_AVG_SQ, opt.exp_avg_sq, "exp_avg_sq"), (TR_SHADOW, eng.shadow, "the 16-bit copy"),
+                              (TR_SHADOW_T, eng.shadow_t, "the transposed 16-bit copy"), (TR_STEP_STATE, opt._step_state, "step_state"),
+                              (TR_CLIP, opt._clip, "the clip floats"), (TR_SCALE_STATE, eng.scale_state, "the gradient-scale state"),
+                              (TR_COUNTER, eng.grad_overflow, "the non-finite counter")):
+            if t is not None:
+                tspan(slot, t, what, STATE)
+        tr_words[TR_FLAGS] = 1 if eng.scale_grads else 0
+        tr_words[TR_GROUPS], tr_words[TR_ARENA_FLOATS] = lr_point[2], eng.arena.size
+        tr_words[TR_LR_ENTRY], tr_words[TR_LR_ARG] = lr_point[0], lr_point[1]
+        both = sections[1][4] & sections[2][4]
+        tr_words[TR_KEPT_BYTES] = sum(b["bytes"] for b in used if b["addr"] in both and b["kind"] == SCRATCH and b["name"] != "workspace")
+        if len(opt.param_groups) != lr_point[2]:
+            raise PlanExportError("export_plan: the recorded update has another number of parameter groups than the optimizer")
+
     # sections
     def words(ws):
         return struct.pack(f"<{len(ws)}Q", *ws)
@@ -368,13 +560,14 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None):
     data, buf_words = bytearray(), []
     for b in used:
         off = 0
-        if b["kind"] == CONSTANT:
+        stored = b["kind"] == STATE and b["stored"] and train is not None
+        if b["kind"] == CONSTANT or stored:
             data.extend(b"\0" * (-len(data) % 64))
             off = len(data)
             raw = _bytes_of(b["tensor"])
             assert len(raw) == b["bytes"]
             data.extend(raw)
-        buf_words += [b["kind"], b["bytes"], off, 0]
+        buf_words += [b["kind"], b["bytes"], off, 1 if stored else 0]
     data.extend(b"\0" * (-len(data) % 8))
     arr_words = []
     for kind, items in arrays:
@@ -393,10 +586,19 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None):
     sections = [names_b, words(buf_words), words(ent_words), words(arr_words), words(io)]
     if adj is not None:
         sections += [words(bwd_words), words(adj_words)]
+    step_words = []
+    if train is not None:
+        step_words = [entry_words(sct[3]) for sct in step_lists]
+        sections += [words(ws) for ws in step_words] + [None]      # (the training words name the lists' offsets: filled in below)
     offs, cur = [], HEADER_WORDS * 8
     for sct in sections:
         offs.append(cur)
-        cur += len(sct) + (-len(sct) % 8)
+        n_sct = TRAIN_WORDS * 8 if sct is None else len(sct)
+        cur += n_sct + (-n_sct % 8)
+    if train is not None:
+        for i in range(3):
+            tr_words[TR_FWD + 3 * i: TR_FWD + 3 * i + 3] = [len(step_lists[i][3]), offs[5 + i], len(step_words[i])]
+        sections[-1] = words(tr_words)
     cur += -cur % 64
     data_off = cur
     total = data_off + len(data)
@@ -405,6 +607,8 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None):
     if adj is not None:
         h[H_FORMAT] = FORMAT_ADJOINT
         h[H_NBACKWARD], h[H_BACKWARD_OFF], h[H_BACKWARD_WORDS], h[H_ADJ_OFF] = len(backward), offs[5], len(bwd_words), offs[6]
+    if train is not None:
+        h[H_FORMAT], h[H_TRAIN_OFF] = FORMAT_TRAINING, offs[8]
     h[H_COMPUTE], h[H_BYTES] = COMPUTE_CODE[model.compute], total
     h[H_NNAMES], h[H_NAMES_OFF] = len(names), offs[0]
     h[H_NBUFFERS], h[H_BUFFERS_OFF] = len(used), offs[1]
@@ -422,16 +626,21 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None):
     return bytes(out)
 
 
-def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labels=None, *, adjoint=()):
+def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labels=None, *, adjoint=(), train=None):
     """Record `model`'s inference forward for exactly these input shapes and write it as a plan image to `path` (None: only return it).
     Returns the image's bytes.  The weights are a snapshot; see the module docstring and DESIGN.md §3 for what a plan does not cover.
     adjoint: () or some of ("pixel_values", "time") — the image (format 2) then also holds the frozen-model backward from a cotangent of
-    the prediction to these inputs' gradients (scot_plan_vjp), and its forward is the one a differentiable call runs."""
+    the prediction to these inputs' gradients (scot_plan_vjp), and its forward is the one a differentiable call runs.
+    train: a FusedAdamW over this model, with labels — the image (format 4) then also holds one optimizer step and the training state by
+    value (scot_plan_train_step, scot_plan_snapshot); the model and the optimizer are left as they were."""
     import torch
     from . import ops
-    _check_request(model, pixel_values, time, pixel_mask, labels)
-    adjoint = _check_adjoint(model, adjoint)
+    _check_request(model, pixel_values, time, pixel_mask, labels, train)
     dev = pixel_values.device
+    if train is not None:
+        model._ensure_arena(dev)
+        _check_training(model, pixel_values, labels, train, adjoint)
+    adjoint = _check_adjoint(model, adjoint)
     model._ensure_arena(dev)
     eng = model._engine
     pv = pixel_values.detach().to(torch.float32).contiguous()
@@ -444,6 +653,14 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
             raise PlanExportError(f"export_plan: time has {t.numel()} values for a batch of {pv.shape[0]}")
     own, peer = _libraries(eng)
     bind(own)
+    if train is not None:
+        lab = labels.detach().to(device=dev, dtype=torch.float32).contiguous()
+        with torch.no_grad():
+            image = _export_training(model, train, pv, t, lab, own, peer)
+        if path is not None:
+            with open(path, "wb") as f:
+                f.write(image)
+        return image
     with torch.no_grad():
         ref_g = None
         if adjoint:      # the engine's own bits of the differentiable call: its prediction, and a vjp
@@ -500,6 +717,106 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
     return image
 
 
+def _export_training(model, opt, pv, t, lab, own, peer):
+    """record, build, and check through the runtime: scratch poisoned, one scot_plan_loss and one scot_plan_train_step on the export
+    inputs — the engine's own prediction bits, a finite loss, finite parameters.  The image that is returned holds the pre-step state."""
+    import torch
+    eng = model._engine
+    _, ref, tape = eng.forward(pv, t, lab, None, train=True, stochastic=False, param_grads=True)      # the engine's own prediction
+    ref = ref.clone()
+    del tape
+    reg, rec, keep, pred, pv_in, t_in, tr = _record_training(model, opt, pv, t, lab)
+    image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer, train=tr)
+    del keep
+    plan = Plan.load(image, lib=own, peer=peer)
+    try:
+        plan.poison(0xFF)
+        loss, got = plan.loss(pv, t, lab)
+        if not torch.equal(got, ref):
+            raise PlanExportError("export_plan: the training plan's prediction differs from the engine's own "
+                                  f"(max |difference| {float((got - ref).abs().max()):.3e})")
+        if not bool(torch.isfinite(loss).all()):
+            raise PlanExportError("export_plan: the training plan's loss is not finite with poisoned scratch")
+        plan.poison(0xFF)
+        loss = plan.train_step(pv, t, lab, [float(g["lr"]) for g in opt.param_groups])
+        if not bool(torch.isfinite(loss).all()):
+            raise PlanExportError("export_plan: the loss of the training plan's step is not finite with poisoned scratch")
+        after = training_state(plan.snapshot(image))
+        if not bool(torch.isfinite(after["arena"]).all()):
+            raise PlanExportError("export_plan: the parameters are not finite after one step of the training plan with poisoned scratch: "
+                                  "the recorded step reads a buffer the image does not initialise")
+    finally:
+        plan.free()
+    plan = Plan.load(image, lib=own, peer=peer)      # (the image as it will be written: the state before any step)
+    plan.free()
+    return image
+
+
+_STATE_SPANS = (("arena", TR_ARENA, "float32"), ("exp_avg", TR_EXP_AVG, "float32"), ("exp_avg_sq", TR_EXP_AVG_SQ, "float32"),
+                ("shadow", TR_SHADOW, "int16"), ("shadow_t", TR_SHADOW_T, "int16"), ("step_state", TR_STEP_STATE, "int32"),
+                ("clip", TR_CLIP, "float32"), ("scale_state", TR_SCALE_STATE, "float32"), ("nonfinite", TR_COUNTER, "int32"))
+
+
+def training_words(image):
+    """the training words of a format-4 image (a tuple of TRAIN_WORDS ints)"""
+    h = Plan.header(image)
+    if h[H_FORMAT] != FORMAT_TRAINING:
+        raise _lib.ScotLibraryError(f"not a training image: format {h[H_FORMAT]}")
+    return struct.unpack_from(f"<{TRAIN_WORDS}Q", image, h[H_TRAIN_OFF])
+
+
+def training_state(image):
+    """{name: tensor} of the state a training image holds by value (copies; the 16-bit copies as raw int16): arena, exp_avg, exp_avg_sq,
+    shadow, shadow_t, step_state, clip, scale_state, nonfinite — absent ones left out"""
+    import torch
+    h, tr = Plan.header(image), training_words(image)
+    out = {}
+    for name, slot, dtype in _STATE_SPANS:
+        buf, off, n = tr[slot:slot + 3]
+        if n:
+            _, _, data_off, _ = struct.unpack_from("<4Q", image, h[H_BUFFERS_OFF] + 32 * buf)
+            start = h[H_DATA_OFF] + data_off + off
+            out[name] = torch.frombuffer(bytearray(image[start:start + n]), dtype=getattr(torch, dtype)).clone()
+    return out
+
+
+def load_training_state(image, model, optimizer=None):
+    """Copy a training image's parameters into `model` (a ScOT of the same configuration: the arena layout is the configuration's, so
+    no name table is needed) and, with `optimizer` (its FusedAdamW), the moments, the step counters and the gradient scale: a fine-tune
+    done from C comes back as a normal checkpoint.  image: bytes or a path."""
+    import torch
+    image = image if isinstance(image, (bytes, bytearray)) else open(image, "rb").read()
+    st = training_state(image)
+    p0 = next(model.parameters())
+    model._ensure_arena(p0.device)
+    eng, arena = model._engine, model._arena
+    if st["arena"].numel() != arena.size:
+        raise ValueError(f"load_training_state: the image's parameter arena holds {st['arena'].numel()} floats, this model's {arena.size}: "
+                         "another configuration")
+    compute = {v: k for k, v in COMPUTE_CODE.items()}.get(Plan.header(image)[H_COMPUTE])
+    if compute != model.compute:
+        raise ValueError(f"load_training_state: the image was exported in compute mode {compute}, this model computes in {model.compute}: "
+                         "the gradient scale and the 16-bit copies belong to the mode")
+    if bool(training_words(image)[TR_FLAGS] & 1) != (eng.scale_state is not None):
+        raise ValueError("load_training_state: the image and this model disagree about a dynamic gradient scale (engine option grad_scale)")
+    with torch.no_grad():
+        arena.data.copy_(st["arena"])
+        model.mark_weights_dirty()
+        if eng.scale_state is not None and "scale_state" in st:
+            eng.scale_state.copy_(st["scale_state"])
+            eng.grad_overflow.copy_(st["nonfinite"])
+            eng._scale_ready = True
+        if optimizer is not None:
+            if optimizer.model is not model:
+                raise ValueError("load_training_state: the optimizer belongs to another model")
+            optimizer.exp_avg.copy_(st["exp_avg"])
+            optimizer.exp_avg_sq.copy_(st["exp_avg_sq"])
+            optimizer._step_state.copy_(st["step_state"])
+            optimizer._clip.copy_(st["clip"])
+            optimizer.step_count = int(st["step_state"].sum())
+    return model
+
+
 # ----------------------------------------------------------------------------------------------------------------- runtime wrapper
 def _load_library(kind):
     """the build of the library for operand format `kind`: through the package's loader when torch is already in the process (its HIP
@@ -534,8 +851,8 @@ def _addr(x, what):
 
 
 class Plan:
-    """A loaded plan.  `run` / `rollout` / `vjp` / `rollout_vjp` take torch tensors (and return them) or raw device addresses (then `out`
-    is required)."""
+    """A loaded plan.  `run` / `rollout` / `vjp` / `rollout_vjp` / `loss` / `train_step` take torch tensors (and return them) or raw
+    device addresses (then `out` is required)."""
 
     def __init__(self, lib, handle):
         self._lib, self._h = lib, handle
@@ -689,6 +1006,74 @@ class Plan:
         out = (ctypes.c_longlong * 2)()
         _lib.check(self._lib.scot_plan_grad_status(self._h, out, self._stream(stream, None)), "scot_plan_grad_status")
         return int(out[0]), int(out[1])
+
+    def describe_training(self):
+        out = (ctypes.c_longlong * 8)()
+        _lib.check(self._lib.scot_plan_describe_training(self._h, out), "scot_plan_describe_training")
+        return dict(zip(DESCRIBE_TRAINING, [int(x) for x in out]))
+
+    def _batch(self, pixel_values, time, labels):
+        d = self.info
+        if _is_tensor(pixel_values):
+            import torch
+            if tuple(pixel_values.shape) != (d["batch"], d["channels"], d["height"], d["width"]):
+                raise ValueError(f"this plan takes pixel_values of shape {(d['batch'], d['channels'], d['height'], d['width'])}")
+            if not _is_tensor(labels) or tuple(labels.shape) != (d["batch"], d["out_channels"], d["height"], d["width"]):
+                raise ValueError(f"this plan takes labels of shape {(d['batch'], d['out_channels'], d['height'], d['width'])}")
+            if time is not None and _is_tensor(time):
+                time = time.reshape(-1).to(torch.float32).contiguous()
+                if time.numel() != d["batch"]:
+                    raise ValueError("time: one value per sample")
+        return _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(labels, "labels")
+
+    def loss(self, pixel_values, time, labels, out=None, stream=None):
+        """-> (loss [1], prediction) of the step's forward at the current weights (scot_plan_loss); changes no state.  out: (loss buffer,
+        prediction buffer or None), required with raw addresses."""
+        d = self.info
+        pv, t, lab = self._batch(pixel_values, time, labels)
+        if out is None:
+            if not _is_tensor(pixel_values):
+                raise ValueError("raw addresses need `out`")
+            import torch
+            out = (torch.empty(1, dtype=torch.float32, device=pixel_values.device),
+                   torch.empty(d["batch"], d["out_channels"], d["height"], d["width"], dtype=torch.float32, device=pixel_values.device))
+        rc = self._lib.scot_plan_loss(self._h, pv, t, lab, _addr(out[0], "loss"), _addr(out[1], "prediction"), self._stream(stream, pixel_values))
+        _lib.check(rc, "scot_plan_loss")
+        return out
+
+    def train_step(self, pixel_values, time, labels, lr, out=None, stream=None):
+        """one optimizer step on the batch (scot_plan_train_step) -> the loss before the update ([1], on the device).  lr: one float
+        per parameter group, in the export's group order (a single float: the same for all).  out: a loss buffer of the caller's."""
+        groups = self.describe_training()["groups"]
+        lr = [float(lr)] * groups if isinstance(lr, (int, float)) else [float(x) for x in lr]
+        if len(lr) != groups:
+            raise ValueError(f"this plan has {groups} parameter groups, lr has {len(lr)} values")
+        pv, t, lab = self._batch(pixel_values, time, labels)
+        if out is None and _is_tensor(pixel_values):
+            import torch
+            out = torch.empty(1, dtype=torch.float32, device=pixel_values.device)
+        rates = (ctypes.c_float * max(1, groups))(*lr)
+        rc = self._lib.scot_plan_train_step(self._h, pv, t, lab, ctypes.cast(rates, ctypes.c_void_p), _addr(out, "loss"),
+                                            self._stream(stream, pixel_values))
+        _lib.check(rc, "scot_plan_train_step")
+        return out
+
+    def train_status(self, stream=None):
+        """-> {applied, skipped, grad_scale, grad_norm, clip_coef, nonfinite} (scot_plan_train_status: waits for the stream)"""
+        out = (ctypes.c_double * 6)()
+        _lib.check(self._lib.scot_plan_train_status(self._h, out, self._stream(stream, None)), "scot_plan_train_status")
+        vals = [float(x) for x in out]
+        return dict(zip(TRAIN_STATUS, [int(vals[0]), int(vals[1]), vals[2], vals[3], vals[4], int(vals[5])]))
+
+    def snapshot(self, image, stream=None):
+        """-> the bytes of `image` (THE image this plan was loaded from) with every state buffer's current value written back
+        (scot_plan_snapshot): a valid training image that resumes exactly"""
+        n = len(image)
+        buf = (ctypes.c_uint64 * ((n + 7) // 8 or 1))()
+        ctypes.memmove(buf, bytes(image), n)
+        rc = self._lib.scot_plan_snapshot(self._h, ctypes.cast(buf, ctypes.c_void_p), n, self._stream(stream, None))
+        _lib.check(rc, "scot_plan_snapshot")
+        return bytes(memoryview(buf).cast("B")[:n])      # (not ctypes.string_at: its size is a C int, an image can pass 2 GiB)
 
     def free(self):
         if self._h is not None and self._h.value:

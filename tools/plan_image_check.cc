@@ -3,7 +3,7 @@
 //   plan_image_check <abi> <operand format> <image file> <expected status> [<image file> <expected status> ...]
 //
 // Runs scot_plan_image_validate over every file and compares the status with the expected one; for an accepted image it also walks
-// everything the validator promised is in bounds (names, entries, arrays, constants' bytes).  Each file is read into a heap block of
+// everything the validator promised is in bounds (names, entries, arrays, constants' bytes; the step lists and stored state of a training image).  Each file is read into a heap block of
 // exactly its size, so a build with -fsanitize=address,undefined turns any read past a truncated image into an error.  Exit status 0
 // when every image got the expected answer.
 #include <stdio.h>
@@ -23,6 +23,14 @@ static uint64_t walk(const scot_plan_view* v) {
   if (v->format == SCOT_PLAN_FORMAT_ADJOINT) {      // the backward section and the adjoint words of a format-2 image
     for (uint64_t w = 0; w < v->backward_words; ++w) sum += v->backward[w];
     for (int w = 0; w < SCOT_PLAN_ADJ_WORDS; ++w) sum += v->adj[w];
+  }
+  if (v->format == SCOT_PLAN_FORMAT_TRAINING) {      // the training words, the three step lists, the stored state buffers' bytes
+    for (int w = 0; w < SCOT_PLAN_TRAIN_WORDS; ++w) sum += v->train[w];
+    for (int s = 0; s < 3; ++s)
+      for (uint64_t w = 0; w < v->step_words[s]; ++w) sum += v->step[s][w];
+    for (uint64_t i = 0; i < v->n_buffers; ++i)
+      if (v->buffers[4 * i] == SCOT_PLAN_BUF_STATE && v->buffers[4 * i + 3] == 1)
+        for (uint64_t k = 0; k < v->buffers[4 * i + 1]; k += 64) sum += v->data[v->buffers[4 * i + 2] + k];
   }
   return sum;
 }
