@@ -1,25 +1,27 @@
-// plan — running a trained model from C: the runtime of exported inference plans (include/scot_plan.h).
+// plan — running a trained model from C: the runtime of exported plans (include/scot_plan.h).
 //
-// poseidon_amd/plan.py records ONE inference forward of the engine for one input signature and writes it as a relocatable image
-// (plan_image.h: the list of C-ABI calls, every device address as (buffer, offset), every stream as a placeholder, the weights and
-// tables by value).  This file owns the memory and replays the list: scot_plan_load validates the image, allocates one slab for all
-// buffers, uploads the constants and builds the program of scot_tape_replay (host_tape.hip) with the final addresses; scot_plan_run
-// copies the caller's inputs in, writes the caller's stream into the program's stream slots, replays, and copies the prediction out.
-// The copies are device-to-device copies and the model's arithmetic is the recorded entry points'; the only kernels of this file's own
-// are the two that carry a gradient from one step of scot_plan_rollout_vjp to the next (below).
+// poseidon_amd/plan.py records the engine for one input signature and writes the recording as a relocatable image (plan_image.h: up
+// to five lists of C-ABI calls, every device address as (buffer, offset), every stream as a placeholder, the weights and tables by
+// value).  This file owns the memory and replays the lists: scot_plan_load validates the image, allocates one slab for all buffers,
+// uploads what the image holds by value and builds, for every list the image has, the program of scot_tape_replay (host_tape.hip) with
+// the final addresses; a call copies the caller's inputs in, writes the caller's stream into a program's stream slots, replays it
+// (`replay`), and copies the results out.  The copies are device-to-device copies and the model's arithmetic is the recorded entry
+// points'; the only kernels of this file's own are the two that carry a gradient from one step of scot_plan_rollout_vjp to the next.
 //
-// An ADJOINT plan (image format 2) also holds the recorded frozen-model backward: scot_plan_run replays the differentiable forward,
+// FORWARD (every image): scot_plan_run and scot_plan_rollout replay it.
+//
+// BACKWARD (an ADJOINT plan, image format 2), the recorded frozen-model backward: scot_plan_run replays the differentiable forward,
 // which leaves its saved activations in the plan's buffers, and scot_plan_vjp copies a cotangent of the prediction in, writes the
-// gradient scale {S, 1/S} into the plan's state buffer on the stream, replays the backward list and copies the input gradients out.
+// gradient scale {S, 1/S} into the plan's state buffer on the stream, replays the backward and copies the input gradients out.
 // One vjp per run: the backward reuses saved rows.  scot_plan_rollout_vjp is the adjoint of the whole rollout: it keeps no activations
 // beyond the caller's predictions (every step's input) and, from the last step to the first, replays the forward to recompute the
 // saved rows, forms the step's cotangent, replays the backward and carries the input gradient on.
 //
-// A TRAINING plan (image format 4) holds, beside the inference forward, one optimizer step as three more lists — the forward through the
-// loss, the backward with the weight gradients, the optimizer update — and everything a step changes as STATE buffers the image stores
-// by value: scot_plan_train_step copies a batch in, writes the caller's learning rates into the host array the recorded
-// scot_adamw_step call reads at issue time, and replays the three lists; scot_plan_snapshot reads the state back into the image.
-// No arithmetic of its own: clipping, the skip decision and the fp16 gradient scale are the recorded kernels', on the device.
+// STEP_FORWARD, STEP_BACKWARD, UPDATE (a TRAINING plan, image format 4), one optimizer step — the forward through the loss, the
+// backward with the weight gradients, the optimizer update — with everything a step changes as STATE buffers the image stores by
+// value: scot_plan_train_step copies a batch in, writes the caller's learning rates into the host array the recorded scot_adamw_step
+// call reads at issue time, and replays the three lists; scot_plan_snapshot reads the state back into the image.  No arithmetic of
+// its own: clipping, the skip decision and the fp16 gradient scale are the recorded kernels', on the device.
 //
 // A plan is one stream's worth of state: its buffers are reused by every run, so runs of ONE plan must be ordered (same stream, or
 // the caller's own events); two plans are independent.
@@ -37,15 +39,14 @@ extern "C" int scot_tape_replay(const uint64_t* prog, size_t n_words, int* fail_
 extern "C" int scot_abi_version();
 extern "C" int scot_operand_format();
 
-// the listed entry points, by address (same order as scot_plan_entry_names)
+// the listed entry points, by address: g_entry_address[table][index], rows in the order of scot_plan_lists[table].names (the training
+// table is the longest: it repeats the forward's)
 #define SCOT_PLAN_DECLARE(n) extern "C" int n(...);
-SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_DECLARE)
-#define SCOT_PLAN_ADDRESS(n) (void*)&n,
-static void* const g_entry_address[] = {SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_ADDRESS)};
 SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_DECLARE)
-static void* const g_adjoint_entry_address[] = {SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_ADDRESS)};
 SCOT_PLAN_TRAINING_ENTRY_POINTS(SCOT_PLAN_DECLARE)
-static void* const g_training_entry_address[] = {SCOT_PLAN_TRAINING_ENTRY_POINTS(SCOT_PLAN_ADDRESS)};
+#define SCOT_PLAN_ADDRESS(n) (void*)&n,
+static void* const g_entry_address[SCOT_PLAN_N_LISTS][SCOT_PLAN_COUNT(scot_plan_training_entry_names)] = {
+    {SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_ADDRESS)}, {SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_ADDRESS)}, {SCOT_PLAN_TRAINING_ENTRY_POINTS(SCOT_PLAN_ADDRESS)}};
 
 // ------------------------------------------------------------------ device memory and copies (plain host memory in the CPU emulation)
 namespace {
@@ -173,18 +174,14 @@ struct Plan {
   size_t slab_bytes = 0;
   std::vector<char*> buf;                          // start of every buffer inside the slab
   std::vector<uint64_t> buf_kind, buf_bytes;
-  std::vector<uint64_t> prog;                      // scot_tape_replay's word format, final addresses
-  std::vector<size_t> stream_slot;                 // words of prog that hold the stream
-  std::vector<uint64_t> prog_bwd;                  // adjoint plans: the backward list, same format
-  std::vector<size_t> stream_slot_bwd;
-  std::vector<std::vector<uint64_t>> ptr_arrays;   // host arrays the entries pass by address
-  std::vector<std::vector<int>> int_arrays;
-  std::vector<std::vector<float>> flt_arrays;
-  // training plans: the three step lists (forward, backward, update), the training words, where the update reads lr[groups], and what
-  // scot_plan_snapshot compares a target image with and writes into (the header, the buffer table, each stored buffer's place)
-  std::vector<uint64_t> prog_step[3];
-  std::vector<size_t> stream_slot_step[3];
-  uint64_t n_step[3] = {0, 0, 0};
+  struct Program {
+    std::vector<uint64_t> prog;                    // scot_tape_replay's word format, final addresses
+    std::vector<size_t> stream_slot;               // words of prog that hold the stream
+    uint64_t calls = 0;
+  } list[SCOT_PLAN_N_CALLS];                       // SCOT_PLAN_CALLS_*; a list the image does not have is empty
+  std::vector<std::vector<uint64_t>> host_arrays;  // host arrays the entries pass by address: pointers, or packed int32 / float
+  // training plans: the training words, where the update reads lr[groups], and what scot_plan_snapshot compares a target image with
+  // and writes into (the header, the buffer table, each stored buffer's place)
   uint64_t train[SCOT_PLAN_TRAIN_WORDS] = {};
   float* lr = nullptr;
   uint64_t header[SCOT_PLAN_HEADER_WORDS] = {};
@@ -192,7 +189,6 @@ struct Plan {
   std::vector<float> host_time;                    // scot_plan_rollout: the divided time on its way back to the device
   uint64_t io[SCOT_PLAN_IO_WORDS] = {};
   uint64_t adj[SCOT_PLAN_ADJ_WORDS] = {};
-  uint64_t n_entries = 0, n_backward = 0;
   int operand_format = 0, compute = 0, format = SCOT_PLAN_FORMAT;
   bool ran = false;                                // a completed scot_plan_run whose saved activations no vjp / poison / rollout has used up
   float host_scale[4] = {1.0f, 1.0f, 0.0f, 0.0f};  // {S, 1/S, 0, 0} on its way to the state buffer
@@ -234,9 +230,7 @@ void* default_peer() {
 void* resolve(const char* name, uint64_t lib, int list) {
   const int index = scot_plan_list_index(name, list);
   if (index < 0) return nullptr;
-  if (lib == 0 || scot_operand_format() == 0)
-    return list == SCOT_PLAN_LIST_TRAINING ? g_training_entry_address[index]
-                                           : (list == SCOT_PLAN_LIST_ADJOINT ? g_adjoint_entry_address[index] : g_entry_address[index]);
+  if (lib == 0 || scot_operand_format() == 0) return g_entry_address[list][index];
   if (!g_peer) g_peer = default_peer();
   return g_peer ? dlsym(g_peer, name) : nullptr;
 }
@@ -253,79 +247,67 @@ bool materialise(Plan* pl, uint64_t tagw, uint64_t val, uint64_t* out, bool* is_
   }
 }
 
-int replay_list(std::vector<uint64_t>& prog, const std::vector<size_t>& slots, uint64_t calls, hipStream_t stream) {
-  for (size_t s : slots) prog[s] = (uint64_t)(uintptr_t)stream;
+// one of the plan's lists (SCOT_PLAN_CALLS_*) on `stream`
+int replay(Plan* pl, int list, hipStream_t stream) {
+  Plan::Program& p = pl->list[list];
+  for (size_t s : p.stream_slot) p.prog[s] = (uint64_t)(uintptr_t)stream;
 #ifdef SCOT_HIPEMU
-  g_emu_issued += (long long)calls;
-#else
-  (void)calls;
+  g_emu_issued += (long long)p.calls;
 #endif
   int fail = -1;
-  return scot_tape_replay(prog.data(), prog.size(), &fail);
+  return scot_tape_replay(p.prog.data(), p.prog.size(), &fail);
 }
 
-int replay(Plan* pl, hipStream_t stream, bool backward = false) {
-  return backward ? replay_list(pl->prog_bwd, pl->stream_slot_bwd, pl->n_backward, stream)
-                  : replay_list(pl->prog, pl->stream_slot, pl->n_entries, stream);
-}
-
-// list s of a training plan's step: 0 forward through the loss, 1 backward, 2 update
-int replay_step(Plan* pl, int s, hipStream_t stream) { return replay_list(pl->prog_step[s], pl->stream_slot_step[s], pl->n_step[s], stream); }
-
-// one entries section -> the entry points' addresses (false: one is missing)
-bool resolve_section(const scot_plan_view& v, const uint64_t* e, uint64_t n, int list, std::vector<void*>* fn) {
-  fn->resize(n);
-  uint64_t w = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    const uint64_t name = e[w], lib = e[w + 1], ni = e[w + 2], nf = e[w + 3];
-    (*fn)[i] = resolve((const char*)(v.names + name * SCOT_PLAN_NAME_BYTES), lib, list);
+// one call list -> the entry points' addresses (false: one is missing)
+bool resolve_section(const scot_plan_view& v, const scot_plan_calls& c, std::vector<void*>* fn) {
+  fn->resize(c.n);
+  const uint64_t* e = c.words;
+  for (uint64_t i = 0; i < c.n; ++i, e += scot_plan_entry_words(e)) {
+    (*fn)[i] = resolve((const char*)(v.names + e[0] * SCOT_PLAN_NAME_BYTES), e[1], c.names);
     if (!(*fn)[i]) return false;
-    w += 4 + 2 * ni + nf;
   }
   return true;
 }
 
-// one entries section -> scot_tape_replay's program with the final addresses
-bool build_program(Plan* pl, const uint64_t* e, uint64_t n, uint64_t words, const std::vector<void*>& fn,
-                   const std::vector<uint64_t>& array_address, std::vector<uint64_t>* prog, std::vector<size_t>* slots) {
-  prog->reserve((size_t)(words + n));
-  uint64_t w = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    const uint64_t ni = e[w + 2], nf = e[w + 3];
-    prog->push_back((uint64_t)(uintptr_t)fn[i]);
-    prog->push_back(ni);
-    prog->push_back(nf);
+// one call list -> scot_tape_replay's program with the final addresses
+bool build_program(Plan* pl, const scot_plan_calls& c, const std::vector<void*>& fn, const std::vector<uint64_t>& array_address,
+                   Plan::Program* out) {
+  out->calls = c.n;
+  out->prog.reserve((size_t)(c.n_words + c.n));
+  const uint64_t* e = c.words;
+  for (uint64_t i = 0; i < c.n; ++i, e += scot_plan_entry_words(e)) {
+    const uint64_t ni = e[2], nf = e[3];
+    out->prog.push_back((uint64_t)(uintptr_t)fn[i]);
+    out->prog.push_back(ni);
+    out->prog.push_back(nf);
     for (uint64_t k = 0; k < ni; ++k) {
-      const uint64_t tagw = e[w + 4 + 2 * k], val = e[w + 5 + 2 * k];
+      const uint64_t tagw = e[4 + 2 * k], val = e[5 + 2 * k];
       uint64_t word = 0;
       bool st = false;
       if ((tagw & 0xff) == SCOT_PLAN_ARG_ARRAY)
         word = array_address[val];
       else if (!materialise(pl, tagw, val, &word, &st))
         return false;
-      if (st) slots->push_back(prog->size());
-      prog->push_back(word);
+      if (st) out->stream_slot.push_back(out->prog.size());
+      out->prog.push_back(word);
     }
-    for (uint64_t k = 0; k < nf; ++k) prog->push_back(e[w + 4 + 2 * ni + k]);
-    w += 4 + 2 * ni + nf;
+    for (uint64_t k = 0; k < nf; ++k) out->prog.push_back(e[4 + 2 * ni + k]);
   }
   return true;
 }
 
-char* adj_ptr(Plan* pl, int span) { return pl->buf[pl->adj[span]] + pl->adj[span + 1]; }
+// the address of a (buffer, offset, bytes) span of the adjoint or training words (pl->adj, pl->train)
+char* span_ptr(Plan* pl, const uint64_t* words, int slot) { return pl->buf[words[slot]] + words[slot + 1]; }
 
-char* train_ptr(Plan* pl, int span) { return pl->buf[pl->train[span]] + pl->train[span + 1]; }
+// ... and of a (buffer, offset) pair of the io words
+char* io_ptr(Plan* pl, int buf_word) { return span_ptr(pl, pl->io, buf_word); }
 
-char* io_ptr(Plan* pl, int buf_word, int off_word) { return pl->buf[pl->io[buf_word]] + pl->io[off_word]; }
+const char* listed_name(int list, int i) { return i >= 0 && i < scot_plan_lists[list].count ? scot_plan_lists[list].names[i] : nullptr; }
 }  // namespace
 
-extern "C" const char* scot_plan_entry_point(int i) { return i >= 0 && i < SCOT_PLAN_N_ENTRY_POINTS ? scot_plan_entry_names[i] : nullptr; }
-extern "C" const char* scot_plan_adjoint_entry_point(int i) {
-  return i >= 0 && i < SCOT_PLAN_N_ADJOINT_ENTRY_POINTS ? scot_plan_adjoint_entry_names[i] : nullptr;
-}
-extern "C" const char* scot_plan_training_entry_point(int i) {
-  return i >= 0 && i < SCOT_PLAN_N_TRAINING_ENTRY_POINTS ? scot_plan_training_entry_names[i] : nullptr;
-}
+extern "C" const char* scot_plan_entry_point(int i) { return listed_name(SCOT_PLAN_LIST_FORWARD, i); }
+extern "C" const char* scot_plan_adjoint_entry_point(int i) { return listed_name(SCOT_PLAN_LIST_ADJOINT, i); }
+extern "C" const char* scot_plan_training_entry_point(int i) { return listed_name(SCOT_PLAN_LIST_TRAINING, i); }
 #ifdef SCOT_HIPEMU
 extern "C" long long scot_plan_emu_issued() { return g_emu_issued; }
 #endif
@@ -363,9 +345,7 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
   int status = SCOT_OK;
   try {
     memcpy(pl->io, v.io, sizeof(pl->io));
-    pl->n_entries = v.n_entries;
     pl->format = (int)v.format;
-    pl->n_backward = v.n_backward;
     if (v.adj) memcpy(pl->adj, v.adj, sizeof(pl->adj));
     if (v.train) memcpy(pl->train, v.train, sizeof(pl->train));
     memcpy(pl->header, v.h, sizeof(pl->header));
@@ -373,15 +353,9 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
     pl->operand_format = (int)v.h[SCOT_PLAN_H_OPERAND];
     pl->compute = (int)v.h[SCOT_PLAN_H_COMPUTE];
     // every entry point, before anything is allocated
-    std::vector<void*> fn, fn_bwd, fn_step[3];
-    uint64_t w = 0;
-    if (!resolve_section(v, v.entries, v.n_entries, SCOT_PLAN_LIST_FORWARD, &fn) ||
-        !resolve_section(v, v.backward, v.n_backward, SCOT_PLAN_LIST_ADJOINT, &fn_bwd))
-      status = SCOT_ERR_UNSUPPORTED;
-    for (int s = 0; s < 3; ++s) {
-      pl->n_step[s] = v.n_step[s];
-      if (!resolve_section(v, v.step[s], v.n_step[s], SCOT_PLAN_LIST_TRAINING, &fn_step[s])) status = SCOT_ERR_UNSUPPORTED;
-    }
+    std::vector<void*> fn[SCOT_PLAN_N_CALLS];
+    for (int c = 0; c < SCOT_PLAN_N_CALLS; ++c)
+      if (!resolve_section(v, v.calls[c], &fn[c])) status = SCOT_ERR_UNSUPPORTED;
     // one slab, every buffer on a 256-byte boundary
     std::vector<size_t> off(v.n_buffers);
     size_t total = 0;
@@ -409,50 +383,34 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
             !dev_copy(pl->buf[i], v.data + v.buffers[4 * i + 2], (size_t)v.buffers[4 * i + 1], H2D, stream))
           status = SCOT_ERR_LAUNCH;
     }
-    // host arrays, with their final contents
+    // host arrays, with their final contents: pointers (kind 1) as words, int32 (0) and float bits (2) packed, four bytes each
     std::vector<uint64_t> array_address;
     if (status == SCOT_OK) {
-      w = 0;
+      uint64_t w = 0;
       for (uint64_t i = 0; i < v.n_arrays; ++i) {
         const uint64_t kind = v.arrays[w], cnt = v.arrays[w + 1];
-        if (kind == 2) {
-          std::vector<float> a(cnt ? cnt : 1);
-          for (uint64_t k = 0; k < cnt; ++k) {
-            const uint32_t bits = (uint32_t)v.arrays[w + 3 + 2 * k];
-            memcpy(&a[k], &bits, 4);
-          }
-          pl->flt_arrays.push_back(std::move(a));
-          array_address.push_back((uint64_t)(uintptr_t)pl->flt_arrays.back().data());
-        } else if (kind == 0) {
-          std::vector<int> a(cnt ? cnt : 1);
-          for (uint64_t k = 0; k < cnt; ++k) a[k] = (int)(int64_t)v.arrays[w + 3 + 2 * k];
-          pl->int_arrays.push_back(std::move(a));
-          array_address.push_back((uint64_t)(uintptr_t)pl->int_arrays.back().data());
-        } else {
-          std::vector<uint64_t> a(cnt ? cnt : 1);
-          for (uint64_t k = 0; k < cnt; ++k) {
-            bool st;
-            if (!materialise(pl, v.arrays[w + 2 + 2 * k], v.arrays[w + 3 + 2 * k], &a[k], &st)) status = SCOT_ERR_SHAPE;
-          }
-          pl->ptr_arrays.push_back(std::move(a));
-          array_address.push_back((uint64_t)(uintptr_t)pl->ptr_arrays.back().data());
+        std::vector<uint64_t> a((size_t)(kind == 1 ? cnt : (cnt + 1) / 2) + 1);
+        for (uint64_t k = 0; k < cnt; ++k) {
+          const uint64_t tagw = v.arrays[w + 2 + 2 * k], val = v.arrays[w + 3 + 2 * k];
+          const uint32_t low = (uint32_t)val;
+          bool st;
+          if (kind != 1)
+            memcpy((char*)a.data() + 4 * k, &low, 4);
+          else if (!materialise(pl, tagw, val, &a[k], &st))
+            status = SCOT_ERR_SHAPE;
         }
+        pl->host_arrays.push_back(std::move(a));
+        array_address.push_back((uint64_t)(uintptr_t)pl->host_arrays.back().data());
         w += 2 + 2 * cnt;
       }
     }
-    // the program(s)
-    if (status == SCOT_OK &&
-        (!build_program(pl, v.entries, v.n_entries, v.entries_words, fn, array_address, &pl->prog, &pl->stream_slot) ||
-         !build_program(pl, v.backward, v.n_backward, v.backward_words, fn_bwd, array_address, &pl->prog_bwd, &pl->stream_slot_bwd)))
-      status = SCOT_ERR_SHAPE;
-    for (int s = 0; s < 3 && status == SCOT_OK; ++s)
-      if (!build_program(pl, v.step[s], v.n_step[s], v.step_words[s], fn_step[s], array_address, &pl->prog_step[s], &pl->stream_slot_step[s]))
-        status = SCOT_ERR_SHAPE;
+    // the programs
+    for (int c = 0; c < SCOT_PLAN_N_CALLS && status == SCOT_OK; ++c)
+      if (!build_program(pl, v.calls[c], fn[c], array_address, &pl->list[c])) status = SCOT_ERR_SHAPE;
     if (status == SCOT_OK && v.train) {      // where the recorded scot_adamw_step reads lr[groups] (validated: an array of that many floats)
-      const uint64_t* e = v.step[2];
-      uint64_t at = 0;
-      for (uint64_t i = 0; i < v.train[SCOT_PLAN_TR_LR_ENTRY]; ++i) at += 4 + 2 * e[at + 2] + e[at + 3];
-      pl->lr = (float*)(uintptr_t)array_address[e[at + 5 + 2 * v.train[SCOT_PLAN_TR_LR_ARG]]];
+      const uint64_t* upd = v.calls[SCOT_PLAN_CALLS_UPDATE].words;
+      const uint64_t* e = upd + scot_plan_entry_at(upd, v.train[SCOT_PLAN_TR_LR_ENTRY]);
+      pl->lr = (float*)(uintptr_t)array_address[e[5 + 2 * v.train[SCOT_PLAN_TR_LR_ARG]]];
     }
     // the image may be released when this returns: the uploads read it
     if (status == SCOT_OK && !dev_sync(stream)) status = SCOT_ERR_LAUNCH;
@@ -480,7 +438,7 @@ extern "C" int scot_plan_describe(void* plan, long long* out) {
                            (long long)io[SCOT_PLAN_IO_W], (long long)io[SCOT_PLAN_IO_COUT], (long long)io[SCOT_PLAN_IO_HAS_TIME],
                            (long long)(io[SCOT_PLAN_IO_HAS_TIME] ? io[SCOT_PLAN_IO_TIME_BYTES] : 0), (long long)io[SCOT_PLAN_IO_HAS_MASK],
                            (long long)(io[SCOT_PLAN_IO_HAS_MASK] ? io[SCOT_PLAN_IO_MASK_BYTES] : 0), pl->operand_format, pl->compute,
-                           (long long)(pl->slab_bytes + pl->holder_bytes), (long long)pl->n_entries, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
+                           (long long)(pl->slab_bytes + pl->holder_bytes), (long long)pl->list[SCOT_PLAN_CALLS_FORWARD].calls, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
                            (long long)(hw * io[SCOT_PLAN_IO_COUT]), pl->format};
   memcpy(out, d, sizeof(d));
   return SCOT_OK;
@@ -497,11 +455,22 @@ extern "C" int scot_plan_poison(void* plan, int byte, hipStream_t stream) {
   return SCOT_OK;
 }
 
-static int check_inputs(Plan* pl, const void* pixel_values, const void* time, const void* pixel_mask, const void* out) {
-  if (!pixel_values || !out) return SCOT_ERR_SHAPE;
+// the caller's input pointers: pixel_values and `other` (where the result goes, or a batch's labels) are required; time, and with
+// `masked` pixel_mask, have to be given exactly where the plan takes them
+static int check_inputs(Plan* pl, const void* pixel_values, const void* time, const void* pixel_mask, const void* other, bool masked = true) {
+  if (!pixel_values || !other) return SCOT_ERR_SHAPE;
   if ((pl->io[SCOT_PLAN_IO_HAS_TIME] != 0) != (time != nullptr)) return SCOT_ERR_SHAPE;
-  if ((pl->io[SCOT_PLAN_IO_HAS_MASK] != 0) != (pixel_mask != nullptr)) return SCOT_ERR_SHAPE;
+  if (masked && (pl->io[SCOT_PLAN_IO_HAS_MASK] != 0) != (pixel_mask != nullptr)) return SCOT_ERR_SHAPE;
   return SCOT_OK;
+}
+
+// the inputs -> the plan's input copies (the caller has checked the pointers; a NULL time or pixel_mask is not copied)
+static bool copy_inputs(Plan* pl, const void* pixel_values, const void* time, const void* pixel_mask, hipStream_t stream) {
+  const uint64_t* io = pl->io;
+  const size_t in_bytes = (size_t)(io[SCOT_PLAN_IO_B] * io[SCOT_PLAN_IO_CIN] * io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * 4);
+  if (!dev_copy(io_ptr(pl, SCOT_PLAN_IO_PV_BUF), pixel_values, in_bytes, D2D, stream)) return false;
+  if (time && !dev_copy(io_ptr(pl, SCOT_PLAN_IO_TIME_BUF), time, (size_t)io[SCOT_PLAN_IO_TIME_BYTES], D2D, stream)) return false;
+  return !pixel_mask || dev_copy(io_ptr(pl, SCOT_PLAN_IO_MASK_BUF), pixel_mask, (size_t)io[SCOT_PLAN_IO_MASK_BYTES], D2D, stream);
 }
 
 extern "C" int scot_plan_run(void* plan, const float* pixel_values, const float* time, const void* pixel_mask, float* prediction,
@@ -512,16 +481,12 @@ extern "C" int scot_plan_run(void* plan, const float* pixel_values, const float*
   if (rc != SCOT_OK) return rc;
   pl->ran = false;
   const uint64_t* io = pl->io;
-  const size_t plane = (size_t)(io[SCOT_PLAN_IO_B] * io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * 4);
-  if (!dev_copy(io_ptr(pl, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF), pixel_values, plane * io[SCOT_PLAN_IO_CIN], D2D, stream)) return SCOT_ERR_LAUNCH;
-  if (time && !dev_copy(io_ptr(pl, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF), time, (size_t)io[SCOT_PLAN_IO_TIME_BYTES], D2D, stream))
-    return SCOT_ERR_LAUNCH;
-  if (pixel_mask && !dev_copy(io_ptr(pl, SCOT_PLAN_IO_MASK_BUF, SCOT_PLAN_IO_MASK_OFF), pixel_mask, (size_t)io[SCOT_PLAN_IO_MASK_BYTES], D2D, stream))
-    return SCOT_ERR_LAUNCH;
-  rc = replay(pl, stream);
+  const size_t out_bytes = (size_t)(io[SCOT_PLAN_IO_B] * io[SCOT_PLAN_IO_COUT] * io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * 4);
+  if (!copy_inputs(pl, pixel_values, time, pixel_mask, stream)) return SCOT_ERR_LAUNCH;
+  rc = replay(pl, SCOT_PLAN_CALLS_FORWARD, stream);
   if (rc != SCOT_OK) return rc;
-  if (!dev_copy(prediction, io_ptr(pl, SCOT_PLAN_IO_OUT_BUF, SCOT_PLAN_IO_OUT_OFF), plane * io[SCOT_PLAN_IO_COUT], D2D, stream)) return SCOT_ERR_LAUNCH;
-  pl->ran = pl->n_backward != 0;
+  if (!dev_copy(prediction, io_ptr(pl, SCOT_PLAN_IO_OUT_BUF), out_bytes, D2D, stream)) return SCOT_ERR_LAUNCH;
+  pl->ran = pl->list[SCOT_PLAN_CALLS_BACKWARD].calls != 0;
   return SCOT_OK;
 }
 
@@ -535,7 +500,7 @@ extern "C" int scot_plan_describe_adjoint(void* plan, long long* out) {
   out[0] = 1;
   out[1] = (long long)(pl->adj[SCOT_PLAN_ADJ_FLAGS] & 1);
   out[2] = (long long)((pl->adj[SCOT_PLAN_ADJ_FLAGS] >> 1) & 1);
-  out[3] = (long long)pl->n_backward;
+  out[3] = (long long)pl->list[SCOT_PLAN_CALLS_BACKWARD].calls;
   out[4] = (long long)pl->adj[SCOT_PLAN_ADJ_KEPT_BYTES];
   out[5] = (long long)(int64_t)pl->adj[SCOT_PLAN_ADJ_SCALE_EXP];
   return SCOT_OK;
@@ -562,7 +527,7 @@ static bool write_scale(Plan* pl, int exponent, hipStream_t stream) {
   pl->host_scale[1] = ldexpf(1.0f, -exponent);
   pl->host_scale[2] = pl->host_scale[3] = 0.0f;
   // (host_scale is pageable memory: the runtime has staged it by the time the copy call returned)
-  return dev_copy(adj_ptr(pl, SCOT_PLAN_ADJ_STATE), pl->host_scale, sizeof(pl->host_scale), H2D, stream);
+  return dev_copy(span_ptr(pl, pl->adj, SCOT_PLAN_ADJ_STATE), pl->host_scale, sizeof(pl->host_scale), H2D, stream);
 }
 
 // (d_pixel_values, d_time) <- J^T d_prediction at the inputs of the last scot_plan_run (include/scot_plan.h).  Every refusal comes before
@@ -578,12 +543,12 @@ extern "C" int scot_plan_vjp(void* plan, const float* d_prediction, float* d_pix
   if (!scale_exponent(pl, grad_scale, &exponent)) return SCOT_ERR_SHAPE;
   if (!pl->ran) return SCOT_ERR_SHAPE;
   pl->ran = false;      // one vjp per run: the backward reuses saved rows
-  if (!dev_copy(adj_ptr(pl, SCOT_PLAN_ADJ_COT), d_prediction, (size_t)a[SCOT_PLAN_ADJ_COT + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
+  if (!dev_copy(span_ptr(pl, pl->adj, SCOT_PLAN_ADJ_COT), d_prediction, (size_t)a[SCOT_PLAN_ADJ_COT + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
   if (!write_scale(pl, exponent, stream)) return SCOT_ERR_LAUNCH;
-  const int rc = replay(pl, stream, true);
+  const int rc = replay(pl, SCOT_PLAN_CALLS_BACKWARD, stream);
   if (rc != SCOT_OK) return rc;
-  if (d_pixel_values && !dev_copy(d_pixel_values, adj_ptr(pl, SCOT_PLAN_ADJ_DPV), (size_t)a[SCOT_PLAN_ADJ_DPV + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
-  if (d_time && !dev_copy(d_time, adj_ptr(pl, SCOT_PLAN_ADJ_DTIME), (size_t)a[SCOT_PLAN_ADJ_DTIME + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
+  if (d_pixel_values && !dev_copy(d_pixel_values, span_ptr(pl, pl->adj, SCOT_PLAN_ADJ_DPV), (size_t)a[SCOT_PLAN_ADJ_DPV + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
+  if (d_time && !dev_copy(d_time, span_ptr(pl, pl->adj, SCOT_PLAN_ADJ_DTIME), (size_t)a[SCOT_PLAN_ADJ_DTIME + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
   return SCOT_OK;
 }
 
@@ -594,7 +559,7 @@ extern "C" int scot_plan_grad_status(void* plan, long long* out, hipStream_t str
   out[0] = out[1] = 0;
   if (pl->format != SCOT_PLAN_FORMAT_ADJOINT) return SCOT_ERR_UNSUPPORTED;
   int count = 0;
-  if (pl->adj[SCOT_PLAN_ADJ_STATE + 2] && !dev_copy(&count, adj_ptr(pl, SCOT_PLAN_ADJ_COUNTER), sizeof(count), D2H, stream)) return SCOT_ERR_LAUNCH;
+  if (pl->adj[SCOT_PLAN_ADJ_STATE + 2] && !dev_copy(&count, span_ptr(pl, pl->adj, SCOT_PLAN_ADJ_COUNTER), sizeof(count), D2H, stream)) return SCOT_ERR_LAUNCH;
   if (!dev_sync(stream)) return SCOT_ERR_LAUNCH;      // (also without a counter: the caller's gradients are complete on return)
   out[0] = count;
   out[1] = pl->last_exponent;
@@ -637,16 +602,13 @@ extern "C" int scot_plan_rollout(void* plan, const float* pixel_values, const fl
   pl->ran = false;      // (a rollout leaves nothing to differentiate: its forwards overwrite each other's saved rows)
   const size_t B = (size_t)io[SCOT_PLAN_IO_B], hw = (size_t)(io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * 4);
   const size_t in_row = hw * io[SCOT_PLAN_IO_CIN], out_row = hw * io[SCOT_PLAN_IO_COUT];
-  char* in = io_ptr(pl, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF);
-  char* out = io_ptr(pl, SCOT_PLAN_IO_OUT_BUF, SCOT_PLAN_IO_OUT_OFF);
-  char* t = io_ptr(pl, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF);
+  char* in = io_ptr(pl, SCOT_PLAN_IO_PV_BUF);
+  char* out = io_ptr(pl, SCOT_PLAN_IO_OUT_BUF);
   if (!read_step_time(pl, time, steps, stream)) return SCOT_ERR_LAUNCH;
-  if (!dev_copy(t, pl->host_time.data(), B * 4, H2D, stream)) return SCOT_ERR_LAUNCH;
-  if (!dev_copy(in, pixel_values, B * in_row, D2D, stream)) return SCOT_ERR_LAUNCH;
-  if (pixel_mask && !dev_copy(io_ptr(pl, SCOT_PLAN_IO_MASK_BUF, SCOT_PLAN_IO_MASK_OFF), pixel_mask, (size_t)io[SCOT_PLAN_IO_MASK_BYTES], D2D, stream))
-    return SCOT_ERR_LAUNCH;
+  if (!dev_copy(io_ptr(pl, SCOT_PLAN_IO_TIME_BUF), pl->host_time.data(), B * 4, H2D, stream)) return SCOT_ERR_LAUNCH;
+  if (!copy_inputs(pl, pixel_values, nullptr, pixel_mask, stream)) return SCOT_ERR_LAUNCH;      // (time: the divided one, above)
   for (int k = 0; k < steps; ++k) {
-    rc = replay(pl, stream);
+    rc = replay(pl, SCOT_PLAN_CALLS_FORWARD, stream);
     if (rc != SCOT_OK) return rc;
     if (!dev_copy((char*)predictions + (size_t)k * B * out_row, out, B * out_row, D2D, stream)) return SCOT_ERR_LAUNCH;
     if (k + 1 < steps && !dev_copy2d(in, in_row, out, out_row, out_row, B, stream)) return SCOT_ERR_LAUNCH;
@@ -691,11 +653,11 @@ extern "C" int scot_plan_rollout_vjp(void* plan, const float* pixel_values, cons
     hold = pl->holder;
   }
   pl->ran = false;      // (the sweep's forwards overwrite the saved rows of any earlier run, and its backwards use their own up)
-  char* in = io_ptr(pl, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF);
-  char* t = io_ptr(pl, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF);
-  float* cot = (float*)adj_ptr(pl, SCOT_PLAN_ADJ_COT);
-  const float* g_pv = has_dpv ? (const float*)adj_ptr(pl, SCOT_PLAN_ADJ_DPV) : nullptr;
-  const float* g_t = has_dt ? (const float*)adj_ptr(pl, SCOT_PLAN_ADJ_DTIME) : nullptr;
+  char* in = io_ptr(pl, SCOT_PLAN_IO_PV_BUF);
+  char* t = io_ptr(pl, SCOT_PLAN_IO_TIME_BUF);
+  float* cot = (float*)span_ptr(pl, pl->adj, SCOT_PLAN_ADJ_COT);
+  const float* g_pv = has_dpv ? (const float*)span_ptr(pl, pl->adj, SCOT_PLAN_ADJ_DPV) : nullptr;
+  const float* g_t = has_dt ? (const float*)span_ptr(pl, pl->adj, SCOT_PLAN_ADJ_DTIME) : nullptr;
   if (!read_step_time(pl, time, steps, stream)) return SCOT_ERR_LAUNCH;
   for (int k = steps - 1; k >= 0; --k) {
     // step k's input: cat(predictions[k-1], pixel_values[:, Cout:]) — pixel_values itself for step 0 — and time / steps
@@ -707,7 +669,7 @@ extern "C" int scot_plan_rollout_vjp(void* plan, const float* pixel_values, cons
         return SCOT_ERR_LAUNCH;
     }
     if (!dev_copy(t, pl->host_time.data(), B * 4, H2D, stream)) return SCOT_ERR_LAUNCH;
-    int rc = replay(pl, stream);
+    int rc = replay(pl, SCOT_PLAN_CALLS_FORWARD, stream);
     if (rc != SCOT_OK) return rc;
     const float* d_pred = (const float*)((const char*)d_predictions + (size_t)k * B * out_row);
     if (k == steps - 1) {
@@ -716,7 +678,7 @@ extern "C" int scot_plan_rollout_vjp(void* plan, const float* pixel_values, cons
       return SCOT_ERR_LAUNCH;
     }
     if (!write_scale(pl, exponent, stream)) return SCOT_ERR_LAUNCH;
-    rc = replay(pl, stream, true);
+    rc = replay(pl, SCOT_PLAN_CALLS_BACKWARD, stream);
     if (rc != SCOT_OK) return rc;
     if ((hold || d_time) && !dev_carry(hold, g_pv, d_time, g_t, B, cin, cout, hw, k == steps - 1, k == 0, steps, stream)) return SCOT_ERR_LAUNCH;
   }
@@ -736,27 +698,23 @@ extern "C" int scot_plan_describe_training(void* plan, long long* out) {
   out[0] = 1;
   out[1] = (long long)t[SCOT_PLAN_TR_GROUPS];
   out[2] = (long long)t[SCOT_PLAN_TR_ARENA_FLOATS];
-  out[3] = (long long)(pl->n_step[0] + pl->n_step[1] + pl->n_step[2]);
+  for (int c = SCOT_PLAN_CALLS_STEP_FORWARD; c <= SCOT_PLAN_CALLS_UPDATE; ++c) out[3] += (long long)pl->list[c].calls;
   out[4] = (long long)t[SCOT_PLAN_TR_LABELS + 2];
   out[5] = (long long)t[SCOT_PLAN_TR_KEPT_BYTES];
   out[6] = (long long)(t[SCOT_PLAN_TR_FLAGS] & 1);
   return SCOT_OK;
 }
 
-// the batch -> the plan's input copies (the caller has checked the pointers)
+// the batch -> the plan's input copies (the caller has checked the pointers): the inputs, and the labels
 static bool copy_batch_in(Plan* pl, const float* pixel_values, const float* time, const float* labels, hipStream_t stream) {
-  const uint64_t* io = pl->io;
-  const size_t plane = (size_t)(io[SCOT_PLAN_IO_B] * io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] * 4);
-  if (!dev_copy(io_ptr(pl, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF), pixel_values, plane * io[SCOT_PLAN_IO_CIN], D2D, stream)) return false;
-  if (time && !dev_copy(io_ptr(pl, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF), time, (size_t)io[SCOT_PLAN_IO_TIME_BYTES], D2D, stream)) return false;
-  return dev_copy(train_ptr(pl, SCOT_PLAN_TR_LABELS), labels, (size_t)pl->train[SCOT_PLAN_TR_LABELS + 2], D2D, stream);
+  return copy_inputs(pl, pixel_values, time, nullptr, stream) &&
+         dev_copy(span_ptr(pl, pl->train, SCOT_PLAN_TR_LABELS), labels, (size_t)pl->train[SCOT_PLAN_TR_LABELS + 2], D2D, stream);
 }
 
+// a batch for a training plan: pixel_values, labels, and time where the plan takes it (a batch has no mask)
 static int check_batch(Plan* pl, const void* pixel_values, const void* time, const void* labels) {
   if (pl->format != SCOT_PLAN_FORMAT_TRAINING) return SCOT_ERR_UNSUPPORTED;
-  if (!pixel_values || !labels) return SCOT_ERR_SHAPE;
-  if ((pl->io[SCOT_PLAN_IO_HAS_TIME] != 0) != (time != nullptr)) return SCOT_ERR_SHAPE;
-  return SCOT_OK;
+  return check_inputs(pl, pixel_values, time, nullptr, labels, false);
 }
 
 // loss [1] <- what model(pixel_values, time, labels=labels).loss returns, prediction (may be NULL) <- its output: the step's forward
@@ -769,10 +727,10 @@ extern "C" int scot_plan_loss(void* plan, const float* pixel_values, const float
   if (rc != SCOT_OK) return rc;
   if (!loss) return SCOT_ERR_SHAPE;
   if (!copy_batch_in(pl, pixel_values, time, labels, stream)) return SCOT_ERR_LAUNCH;
-  rc = replay_step(pl, 0, stream);
+  rc = replay(pl, SCOT_PLAN_CALLS_STEP_FORWARD, stream);
   if (rc != SCOT_OK) return rc;
-  if (!dev_copy(loss, train_ptr(pl, SCOT_PLAN_TR_LOSS), 4, D2D, stream)) return SCOT_ERR_LAUNCH;
-  if (prediction && !dev_copy(prediction, train_ptr(pl, SCOT_PLAN_TR_PRED), (size_t)pl->train[SCOT_PLAN_TR_PRED + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
+  if (!dev_copy(loss, span_ptr(pl, pl->train, SCOT_PLAN_TR_LOSS), 4, D2D, stream)) return SCOT_ERR_LAUNCH;
+  if (prediction && !dev_copy(prediction, span_ptr(pl, pl->train, SCOT_PLAN_TR_PRED), (size_t)pl->train[SCOT_PLAN_TR_PRED + 2], D2D, stream)) return SCOT_ERR_LAUNCH;
   return SCOT_OK;
 }
 
@@ -788,8 +746,8 @@ extern "C" int scot_plan_train_step(void* plan, const float* pixel_values, const
   if (!copy_batch_in(pl, pixel_values, time, labels, stream)) return SCOT_ERR_LAUNCH;
   memcpy(pl->lr, lr, (size_t)pl->train[SCOT_PLAN_TR_GROUPS] * sizeof(float));
   for (int s = 0; s < 3; ++s)
-    if ((rc = replay_step(pl, s, stream)) != SCOT_OK) return rc;
-  if (loss && !dev_copy(loss, train_ptr(pl, SCOT_PLAN_TR_LOSS), 4, D2D, stream)) return SCOT_ERR_LAUNCH;
+    if ((rc = replay(pl, SCOT_PLAN_CALLS_STEP_FORWARD + s, stream)) != SCOT_OK) return rc;
+  if (loss && !dev_copy(loss, span_ptr(pl, pl->train, SCOT_PLAN_TR_LOSS), 4, D2D, stream)) return SCOT_ERR_LAUNCH;
   return SCOT_OK;
 }
 
@@ -803,10 +761,10 @@ extern "C" int scot_plan_train_status(void* plan, double* out, hipStream_t strea
   int steps[2] = {0, 0}, counted = 0;
   float clip[3] = {0.0f, 0.0f, 0.0f}, scale[4] = {1.0f, 1.0f, 0.0f, 0.0f};
   const bool dyn = (pl->train[SCOT_PLAN_TR_FLAGS] & 1) != 0;
-  if (!dev_copy(steps, train_ptr(pl, SCOT_PLAN_TR_STEP_STATE), sizeof(steps), D2H, stream)) return SCOT_ERR_LAUNCH;
-  if (!dev_copy(clip, train_ptr(pl, SCOT_PLAN_TR_CLIP), sizeof(clip), D2H, stream)) return SCOT_ERR_LAUNCH;
-  if (dyn && (!dev_copy(scale, train_ptr(pl, SCOT_PLAN_TR_SCALE_STATE), sizeof(scale), D2H, stream) ||
-              !dev_copy(&counted, train_ptr(pl, SCOT_PLAN_TR_COUNTER), sizeof(counted), D2H, stream)))
+  if (!dev_copy(steps, span_ptr(pl, pl->train, SCOT_PLAN_TR_STEP_STATE), sizeof(steps), D2H, stream)) return SCOT_ERR_LAUNCH;
+  if (!dev_copy(clip, span_ptr(pl, pl->train, SCOT_PLAN_TR_CLIP), sizeof(clip), D2H, stream)) return SCOT_ERR_LAUNCH;
+  if (dyn && (!dev_copy(scale, span_ptr(pl, pl->train, SCOT_PLAN_TR_SCALE_STATE), sizeof(scale), D2H, stream) ||
+              !dev_copy(&counted, span_ptr(pl, pl->train, SCOT_PLAN_TR_COUNTER), sizeof(counted), D2H, stream)))
     return SCOT_ERR_LAUNCH;
   if (!dev_sync(stream)) return SCOT_ERR_LAUNCH;
   out[0] = steps[0];

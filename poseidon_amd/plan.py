@@ -25,6 +25,7 @@ torch only if the caller hands it tensors).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import struct
 import sys
@@ -43,10 +44,22 @@ MAX_INT, MAX_FLT = 48, 8
 (H_MAGIC, H_FORMAT, H_ABI, H_OPERAND, H_COMPUTE, H_BYTES, H_NNAMES, H_NAMES_OFF, H_NBUFFERS, H_BUFFERS_OFF, H_NENTRIES, H_ENTRIES_OFF,
  H_ENTRIES_WORDS, H_NARRAYS, H_ARRAYS_OFF, H_ARRAYS_WORDS, H_IO_OFF, H_DATA_OFF, H_DATA_BYTES, H_NBACKWARD, H_BACKWARD_OFF,
  H_BACKWARD_WORDS, H_ADJ_OFF, H_TRAIN_OFF) = range(24)
-ADJ_FLAGS, ADJ_COT, ADJ_DPV, ADJ_DTIME, ADJ_STATE, ADJ_COUNTER, ADJ_SCALE_EXP, ADJ_KEPT_BYTES = 0, 1, 4, 7, 10, 13, 16, 17
+
+
+def _slots(*words):
+    """the first word of each slot, given every slot's length in order — as the C enums of csrc/plan_image.h compute them
+    (1: a plain word; 3: a list (count, offset, words) or a span (buffer, offset, bytes))"""
+    return [sum(words[:i]) for i in range(len(words))]
+
+
+ADJ_FLAGS, ADJ_COT, ADJ_DPV, ADJ_DTIME, ADJ_STATE, ADJ_COUNTER, ADJ_SCALE_EXP, ADJ_KEPT_BYTES = _slots(1, 3, 3, 3, 3, 3, 1, 1)
 (TR_FLAGS, TR_GROUPS, TR_ARENA_FLOATS, TR_FWD, TR_BWD, TR_UPD, TR_LR_ENTRY, TR_LR_ARG, TR_KEPT_BYTES, TR_LABELS, TR_LOSS, TR_PRED, TR_ARENA,
- TR_EXP_AVG, TR_EXP_AVG_SQ, TR_SHADOW, TR_SHADOW_T, TR_STEP_STATE, TR_CLIP, TR_SCALE_STATE, TR_COUNTER) = (0, 1, 2, 3, 6, 9, 12, 13, 14, 15, 18, 21,
-                                                                                                     24, 27, 30, 33, 36, 39, 42, 45, 48)
+ TR_EXP_AVG, TR_EXP_AVG_SQ, TR_SHADOW, TR_SHADOW_T, TR_STEP_STATE, TR_CLIP, TR_SCALE_STATE, TR_COUNTER) = _slots(1, 1, 1, 3, 3, 3, 1, 1, 1, *[3] * 12)
+assert ADJ_KEPT_BYTES < ADJ_WORDS and TR_COUNTER + 3 <= TRAIN_WORDS
+# the runtime's three tables of entry points: which call enumerates each, and the X-macro of csrc/plan_image.h behind it
+ENTRY_POINT_TABLES = {"forward": ("scot_plan_entry_point", "SCOT_PLAN_ENTRY_POINTS"),
+                      "adjoint": ("scot_plan_adjoint_entry_point", "SCOT_PLAN_ADJOINT_ENTRY_POINTS"),
+                      "training": ("scot_plan_training_entry_point", "SCOT_PLAN_TRAINING_ENTRY_POINTS")}
 DESCRIBE_TRAINING = ("has_training", "groups", "arena_floats", "step_calls", "labels_bytes", "kept_bytes", "dynamic_scale")
 TRAIN_STATUS = ("applied", "skipped", "grad_scale", "grad_norm", "clip_coef", "nonfinite")
 # host arrays of floats among the recorded arguments: {entry point: {argument index: index of the argument that holds the count}}
@@ -74,7 +87,8 @@ def runtime_entry_points(lib, adjoint=False, training=False):
     """the entry points the runtime of this build lists: what a plan's forward (adjoint: its backward; training: the three step lists
     of a training plan) may call"""
     bind(lib)
-    query = lib.scot_plan_training_entry_point if training else (lib.scot_plan_adjoint_entry_point if adjoint else lib.scot_plan_entry_point)
+    table = next(name for name, asked in (("training", training), ("adjoint", adjoint), ("forward", True)) if asked)
+    query = getattr(lib, ENTRY_POINT_TABLES[table][0])
     out, i = [], 0
     while True:
         n = query(i)
@@ -207,65 +221,86 @@ def _register(reg, buffers, only_new=False):
                 reg.add(ten, _kind(const), name)
 
 
-def _record(model, pv, t, adjoint=()):
-    """-> (registry, recorded calls, kept tensors, prediction tensor, input copies, adjoint record or None): ONE dedicated, linear
-    recording of engine._forward — with `adjoint`, of the forward a differentiable call runs (train=True without stochastic depth,
-    these input gradients, no parameter gradient) followed by engine._backward from a cotangent of the prediction alone; the adjoint
-    record holds where the second list starts and the cotangent / gradient tensors"""
-    import torch
+_ENGINE_SWITCHES = ("use_side", "stage_timing", "stochastic", "collect_attn")
+_ENGINE_SAVED = _ENGINE_SWITCHES + ("last_hidden", "last_hidden_aliased", "_rec", "_rec_keep", "_fwd_flags")
+
+
+@contextlib.contextmanager
+def _recording(eng, reg, side_rows, refresh, extra_saved=(), snapshot=None):
+    """What every export's recording run needs around it -> (recorded calls, kept tensors), both filled by the body: the engine's build
+    of the library in use, the 16-bit weight copies current (`refresh`: the transposed ones too; never part of a recording), the
+    engine's switches off, `ops.workspace` registering itself, the registry and the recorder installed — and all of it put back
+    afterwards.  snapshot() is called once the copies are current and returns what to call right after the recorder has been taken out."""
     from . import ops
-    eng = model._engine
-    reg = _Registry()
-    _register(reg, eng.plan_buffers(adjoint=bool(adjoint)))
-    pv_in = pv.clone()
-    t_in = None if t is None else t.clone()
-    reg.add(pv_in, INPUT, "pixel_values")
-    if t_in is not None:
-        reg.add(t_in, INPUT, "time")
-    adj = None
-    if adjoint:
-        cot = torch.zeros(pv.shape[0], model.config.num_out_channels, pv.shape[2], pv.shape[3], dtype=torch.float32, device=pv.device)
-        reg.add(cot, INPUT, "d_prediction")
     inner_workspace = ops.workspace
 
     def workspace(need=0):      # the split-K scratch of the wrappers is an allocation funnel too
         w = inner_workspace(need)
         reg.add(w, SCRATCH, "workspace")
         return w
-    saved = dict(use_side=eng.use_side, stage_timing=eng.stage_timing, stochastic=eng.stochastic, collect_attn=eng.collect_attn,
-                 last_hidden=eng.last_hidden, last_hidden_aliased=eng.last_hidden_aliased, _rec=eng._rec, _rec_keep=eng._rec_keep,
-                 _fwd_flags=eng._fwd_flags)
+    saved = {k: getattr(eng, k) for k in _ENGINE_SAVED + tuple(extra_saved)}
     rec, keep = [], []
     prev_lib = ops.use(eng.lib_kind)
     try:
-        eng.refresh_weight_copies(bool(adjoint))      # (never part of a recording: the 16-bit copies are constants of the image)
+        eng.refresh_weight_copies(refresh)
+        put_back = snapshot() if snapshot is not None else None
         ops.workspace = workspace
-        eng.use_side = eng.stage_timing = eng.stochastic = eng.collect_attn = False
+        for k in _ENGINE_SWITCHES:
+            setattr(eng, k, False)
         eng._export, eng._rec, eng._rec_keep = reg, rec, keep
-        eng._export_side_rows = bool(saved["use_side"] and not saved["stage_timing"])
+        eng._export_side_rows = side_rows
         prev_rec = ops.set_recorder(rec)
         try:
-            if adjoint:      # forced for the export, whatever the caller's tensors require
-                eng._fwd_flags = (adjoint, False)
-                _, pred, tape = eng._forward(pv_in, t_in, None, None, True)
-                n_fwd = len(rec)
-                cot.copy_(pred / float(pred.numel()))      # (a value for the recording run; a vjp copies the caller's in)
-                counted = None if eng.grad_overflow is None else eng.grad_overflow.clone()
-                d_pv, d_t = eng._backward(tape, None, cot)
-                if counted is not None:      # (the recording run is not a step of the model's: its un-scale passes do not count)
-                    eng.grad_overflow.copy_(counted)
-                keep.append(tape)
-                adj = dict(n_fwd=n_fwd, cot=cot, d_pv=d_pv, d_t=d_t)
-            else:
-                _, pred, _ = eng._forward(pv_in, t_in, None, None, False)
+            yield rec, keep
         finally:
             ops.set_recorder(prev_rec)
+            if put_back is not None:
+                put_back()
     finally:
         ops.workspace = inner_workspace
         eng._export = None
         for k, v in saved.items():
             setattr(eng, k, v)
         ops.use(prev_lib)
+
+
+def _input_copies(reg, pv, t):
+    pv_in = pv.clone()
+    t_in = None if t is None else t.clone()
+    reg.add(pv_in, INPUT, "pixel_values")
+    if t_in is not None:
+        reg.add(t_in, INPUT, "time")
+    return pv_in, t_in
+
+
+def _record(model, pv, t, adjoint=()):
+    """-> (registry, recorded calls, kept tensors, prediction tensor, input copies, adjoint record or None): ONE dedicated, linear
+    recording of engine._forward — with `adjoint`, of the forward a differentiable call runs (train=True without stochastic depth,
+    these input gradients, no parameter gradient) followed by engine._backward from a cotangent of the prediction alone; the adjoint
+    record holds where the second list starts and the cotangent / gradient tensors"""
+    import torch
+    eng = model._engine
+    reg = _Registry()
+    _register(reg, eng.plan_buffers(adjoint=bool(adjoint)))
+    pv_in, t_in = _input_copies(reg, pv, t)
+    adj = None
+    if adjoint:
+        cot = torch.zeros(pv.shape[0], model.config.num_out_channels, pv.shape[2], pv.shape[3], dtype=torch.float32, device=pv.device)
+        reg.add(cot, INPUT, "d_prediction")
+    with _recording(eng, reg, bool(eng.use_side and not eng.stage_timing), bool(adjoint)) as (rec, keep):
+        if adjoint:      # forced for the export, whatever the caller's tensors require
+            eng._fwd_flags = (adjoint, False)
+            _, pred, tape = eng._forward(pv_in, t_in, None, None, True)
+            n_fwd = len(rec)
+            cot.copy_(pred / float(pred.numel()))      # (a value for the recording run; a vjp copies the caller's in)
+            counted = None if eng.grad_overflow is None else eng.grad_overflow.clone()
+            d_pv, d_t = eng._backward(tape, None, cot)
+            if counted is not None:      # (the recording run is not a step of the model's: its un-scale passes do not count)
+                eng.grad_overflow.copy_(counted)
+            keep.append(tape)
+            adj = dict(n_fwd=n_fwd, cot=cot, d_pv=d_pv, d_t=d_t)
+        else:
+            _, pred, _ = eng._forward(pv_in, t_in, None, None, False)
     _register(reg, eng.plan_buffers(adjoint=bool(adjoint)), only_new=True)      # (tables the forward created on first use)
     return reg, rec, keep, pred, pv_in, t_in, adj
 
@@ -289,58 +324,20 @@ def _record_training(model, opt, pv, t, labels):
     eng = model._engine
     reg = _Registry()
     _register(reg, eng.plan_buffers(train=opt))
-    pv_in, lab_in = pv.clone(), labels.clone()
-    t_in = None if t is None else t.clone()
-    reg.add(pv_in, INPUT, "pixel_values")
-    if t_in is not None:
-        reg.add(t_in, INPUT, "time")
+    pv_in, t_in = _input_copies(reg, pv, t)
+    lab_in = labels.clone()
     reg.add(lab_in, INPUT, "labels")
     one = None
     if not eng.scale_grads:      # d loss = 1 as a constant of the image (under a gradient scale the backward copies S from the state)
         one = torch.ones(1, dtype=torch.float32, device=pv.device)
         reg.add(one, CONSTANT, "one")
-    inner_workspace = ops.workspace
-
-    def workspace(need=0):
-        w = inner_workspace(need)
-        reg.add(w, SCRATCH, "workspace")
-        return w
-    saved = dict(use_side=eng.use_side, stage_timing=eng.stage_timing, stochastic=eng.stochastic, collect_attn=eng.collect_attn,
-                 last_hidden=eng.last_hidden, last_hidden_aliased=eng.last_hidden_aliased, _rec=eng._rec, _rec_keep=eng._rec_keep,
-                 _fwd_flags=eng._fwd_flags, grad_fill_event=eng.grad_fill_event)
-    rec, keep = [], []
-    prev_lib = ops.use(eng.lib_kind)
     state = _training_state(model, opt)
-    try:
-        eng.refresh_weight_copies(True)      # (both 16-bit copies current BEFORE they are saved: the image stores them by value)
+
+    def snapshot():      # (both 16-bit copies are current by now: the image stores them by value)
         before, step_count = [x.clone() for x in state], opt.step_count
         grads_before = (eng.arena.grad.clone(), eng.grads_are_zero, eng.lazy_grads)      # (what the caller has accumulated so far)
-        ops.workspace = workspace
-        eng.use_side = eng.stage_timing = eng.stochastic = eng.collect_attn = False
-        eng.grad_fill_event = None
-        eng._export, eng._rec, eng._rec_keep = reg, rec, keep
-        eng._export_side_rows = False
-        prev_rec = ops.set_recorder(rec)
-        try:
-            eng._fwd_flags = ((), True)
-            _, pred, _ = eng._forward(pv_in, t_in, None, None, False)
-            n_inf = len(rec)
-            loss, pred_step, tape = eng._forward(pv_in, t_in, lab_in, None, True)
-            n_fwd = len(rec)
-            _register(reg, eng.plan_buffers(train=opt), only_new=True)
-            lazy = eng._small_chunks is not None      # ScOT.zero_grad(overlap=True): only what is accumulated into is filled
-            if lazy:
-                eng.fill_small_grads()
-            else:
-                ops.memset_async(eng.arena.grad, 0)
-            eng.grads_are_zero, eng.lazy_grads = True, lazy
-            eng._backward(tape, one, None)
-            eng.grads_are_zero = eng.lazy_grads = False
-            n_bwd = len(rec)
-            opt.step()
-            keep.append(tape)
-        finally:
-            ops.set_recorder(prev_rec)
+
+        def put_back():
             with torch.no_grad():
                 for x, b in zip(state, before):
                     x.copy_(b)
@@ -350,12 +347,26 @@ def _record_training(model, opt, pv, t, labels):
             model.mark_weights_dirty()
             if eng.shadow is not None:      # (put back with the master weights: current again)
                 eng._shadow_v = eng._shadow_t_v = model._weights_version()
-    finally:
-        ops.workspace = inner_workspace
-        eng._export = None
-        for k, v in saved.items():
-            setattr(eng, k, v)
-        ops.use(prev_lib)
+        return put_back
+    with _recording(eng, reg, False, True, extra_saved=("grad_fill_event",), snapshot=snapshot) as (rec, keep):
+        eng.grad_fill_event = None
+        eng._fwd_flags = ((), True)
+        _, pred, _ = eng._forward(pv_in, t_in, None, None, False)
+        n_inf = len(rec)
+        loss, pred_step, tape = eng._forward(pv_in, t_in, lab_in, None, True)
+        n_fwd = len(rec)
+        _register(reg, eng.plan_buffers(train=opt), only_new=True)
+        lazy = eng._small_chunks is not None      # ScOT.zero_grad(overlap=True): only what is accumulated into is filled
+        if lazy:
+            eng.fill_small_grads()
+        else:
+            ops.memset_async(eng.arena.grad, 0)
+        eng.grads_are_zero, eng.lazy_grads = True, lazy
+        eng._backward(tape, one, None)
+        eng.grads_are_zero = eng.lazy_grads = False
+        n_bwd = len(rec)
+        opt.step()
+        keep.append(tape)
     _register(reg, eng.plan_buffers(train=opt), only_new=True)      # (tables the step created on first use)
     tr = dict(n_inf=n_inf, n_fwd=n_fwd, n_bwd=n_bwd, labels=lab_in, loss=loss, pred=pred_step, opt=opt)
     return reg, rec, keep, pred, pv_in, t_in, tr
@@ -378,53 +389,81 @@ def _bytes_of(t):
     return t.detach().reshape(-1).cpu().contiguous().view(__import__("torch").uint8).numpy().tobytes()
 
 
-def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=None):
-    """recorded calls + registered buffers -> the bytes of a plan image (adj: the adjoint record of _record -> a format-2 image; train:
-    the training record of _record_training -> a format-4 image)"""
-    eng = model._engine
-    reg.freeze()
-    used, names, name_index = [], [], {}
-    index_of = {}
+class _CallList:
+    """one recorded call list on its way into an image: `what` it is (in messages, and its section's name in the layout), the table of
+    entry points it is held to, where it ends in the recording; then its encoded entries and the buffers its arguments touch"""
 
-    def buffer_index(b):
-        i = index_of.get(b["addr"])
+    def __init__(self, what, table, end, own):
+        self.what, self.table, self.end = what, table, end
+        self.macro = ENTRY_POINT_TABLES[table][1]
+        self.listed = set(runtime_entry_points(own, **({} if table == "forward" else {table: True})))
+        self.entries, self.touched = [], set()
+
+    def words(self):
+        ws = []
+        for name, which, ints, flts in self.entries:
+            ws += [name, which, len(ints), len(flts)]
+            for tag, val in ints:
+                ws += [tag, val]
+            ws += flts
+        return ws
+
+
+class _Relocator:
+    """device addresses -> (buffer index, byte offset) over the frozen registry; `used` numbers the buffers in the order of first use"""
+
+    def __init__(self, reg):
+        self.reg, self.used, self._index = reg, [], {}
+
+    def index(self, b):
+        i = self._index.get(b["addr"])
         if i is None:
-            i = index_of[b["addr"]] = len(used)
-            used.append(b)
+            i = self._index[b["addr"]] = len(self.used)
+            self.used.append(b)
         return i
 
-    def pair(value, what):
-        """a device address -> argument pair"""
+    def pair(self, value, what, touched):
+        """a device address among a call's arguments -> argument pair"""
         if not value:
             return (ARG_NULL, 0)
-        b, off = reg.resolve(value)
+        b, off = self.reg.resolve(value)
         if b is None:
             raise PlanExportError(f"export_plan: {what} is a device address (0x{value:x}) inside no buffer the export registered")
-        if touching is not None:
-            touching.add(b["addr"])
-        return (ARG_PTR | (buffer_index(b) << 8), off)
+        touched.add(b["addr"])
+        return (ARG_PTR | (self.index(b) << 8), off)
 
-    arrays, touching = [], None
-    n_fwd = len(rec) if adj is None else adj["n_fwd"]
-    listed_fwd = set(runtime_entry_points(own))
-    listed_bwd = set(runtime_entry_points(own, adjoint=True)) if adj is not None else set()
-    sections = [("forward", "SCOT_PLAN_ENTRY_POINTS", listed_fwd, [], set()), ("backward", "SCOT_PLAN_ADJOINT_ENTRY_POINTS", listed_bwd, [], set())]
-    bounds = [n_fwd, len(rec)]
-    lr_point = None
-    if train is not None:
-        listed_tr = set(runtime_entry_points(own, training=True))
-        sections = [sections[0]] + [(what, "SCOT_PLAN_TRAINING_ENTRY_POINTS", listed_tr, [], set())
-                                    for what in ("step forward", "step backward", "update")]
-        bounds = [train["n_inf"], train["n_fwd"], train["n_bwd"], len(rec)]
+    def span(self, t, what, kind):
+        """a tensor the runtime itself addresses -> [buffer index, byte offset, bytes]; its buffer becomes one of `kind`"""
+        n = t.numel() * t.element_size()
+        b, off = self.reg.resolve(t.data_ptr())
+        if b is None or off + n > b["bytes"]:
+            raise PlanExportError(f"export_plan: {what} lies in no registered buffer")
+        b["kind"] = kind
+        return [self.index(b), off, n]
+
+    def kept_bytes(self, first, second):
+        """what `first` leaves for `second`: the scratch both lists name (saved activations; the split-K workspace aside)"""
+        both = first.touched & second.touched
+        return sum(b["bytes"] for b in self.used if b["addr"] in both and b["kind"] == SCRATCH and b["name"] != "workspace")
+
+
+def _float_bits(x):
+    return struct.unpack("<I", struct.pack("<f", float(x)))[0]
+
+
+def _encode_calls(rec, lists, loc, own, peer, host_floats):
+    """(a) the recorded calls -> the entries of the list each falls into.  -> (names, host arrays, lr patch point or None: (entry,
+    argument, groups) of the scot_adamw_step call).  host_floats: classify HOST_FLOAT_ARRAYS (a training recording)"""
+    names, name_index, arrays, lr_point = [], {}, [], None
     for pos, (fn, args) in enumerate(rec):
-        what_list, macro, listed, entries, touching = sections[next(i for i, hi in enumerate(bounds) if pos < hi)]
+        lst = next(x for x in lists if pos < x.end)
         if args is None:
             label = getattr(fn, "__qualname__", None) or getattr(fn, "__name__", None) or repr(fn)
-            raise PlanExportError(f"export_plan: the recorded {what_list} holds a host-side Python step ({label}); a plan is C-ABI calls only")
+            raise PlanExportError(f"export_plan: the recorded {lst.what} holds a host-side Python step ({label}); a plan is C-ABI calls only")
         name = fn.__name__
-        if name not in listed:
-            raise PlanExportError(f"export_plan: the {what_list} calls {name}, which the plan runtime of this library does not list "
-                                  f"(csrc/plan_image.h, {macro})")
+        if name not in lst.listed:
+            raise PlanExportError(f"export_plan: the {lst.what} calls {name}, which the plan runtime of this library does not list "
+                                  f"(csrc/plan_image.h, {lst.macro})")
         addr = _address(fn)
         if addr == _address(getattr(own, name)):
             which = 0
@@ -440,16 +479,16 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=N
         for k, (a, ty) in enumerate(zip(args, argtypes)):
             what = f"argument {k} of {name}"
             if ty is ctypes.c_float:
-                flts.append(struct.unpack("<I", struct.pack("<f", float(a)))[0])
-            elif train is not None and k in HOST_FLOAT_ARRAYS.get(name, ()):      # a host array of floats, passed by address
+                flts.append(_float_bits(a))
+            elif host_floats and k in HOST_FLOAT_ARRAYS.get(name, ()):      # a host array of floats, passed by address
                 count = int(args[HOST_FLOAT_ARRAYS[name][k]])
                 values = (ctypes.c_float * count).from_address(a.value if isinstance(a, ctypes.c_void_p) else int(a))
                 if (name, k) == LR_ARGUMENT:
                     if lr_point is not None:
                         raise PlanExportError(f"export_plan: the update calls {name} more than once")
-                    lr_point = (len(entries), len(ints), count)
+                    lr_point = (len(lst.entries), len(ints), count)
                 ints.append((ARG_ARRAY, len(arrays)))
-                arrays.append((2, [(ARG_INT, struct.unpack("<I", struct.pack("<f", float(x)))[0]) for x in values]))
+                arrays.append((2, [(ARG_INT, _float_bits(x)) for x in values]))
             elif ty is ctypes.c_void_p and k == last:
                 ints.append((ARG_STREAM, 0))      # one stream per entry point, last: the caller's at run time
             elif isinstance(a, ctypes.Array):
@@ -458,7 +497,7 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=N
                     items = [(ARG_INT, int(x) & 0xFFFFFFFFFFFFFFFF) for x in a]
                     kind = 0
                 elif elem is ctypes.c_void_p:
-                    items = [pair(x or 0, f"element {j} of {what}") for j, x in enumerate(a)]
+                    items = [loc.pair(x or 0, f"element {j} of {what}", lst.touched) for j, x in enumerate(a)]
                     kind = 1
                 else:
                     raise PlanExportError(f"export_plan: {what} is a host array of {elem!r}")
@@ -466,7 +505,7 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=N
                 arrays.append((kind, items))
             elif ty is ctypes.c_void_p:
                 v = a.value if isinstance(a, ctypes.c_void_p) else a
-                ints.append(pair(int(v or 0), what))
+                ints.append(loc.pair(int(v or 0), what, lst.touched))
             elif a is None:
                 ints.append((ARG_INT, 0))
             elif isinstance(a, int):
@@ -478,87 +517,98 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=N
         if name not in name_index:
             name_index[name] = len(names)
             names.append(name)
-        entries.append((name_index[name], which, ints, flts))
-    touching = None
-    step_lists = sections[1:] if train is not None else []
-    entries, backward = sections[0][3], (sections[1][3] if train is None else [])
+        lst.entries.append((name_index[name], which, ints, flts))
+    return names, arrays, lr_point
 
-    B, Cin, H, W = pv_in.shape
-    Cout = pred.shape[1]
+
+def _adjoint_words(eng, loc, adj, forward, backward):
+    """(b) the adjoint words of a format-2 image"""
+    w = [0] * ADJ_WORDS
+    w[ADJ_COT:ADJ_COT + 3] = loc.span(adj["cot"], "the cotangent copy", INPUT)
+    if adj["d_pv"] is not None:
+        w[ADJ_FLAGS] |= 1
+        w[ADJ_DPV:ADJ_DPV + 3] = loc.span(adj["d_pv"], "d_pixel_values", OUTPUT)
+    if adj["d_t"] is not None:
+        w[ADJ_FLAGS] |= 2
+        w[ADJ_DTIME:ADJ_DTIME + 3] = loc.span(adj["d_t"], "d_time", OUTPUT)
+    if eng.scale_grads:
+        import math
+        w[ADJ_STATE:ADJ_STATE + 3] = loc.span(eng.scale_state, "the gradient-scale state", STATE)
+        w[ADJ_COUNTER:ADJ_COUNTER + 3] = loc.span(eng.grad_overflow, "the non-finite counter", STATE)
+        S = eng.grad_scale_value()
+        m, e = math.frexp(S)
+        if m != 0.5:
+            raise PlanExportError(f"export_plan: the engine's gradient scale {S} is not a power of two")
+        w[ADJ_SCALE_EXP] = (e - 1) & 0xFFFFFFFFFFFFFFFF
+    w[ADJ_KEPT_BYTES] = loc.kept_bytes(forward, backward)      # what a run leaves for the vjp (the prediction aside)
+    return w
+
+
+def _training_words(eng, loc, train, names, lr_point, step_forward, step_backward, update):
+    """(b) the training words of a format-4 image, but for the three lists' places in the file (the layout's)"""
+    opt = train["opt"]
+    if lr_point is None or names[update.entries[lr_point[0]][0]] != LR_ARGUMENT[0]:
+        raise PlanExportError("export_plan: the recorded update holds no scot_adamw_step call")
+    w = [0] * TRAIN_WORDS
+    for slot, t, what, kind in ((TR_LABELS, train["labels"], "the labels' copy", INPUT), (TR_LOSS, train["loss"], "the loss", OUTPUT),
+                                (TR_PRED, train["pred"], "the step forward's prediction", OUTPUT),
+                                (TR_ARENA, eng.arena.data, "the parameter arena", STATE), (TR_EXP_AVG, opt.exp_avg, "exp_avg", STATE),
+                                (TR_EXP_AVG_SQ, opt.exp_avg_sq, "exp_avg_sq", STATE), (TR_SHADOW, eng.shadow, "the 16-bit copy", STATE),
+                                (TR_SHADOW_T, eng.shadow_t, "the transposed 16-bit copy", STATE),
+                                (TR_STEP_STATE, opt._step_state, "step_state", STATE), (TR_CLIP, opt._clip, "the clip floats", STATE),
+                                (TR_SCALE_STATE, eng.scale_state, "the gradient-scale state", STATE),
+                                (TR_COUNTER, eng.grad_overflow, "the non-finite counter", STATE)):
+        if t is not None:
+            w[slot:slot + 3] = loc.span(t, what, kind)
+    w[TR_FLAGS] = 1 if eng.scale_grads else 0
+    w[TR_GROUPS], w[TR_ARENA_FLOATS] = lr_point[2], eng.arena.size
+    w[TR_LR_ENTRY], w[TR_LR_ARG] = lr_point[0], lr_point[1]
+    w[TR_KEPT_BYTES] = loc.kept_bytes(step_forward, step_backward)
+    if len(opt.param_groups) != lr_point[2]:
+        raise PlanExportError("export_plan: the recorded update has another number of parameter groups than the optimizer")
+    return w
+
+
+def _layout(sections):
+    """(c) {section name: bytes} in file order -> ({section name: offset in the file}, offset of the data section): every section on an
+    8-byte boundary behind the header, the data on a 64-byte boundary behind the last one"""
+    offs, cur = {}, HEADER_WORDS * 8
+    for name, sct in sections.items():
+        offs[name] = cur
+        cur += len(sct) + (-len(sct) % 8)
+    return offs, cur + (-cur % 64)
+
+
+def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=None):
+    """recorded calls + registered buffers -> the bytes of a plan image (adj: the adjoint record of _record -> a format-2 image; train:
+    the training record of _record_training -> a format-4 image)"""
+    eng = model._engine
+    reg.freeze()
+    loc = _Relocator(reg)
+    if train is not None:
+        ends = zip(("step forward", "step backward", "update"), (train["n_fwd"], train["n_bwd"], len(rec)))
+        lists = [_CallList("forward", "forward", train["n_inf"], own)] + [_CallList(what, "training", end, own) for what, end in ends]
+    elif adj is not None:
+        lists = [_CallList("forward", "forward", adj["n_fwd"], own), _CallList("backward", "adjoint", len(rec), own)]
+    else:
+        lists = [_CallList("forward", "forward", len(rec), own)]
+    forward, others = lists[0], lists[1:]
+    names, arrays, lr_point = _encode_calls(rec, lists, loc, own, peer, host_floats=train is not None)
+
     io = [0] * IO_WORDS
-    io[0:5] = [B, Cin, H, W, Cout]
-
-    def whole(t, what, kind):
-        b, off = reg.resolve(t.data_ptr())
-        if b is None or off + t.numel() * t.element_size() > b["bytes"]:
-            raise PlanExportError(f"export_plan: {what} lies in no registered buffer")
-        b["kind"] = kind
-        return buffer_index(b), off
-    io[5], io[6] = whole(pv_in, "the input copy", INPUT)
+    io[0:5] = [*pv_in.shape, pred.shape[1]]      # B, Cin, H, W, Cout
+    io[5:7] = loc.span(pv_in, "the input copy", INPUT)[:2]
     if t_in is not None:
         io[7] = 1
-        io[8], io[9] = whole(t_in, "the time copy", INPUT)
-        io[10] = t_in.numel() * 4
-    io[15], io[16] = whole(pred, "the prediction", OUTPUT)
-    adj_words = [0] * ADJ_WORDS
-    if adj is not None:
-        def span(slot, t, what, kind):
-            adj_words[slot], adj_words[slot + 1] = whole(t, what, kind)
-            adj_words[slot + 2] = t.numel() * t.element_size()
-        span(ADJ_COT, adj["cot"], "the cotangent copy", INPUT)
-        if adj["d_pv"] is not None:
-            adj_words[ADJ_FLAGS] |= 1
-            span(ADJ_DPV, adj["d_pv"], "d_pixel_values", OUTPUT)
-        if adj["d_t"] is not None:
-            adj_words[ADJ_FLAGS] |= 2
-            span(ADJ_DTIME, adj["d_t"], "d_time", OUTPUT)
-        S = 1.0
-        if eng.scale_grads:
-            import math
-            span(ADJ_STATE, eng.scale_state, "the gradient-scale state", STATE)
-            span(ADJ_COUNTER, eng.grad_overflow, "the non-finite counter", STATE)
-            S = eng.grad_scale_value()
-            m, e = math.frexp(S)
-            if m != 0.5:
-                raise PlanExportError(f"export_plan: the engine's gradient scale {S} is not a power of two")
-            adj_words[ADJ_SCALE_EXP] = (e - 1) & 0xFFFFFFFFFFFFFFFF
-        # what a run leaves for the vjp: the forward's buffers the backward names too (saved activations, the prediction aside)
-        both = sections[0][4] & sections[1][4]
-        adj_words[ADJ_KEPT_BYTES] = sum(b["bytes"] for b in used if b["addr"] in both and b["kind"] == SCRATCH and b["name"] != "workspace")
+        io[8:11] = loc.span(t_in, "the time copy", INPUT)
+    io[15:17] = loc.span(pred, "the prediction", OUTPUT)[:2]
+    adj_words = _adjoint_words(eng, loc, adj, forward, *others) if adj is not None else None
+    tr_words = _training_words(eng, loc, train, names, lr_point, *others) if train is not None else None
 
-    tr_words = [0] * TRAIN_WORDS
-    if train is not None:
-        opt = train["opt"]
-        if lr_point is None or sections[3][3][lr_point[0]][0] != name_index.get(LR_ARGUMENT[0]):
-            raise PlanExportError("export_plan: the recorded update holds no scot_adamw_step call")
-
-        def tspan(slot, t, what, kind):
-            tr_words[slot], tr_words[slot + 1] = whole(t, what, kind)
-            tr_words[slot + 2] = t.numel() * t.element_size()
-        tspan(TR_LABELS, train["labels"], "the labels' copy", INPUT)
-        tspan(TR_LOSS, train["loss"], "the loss", OUTPUT)
-        tspan(TR_PRED, train["pred"], "the step forward's prediction", OUTPUT)
-        for slot, t, what in ((TR_ARENA, eng.arena.data, "the parameter arena"), (TR_EXP_AVG, opt.exp_avg, "exp_avg"),
-                              (TR_EXP_AVG_SQ, opt.exp_avg_sq, "exp_avg_sq"), (TR_SHADOW, eng.shadow, "the 16-bit copy"),
-                              (TR_SHADOW_T, eng.shadow_t, "the transposed 16-bit copy"), (TR_STEP_STATE, opt._step_state, "step_state"),
-                              (TR_CLIP, opt._clip, "the clip floats"), (TR_SCALE_STATE, eng.scale_state, "the gradient-scale state"),
-                              (TR_COUNTER, eng.grad_overflow, "the non-finite counter")):
-            if t is not None:
-                tspan(slot, t, what, STATE)
-        tr_words[TR_FLAGS] = 1 if eng.scale_grads else 0
-        tr_words[TR_GROUPS], tr_words[TR_ARENA_FLOATS] = lr_point[2], eng.arena.size
-        tr_words[TR_LR_ENTRY], tr_words[TR_LR_ARG] = lr_point[0], lr_point[1]
-        both = sections[1][4] & sections[2][4]
-        tr_words[TR_KEPT_BYTES] = sum(b["bytes"] for b in used if b["addr"] in both and b["kind"] == SCRATCH and b["name"] != "workspace")
-        if len(opt.param_groups) != lr_point[2]:
-            raise PlanExportError("export_plan: the recorded update has another number of parameter groups than the optimizer")
-
-    # sections
     def words(ws):
         return struct.pack(f"<{len(ws)}Q", *ws)
-    names_b = b"".join(n.encode().ljust(NAME_BYTES, b"\0") for n in names)
     data, buf_words = bytearray(), []
-    for b in used:
+    for b in loc.used:
         off = 0
         stored = b["kind"] == STATE and b["stored"] and train is not None
         if b["kind"] == CONSTANT or stored:
@@ -574,55 +624,43 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=N
         arr_words += [kind, len(items)]
         for tag, val in items:
             arr_words += [tag, val]
-    def entry_words(es):
-        ws = []
-        for ni, which, ints, flts in es:
-            ws += [ni, which, len(ints), len(flts)]
-            for tag, val in ints:
-                ws += [tag, val]
-            ws += flts
-        return ws
-    ent_words, bwd_words = entry_words(entries), entry_words(backward)
-    sections = [names_b, words(buf_words), words(ent_words), words(arr_words), words(io)]
+    # the sections in file order; a list's section has the list's name
+    sections = {"names": b"".join(n.encode().ljust(NAME_BYTES, b"\0") for n in names), "buffers": words(buf_words),
+                "forward": words(forward.words()), "arrays": words(arr_words), "io": words(io)}
+    sections.update((x.what, words(x.words())) for x in others)
     if adj is not None:
-        sections += [words(bwd_words), words(adj_words)]
-    step_words = []
+        sections["adjoint"] = words(adj_words)
     if train is not None:
-        step_words = [entry_words(sct[3]) for sct in step_lists]
-        sections += [words(ws) for ws in step_words] + [None]      # (the training words name the lists' offsets: filled in below)
-    offs, cur = [], HEADER_WORDS * 8
-    for sct in sections:
-        offs.append(cur)
-        n_sct = TRAIN_WORDS * 8 if sct is None else len(sct)
-        cur += n_sct + (-n_sct % 8)
-    if train is not None:
-        for i in range(3):
-            tr_words[TR_FWD + 3 * i: TR_FWD + 3 * i + 3] = [len(step_lists[i][3]), offs[5 + i], len(step_words[i])]
-        sections[-1] = words(tr_words)
-    cur += -cur % 64
-    data_off = cur
-    total = data_off + len(data)
+        sections["training"] = bytes(TRAIN_WORDS * 8)      # (names the step lists' offsets: filled in once they are known)
+    offs, data_off = _layout(sections)
+
+    def named(x):      # how a header or the training words name a list: (count, offset, words)
+        return [len(x.entries), offs[x.what], len(sections[x.what]) // 8]
     h = [0] * HEADER_WORDS
     h[H_MAGIC], h[H_FORMAT], h[H_ABI], h[H_OPERAND] = MAGIC, FORMAT, own.scot_abi_version(), own.scot_operand_format()
+    h[H_COMPUTE], h[H_BYTES] = COMPUTE_CODE[model.compute], data_off + len(data)
+    h[H_NNAMES], h[H_NAMES_OFF] = len(names), offs["names"]
+    h[H_NBUFFERS], h[H_BUFFERS_OFF] = len(loc.used), offs["buffers"]
+    h[H_NENTRIES:H_NENTRIES + 3] = named(forward)
+    h[H_NARRAYS], h[H_ARRAYS_OFF], h[H_ARRAYS_WORDS] = len(arrays), offs["arrays"], len(arr_words)
+    h[H_IO_OFF], h[H_DATA_OFF], h[H_DATA_BYTES] = offs["io"], data_off, len(data)
     if adj is not None:
-        h[H_FORMAT] = FORMAT_ADJOINT
-        h[H_NBACKWARD], h[H_BACKWARD_OFF], h[H_BACKWARD_WORDS], h[H_ADJ_OFF] = len(backward), offs[5], len(bwd_words), offs[6]
+        (backward,) = others
+        h[H_FORMAT], h[H_ADJ_OFF] = FORMAT_ADJOINT, offs["adjoint"]
+        h[H_NBACKWARD:H_NBACKWARD + 3] = named(backward)
     if train is not None:
-        h[H_FORMAT], h[H_TRAIN_OFF] = FORMAT_TRAINING, offs[8]
-    h[H_COMPUTE], h[H_BYTES] = COMPUTE_CODE[model.compute], total
-    h[H_NNAMES], h[H_NAMES_OFF] = len(names), offs[0]
-    h[H_NBUFFERS], h[H_BUFFERS_OFF] = len(used), offs[1]
-    h[H_NENTRIES], h[H_ENTRIES_OFF], h[H_ENTRIES_WORDS] = len(entries), offs[2], len(ent_words)
-    h[H_NARRAYS], h[H_ARRAYS_OFF], h[H_ARRAYS_WORDS] = len(arrays), offs[3], len(arr_words)
-    h[H_IO_OFF], h[H_DATA_OFF], h[H_DATA_BYTES] = offs[4], data_off, len(data)
+        h[H_FORMAT], h[H_TRAIN_OFF] = FORMAT_TRAINING, offs["training"]
+        for slot, x in zip((TR_FWD, TR_BWD, TR_UPD), others):
+            tr_words[slot:slot + 3] = named(x)
+        sections["training"] = words(tr_words)
     out = bytearray(words(h))
-    for sct, off in zip(sections, offs):
-        assert len(out) == off
+    for name, sct in sections.items():
+        assert len(out) == offs[name]
         out.extend(sct)
         out.extend(b"\0" * (-len(sct) % 8))
     out.extend(b"\0" * (data_off - len(out)))
     out.extend(data)
-    assert len(out) == total
+    assert len(out) == h[H_BYTES]
     return bytes(out)
 
 
@@ -634,7 +672,6 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
     train: a FusedAdamW over this model, with labels — the image (format 4) then also holds one optimizer step and the training state by
     value (scot_plan_train_step, scot_plan_snapshot); the model and the optimizer are left as they were."""
     import torch
-    from . import ops
     _check_request(model, pixel_values, time, pixel_mask, labels, train)
     dev = pixel_values.device
     if train is not None:
@@ -642,7 +679,6 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
         _check_training(model, pixel_values, labels, train, adjoint)
     adjoint = _check_adjoint(model, adjoint)
     model._ensure_arena(dev)
-    eng = model._engine
     pv = pixel_values.detach().to(torch.float32).contiguous()
     t = None
     if model.config.use_conditioning:      # as ScOT.forward prepares it
@@ -651,69 +687,78 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
             t = t.expand(pv.shape[0]).contiguous()
         if t.numel() != pv.shape[0]:
             raise PlanExportError(f"export_plan: time has {t.numel()} values for a batch of {pv.shape[0]}")
-    own, peer = _libraries(eng)
+    own, peer = _libraries(model._engine)
     bind(own)
-    if train is not None:
-        lab = labels.detach().to(device=dev, dtype=torch.float32).contiguous()
-        with torch.no_grad():
-            image = _export_training(model, train, pv, t, lab, own, peer)
-        if path is not None:
-            with open(path, "wb") as f:
-                f.write(image)
-        return image
     with torch.no_grad():
-        ref_g = None
-        if adjoint:      # the engine's own bits of the differentiable call: its prediction, and a vjp
-            _, ref, tape = eng.forward(pv, t, None, None, train=True, stochastic=False, input_grads=adjoint, param_grads=False)
-            ref = ref.clone()
-            # (the cotangent of the self-check: the prediction brought to at most 1 / its element count — the magnitude a mean loss
-            # hands back and the fp16 gradient scale is chosen for)
-            cot = ref / (float(ref.numel()) * max(1.0, float(ref.abs().max())))
-            counted = 0 if eng.grad_overflow is None else int(eng.grad_overflow)
-            ref_g = eng.backward(tape, None, cot.clone())
-            counted = 0 if eng.grad_overflow is None else int(eng.grad_overflow) - counted
-            del tape
-            for p in model._params:      # (as after any frozen backward: by-products of the fused tails may sit in the gradient arena)
-                p.grad = None
+        if train is not None:
+            image = _export_training(model, train, pv, t, labels.detach().to(device=dev, dtype=torch.float32).contiguous(), own, peer)
         else:
-            _, ref, _ = eng.forward(pv, t, None, None, train=False, stochastic=False)      # the model's own prediction
-        reg, rec, keep, pred, pv_in, t_in, adj = _record(model, pv, t, adjoint)
-        image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj)
-        # load what was built through the runtime, scratch poisoned, and require the model's own bits: a constant the export missed fails
-        # here, not at a user's site
-        plan = Plan.load(image, lib=own, peer=peer)
-        try:
-            plan.poison(0xFF)
-            got = plan.run(pv, t)
-            if dev.type == "cuda":
-                torch.cuda.synchronize(dev)
-            if not bool(torch.isfinite(got).all()):
-                raise PlanExportError("export_plan: the plan's prediction is not finite with poisoned scratch: the recorded forward reads "
-                                      "a buffer the image does not initialise")
-            if not torch.equal(got, ref):
-                raise PlanExportError("export_plan: the plan's prediction differs from the model's own "
-                                      f"(max |difference| {float((got - ref).abs().max()):.3e})")
-            if adjoint:
-                got_g = plan.vjp(cot.clone())
-                if dev.type == "cuda":
-                    torch.cuda.synchronize(dev)
-                for name, a, b in zip(("d_pixel_values", "d_time"), got_g, ref_g):
-                    # the engine's own bits; where its fp16 backward overflowed, the same elements are non-finite (never clipped)
-                    same = (a is None) == (b is None)
-                    if same and a is not None:
-                        fin = torch.isfinite(b)
-                        same = torch.equal(torch.isfinite(a), fin) and torch.equal(a[fin], b[fin])
-                    if not same:
-                        raise PlanExportError(f"export_plan: the plan's {name} differs from the engine's own for the export inputs")
-                if plan.grad_status()[0] != counted:
-                    raise PlanExportError(f"export_plan: the plan's un-scale passes counted {plan.grad_status()[0]} non-finite values, the "
-                                          f"engine's {counted}")
-        finally:
-            plan.free()
-    del keep
+            image = _export_frozen(model, pv, t, adjoint, own, peer)
     if path is not None:
         with open(path, "wb") as f:
             f.write(image)
+    return image
+
+
+@contextlib.contextmanager
+def _self_check(image, own, peer):
+    """the image that was built, loaded through the runtime with its scratch poisoned: a constant the export missed fails here, not at a
+    user's site"""
+    plan = Plan.load(image, lib=own, peer=peer)
+    try:
+        plan.poison(0xFF)
+        yield plan
+    finally:
+        plan.free()
+
+
+def _export_frozen(model, pv, t, adjoint, own, peer):
+    """record, build, and check through the runtime: the model's own prediction bits and, with `adjoint`, the engine's own gradients"""
+    import torch
+    eng, dev = model._engine, pv.device
+    ref_g = None
+    if adjoint:      # the engine's own bits of the differentiable call: its prediction, and a vjp
+        _, ref, tape = eng.forward(pv, t, None, None, train=True, stochastic=False, input_grads=adjoint, param_grads=False)
+        ref = ref.clone()
+        # (the cotangent of the self-check: the prediction brought to at most 1 / its element count — the magnitude a mean loss
+        # hands back and the fp16 gradient scale is chosen for)
+        cot = ref / (float(ref.numel()) * max(1.0, float(ref.abs().max())))
+        counted = 0 if eng.grad_overflow is None else int(eng.grad_overflow)
+        ref_g = eng.backward(tape, None, cot.clone())
+        counted = 0 if eng.grad_overflow is None else int(eng.grad_overflow) - counted
+        del tape
+        for p in model._params:      # (as after any frozen backward: by-products of the fused tails may sit in the gradient arena)
+            p.grad = None
+    else:
+        _, ref, _ = eng.forward(pv, t, None, None, train=False, stochastic=False)      # the model's own prediction
+    reg, rec, keep, pred, pv_in, t_in, adj = _record(model, pv, t, adjoint)
+    image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj)
+    with _self_check(image, own, peer) as plan:
+        got = plan.run(pv, t)
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        if not bool(torch.isfinite(got).all()):
+            raise PlanExportError("export_plan: the plan's prediction is not finite with poisoned scratch: the recorded forward reads "
+                                  "a buffer the image does not initialise")
+        if not torch.equal(got, ref):
+            raise PlanExportError("export_plan: the plan's prediction differs from the model's own "
+                                  f"(max |difference| {float((got - ref).abs().max()):.3e})")
+        if adjoint:
+            got_g = plan.vjp(cot.clone())
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)
+            for name, a, b in zip(("d_pixel_values", "d_time"), got_g, ref_g):
+                # the engine's own bits; where its fp16 backward overflowed, the same elements are non-finite (never clipped)
+                same = (a is None) == (b is None)
+                if same and a is not None:
+                    fin = torch.isfinite(b)
+                    same = torch.equal(torch.isfinite(a), fin) and torch.equal(a[fin], b[fin])
+                if not same:
+                    raise PlanExportError(f"export_plan: the plan's {name} differs from the engine's own for the export inputs")
+            if plan.grad_status()[0] != counted:
+                raise PlanExportError(f"export_plan: the plan's un-scale passes counted {plan.grad_status()[0]} non-finite values, the "
+                                      f"engine's {counted}")
+    del keep
     return image
 
 
@@ -728,9 +773,7 @@ def _export_training(model, opt, pv, t, lab, own, peer):
     reg, rec, keep, pred, pv_in, t_in, tr = _record_training(model, opt, pv, t, lab)
     image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer, train=tr)
     del keep
-    plan = Plan.load(image, lib=own, peer=peer)
-    try:
-        plan.poison(0xFF)
+    with _self_check(image, own, peer) as plan:
         loss, got = plan.loss(pv, t, lab)
         if not torch.equal(got, ref):
             raise PlanExportError("export_plan: the training plan's prediction differs from the engine's own "
@@ -745,8 +788,6 @@ def _export_training(model, opt, pv, t, lab, own, peer):
         if not bool(torch.isfinite(after["arena"]).all()):
             raise PlanExportError("export_plan: the parameters are not finite after one step of the training plan with poisoned scratch: "
                                   "the recorded step reads a buffer the image does not initialise")
-    finally:
-        plan.free()
     plan = Plan.load(image, lib=own, peer=peer)      # (the image as it will be written: the state before any step)
     plan.free()
     return image
@@ -887,13 +928,17 @@ class Plan:
             raise _lib.ScotLibraryError(f"scot_plan_load refused the image: status {rc} ({_lib._ERR.get(rc, rc)})")
         return cls(lib, handle)
 
+    def _call(self, name, *args):
+        """the runtime's `name`(this plan, ...), its status checked"""
+        _lib.check(getattr(self._lib, name)(self._h, *args), name)
+
     def describe(self):
         out = (ctypes.c_longlong * 16)()
-        _lib.check(self._lib.scot_plan_describe(self._h, out), "scot_plan_describe")
+        self._call("scot_plan_describe", out)
         return dict(zip(DESCRIBE, [int(x) for x in out]))
 
     def poison(self, byte=0xFF, stream=None):
-        _lib.check(self._lib.scot_plan_poison(self._h, int(byte), self._stream(stream, None)), "scot_plan_poison")
+        self._call("scot_plan_poison", int(byte), self._stream(stream, None))
 
     @staticmethod
     def _stream(stream, like):
@@ -908,65 +953,78 @@ class Plan:
                 return torch.cuda.current_stream().cuda_stream
         return None
 
-    def run(self, pixel_values, time=None, pixel_mask=None, out=None, stream=None):
+    def _shape(self, channels="channels"):
         d = self.info
+        return (d["batch"], d[channels], d["height"], d["width"])
+
+    def _require(self, x, what, channels="channels"):
+        """x is a tensor of this plan's shape"""
+        if not _is_tensor(x) or tuple(x.shape) != self._shape(channels):
+            raise ValueError(f"this plan takes {what} of shape {self._shape(channels)}")
+
+    def _time(self, time, counted=True):
+        """a time tensor as the runtime reads it: flat, float32, contiguous (counted: one value per sample)"""
+        if time is None or not _is_tensor(time):
+            return time
+        import torch
+        time = time.reshape(-1).to(torch.float32).contiguous()
+        if counted and time.numel() != self.info["batch"]:
+            raise ValueError("time: one value per sample")
+        return time
+
+    def _empty(self, like, channels="out_channels", steps=()):
+        import torch
+        return torch.empty(*steps, *self._shape(channels), dtype=torch.float32, device=like.device)
+
+    def _gradient_pair(self, like):
+        """buffers for (d_pixel_values, d_time): None for a gradient the plan was not exported with"""
+        import torch
+        a = self.describe_adjoint()
+        return (self._empty(like, "channels") if a["d_pixel_values"] else None,
+                torch.empty(self.info["batch"], dtype=torch.float32, device=like.device) if a["d_time"] else None)
+
+    def run(self, pixel_values, time=None, pixel_mask=None, out=None, stream=None):
         if _is_tensor(pixel_values):
-            import torch
-            if tuple(pixel_values.shape) != (d["batch"], d["channels"], d["height"], d["width"]):
-                raise ValueError(f"this plan takes pixel_values of shape {(d['batch'], d['channels'], d['height'], d['width'])}")
-            if time is not None and _is_tensor(time):
-                time = time.reshape(-1).to(torch.float32).contiguous()
-                if time.numel() != d["batch"]:
-                    raise ValueError("time: one value per sample")
+            self._require(pixel_values, "pixel_values")
+            time = self._time(time)
             if out is None:
-                out = torch.empty(d["batch"], d["out_channels"], d["height"], d["width"], dtype=torch.float32, device=pixel_values.device)
+                out = self._empty(pixel_values)
         elif out is None:
             raise ValueError("raw addresses need `out`")
-        rc = self._lib.scot_plan_run(self._h, _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(pixel_mask, "pixel_mask"),
-                                     _addr(out, "out"), self._stream(stream, pixel_values))
-        _lib.check(rc, "scot_plan_run")
+        self._call("scot_plan_run", _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(pixel_mask, "pixel_mask"), _addr(out, "out"),
+                   self._stream(stream, pixel_values))
         return out
 
     def rollout(self, pixel_values, time, steps, pixel_mask=None, out=None, stream=None):
         """-> [B, steps, Cout, H, W] for tensors (what harness.rollout(..., output_all_steps=True).output is); with raw addresses `out`
         receives the C layout [steps][B, Cout, H, W]."""
-        d = self.info
         tensors = _is_tensor(pixel_values)
         if tensors:
-            import torch
-            if time is not None and _is_tensor(time):
-                time = time.reshape(-1).to(torch.float32).contiguous()
+            time = self._time(time, counted=False)
             if out is None:
-                out = torch.empty(int(steps), d["batch"], d["out_channels"], d["height"], d["width"], dtype=torch.float32, device=pixel_values.device)
+                out = self._empty(pixel_values, steps=(int(steps),))
         elif out is None:
             raise ValueError("raw addresses need `out`")
-        rc = self._lib.scot_plan_rollout(self._h, _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(pixel_mask, "pixel_mask"),
-                                         _addr(out, "out"), int(steps), self._stream(stream, pixel_values))
-        _lib.check(rc, "scot_plan_rollout")
+        self._call("scot_plan_rollout", _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(pixel_mask, "pixel_mask"), _addr(out, "out"),
+                   int(steps), self._stream(stream, pixel_values))
         return out.transpose(0, 1).contiguous() if tensors and _is_tensor(out) else out
 
     def describe_adjoint(self):
         out = (ctypes.c_longlong * 8)()
-        _lib.check(self._lib.scot_plan_describe_adjoint(self._h, out), "scot_plan_describe_adjoint")
+        self._call("scot_plan_describe_adjoint", out)
         return dict(zip(DESCRIBE_ADJOINT, [int(x) for x in out]))
 
     def vjp(self, d_prediction, grad_scale=0, out=None, stream=None):
         """-> (d_pixel_values, d_time) = J^T d_prediction at the inputs of the last `run` (None for a gradient the plan was not exported
         with).  out: (buffer or None, buffer or None) to receive them; required with raw addresses.  grad_scale: scot_plan.h."""
-        d, a = self.info, self.describe_adjoint()
         if _is_tensor(d_prediction):
-            import torch
-            if tuple(d_prediction.shape) != (d["batch"], d["out_channels"], d["height"], d["width"]):
-                raise ValueError(f"this plan takes a cotangent of shape {(d['batch'], d['out_channels'], d['height'], d['width'])}")
+            self._require(d_prediction, "a cotangent", "out_channels")
             if out is None:
-                dev = d_prediction.device
-                out = (torch.empty(d["batch"], d["channels"], d["height"], d["width"], dtype=torch.float32, device=dev) if a["d_pixel_values"] else None,
-                       torch.empty(d["batch"], dtype=torch.float32, device=dev) if a["d_time"] else None)
+                out = self._gradient_pair(d_prediction)
         elif out is None:
             raise ValueError("raw addresses need `out`")
-        rc = self._lib.scot_plan_vjp(self._h, _addr(d_prediction, "d_prediction"), _addr(out[0], "d_pixel_values"), _addr(out[1], "d_time"),
-                                     float(grad_scale), self._stream(stream, d_prediction))
-        _lib.check(rc, "scot_plan_vjp")
+        self._call("scot_plan_vjp", _addr(d_prediction, "d_prediction"), _addr(out[0], "d_pixel_values"), _addr(out[1], "d_time"), float(grad_scale),
+                   self._stream(stream, d_prediction))
         return out
 
     def rollout_vjp(self, pixel_values, time, predictions, d_predictions, grad_scale=0, out=None, stream=None, steps=None):
@@ -975,70 +1033,56 @@ class Plan:
         layout `rollout` returns, [B, steps, Cout, H, W], `predictions` being what `rollout(pixel_values, time, steps)` gave.  None for
         a gradient the plan was not exported with.  out: (buffer or None, buffer or None) to receive them.  With raw addresses
         `predictions` / `d_predictions` are in the C layout [steps][B, Cout, H, W], and `out` and `steps=` are required."""
-        d, a = self.info, self.describe_adjoint()
         if _is_tensor(pixel_values):
             import torch
             if not (_is_tensor(predictions) and _is_tensor(d_predictions)) or predictions.dim() != 5 or predictions.shape != d_predictions.shape:
                 raise ValueError("predictions and d_predictions: tensors of one shape [B, steps, Cout, H, W]")
-            if tuple(predictions.shape[:1] + predictions.shape[2:]) != (d["batch"], d["out_channels"], d["height"], d["width"]):
-                raise ValueError(f"this plan's rollout is of shape {(d['batch'], 'steps', d['out_channels'], d['height'], d['width'])}")
+            if tuple(predictions.shape[:1] + predictions.shape[2:]) != self._shape("out_channels"):
+                b, c, h, w = self._shape("out_channels")
+                raise ValueError(f"this plan's rollout is of shape {(b, 'steps', c, h, w)}")
             if steps is not None and int(steps) != predictions.shape[1]:
                 raise ValueError(f"steps={steps}, predictions hold {predictions.shape[1]} steps")
             steps = predictions.shape[1]
             predictions = predictions.to(torch.float32).transpose(0, 1).contiguous()
             d_predictions = d_predictions.to(torch.float32).transpose(0, 1).contiguous()
-            if time is not None and _is_tensor(time):
-                time = time.reshape(-1).to(torch.float32).contiguous()
+            time = self._time(time, counted=False)
             if out is None:
-                dev = pixel_values.device
-                out = (torch.empty(d["batch"], d["channels"], d["height"], d["width"], dtype=torch.float32, device=dev) if a["d_pixel_values"] else None,
-                       torch.empty(d["batch"], dtype=torch.float32, device=dev) if a["d_time"] else None)
+                out = self._gradient_pair(pixel_values)
         elif out is None or steps is None:
             raise ValueError("raw addresses need `out` and `steps`")
-        rc = self._lib.scot_plan_rollout_vjp(self._h, _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(predictions, "predictions"),
-                                             _addr(d_predictions, "d_predictions"), int(steps), _addr(out[0], "d_pixel_values"),
-                                             _addr(out[1], "d_time"), float(grad_scale), self._stream(stream, pixel_values))
-        _lib.check(rc, "scot_plan_rollout_vjp")
+        self._call("scot_plan_rollout_vjp", _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(predictions, "predictions"),
+                   _addr(d_predictions, "d_predictions"), int(steps), _addr(out[0], "d_pixel_values"), _addr(out[1], "d_time"), float(grad_scale),
+                   self._stream(stream, pixel_values))
         return out
 
     def grad_status(self, stream=None):
         """-> (non-finite values the un-scale passes have counted since load, the last vjp's scale as a power-of-two exponent)"""
         out = (ctypes.c_longlong * 2)()
-        _lib.check(self._lib.scot_plan_grad_status(self._h, out, self._stream(stream, None)), "scot_plan_grad_status")
+        self._call("scot_plan_grad_status", out, self._stream(stream, None))
         return int(out[0]), int(out[1])
 
     def describe_training(self):
         out = (ctypes.c_longlong * 8)()
-        _lib.check(self._lib.scot_plan_describe_training(self._h, out), "scot_plan_describe_training")
+        self._call("scot_plan_describe_training", out)
         return dict(zip(DESCRIBE_TRAINING, [int(x) for x in out]))
 
     def _batch(self, pixel_values, time, labels):
-        d = self.info
         if _is_tensor(pixel_values):
-            import torch
-            if tuple(pixel_values.shape) != (d["batch"], d["channels"], d["height"], d["width"]):
-                raise ValueError(f"this plan takes pixel_values of shape {(d['batch'], d['channels'], d['height'], d['width'])}")
-            if not _is_tensor(labels) or tuple(labels.shape) != (d["batch"], d["out_channels"], d["height"], d["width"]):
-                raise ValueError(f"this plan takes labels of shape {(d['batch'], d['out_channels'], d['height'], d['width'])}")
-            if time is not None and _is_tensor(time):
-                time = time.reshape(-1).to(torch.float32).contiguous()
-                if time.numel() != d["batch"]:
-                    raise ValueError("time: one value per sample")
+            self._require(pixel_values, "pixel_values")
+            self._require(labels, "labels", "out_channels")
+            time = self._time(time)
         return _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(labels, "labels")
 
     def loss(self, pixel_values, time, labels, out=None, stream=None):
         """-> (loss [1], prediction) of the step's forward at the current weights (scot_plan_loss); changes no state.  out: (loss buffer,
         prediction buffer or None), required with raw addresses."""
-        d = self.info
         pv, t, lab = self._batch(pixel_values, time, labels)
         if out is None:
             if not _is_tensor(pixel_values):
                 raise ValueError("raw addresses need `out`")
             import torch
-            out = (torch.empty(1, dtype=torch.float32, device=pixel_values.device),
-                   torch.empty(d["batch"], d["out_channels"], d["height"], d["width"], dtype=torch.float32, device=pixel_values.device))
-        rc = self._lib.scot_plan_loss(self._h, pv, t, lab, _addr(out[0], "loss"), _addr(out[1], "prediction"), self._stream(stream, pixel_values))
-        _lib.check(rc, "scot_plan_loss")
+            out = (torch.empty(1, dtype=torch.float32, device=pixel_values.device), self._empty(pixel_values))
+        self._call("scot_plan_loss", pv, t, lab, _addr(out[0], "loss"), _addr(out[1], "prediction"), self._stream(stream, pixel_values))
         return out
 
     def train_step(self, pixel_values, time, labels, lr, out=None, stream=None):
@@ -1053,26 +1097,22 @@ class Plan:
             import torch
             out = torch.empty(1, dtype=torch.float32, device=pixel_values.device)
         rates = (ctypes.c_float * max(1, groups))(*lr)
-        rc = self._lib.scot_plan_train_step(self._h, pv, t, lab, ctypes.cast(rates, ctypes.c_void_p), _addr(out, "loss"),
-                                            self._stream(stream, pixel_values))
-        _lib.check(rc, "scot_plan_train_step")
+        self._call("scot_plan_train_step", pv, t, lab, ctypes.cast(rates, ctypes.c_void_p), _addr(out, "loss"),
+                   self._stream(stream, pixel_values))
         return out
 
     def train_status(self, stream=None):
         """-> {applied, skipped, grad_scale, grad_norm, clip_coef, nonfinite} (scot_plan_train_status: waits for the stream)"""
         out = (ctypes.c_double * 6)()
-        _lib.check(self._lib.scot_plan_train_status(self._h, out, self._stream(stream, None)), "scot_plan_train_status")
+        self._call("scot_plan_train_status", out, self._stream(stream, None))
         vals = [float(x) for x in out]
         return dict(zip(TRAIN_STATUS, [int(vals[0]), int(vals[1]), vals[2], vals[3], vals[4], int(vals[5])]))
 
     def snapshot(self, image, stream=None):
         """-> the bytes of `image` (THE image this plan was loaded from) with every state buffer's current value written back
         (scot_plan_snapshot): a valid training image that resumes exactly"""
-        n = len(image)
-        buf = (ctypes.c_uint64 * ((n + 7) // 8 or 1))()
-        ctypes.memmove(buf, bytes(image), n)
-        rc = self._lib.scot_plan_snapshot(self._h, ctypes.cast(buf, ctypes.c_void_p), n, self._stream(stream, None))
-        _lib.check(rc, "scot_plan_snapshot")
+        buf, n = _aligned_copy(image)
+        self._call("scot_plan_snapshot", ctypes.cast(buf, ctypes.c_void_p), n, self._stream(stream, None))
         return bytes(memoryview(buf).cast("B")[:n])      # (not ctypes.string_at: its size is a C int, an image can pass 2 GiB)
 
     def free(self):
@@ -1087,10 +1127,16 @@ class Plan:
             pass
 
 
-def load_raw(lib, image, handle, stream=None):
-    """scot_plan_load on `image` (bytes) -> status; `handle` (c_void_p) receives the plan.  The image is copied to 8-byte aligned memory."""
-    bind(lib)
+def _aligned_copy(image):
+    """-> (a copy of the image's bytes in 8-byte aligned memory, their number)"""
     n = len(image)
     buf = (ctypes.c_uint64 * ((n + 7) // 8 or 1))()
     ctypes.memmove(buf, bytes(image), n)
+    return buf, n
+
+
+def load_raw(lib, image, handle, stream=None):
+    """scot_plan_load on `image` (bytes) -> status; `handle` (c_void_p) receives the plan.  The image is copied to 8-byte aligned memory."""
+    bind(lib)
+    buf, n = _aligned_copy(image)
     return lib.scot_plan_load(ctypes.cast(buf, ctypes.c_void_p), n, ctypes.byref(handle), stream)

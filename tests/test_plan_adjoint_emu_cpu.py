@@ -10,59 +10,21 @@ the plan runtime has issued (emulated build only; not part of the C ABI)."""
 import ctypes
 import os
 import re
-import struct
-import subprocess
 import sys
 
 import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "hipemu"))
-from conftest import ROOT  # noqa: E402
+sys.path.insert(0, HERE)
+from plan_support import BOTH, ROOT, SMALL, check_images_stand_alone, emu, frozen_exports, issued, names_of, other_inputs  # noqa: E402,F401
+from plan_support import frozen_model as build_model, patched, relocation_beyond_its_buffer, renamed, truncations, word  # noqa: E402
 from poseidon_amd import engine as engine_mod, lib as scotlib, plan as plan_mod  # noqa: E402
 from poseidon_amd.config import ScOTConfig  # noqa: E402
-from poseidon_amd.geometry import param_shapes  # noqa: E402
 from poseidon_amd.plan import Plan, PlanExportError  # noqa: E402
-from poseidon_amd.synth import synth_inputs, synth_state_dict  # noqa: E402
 
-BOTH = ("pixel_values", "time")
 NEVER_LISTED = ("scot_wgrad_group", "scot_wgrad_mlp", "scot_colsum", "scot_conv5_wgrad", "scot_dwconv7_wgrad", "scot_adamw_step")
-SMALL = dict(image_size=32, patch_size=4, num_channels=4, num_out_channels=4, embed_dim=16, depths=[2, 2], num_heads=[1, 2],
-             skip_connections=[1, 0], window_size=4, mlp_ratio=4.0, p=1, channel_slice_list_normalized_loss=[0, 1, 3, 4],
-             drop_path_rate=0.0, use_conditioning=True)
-RESID = dict(SMALL, num_channels=5, num_out_channels=3, channel_slice_list_normalized_loss=[0, 1, 3], learn_residual=True)
-WIDE = dict(image_size=64, patch_size=4, num_channels=4, num_out_channels=4, embed_dim=96, depths=[1, 1], num_heads=[3, 6],
-            skip_connections=[1, 0], window_size=16, mlp_ratio=4.0, qkv_bias=True, drop_path_rate=0.0, hidden_act="gelu", p=1,
-            channel_slice_list_normalized_loss=[0, 1, 3, 4], residual_model="convnext", use_conditioning=True, learn_residual=False)
-MODELS = {"small": (SMALL, "fp32", 2), "resid": (RESID, "fp32", 2), "c96": (WIDE, "fp16", 1)}
-
-
-@pytest.fixture()
-def emu(monkeypatch):
-    import emu_session
-    import scOT.model as M
-    lib = emu_session.load_emu()
-    emu_session.patch_ops(monkeypatch, lib)
-    monkeypatch.setenv("SCOT_SIDE_STREAM", "0")
-    monkeypatch.setenv("SCOT_TAPE", "0")
-    monkeypatch.setitem(engine_mod.ENGINE_OPTIONS, "fused_min_rows", 0)      # the 96-wide model runs the fused layer tails
-    monkeypatch.setattr(M, "_require_hip", lambda t: None)
-    return lib
-
-
-def build_model(name, engine_options=None):
-    from scOT.model import ScOT
-    kw, compute, batch = MODELS[name]
-    cfg = ScOTConfig(**kw)
-    model = ScOT(cfg, compute=compute, engine_options=engine_options)
-    model.load_state_dict(synth_state_dict(param_shapes(cfg), "trained"))
-    model.eval()
-    for p in model.parameters():
-        p.requires_grad_(False)
-    model._ensure_arena(torch.device("cpu"))
-    pv, t, _ = synth_inputs(batch, cfg.num_channels, cfg.num_out_channels, cfg.image_size, "smooth")
-    return model, pv, t
+exported = frozen_exports()
 
 
 def cotangent(model, pv, seed):
@@ -80,48 +42,9 @@ def python_side(model, pv, t, g, wrt=BOTH):
     return (out.detach().clone(), grads.pop(0) if a.requires_grad else None, grads.pop(0) if b.requires_grad else None)
 
 
-def other_inputs(pv, t):
-    g = torch.Generator().manual_seed(7)
-    return pv.flip(0).flip(3) * 0.5 + 0.1 * torch.randn(pv.shape, generator=g), (t * 0.37 + 0.05)
-
-
-_cache = {}
-
-
-def exported(name, tmp_path_factory, adjoint=BOTH):
-    """one export per (configuration, request) for the whole module -> (model, pixel_values, time, path)"""
-    key = (name, adjoint)
-    if key not in _cache:
-        model, pv, t = build_model(name)
-        path = str(tmp_path_factory.mktemp("plan") / f"{name}_{len(adjoint)}.plan")
-        model.export_plan(pv, time=t, path=path, adjoint=adjoint)
-        _cache[key] = (model, pv, t, path)
-    return _cache[key]
-
-
-def issued(plan):
-    fn = plan._lib.scot_plan_emu_issued
-    fn.restype, fn.argtypes = ctypes.c_longlong, []
-    return int(fn())
-
-
 def raw_vjp(plan, g, d_pv, d_t, scale=0.0):
     return plan._lib.scot_plan_vjp(plan._h, g.data_ptr(), None if d_pv is None else d_pv.data_ptr(), None if d_t is None else d_t.data_ptr(),
                                    float(scale), None)
-
-
-def names_of(image, section):
-    """entry-point names of the calls in one entries section of an image ("forward" / "backward")"""
-    h = Plan.header(image)
-    H = plan_mod
-    names = [image[h[H.H_NAMES_OFF] + i * H.NAME_BYTES:][:H.NAME_BYTES].split(b"\0")[0].decode() for i in range(h[H.H_NNAMES])]
-    n, off = (h[H.H_NENTRIES], h[H.H_ENTRIES_OFF]) if section == "forward" else (h[H.H_NBACKWARD], h[H.H_BACKWARD_OFF])
-    out = []
-    for _ in range(n):
-        ni_name, _, ni, nf = struct.unpack_from("<4Q", image, off)
-        out.append(names[ni_name])
-        off += 8 * (4 + 2 * ni + nf)
-    return out
 
 
 # ------------------------------------------------------------------------------------------------------- round trip
@@ -281,42 +204,19 @@ def test_fp16_grad_scale_argument(emu, tmp_path_factory):
 # ------------------------------------------------------------------------------------------------------- refusals at load
 def corrupt_images(image):
     """{label: (bytes, expected status)}: the corrupt variants of a good format-2 image"""
-    h = list(Plan.header(image))
+    h = Plan.header(image)
     H = plan_mod
-    out = {}
-    cuts = sorted({H.HEADER_WORDS * 8, h[H.H_NAMES_OFF], h[H.H_BUFFERS_OFF], h[H.H_ENTRIES_OFF], h[H.H_ARRAYS_OFF], h[H.H_IO_OFF],
-                   h[H.H_BACKWARD_OFF], h[H.H_BACKWARD_OFF] + 8 * h[H.H_BACKWARD_WORDS] - 8, h[H.H_ADJ_OFF], h[H.H_ADJ_OFF] + 8 * H.ADJ_WORDS - 8,
-                   h[H.H_DATA_OFF], len(image) - 8, 8, 0})
-    for c in cuts:
-        out[f"truncated at {c}"] = (image[:c], -1)
-
-    def patched(off, value, src=image):
-        b = bytearray(src)
-        b[off:off + 8] = struct.pack("<Q", value)
-        return bytes(b)
-
-    def renamed(index, name):
-        b = bytearray(image)
-        o = h[H.H_NAMES_OFF] + index * H.NAME_BYTES
-        b[o:o + H.NAME_BYTES] = name.encode().ljust(H.NAME_BYTES, b"\0")
-        return bytes(b)
-    # first relocation of the first backward entry: offset = its buffer's size
+    out = truncations(image, (h[H.H_NAMES_OFF], h[H.H_BUFFERS_OFF], h[H.H_ENTRIES_OFF], h[H.H_ARRAYS_OFF], h[H.H_IO_OFF], h[H.H_BACKWARD_OFF],
+                              h[H.H_BACKWARD_OFF] + 8 * h[H.H_BACKWARD_WORDS] - 8, h[H.H_ADJ_OFF], h[H.H_ADJ_OFF] + 8 * H.ADJ_WORDS - 8,
+                              h[H.H_DATA_OFF]))
+    out["backward relocation beyond its buffer"] = (relocation_beyond_its_buffer(image, "backward"), -1)
     w = h[H.H_BACKWARD_OFF]
-    ni = struct.unpack_from("<Q", image, w + 16)[0]
-    for k in range(ni):
-        tag, val = struct.unpack_from("<2Q", image, w + 32 + 16 * k)
-        if tag & 0xFF == H.ARG_PTR:
-            size = struct.unpack_from("<Q", image, h[H.H_BUFFERS_OFF] + 32 * (tag >> 8) + 8)[0]
-            out["backward relocation beyond its buffer"] = (patched(w + 32 + 16 * k + 8, size), -1)
-            break
-    assert "backward relocation beyond its buffer" in out
-    out["backward entry renamed to a weight-gradient kernel"] = (renamed(struct.unpack_from("<Q", image, w)[0], "scot_wgrad_group"), -3)
-    fwd_only = struct.unpack_from("<Q", image, h[H.H_ENTRIES_OFF])[0]
-    out["forward entry renamed to a backward-only name"] = (renamed(fwd_only, "scot_cln_bwd"), -3)
-    out["backward n_int = 49"] = (patched(w + 16, 49), -1)
-    out["backward section past the end"] = (patched(8 * H.H_BACKWARD_WORDS, 1 << 31), -1)
-    out["gradient in an input buffer"] = (patched(h[H.H_ADJ_OFF] + 8 * H.ADJ_DPV, struct.unpack_from("<Q", image, h[H.H_ADJ_OFF] + 8 * H.ADJ_COT)[0]), -1)
-    out["format 3"] = (patched(8 * H.H_FORMAT, 3), -3)
+    out["backward entry renamed to a weight-gradient kernel"] = (renamed(image, word(image, w), "scot_wgrad_group"), -3)
+    out["forward entry renamed to a backward-only name"] = (renamed(image, word(image, h[H.H_ENTRIES_OFF]), "scot_cln_bwd"), -3)
+    out["backward n_int = 49"] = (patched(image, w + 16, 49), -1)
+    out["backward section past the end"] = (patched(image, 8 * H.H_BACKWARD_WORDS, 1 << 31), -1)
+    out["gradient in an input buffer"] = (patched(image, h[H.H_ADJ_OFF] + 8 * H.ADJ_DPV, word(image, h[H.H_ADJ_OFF] + 8 * H.ADJ_COT)), -1)
+    out["format 3"] = (patched(image, 8 * H.H_FORMAT, 3), -3)
     return out
 
 
@@ -340,23 +240,9 @@ def test_load_refusals(emu, tmp_path_factory):
 def test_stand_alone_image_check_under_sanitizers(emu, tmp_path_factory, tmp_path):
     """tools/plan_image_check.cc: the validator alone, built with the address and undefined-behaviour sanitizers, over a good format-2
     image, a good format-1 image and the corrupt variants — a child process on the CPU, nothing preloaded."""
-    import build_emu
     model, pv, t, path = exported("small", tmp_path_factory)
     image = open(path, "rb").read()
-    exe = str(tmp_path / "plan_image_check")
-    cc = subprocess.run([build_emu.CLANG, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                         "-I", os.path.join(ROOT, "poseidon_amd", "csrc"), os.path.join(ROOT, "tools", "plan_image_check.cc"), "-o", exe],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-    args = [exe, str(scotlib.ABI_VERSION), "0"]
-    cases = {"good": (image, 0), "good format 1": (model.export_plan(pv, time=t), 0), **corrupt_images(image)}
-    for i, (label, (data, status)) in enumerate(cases.items()):
-        p = tmp_path / f"case{i}.plan"
-        p.write_bytes(data)
-        args += [str(p), str(status)]
-    run = subprocess.run(args, capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-3000:])
-    assert f"{len(cases)} images checked" in run.stdout
+    check_images_stand_alone(tmp_path, {"good": (image, 0), "good format 1": (model.export_plan(pv, time=t), 0), **corrupt_images(image)})
 
 
 # ------------------------------------------------------------------------------------------------------- overflow is seen

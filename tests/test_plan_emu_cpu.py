@@ -4,59 +4,31 @@ Bit-identity with the engine's own forward, the refusals of the exporter and of 
 import ctypes
 import os
 import re
-import struct
-import subprocess
 import sys
 
 import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "hipemu"))
-from conftest import ROOT, load_fixture  # noqa: E402
+sys.path.insert(0, HERE)
+from conftest import load_fixture  # noqa: E402
+from plan_support import CFG96, CFG_ROLL, ROOT, check_images_stand_alone, emulated, other_inputs, patched, relocation_beyond_its_buffer  # noqa: E402
+from plan_support import renamed, synth_model as build_model, truncations  # noqa: E402
 from poseidon_amd import engine as engine_mod, harness, lib as scotlib, plan as plan_mod  # noqa: E402
 from poseidon_amd.config import ScOTConfig  # noqa: E402
-from poseidon_amd.geometry import param_shapes  # noqa: E402
 from poseidon_amd.plan import Plan, PlanExportError  # noqa: E402
-from poseidon_amd.synth import synth_inputs, synth_state_dict  # noqa: E402
+from poseidon_amd.synth import synth_inputs  # noqa: E402
 from scOT.model import ScOT  # noqa: E402
-
-CFG96 = dict(image_size=64, patch_size=4, num_channels=4, num_out_channels=4, embed_dim=96, depths=[2, 1], num_heads=[3, 6],
-             skip_connections=[1, 0], window_size=16, mlp_ratio=4.0, qkv_bias=True, drop_path_rate=0.0, hidden_act="gelu", p=1,
-             channel_slice_list_normalized_loss=[0, 1, 3, 4], residual_model="convnext", use_conditioning=True, learn_residual=False)
-# more input than output channels: the rollout passes the extra channels through
-CFG_ROLL = dict(image_size=16, patch_size=4, num_channels=5, num_out_channels=3, embed_dim=16, depths=[1, 1], num_heads=[1, 2],
-                skip_connections=[1, 0], window_size=4, mlp_ratio=2.0, qkv_bias=True, drop_path_rate=0.0, p=1,
-                channel_slice_list_normalized_loss=[0, 1, 3], use_conditioning=True)
 
 
 @pytest.fixture()
 def emu(monkeypatch):
-    import emu_session
-    lib = emu_session.load_emu()
-    emu_session.patch_ops(monkeypatch, lib)
-    monkeypatch.setenv("SCOT_SIDE_STREAM", "0")
-    monkeypatch.setenv("SCOT_TAPE", "0")
-    monkeypatch.setitem(engine_mod.ENGINE_OPTIONS, "fused_min_rows", 0)      # the tiny models run the fused layer tails
-    return lib
-
-
-def build_model(cfg, compute):
-    model = ScOT(cfg, compute=compute)
-    model.load_state_dict(synth_state_dict(param_shapes(cfg), "trained"))
-    model.eval()
-    model._ensure_arena(torch.device("cpu"))
-    return model
+    return emulated(monkeypatch, hip_guard=True)      # (ScOT.forward keeps refusing CPU tensors here)
 
 
 def own_forward(model, pv, t):
     with torch.no_grad():
         return model._engine.forward(pv, t, None, None, train=False, stochastic=False)[1].clone()
-
-
-def other_inputs(pv, t):
-    g = torch.Generator().manual_seed(7)
-    return pv.flip(0).flip(3) * 0.5 + 0.1 * torch.randn(pv.shape, generator=g), (t * 0.37 + 0.05)
 
 
 _cache = {}
@@ -205,34 +177,14 @@ def test_export_refuses_a_cpu_model():
 # ------------------------------------------------------------------------------------------------------- refusals at load
 def corrupt_images(image):
     """{label: (bytes, expected status)}: the corrupt variants of a good image"""
-    h = list(Plan.header(image))
+    h = Plan.header(image)
     H = plan_mod
-    out = {}
-    cuts = sorted({H.HEADER_WORDS * 8, h[H.H_NAMES_OFF], h[H.H_BUFFERS_OFF], h[H.H_ENTRIES_OFF], h[H.H_ARRAYS_OFF], h[H.H_IO_OFF],
-                   h[H.H_DATA_OFF], len(image) - 8, 8, 0})
-    for c in cuts:
-        out[f"truncated at {c}"] = (image[:c], -1)
-
-    def patched(off, value):
-        b = bytearray(image)
-        b[off:off + 8] = struct.pack("<Q", value)
-        return bytes(b)
-    # first relocation of the first entry: offset = its buffer's size
-    w = h[H.H_ENTRIES_OFF]
-    ni = struct.unpack_from("<Q", image, w + 16)[0]
-    for k in range(ni):
-        tag, val = struct.unpack_from("<2Q", image, w + 32 + 16 * k)
-        if tag & 0xFF == H.ARG_PTR:
-            size = struct.unpack_from("<Q", image, h[H.H_BUFFERS_OFF] + 32 * (tag >> 8) + 8)[0]
-            out["relocation beyond its buffer"] = (patched(w + 32 + 16 * k + 8, size), -1)
-            break
-    assert "relocation beyond its buffer" in out
-    b = bytearray(image)
-    b[h[H.H_NAMES_OFF]:h[H.H_NAMES_OFF] + H.NAME_BYTES] = b"scot_adamw_step".ljust(H.NAME_BYTES, b"\0")
-    out["unknown entry point"] = (bytes(b), -3)
-    out["n_int = 49"] = (patched(w + 16, 49), -1)
-    out["wrong ABI"] = (patched(8 * H.H_ABI, h[H.H_ABI] + 1), -3)
-    out["other operand format"] = (patched(8 * H.H_OPERAND, 1 - h[H.H_OPERAND]), -3)
+    out = truncations(image, (h[H.H_NAMES_OFF], h[H.H_BUFFERS_OFF], h[H.H_ENTRIES_OFF], h[H.H_ARRAYS_OFF], h[H.H_IO_OFF], h[H.H_DATA_OFF]))
+    out["relocation beyond its buffer"] = (relocation_beyond_its_buffer(image, "forward"), -1)
+    out["unknown entry point"] = (renamed(image, 0, "scot_adamw_step"), -3)
+    out["n_int = 49"] = (patched(image, h[H.H_ENTRIES_OFF] + 16, 49), -1)
+    out["wrong ABI"] = (patched(image, 8 * H.H_ABI, h[H.H_ABI] + 1), -3)
+    out["other operand format"] = (patched(image, 8 * H.H_OPERAND, 1 - h[H.H_OPERAND]), -3)
     return out
 
 
@@ -299,20 +251,6 @@ def test_gfx950_builds_export_the_plan_calls():
 def test_stand_alone_image_check_under_sanitizers(emu, tmp_path_factory, tmp_path):
     """tools/plan_image_check.cc: csrc/plan_image.h's validator alone, built with the address and undefined-behaviour sanitizers, over a
     good image and the corrupt variants — a child process on the CPU."""
-    import build_emu
     model, pv, t, path = exported("roll", tmp_path_factory)
     image = open(path, "rb").read()
-    exe = str(tmp_path / "plan_image_check")
-    cc = subprocess.run([build_emu.CLANG, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                         "-I", os.path.join(ROOT, "poseidon_amd", "csrc"), os.path.join(ROOT, "tools", "plan_image_check.cc"), "-o", exe],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-    args = [exe, str(scotlib.ABI_VERSION), "0"]
-    cases = {"good": (image, 0), **corrupt_images(image)}
-    for i, (label, (data, status)) in enumerate(cases.items()):
-        p = tmp_path / f"case{i}.plan"
-        p.write_bytes(data)
-        args += [str(p), str(status)]
-    run = subprocess.run(args, capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-3000:])
-    assert f"{len(cases)} images checked" in run.stdout
+    check_images_stand_alone(tmp_path, {"good": (image, 0), **corrupt_images(image)})

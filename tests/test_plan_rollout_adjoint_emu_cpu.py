@@ -16,79 +16,25 @@ import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "hipemu"))
-from conftest import ROOT  # noqa: E402
+sys.path.insert(0, HERE)
 import plan_rollout_reference as ref_mod  # noqa: E402
-from poseidon_amd import engine as engine_mod, lib as scotlib, plan as plan_mod  # noqa: E402
+from plan_support import BOTH, ROOT, SMALL, emu, frozen_exports, issued, other_inputs  # noqa: E402,F401
+from plan_support import frozen_model as build_model  # noqa: E402
+from poseidon_amd import lib as scotlib, plan as plan_mod  # noqa: E402
 from poseidon_amd.config import ScOTConfig  # noqa: E402
 from poseidon_amd.geometry import param_shapes  # noqa: E402
 from poseidon_amd.plan import Plan  # noqa: E402
-from poseidon_amd.synth import synth_inputs, synth_state_dict  # noqa: E402
+from poseidon_amd.synth import synth_state_dict  # noqa: E402
 
-BOTH = ("pixel_values", "time")
 NAME = "scot_plan_rollout_vjp"
-# the model definitions of tests/test_plan_adjoint_emu_cpu.py
-SMALL = dict(image_size=32, patch_size=4, num_channels=4, num_out_channels=4, embed_dim=16, depths=[2, 2], num_heads=[1, 2],
-             skip_connections=[1, 0], window_size=4, mlp_ratio=4.0, p=1, channel_slice_list_normalized_loss=[0, 1, 3, 4],
-             drop_path_rate=0.0, use_conditioning=True)
-RESID = dict(SMALL, num_channels=5, num_out_channels=3, channel_slice_list_normalized_loss=[0, 1, 3], learn_residual=True)
-WIDE = dict(image_size=64, patch_size=4, num_channels=4, num_out_channels=4, embed_dim=96, depths=[1, 1], num_heads=[3, 6],
-            skip_connections=[1, 0], window_size=16, mlp_ratio=4.0, qkv_bias=True, drop_path_rate=0.0, hidden_act="gelu", p=1,
-            channel_slice_list_normalized_loss=[0, 1, 3, 4], residual_model="convnext", use_conditioning=True, learn_residual=False)
-MODELS = {"small": (SMALL, "fp32", 2), "resid": (RESID, "fp32", 2), "c96": (WIDE, "fp16", 1)}
 CASES = [("small", 1), ("small", 3), ("resid", 3), ("c96", 2)]
-
-
-@pytest.fixture()
-def emu(monkeypatch):
-    import emu_session
-    import scOT.model as M
-    lib = emu_session.load_emu()
-    emu_session.patch_ops(monkeypatch, lib)
-    monkeypatch.setenv("SCOT_SIDE_STREAM", "0")
-    monkeypatch.setenv("SCOT_TAPE", "0")
-    monkeypatch.setitem(engine_mod.ENGINE_OPTIONS, "fused_min_rows", 0)      # the 96-wide model runs the fused layer tails
-    monkeypatch.setattr(M, "_require_hip", lambda t: None)
-    return lib
-
-
-def build_model(name, engine_options=None):
-    from scOT.model import ScOT
-    kw, compute, batch = MODELS[name]
-    cfg = ScOTConfig(**kw)
-    model = ScOT(cfg, compute=compute, engine_options=engine_options)
-    model.load_state_dict(synth_state_dict(param_shapes(cfg), "trained"))
-    model.eval()
-    for p in model.parameters():
-        p.requires_grad_(False)
-    model._ensure_arena(torch.device("cpu"))
-    pv, t, _ = synth_inputs(batch, cfg.num_channels, cfg.num_out_channels, cfg.image_size, "smooth")
-    return model, pv, t
+exported = frozen_exports()
 
 
 def cotangents(model, pv, steps, seed):
     """[B, steps, Cout, H, W], O(1 / elements of one prediction)"""
     shape = (pv.shape[0], steps, model.config.num_out_channels, pv.shape[2], pv.shape[3])
     return torch.randn(shape, generator=torch.Generator().manual_seed(seed)) / (shape[0] * shape[2] * shape[3] * shape[4])
-
-
-def other_inputs(pv, t):
-    g = torch.Generator().manual_seed(7)
-    return pv.flip(0).flip(3) * 0.5 + 0.1 * torch.randn(pv.shape, generator=g), (t * 0.37 + 0.05)
-
-
-_cache = {}
-
-
-def exported(name, tmp_path_factory, adjoint=BOTH):
-    """one export per (configuration, request) for the whole module -> (model, pixel_values, time, path)"""
-    key = (name, adjoint)
-    if key not in _cache:
-        model, pv, t = build_model(name)
-        path = str(tmp_path_factory.mktemp("plan") / f"{name}_{len(adjoint)}.plan")
-        model.export_plan(pv, time=t, path=path, adjoint=adjoint)
-        _cache[key] = (model, pv, t, path)
-    return _cache[key]
 
 
 _refs = {}
@@ -104,12 +50,6 @@ def references(name, steps, tmp_path_factory):
         d_pv1, d_t1, terms = ref_mod.r1(model, pv, t, preds, g)
         _refs[key] = dict(preds=preds, g=g, r1=(d_pv1, d_t1), r2=(d_pv2, d_t2), terms=terms)
     return _refs[key]
-
-
-def issued(plan):
-    fn = plan._lib.scot_plan_emu_issued
-    fn.restype, fn.argtypes = ctypes.c_longlong, []
-    return int(fn())
 
 
 def c_layout(x):

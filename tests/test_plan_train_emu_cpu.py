@@ -10,22 +10,19 @@ learning rate per group: a stale input copy or an unpatched lr shows.  "Launches
 import ctypes
 import os
 import re
-import struct
-import subprocess
 import sys
 
 import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "hipemu"))
-from conftest import ROOT  # noqa: E402
-from poseidon_amd import engine as engine_mod, lib as scotlib, plan as plan_mod  # noqa: E402
+sys.path.insert(0, HERE)
+from plan_support import ROOT, SMALL, WIDE, check_images_stand_alone, emu, frozen_model, issued, names_of, patched  # noqa: E402,F401
+from plan_support import relocation_beyond_its_buffer, renamed, synth_model, word  # noqa: E402
+from poseidon_amd import lib as scotlib, plan as plan_mod  # noqa: E402
 from poseidon_amd.config import ScOTConfig  # noqa: E402
-from poseidon_amd.geometry import param_shapes  # noqa: E402
 from poseidon_amd.plan import Plan, PlanExportError  # noqa: E402
-from poseidon_amd.synth import synth_inputs, synth_state_dict  # noqa: E402
-from test_plan_adjoint_emu_cpu import SMALL, WIDE, issued  # noqa: E402
+from poseidon_amd.synth import synth_inputs  # noqa: E402
 
 H = plan_mod
 MODELS = {"small": (SMALL, "fp32", 2), "c96": (WIDE, "fp16", 1), "small16": (SMALL, "fp16", 2)}
@@ -35,29 +32,11 @@ NEW_CALLS = {"scot_plan_describe_training", "scot_plan_loss", "scot_plan_train_s
 STATE = ("arena", "exp_avg", "exp_avg_sq", "step_state", "scale_state")
 
 
-@pytest.fixture()
-def emu(monkeypatch):
-    import emu_session
-    import scOT.model as M
-    lib = emu_session.load_emu()
-    emu_session.patch_ops(monkeypatch, lib)
-    monkeypatch.setenv("SCOT_SIDE_STREAM", "0")
-    monkeypatch.setenv("SCOT_TAPE", "0")
-    monkeypatch.setitem(engine_mod.ENGINE_OPTIONS, "fused_min_rows", 0)      # the 96-wide model runs the fused layer tails
-    monkeypatch.setattr(M, "_require_hip", lambda t: None)
-    return lib
-
-
 def build_model(name, **opt_kw):
     """-> (model in training mode with every parameter trainable, its FusedAdamW)"""
     import emu_session
-    from scOT.model import ScOT
     kw, compute, _ = MODELS[name]
-    cfg = ScOTConfig(**kw)
-    model = ScOT(cfg, compute=compute)
-    model.load_state_dict(synth_state_dict(param_shapes(cfg), "trained"))
-    model.train()
-    model._ensure_arena(torch.device("cpu"))
+    model = synth_model(ScOTConfig(**kw), compute, train=True)
     opt = emu_session.fused_adamw(model, **dict(dict(lr=1e-3, weight_decay=0.01, max_grad_norm=5.0), **opt_kw))
     return model, opt
 
@@ -119,19 +98,6 @@ def exported(name):
         assert float(model._arena.grad.abs().max()) == 0.0
         _cache[name] = image
     return _cache[name]
-
-
-def names_of(image, which):
-    """entry-point names of one list of a training image: "forward" (inference) or step list 0 / 1 / 2"""
-    h, tr = Plan.header(image), plan_mod.training_words(image)
-    names = [image[h[H.H_NAMES_OFF] + i * H.NAME_BYTES:][:H.NAME_BYTES].split(b"\0")[0].decode() for i in range(h[H.H_NNAMES])]
-    n, off = (h[H.H_NENTRIES], h[H.H_ENTRIES_OFF]) if which == "forward" else tr[H.TR_FWD + 3 * which: H.TR_FWD + 3 * which + 2]
-    out = []
-    for _ in range(n):
-        ni_name, _, ni, nf = struct.unpack_from("<4Q", image, off)
-        out.append(names[ni_name])
-        off += 8 * (4 + 2 * ni + nf)
-    return out
 
 
 # ------------------------------------------------------------------------------------------------------- steps
@@ -313,7 +279,6 @@ def test_runtime_refusals_launch_nothing(emu):
     refused(-3, lambda: L.scot_plan_rollout_vjp(hnd, pv.data_ptr(), t.data_ptr(), g.data_ptr(), g.data_ptr(), 1, pv.data_ptr(), None, 0.0, None))
     plan.free()
     # the training calls on a format-1 and on a format-2 plan
-    from test_plan_adjoint_emu_cpu import build_model as frozen_model
     model, fpv, ft = frozen_model("small")
     for kw in ({}, {"adjoint": ("pixel_values",)}):
         plan = Plan.load(model.export_plan(fpv, time=ft, **kw))
@@ -373,50 +338,32 @@ def corrupt_images(image):
     h, tr = Plan.header(image), plan_mod.training_words(image)
     out = {}
 
-    def patched(off, value, src=image):
-        b = bytearray(src)
-        b[off:off + 8] = struct.pack("<Q", value)
-        return bytes(b)
-
-    def renamed(index, name):
-        b = bytearray(image)
-        o = h[H.H_NAMES_OFF] + index * H.NAME_BYTES
-        b[o:o + H.NAME_BYTES] = name.encode().ljust(H.NAME_BYTES, b"\0")
-        return bytes(b)
-
-    def buffer_word(buf, word):
-        return struct.unpack_from("<Q", image, h[H.H_BUFFERS_OFF] + 32 * buf + 8 * word)[0]
+    def buffer_word(buf, w):
+        return word(image, h[H.H_BUFFERS_OFF] + 32 * buf + 8 * w)
     for s, what in enumerate(("step forward", "step backward", "update")):      # first relocation of the list's first entry
-        w = tr[H.TR_FWD + 3 * s + 1]
-        ni = struct.unpack_from("<Q", image, w + 16)[0]
-        for k in range(ni):
-            tag, val = struct.unpack_from("<2Q", image, w + 32 + 16 * k)
-            if tag & 0xFF == H.ARG_PTR:
-                out[f"{what}: relocation beyond its buffer"] = (patched(w + 32 + 16 * k + 8, buffer_word(tag >> 8, 1)), -1)
-                break
-        assert f"{what}: relocation beyond its buffer" in out
+        out[f"{what}: relocation beyond its buffer"] = (relocation_beyond_its_buffer(image, s), -1)
     upd = tr[H.TR_UPD + 1]
-    out["update entry renamed to a name outside the training list"] = (renamed(struct.unpack_from("<Q", image, upd)[0], "scot_dp_pack"), -3)
-    out["inference entry renamed to scot_adamw_step"] = (renamed(struct.unpack_from("<Q", image, h[H.H_ENTRIES_OFF])[0], "scot_adamw_step"), -3)
+    out["update entry renamed to a name outside the training list"] = (renamed(image, word(image, upd), "scot_dp_pack"), -3)
+    out["inference entry renamed to scot_adamw_step"] = (renamed(image, word(image, h[H.H_ENTRIES_OFF]), "scot_adamw_step"), -3)
     t_off = h[H.H_TRAIN_OFF]
     assert tr[H.TR_LR_ENTRY] != 0
-    out["lr patch point on another entry"] = (patched(t_off + 8 * H.TR_LR_ENTRY, 0), -1)
-    out["lr patch point past the update"] = (patched(t_off + 8 * H.TR_LR_ENTRY, tr[H.TR_UPD]), -1)
-    out["lr patch point on another argument"] = (patched(t_off + 8 * H.TR_LR_ARG, 0), -1)
+    out["lr patch point on another entry"] = (patched(image, t_off + 8 * H.TR_LR_ENTRY, 0), -1)
+    out["lr patch point past the update"] = (patched(image, t_off + 8 * H.TR_LR_ENTRY, tr[H.TR_UPD]), -1)
+    out["lr patch point on another argument"] = (patched(image, t_off + 8 * H.TR_LR_ARG, 0), -1)
     wd_arg = tr[H.TR_LR_ARG] + 1      # (the weight-decay array: same kind, same length, not a patch point)
-    out["lr patch point on the weight-decay array"] = (patched(t_off + 8 * H.TR_LR_ARG, wd_arg), -1)
-    out["two state spans over the same bytes"] = (patched(t_off + 8 * H.TR_EXP_AVG_SQ, tr[H.TR_EXP_AVG]), -1)
-    out["lr patch point with the wrong length"] = (patched(t_off + 8 * H.TR_GROUPS, tr[H.TR_GROUPS] + 1), -1)
+    out["lr patch point on the weight-decay array"] = (patched(image, t_off + 8 * H.TR_LR_ARG, wd_arg), -1)
+    out["two state spans over the same bytes"] = (patched(image, t_off + 8 * H.TR_EXP_AVG_SQ, tr[H.TR_EXP_AVG]), -1)
+    out["lr patch point with the wrong length"] = (patched(image, t_off + 8 * H.TR_GROUPS, tr[H.TR_GROUPS] + 1), -1)
     constant = next(i for i in range(h[H.H_NBUFFERS]) if buffer_word(i, 0) == H.CONSTANT and buffer_word(i, 1) >= 8)
-    out["state span inside a constant"] = (patched(t_off + 8 * H.TR_STEP_STATE, constant, patched(t_off + 8 * (H.TR_STEP_STATE + 1), 0)), -1)
-    out["labels in an output buffer"] = (patched(t_off + 8 * H.TR_LABELS, tr[H.TR_PRED]), -1)
-    out["state buffer not stored"] = (patched(h[H.H_BUFFERS_OFF] + 32 * tr[H.TR_ARENA] + 24, 0), -1)
-    out["state content past the data section"] = (patched(h[H.H_BUFFERS_OFF] + 32 * tr[H.TR_ARENA] + 16, h[H.H_DATA_BYTES]), -1)
-    out["training section past the end"] = (patched(8 * H.H_TRAIN_OFF, len(image) - 8 * (H.TRAIN_WORDS - 1)), -1)
-    out["update list past the end"] = (patched(t_off + 8 * (H.TR_UPD + 2), 1 << 31), -1)
+    out["state span inside a constant"] = (patched(patched(image, t_off + 8 * (H.TR_STEP_STATE + 1), 0), t_off + 8 * H.TR_STEP_STATE, constant), -1)
+    out["labels in an output buffer"] = (patched(image, t_off + 8 * H.TR_LABELS, tr[H.TR_PRED]), -1)
+    out["state buffer not stored"] = (patched(image, h[H.H_BUFFERS_OFF] + 32 * tr[H.TR_ARENA] + 24, 0), -1)
+    out["state content past the data section"] = (patched(image, h[H.H_BUFFERS_OFF] + 32 * tr[H.TR_ARENA] + 16, h[H.H_DATA_BYTES]), -1)
+    out["training section past the end"] = (patched(image, 8 * H.H_TRAIN_OFF, len(image) - 8 * (H.TRAIN_WORDS - 1)), -1)
+    out["update list past the end"] = (patched(image, t_off + 8 * (H.TR_UPD + 2), 1 << 31), -1)
     out["truncated"] = (image[:t_off + 8], -1)
-    out["format 3"] = (patched(8 * H.H_FORMAT, 3), -3)
-    out["relabelled format 1"] = (patched(8 * H.H_FORMAT, 1), -3)      # (its name table holds names no inference image may hold)
+    out["format 3"] = (patched(image, 8 * H.H_FORMAT, 3), -3)
+    out["relabelled format 1"] = (patched(image, 8 * H.H_FORMAT, 1), -3)      # (its name table holds names no inference image may hold)
     return out
 
 
@@ -436,22 +383,8 @@ def test_load_refusals(emu):
 def test_stand_alone_image_check_under_sanitizers(emu, tmp_path):
     """tools/plan_image_check.cc: the validator alone, built with the address and undefined-behaviour sanitizers, over a good format-4
     image and the corrupt variants — a child process on the CPU, nothing preloaded."""
-    import build_emu
     image = exported("small")
-    exe = str(tmp_path / "plan_image_check")
-    cc = subprocess.run([build_emu.CLANG, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                         "-I", os.path.join(ROOT, "poseidon_amd", "csrc"), os.path.join(ROOT, "tools", "plan_image_check.cc"), "-o", exe],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-    args = [exe, str(scotlib.ABI_VERSION), "0"]
-    cases = {"good": (image, 0), **corrupt_images(image)}
-    for i, (label, (data, status)) in enumerate(cases.items()):
-        p = tmp_path / f"case{i}.plan"
-        p.write_bytes(data)
-        args += [str(p), str(status)]
-    run = subprocess.run(args, capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-3000:])
-    assert f"{len(cases)} images checked" in run.stdout
+    check_images_stand_alone(tmp_path, {"good": (image, 0), **corrupt_images(image)})
 
 
 # ------------------------------------------------------------------------------------------------------- header, table, lists

@@ -3,9 +3,10 @@
 //   plan_image_check <abi> <operand format> <image file> <expected status> [<image file> <expected status> ...]
 //
 // Runs scot_plan_image_validate over every file and compares the status with the expected one; for an accepted image it also walks
-// everything the validator promised is in bounds (names, entries, arrays, constants' bytes; the step lists and stored state of a training image).  Each file is read into a heap block of
-// exactly its size, so a build with -fsanitize=address,undefined turns any read past a truncated image into an error.  Exit status 0
-// when every image got the expected answer.
+// everything the validator promised is in bounds: the names, every call list, the arrays, the io / adjoint / training words, and the
+// bytes of the constants and of the stored state.  Each file is read into a heap block of exactly its size, so a build with
+// -fsanitize=address,undefined turns any read past a truncated image into an error.  Exit status 0 when every image got the expected
+// answer.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -14,24 +15,17 @@
 static uint64_t walk(const scot_plan_view* v) {
   uint64_t sum = 0;
   for (uint64_t i = 0; i < v->n_names; ++i) sum += strlen((const char*)(v->names + i * SCOT_PLAN_NAME_BYTES));
-  for (uint64_t i = 0; i < v->n_buffers; ++i)
-    if (v->buffers[4 * i] == SCOT_PLAN_BUF_CONSTANT)
-      for (uint64_t k = 0; k < v->buffers[4 * i + 1]; k += 64) sum += v->data[v->buffers[4 * i + 2] + k];
-  for (uint64_t w = 0; w < v->entries_words; ++w) sum += v->entries[w];
+  for (uint64_t i = 0; i < v->n_buffers; ++i) {      // what the image holds by value: constants, and the stored state of a training image
+    const uint64_t* buf = v->buffers + 4 * i;
+    if (buf[0] == SCOT_PLAN_BUF_CONSTANT || (v->train && buf[0] == SCOT_PLAN_BUF_STATE && buf[3] == 1))
+      for (uint64_t k = 0; k < buf[1]; k += 64) sum += v->data[buf[2] + k];
+  }
+  for (int c = 0; c < SCOT_PLAN_N_CALLS; ++c)
+    for (uint64_t w = 0; w < v->calls[c].n_words; ++w) sum += v->calls[c].words[w];
   for (uint64_t w = 0; w < v->arrays_words; ++w) sum += v->arrays[w];
   for (int w = 0; w < SCOT_PLAN_IO_WORDS; ++w) sum += v->io[w];
-  if (v->format == SCOT_PLAN_FORMAT_ADJOINT) {      // the backward section and the adjoint words of a format-2 image
-    for (uint64_t w = 0; w < v->backward_words; ++w) sum += v->backward[w];
-    for (int w = 0; w < SCOT_PLAN_ADJ_WORDS; ++w) sum += v->adj[w];
-  }
-  if (v->format == SCOT_PLAN_FORMAT_TRAINING) {      // the training words, the three step lists, the stored state buffers' bytes
-    for (int w = 0; w < SCOT_PLAN_TRAIN_WORDS; ++w) sum += v->train[w];
-    for (int s = 0; s < 3; ++s)
-      for (uint64_t w = 0; w < v->step_words[s]; ++w) sum += v->step[s][w];
-    for (uint64_t i = 0; i < v->n_buffers; ++i)
-      if (v->buffers[4 * i] == SCOT_PLAN_BUF_STATE && v->buffers[4 * i + 3] == 1)
-        for (uint64_t k = 0; k < v->buffers[4 * i + 1]; k += 64) sum += v->data[v->buffers[4 * i + 2] + k];
-  }
+  for (int w = 0; v->adj && w < SCOT_PLAN_ADJ_WORDS; ++w) sum += v->adj[w];
+  for (int w = 0; v->train && w < SCOT_PLAN_TRAIN_WORDS; ++w) sum += v->train[w];
   return sum;
 }
 
