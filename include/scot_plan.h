@@ -1,11 +1,12 @@
-/* scot_plan.h — running AND fine-tuning a trained ScOT model from C: exported inference plans, their adjoints, training plans (ABI 8).
+/* scot_plan.h — running AND fine-tuning a trained ScOT model from C: exported inference plans, their adjoints, training plans, on one
+ * stream or two (ABI 8).
  *
  * scot_hip.h is the kernel-level boundary: about a hundred entry points that a host program has to order itself.  This header is the
  * model-level one.  `ScOT.export_plan` (poseidon_amd/plan.py) records one inference forward for one input signature and writes it,
  * with the weights, as a relocatable plan image; the calls below load such a file and run it.  A host needs nothing but the
  * shared library and the HIP runtime: no Python, no torch.  The prediction is bit-identical to `model(...)` in Python.
  *
- * What a plan covers: the engine's inference forward at config.image_size on ONE stream — no training, no spectral resize, no hidden
+ * What a plan covers: the engine's inference forward at config.image_size on ONE stream (or two: TWO-STREAM plans below) — no training, no spectral resize, no hidden
  * states or attention outputs, no labels (so no pixel_mask: the mask overwrites the prediction with label values).  The weights are a
  * snapshot taken at export.  A plan recorded by the binary16 build (libscot_hip_f16.so) loads into that build only; its split-MFMA
  * trunk products run in the bfloat16 build, which the runtime opens from the same directory (or from where the peer call points).
@@ -25,9 +26,21 @@
  * modes (arena 1x, two moments 2x, two 16-bit copies 1x), 3x in fp32 / bf16x3, plus the small tables.  The runtime owns them after
  * load, scot_plan_run sees the current ones and scot_plan_snapshot writes them back into the image.
  * Weight decay, betas, eps, clipping and the scale schedule are fixed at export; the learning rates are an argument of every step.  Not
- * covered: gradient accumulation, data parallelism, stochastic depth, pixel_mask, partially frozen models, more than one stream, a
- * trimmed image.  It runs on ONE stream, the weight gradients in line (the Python engine puts them on a second stream: measured on
+ * covered: gradient accumulation, data parallelism, stochastic depth, pixel_mask, partially frozen models, a trimmed image.  By
+ * default it runs on ONE stream, the weight gradients in line (the Python engine puts them on a second stream: measured on
  * Poseidon-B fp16, a plan's step takes 22.7 ms against the Python loop's 19.3 at batch 64, 11.1 against 10.7 at batch 1).
+ *
+ * A TWO-STREAM plan (`export_plan(..., streams=2)`; image format 5 = an inference plan, 6 = a training plan) holds the engine's own
+ * two-stream program instead: the bias tables, the skip blocks, the weight gradients, the gradient fill and the un-scale passes on a
+ * SIDE stream beside the main chain, with the engine's fork and join edges as event entries of the image.  The load creates the events
+ * and picks a side stream that it MEASURES to run beside the load's stream (scot_stream_overlaps; scot_plan_set_side_stream hands it the
+ * host's own instead).  Every call below works on such a plan unchanged and still takes ONE stream: each recorded list forks from it and
+ * joins back into it, so runs of one plan stay ordered on the stream you pass.  Results: the prediction is bit-identical to the
+ * one-stream plan's; a training step is the engine's two-stream step.  Not covered: adjoint plans (the frozen backward has no
+ * weight-gradient stream), more than two streams, and everything a format-4 plan does not cover.  `streams=1` stays the default.
+ * Measured on Poseidon-B fp16 with the overlap flag at 1 (profiles/plan_streams/README.md): a training step takes 19.3 ms at batch 64 and
+ * 10.5 at batch 1, the Python loop's 19.3 / 10.6, against 22.6 / 11.0 on one stream; inference 6.11 against 6.15 ms at batch 64 — but
+ * 3.95 against 3.62 ms at batch 1: for launch-bound inference the event edges cost more than the side stream hides, keep streams=1 there.
  *
  * Status codes as in scot_hip.h: 0, -1 (malformed image / bad argument), -3 (not for this library: ABI, operand format, entry point;
  * or a host other than x86-64 System V, where the replay underneath does not exist), -4 (allocation, copy or launch failed).
@@ -55,8 +68,8 @@ int scot_plan_load(const void* image, size_t bytes, scot_plan_t* plan, scot_stre
  * recorded calls, bytes of pixel_values, bytes of the prediction, image format version. */
 int scot_plan_describe(scot_plan_t plan, long long* out);
 /* prediction [B, Cout, H, W] <- model(pixel_values [B, Cin, H, W], time [B]); fp32 device buffers of the caller.  time / pixel_mask
- * are NULL exactly when the plan has no such input.  Copies in, replays the recorded calls with every stream slot = `stream`, copies
- * out; everything is asynchronous on `stream`. */
+ * are NULL exactly when the plan has no such input.  Copies in, replays the recorded calls with every stream slot = `stream` (a
+ * two-stream plan: the slots of stream 1 = its side stream), copies out; everything is asynchronous on `stream`. */
 int scot_plan_run(scot_plan_t plan, const float* pixel_values, const float* time, const void* pixel_mask, float* prediction,
                   scot_stream_t stream);
 /* Autoregressive rollout, the integer form of the reference's (trainer.py:452-603, output_all_steps): time / steps once (rounded as torch
@@ -147,6 +160,26 @@ int scot_plan_snapshot(scot_plan_t plan, void* image, size_t bytes, scot_stream_
 /* Name i of the entry points the three step lists of a training plan may call (NULL past the end).  The weight-gradient kernels and
  * the optimizer are listed here and ONLY here. */
 const char* scot_plan_training_entry_point(int i);
+/* ---- two-stream plans ---- */
+/* *overlaps <- 1 when stream `b` really runs beside stream `a` under the engine's fork / join pattern, 0 when the pair serialises (two
+ * streams that share a hardware queue do, silently, as soon as they exchange events) or a == b.  The measurement: one spin kernel of
+ * ~0.5 ms on `a`; then K1 on a, an event b waits for, K2 on b beside K3 on a, a second event a waits for — accepted below 2.5 kernel
+ * times, the best of two trials.  Waits for both streams; ~4 ms.  For any host that needs a second stream that is worth having: a plan's
+ * side stream, the comm stream of the native data-parallel backend.  (The CPU emulation answers 0.) */
+int scot_stream_overlaps(scot_stream_t a, scot_stream_t b, int* overlaps);
+/* The host's own side stream for a two-stream plan, instead of the one the load picked (which is destroyed): between the load and the
+ * first run, otherwise -1; NULL or the load's own stream: -1.  It is measured against the load's stream (scot_plan_describe_streams
+ * reports the answer) and used whatever the answer.  The host keeps it alive until the plan is freed.  On a one-stream plan: -3. */
+int scot_plan_set_side_stream(scot_plan_t plan, scot_stream_t side);
+/* out[4]: streams (1 or 2), events, whether the side stream was measured to run beside the load's stream (0: the plan is correct but
+ * its two streams may serialise — the load tried eight candidates and kept the first), whether the side stream is the host's. */
+int scot_plan_describe_streams(scot_plan_t plan, long long* out);
+/* Test aid, next to scot_plan_poison: later calls issue call list `list` (0 forward, 2 / 3 / 4 the step's forward, backward, update)
+ * entry by entry in `order`, a permutation of 0 .. n-1 over the list's n entries (anything else: -1), and synchronise both streams
+ * whenever the stream of the next entry differs from the previous one's and at the end: the device executes exactly that order.
+ * order = NULL restores the normal replay.  The call does NOT judge whether the order is legal. */
+int scot_plan_issue_order(scot_plan_t plan, int list, const int* order, int n);
+
 /* Refused before anything is copied or launched: scot_plan_loss / _train_step / _train_status / _snapshot on a format-1/2 plan: -3
  * (as scot_plan_vjp / scot_plan_rollout_vjp on a training plan); a NULL pixel_values, labels or lr, a NULL loss of scot_plan_loss, a NULL
  * time on a plan with a time input (or a time on one without), a snapshot target that is not this plan's image: -1. */

@@ -23,6 +23,13 @@
 // call reads at issue time, and replays the three lists; scot_plan_snapshot reads the state back into the image.  No arithmetic of
 // its own: clipping, the skip decision and the fp16 gradient scale are the recorded kernels', on the device.
 //
+// TWO-STREAM plans (image formats 5 and 6: a format-1 / format-4 image whose lists hold the engine's own two-stream program).  The load
+// creates the plan's events (timing disabled; their handles go into the programs once, there) and obtains a side stream: one that is
+// MEASURED to run beside the load's stream under the engine's fork / join pattern (scot_stream_overlaps, the C form of
+// poseidon_amd/streams.py), or the host's (scot_plan_set_side_stream).  `replay` writes the caller's stream and the side stream into the
+// program's stream slots.  Every list of such an image is closed (plan_image.h), so the copies in and out stay on the caller's stream
+// and every call above works unchanged.  scot_plan_issue_order is a test aid: it issues a list entry by entry in a given order.
+//
 // A plan is one stream's worth of state: its buffers are reused by every run, so runs of ONE plan must be ordered (same stream, or
 // the caller's own events); two plans are independent.
 #include "common.h"
@@ -44,9 +51,11 @@ extern "C" int scot_operand_format();
 #define SCOT_PLAN_DECLARE(n) extern "C" int n(...);
 SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_DECLARE)
 SCOT_PLAN_TRAINING_ENTRY_POINTS(SCOT_PLAN_DECLARE)
+SCOT_PLAN_SYNC_ENTRY_POINTS(SCOT_PLAN_DECLARE)
 #define SCOT_PLAN_ADDRESS(n) (void*)&n,
 static void* const g_entry_address[SCOT_PLAN_N_LISTS][SCOT_PLAN_COUNT(scot_plan_training_entry_names)] = {
-    {SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_ADDRESS)}, {SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_ADDRESS)}, {SCOT_PLAN_TRAINING_ENTRY_POINTS(SCOT_PLAN_ADDRESS)}};
+    {SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_ADDRESS)}, {SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_ADDRESS)}, {SCOT_PLAN_TRAINING_ENTRY_POINTS(SCOT_PLAN_ADDRESS)},
+    {SCOT_PLAN_SYNC_ENTRY_POINTS(SCOT_PLAN_ADDRESS)}};
 
 // ------------------------------------------------------------------ device memory and copies (plain host memory in the CPU emulation)
 namespace {
@@ -66,6 +75,13 @@ inline bool dev_copy2d(void* dst, size_t dpitch, const void* src, size_t spitch,
   return true;
 }
 inline bool dev_sync(hipStream_t) { return true; }
+// streams and events of a two-stream plan: stubs (the emulation runs every entry to completion where it is issued)
+typedef void* dev_event_t;
+inline bool dev_event_create(dev_event_t* e) { *e = (void*)(uintptr_t)1; return true; }
+inline void dev_event_destroy(dev_event_t) {}
+inline bool dev_stream_create(hipStream_t* s) { *s = (hipStream_t)(uintptr_t)1; return true; }
+inline void dev_stream_destroy(hipStream_t) {}
+inline int dev_overlaps(hipStream_t, hipStream_t) { return 0; }
 // the carry of scot_plan_rollout_vjp as host loops (the kernels further down, element for element)
 inline bool dev_carry(float* hold, const float* g, float* hold_t, const float* g_t, size_t B, size_t cin, size_t cout, size_t hw, bool first,
                       bool last, int steps, hipStream_t) {
@@ -100,6 +116,64 @@ inline bool dev_copy2d(void* dst, size_t dpitch, const void* src, size_t spitch,
   return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDeviceToDevice, s) == hipSuccess;
 }
 inline bool dev_sync(hipStream_t s) { return hipStreamSynchronize(s) == hipSuccess; }
+typedef hipEvent_t dev_event_t;
+inline bool dev_event_create(dev_event_t* e) { return hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess; }
+inline void dev_event_destroy(dev_event_t e) { (void)hipEventDestroy(e); }
+inline bool dev_stream_create(hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess; }
+inline void dev_stream_destroy(hipStream_t s) { (void)hipStreamDestroy(s); }
+
+// ---- the stream probe (scot_stream_overlaps).  One wavefront that spins on the constant-rate clock (100 MHz on gfx950) for `ticks`, inside
+// a loop bounded by `max_rounds`; it reads nothing and writes nothing.
+__global__ __launch_bounds__(64) void plan_spin_kernel(long long ticks, int max_rounds) {
+  const long long t0 = (long long)wall_clock64();
+  for (int r = 0; r < max_rounds; ++r) {
+    if ((long long)wall_clock64() - t0 >= ticks) break;
+    __builtin_amdgcn_s_sleep(32);
+  }
+}
+const long long SPIN_TICKS = 50000;      // 0.5 ms: long against event / launch latencies, short against anything a user would notice
+const int SPIN_ROUNDS = 1 << 13;         // (a round is at least the sleep's 32 x 64 cycles, ~1 us: the bound is ~20 spins, reached only by a dead clock)
+inline void spin(hipStream_t s, long long ticks = SPIN_TICKS) { hipLaunchKernelGGL(plan_spin_kernel, dim3(1), dim3(64), 0, s, ticks, SPIN_ROUNDS); }
+
+// GPU milliseconds on `a` of: K1 on a; b waits for it; K2 on b beside K3 on a; a waits for K2 (`single`: of K1 alone, one kernel time)
+inline bool spin_ms(hipStream_t a, hipStream_t b, bool single, hipEvent_t e0, hipEvent_t e1, hipEvent_t fork, hipEvent_t join, float* ms) {
+  bool ok = hipEventRecord(e0, a) == hipSuccess;
+  spin(a);
+  if (!single) {
+    ok = ok && hipEventRecord(fork, a) == hipSuccess && hipStreamWaitEvent(b, fork, 0) == hipSuccess;
+    spin(b);
+    ok = ok && hipEventRecord(join, b) == hipSuccess;
+    spin(a);
+    ok = ok && hipStreamWaitEvent(a, join, 0) == hipSuccess;
+  }
+  ok = ok && hipEventRecord(e1, a) == hipSuccess && scot_check_launch() == SCOT_OK;
+  ok = ok && hipStreamSynchronize(a) == hipSuccess && (single || hipStreamSynchronize(b) == hipSuccess);
+  return ok && hipEventElapsedTime(ms, e0, e1) == hipSuccess;
+}
+
+// 1: `b` runs beside `a` under the fork / join pattern — three spin kernels take about two kernel times, the best of two trials; 0: they
+// serialise (or a == b); -1: the measurement itself failed
+inline int dev_overlaps(hipStream_t a, hipStream_t b) {
+  if (a == b) return 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool ok = true;
+  for (int i = 0; i < 4 && ok; ++i) ok = hipEventCreateWithFlags(&ev[i], i < 2 ? hipEventDefault : hipEventDisableTiming) == hipSuccess;
+  // (both streams are used once first: the runtime attaches a stream to its hardware queue at its first submission)
+  if (ok) {
+    spin(a, 100);
+    spin(b, 100);
+    ok = hipStreamSynchronize(a) == hipSuccess && hipStreamSynchronize(b) == hipSuccess;
+  }
+  float one = 0.0f, best = 0.0f, ms = 0.0f;
+  ok = ok && spin_ms(a, b, true, ev[0], ev[1], ev[2], ev[3], &one);
+  for (int trial = 0; trial < 2 && ok; ++trial) {
+    ok = spin_ms(a, b, false, ev[0], ev[1], ev[2], ev[3], &ms);
+    best = trial == 0 || ms < best ? ms : best;
+  }
+  for (int i = 0; i < 4; ++i)
+    if (ev[i]) (void)hipEventDestroy(ev[i]);
+  return ok ? (best < 2.5f * one ? 1 : 0) : -1;
+}
 
 // ---- the carry of scot_plan_rollout_vjp: the only kernels the plan runtime launches itself.  Internal (no entry points of scot_hip.h);
 // T = float4 where every (sample, channel) plane is a whole number of 16-byte aligned vectors, float otherwise.  Plain fp32 adds in the
@@ -176,9 +250,20 @@ struct Plan {
   std::vector<uint64_t> buf_kind, buf_bytes;
   struct Program {
     std::vector<uint64_t> prog;                    // scot_tape_replay's word format, final addresses
-    std::vector<size_t> stream_slot;               // words of prog that hold the stream
+    std::vector<size_t> stream_slot;               // words of prog that hold a stream ...
+    std::vector<uint8_t> slot_stream;              // ... and which: 0 = the caller's, 1 = the plan's side stream
+    std::vector<size_t> entry_at;                  // two-stream plans: the word offset of every entry in prog (and prog's end) ...
+    std::vector<uint8_t> entry_stream;             // ... and the stream it is issued on
+    std::vector<int> order;                        // scot_plan_issue_order: the order later replays issue the entries in (empty: as recorded)
     uint64_t calls = 0;
   } list[SCOT_PLAN_N_CALLS];                       // SCOT_PLAN_CALLS_*; a list the image does not have is empty
+  // two-stream plans (formats 5 and 6): the events and the side stream, whether the load created it, whether it was measured to run beside
+  // the load's stream, and whether a list has been issued (the side stream is fixed from then on)
+  uint64_t n_streams = 1;
+  std::vector<dev_event_t> events;
+  hipStream_t side = nullptr, load_stream = nullptr;
+  bool side_own = false, side_host = false, started = false;
+  int side_overlaps = 0;
   std::vector<std::vector<uint64_t>> host_arrays;  // host arrays the entries pass by address: pointers, or packed int32 / float
   // training plans: the training words, where the update reads lr[groups], and what scot_plan_snapshot compares a target image with
   // and writes into (the header, the buffer table, each stored buffer's place)
@@ -189,7 +274,7 @@ struct Plan {
   std::vector<float> host_time;                    // scot_plan_rollout: the divided time on its way back to the device
   uint64_t io[SCOT_PLAN_IO_WORDS] = {};
   uint64_t adj[SCOT_PLAN_ADJ_WORDS] = {};
-  int operand_format = 0, compute = 0, format = SCOT_PLAN_FORMAT;
+  int operand_format = 0, compute = 0, format = SCOT_PLAN_FORMAT;      // format: the ONE-stream format (1, 2, 4) the image extends
   bool ran = false;                                // a completed scot_plan_run whose saved activations no vjp / poison / rollout has used up
   float host_scale[4] = {1.0f, 1.0f, 0.0f, 0.0f};  // {S, 1/S, 0, 0} on its way to the state buffer
   int last_exponent = 0;                           // log2 S of the last vjp
@@ -227,15 +312,16 @@ void* default_peer() {
   return open_peer((dir + "/libscot_hip.so").c_str());
 }
 
-void* resolve(const char* name, uint64_t lib, int list) {
-  const int index = scot_plan_list_index(name, list);
+void* resolve(const char* name, uint64_t lib, int list, bool streamed) {
+  int index = scot_plan_list_index(name, list);
+  if (index < 0 && streamed && (index = scot_plan_list_index(name, SCOT_PLAN_LIST_SYNC)) >= 0) list = SCOT_PLAN_LIST_SYNC;
   if (index < 0) return nullptr;
   if (lib == 0 || scot_operand_format() == 0) return g_entry_address[list][index];
   if (!g_peer) g_peer = default_peer();
   return g_peer ? dlsym(g_peer, name) : nullptr;
 }
 
-// one argument pair -> the word the call receives; `slot` = stream placeholder (patched per run)
+// one argument pair -> the word the call receives; a stream is a placeholder (patched per run), an event is the plan's own
 bool materialise(Plan* pl, uint64_t tagw, uint64_t val, uint64_t* out, bool* is_stream) {
   *is_stream = false;
   switch (tagw & 0xff) {
@@ -243,19 +329,32 @@ bool materialise(Plan* pl, uint64_t tagw, uint64_t val, uint64_t* out, bool* is_
     case SCOT_PLAN_ARG_NULL: *out = 0; return true;
     case SCOT_PLAN_ARG_PTR: *out = (uint64_t)(uintptr_t)(pl->buf[tagw >> 8] + val); return true;
     case SCOT_PLAN_ARG_STREAM: *out = 0; *is_stream = true; return true;
+    case SCOT_PLAN_ARG_EVENT: *out = (uint64_t)(uintptr_t)pl->events[val]; return true;
     default: return false;
   }
 }
 
-// one of the plan's lists (SCOT_PLAN_CALLS_*) on `stream`
+// one of the plan's lists (SCOT_PLAN_CALLS_*) on `stream` (and, a two-stream plan, its side stream): as recorded in one run of
+// scot_tape_replay, or — scot_plan_issue_order — entry by entry in the installed order, both streams synchronised at every switch
 int replay(Plan* pl, int list, hipStream_t stream) {
   Plan::Program& p = pl->list[list];
-  for (size_t s : p.stream_slot) p.prog[s] = (uint64_t)(uintptr_t)stream;
+  const hipStream_t streams[2] = {stream, pl->side};
+  for (size_t k = 0; k < p.stream_slot.size(); ++k) p.prog[p.stream_slot[k]] = (uint64_t)(uintptr_t)streams[p.slot_stream[k]];
+  pl->started = true;
 #ifdef SCOT_HIPEMU
   g_emu_issued += (long long)p.calls;
 #endif
   int fail = -1;
-  return scot_tape_replay(p.prog.data(), p.prog.size(), &fail);
+  if (p.order.empty()) return scot_tape_replay(p.prog.data(), p.prog.size(), &fail);
+  int prev = -1;
+  for (int j : p.order) {
+    const int on = p.entry_stream[j];
+    if (prev >= 0 && on != prev && !(dev_sync(stream) && dev_sync(pl->side))) return SCOT_ERR_LAUNCH;
+    const int rc = scot_tape_replay(p.prog.data() + p.entry_at[j], p.entry_at[j + 1] - p.entry_at[j], &fail);
+    if (rc != SCOT_OK) return rc;
+    prev = on;
+  }
+  return dev_sync(stream) && dev_sync(pl->side) ? SCOT_OK : SCOT_ERR_LAUNCH;
 }
 
 // one call list -> the entry points' addresses (false: one is missing)
@@ -263,7 +362,7 @@ bool resolve_section(const scot_plan_view& v, const scot_plan_calls& c, std::vec
   fn->resize(c.n);
   const uint64_t* e = c.words;
   for (uint64_t i = 0; i < c.n; ++i, e += scot_plan_entry_words(e)) {
-    (*fn)[i] = resolve((const char*)(v.names + e[0] * SCOT_PLAN_NAME_BYTES), e[1], c.names);
+    (*fn)[i] = resolve((const char*)(v.names + e[0] * SCOT_PLAN_NAME_BYTES), e[1], c.names, v.n_streams > 1);
     if (!(*fn)[i]) return false;
   }
   return true;
@@ -277,6 +376,8 @@ bool build_program(Plan* pl, const scot_plan_calls& c, const std::vector<void*>&
   const uint64_t* e = c.words;
   for (uint64_t i = 0; i < c.n; ++i, e += scot_plan_entry_words(e)) {
     const uint64_t ni = e[2], nf = e[3];
+    out->entry_at.push_back(out->prog.size());
+    out->entry_stream.push_back(0);
     out->prog.push_back((uint64_t)(uintptr_t)fn[i]);
     out->prog.push_back(ni);
     out->prog.push_back(nf);
@@ -288,11 +389,16 @@ bool build_program(Plan* pl, const scot_plan_calls& c, const std::vector<void*>&
         word = array_address[val];
       else if (!materialise(pl, tagw, val, &word, &st))
         return false;
-      if (st) out->stream_slot.push_back(out->prog.size());
+      if (st) {
+        out->stream_slot.push_back(out->prog.size());
+        out->slot_stream.push_back((uint8_t)val);
+        out->entry_stream.back() = (uint8_t)val;
+      }
       out->prog.push_back(word);
     }
     for (uint64_t k = 0; k < nf; ++k) out->prog.push_back(e[4 + 2 * ni + k]);
   }
+  out->entry_at.push_back(out->prog.size());
   return true;
 }
 
@@ -325,6 +431,8 @@ extern "C" int scot_plan_free(void* plan) {
   if (!pl) return plan ? SCOT_ERR_SHAPE : SCOT_OK;
   if (pl->slab) dev_free(pl->slab);
   if (pl->holder) dev_free(pl->holder);
+  for (dev_event_t e : pl->events) dev_event_destroy(e);
+  if (pl->side_own) dev_stream_destroy(pl->side);
   pl->magic = 0;
   delete pl;
   return SCOT_OK;
@@ -345,7 +453,9 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
   int status = SCOT_OK;
   try {
     memcpy(pl->io, v.io, sizeof(pl->io));
-    pl->format = (int)v.format;
+    pl->format = v.format == SCOT_PLAN_FORMAT_STREAMS ? SCOT_PLAN_FORMAT : (v.format == SCOT_PLAN_FORMAT_TRAINING_STREAMS ? SCOT_PLAN_FORMAT_TRAINING : (int)v.format);
+    pl->n_streams = v.n_streams;
+    pl->load_stream = stream;
     if (v.adj) memcpy(pl->adj, v.adj, sizeof(pl->adj));
     if (v.train) memcpy(pl->train, v.train, sizeof(pl->train));
     memcpy(pl->header, v.h, sizeof(pl->header));
@@ -404,6 +514,32 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
         w += 2 + 2 * cnt;
       }
     }
+    // a two-stream plan's events, and a side stream that runs beside `stream`: the first of up to eight candidates that is measured to
+    // (scot_stream_overlaps); if none is, the first candidate — the plan is then correct but may serialise, and says so
+    // (scot_plan_describe_streams).  Never a reason to fail the load.
+    if (status == SCOT_OK && v.n_streams > 1) {
+      for (uint64_t i = 0; i < v.n_events && status == SCOT_OK; ++i) {
+        dev_event_t e;
+        if (dev_event_create(&e)) pl->events.push_back(e);
+        else status = SCOT_ERR_LAUNCH;
+      }
+      std::vector<hipStream_t> tried;
+      for (int t = 0; t < 8 && status == SCOT_OK && !pl->side_overlaps; ++t) {
+        hipStream_t s;
+        if (!dev_stream_create(&s)) {
+          if (tried.empty()) status = SCOT_ERR_LAUNCH;
+          break;
+        }
+        tried.push_back(s);
+        pl->side_overlaps = dev_overlaps(stream, s) == 1;
+      }
+      if (!tried.empty()) {
+        pl->side = pl->side_overlaps ? tried.back() : tried.front();
+        pl->side_own = true;
+        for (hipStream_t s : tried)
+          if (s != pl->side) dev_stream_destroy(s);
+      }
+    }
     // the programs
     for (int c = 0; c < SCOT_PLAN_N_CALLS && status == SCOT_OK; ++c)
       if (!build_program(pl, v.calls[c], fn[c], array_address, &pl->list[c])) status = SCOT_ERR_SHAPE;
@@ -439,7 +575,7 @@ extern "C" int scot_plan_describe(void* plan, long long* out) {
                            (long long)(io[SCOT_PLAN_IO_HAS_TIME] ? io[SCOT_PLAN_IO_TIME_BYTES] : 0), (long long)io[SCOT_PLAN_IO_HAS_MASK],
                            (long long)(io[SCOT_PLAN_IO_HAS_MASK] ? io[SCOT_PLAN_IO_MASK_BYTES] : 0), pl->operand_format, pl->compute,
                            (long long)(pl->slab_bytes + pl->holder_bytes), (long long)pl->list[SCOT_PLAN_CALLS_FORWARD].calls, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
-                           (long long)(hw * io[SCOT_PLAN_IO_COUT]), pl->format};
+                           (long long)(hw * io[SCOT_PLAN_IO_COUT]), (long long)pl->header[SCOT_PLAN_H_FORMAT]};
   memcpy(out, d, sizeof(d));
   return SCOT_OK;
 }
@@ -793,4 +929,68 @@ extern "C" int scot_plan_snapshot(void* plan, void* image, size_t bytes, hipStre
         !dev_copy(b + h[SCOT_PLAN_H_DATA_OFF] + pl->buffer_table[4 * i + 2], pl->buf[i], (size_t)pl->buf_bytes[i], D2H, stream))
       return SCOT_ERR_LAUNCH;
   return dev_sync(stream) ? SCOT_OK : SCOT_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------ two-stream plans (image formats 5 and 6)
+// *overlaps <- 1 when `b` runs beside `a` under the engine's fork / join pattern (K1 on a; b waits for it; K2 on b beside K3 on a; a
+// waits for K2: three spin kernels of ~0.5 ms in less than 2.5 kernel times, the best of two trials), 0 when the pair serialises or
+// a == b.  Waits for both streams.  The CPU emulation answers 0.
+extern "C" int scot_stream_overlaps(hipStream_t a, hipStream_t b, int* overlaps) {
+  if (!overlaps) return SCOT_ERR_SHAPE;
+  const int r = dev_overlaps(a, b);
+  *overlaps = r == 1;
+  return r < 0 ? SCOT_ERR_LAUNCH : SCOT_OK;
+}
+
+// the host's own side stream instead of the one the load picked: between the load and the first run.  -3 on a one-stream plan.
+extern "C" int scot_plan_set_side_stream(void* plan, hipStream_t side) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  if (pl->n_streams < 2) return SCOT_ERR_UNSUPPORTED;
+  if (pl->started || !side || side == pl->load_stream) return SCOT_ERR_SHAPE;
+  const int measured = dev_overlaps(pl->load_stream, side);
+  if (measured < 0) return SCOT_ERR_LAUNCH;
+  if (pl->side_own) dev_stream_destroy(pl->side);
+  pl->side = side;
+  pl->side_own = false;
+  pl->side_host = true;
+  pl->side_overlaps = measured;
+  return SCOT_OK;
+}
+
+// out[4]: streams (1 or 2), events, whether the side stream was measured to run beside the load's stream, whether it is the host's
+extern "C" int scot_plan_describe_streams(void* plan, long long* out) {
+  Plan* pl = as_plan(plan);
+  if (!pl || !out) return SCOT_ERR_SHAPE;
+  out[0] = (long long)pl->n_streams;
+  out[1] = (long long)pl->events.size();
+  out[2] = pl->side_overlaps;
+  out[3] = pl->side_host;
+  return SCOT_OK;
+}
+
+// A test aid, like scot_plan_poison: later calls issue list `list` (SCOT_PLAN_CALLS_*) entry by entry in `order` — a permutation of
+// 0 .. n-1 over the list's n entries, anything else -1 — with both streams synchronised whenever the stream of the next entry differs from
+// the previous one's, so that the device executes exactly that order.  order = NULL restores the normal replay.  Whether an order is
+// LEGAL (respects stream order and the event edges) is for the caller to know: tests/tape_schedule.py derives the legal ones.
+extern "C" int scot_plan_issue_order(void* plan, int list, const int* order, int n) {
+  Plan* pl = as_plan(plan);
+  if (!pl || list < 0 || list >= SCOT_PLAN_N_CALLS) return SCOT_ERR_SHAPE;
+  Plan::Program& p = pl->list[list];
+  if (!order) {
+    p.order.clear();
+    return SCOT_OK;
+  }
+  if (n < 0 || (uint64_t)n != p.calls || n == 0) return SCOT_ERR_SHAPE;
+  try {
+    std::vector<char> seen((size_t)n, 0);
+    for (int k = 0; k < n; ++k) {
+      if (order[k] < 0 || order[k] >= n || seen[order[k]]) return SCOT_ERR_SHAPE;
+      seen[order[k]] = 1;
+    }
+    p.order.assign(order, order + n);
+  } catch (const std::bad_alloc&) {
+    return SCOT_ERR_LAUNCH;
+  }
+  return SCOT_OK;
 }

@@ -20,7 +20,18 @@
 //   data     the constants' and the stored state's bytes, each piece 64-byte aligned
 //
 // An argument pair is {tag | buffer << 8, value}: SCOT_PLAN_ARG_INT (value as is), _NULL, _PTR (buffer index, byte offset), _STREAM
-// (the caller's stream at run time) or _ARRAY (value = index into `arrays`).
+// (value 0: the caller's stream at run time; value 1, formats 5 and 6: the plan's side stream), _ARRAY (value = index into `arrays`) or
+// _EVENT (formats 5 and 6: value = index of one of the plan's events).
+//
+// TWO-STREAM images (`export_plan(..., streams=2)`): format 5 is a format-1 image, format 6 a format-4 image, whose lists hold the
+// engine's own two-stream program: entries on stream 0 and stream 1 with the engine's fork and join edges as ordinary entries,
+// scot_event_record (EVENT, STREAM) and scot_stream_wait_event (STREAM, EVENT) — the one more table of names, SCOT_PLAN_LIST_SYNC, which
+// only these formats enable.  ONE header word (SCOT_PLAN_H_STREAMS_OFF) names the streams section: the number of streams (exactly 2) and
+// the number of events.  Every list of such an image is CLOSED, and the validator holds it to that: a wait pairs with an earlier record
+// of its event in the SAME list; the first entry on stream 1 is a wait for an event recorded on stream 0 of that list; the last entry on
+// stream 1 is a record that stream 0 waits for further down.  So whatever runs in front of a list or behind it on stream 0 — the
+// runtime's copies in and out, the next list, the caller's own work — is ordered with all of it, and the caller's contract stays "runs
+// of one plan are ordered on the one stream you pass".  A library from before these formats refuses them by the format word (-3).
 //
 // The five lists (SCOT_PLAN_CALLS_*), each held to ONE table of entry points (SCOT_PLAN_LIST_*): what can run is what is listed.
 //
@@ -51,6 +62,10 @@
 #define SCOT_PLAN_FORMAT 1
 #define SCOT_PLAN_FORMAT_ADJOINT 2
 #define SCOT_PLAN_FORMAT_TRAINING 4 /* (3 is unassigned) */
+#define SCOT_PLAN_FORMAT_STREAMS 5          /* format 1 + the streams section */
+#define SCOT_PLAN_FORMAT_TRAINING_STREAMS 6 /* format 4 + the streams section */
+#define SCOT_PLAN_STREAMS_WORDS 2
+#define SCOT_PLAN_MAX_EVENTS 4096
 #define SCOT_PLAN_HEADER_WORDS 32
 #define SCOT_PLAN_NAME_BYTES 48
 #define SCOT_PLAN_IO_WORDS 24
@@ -66,9 +81,11 @@ enum { SCOT_PLAN_H_MAGIC, SCOT_PLAN_H_FORMAT, SCOT_PLAN_H_ABI, SCOT_PLAN_H_OPERA
        SCOT_PLAN_H_ENTRIES_OFF, SCOT_PLAN_H_ENTRIES_WORDS, SCOT_PLAN_H_NARRAYS, SCOT_PLAN_H_ARRAYS_OFF, SCOT_PLAN_H_ARRAYS_WORDS,
        SCOT_PLAN_H_IO_OFF, SCOT_PLAN_H_DATA_OFF, SCOT_PLAN_H_DATA_BYTES,
        /* format 2 */ SCOT_PLAN_H_NBACKWARD, SCOT_PLAN_H_BACKWARD_OFF, SCOT_PLAN_H_BACKWARD_WORDS, SCOT_PLAN_H_ADJ_OFF,
-       /* format 4 */ SCOT_PLAN_H_TRAIN_OFF };
+       /* format 4 */ SCOT_PLAN_H_TRAIN_OFF,
+       /* formats 5, 6 */ SCOT_PLAN_H_STREAMS_OFF };
+enum { SCOT_PLAN_ST_STREAMS, SCOT_PLAN_ST_EVENTS }; /* the streams section */
 enum { SCOT_PLAN_BUF_CONSTANT, SCOT_PLAN_BUF_INPUT, SCOT_PLAN_BUF_OUTPUT, SCOT_PLAN_BUF_SCRATCH, SCOT_PLAN_BUF_STATE };
-enum { SCOT_PLAN_ARG_INT, SCOT_PLAN_ARG_NULL, SCOT_PLAN_ARG_PTR, SCOT_PLAN_ARG_STREAM, SCOT_PLAN_ARG_ARRAY };
+enum { SCOT_PLAN_ARG_INT, SCOT_PLAN_ARG_NULL, SCOT_PLAN_ARG_PTR, SCOT_PLAN_ARG_STREAM, SCOT_PLAN_ARG_ARRAY, SCOT_PLAN_ARG_EVENT };
 enum { SCOT_PLAN_IO_B, SCOT_PLAN_IO_CIN, SCOT_PLAN_IO_H, SCOT_PLAN_IO_W, SCOT_PLAN_IO_COUT, SCOT_PLAN_IO_PV_BUF, SCOT_PLAN_IO_PV_OFF,
        SCOT_PLAN_IO_HAS_TIME, SCOT_PLAN_IO_TIME_BUF, SCOT_PLAN_IO_TIME_OFF, SCOT_PLAN_IO_TIME_BYTES, SCOT_PLAN_IO_HAS_MASK,
        SCOT_PLAN_IO_MASK_BUF, SCOT_PLAN_IO_MASK_OFF, SCOT_PLAN_IO_MASK_BYTES, SCOT_PLAN_IO_OUT_BUF, SCOT_PLAN_IO_OUT_OFF };
@@ -111,21 +128,28 @@ enum { SCOT_PLAN_TR_FLAGS, SCOT_PLAN_TR_GROUPS, SCOT_PLAN_TR_ARENA_FLOATS, SCOT_
   X(scot_replica_reduce) X(scot_cpb_bwd_batched) X(scot_batch_sum) X(scot_segments_scale) X(scot_grad_sqnorm) X(scot_clip_coef)     \
   X(scot_adamw_step) X(scot_optim_finish) X(scot_transpose_cast)
 
-// the three tables of entry points, and which of them each of the five call lists is held to
-enum { SCOT_PLAN_LIST_FORWARD, SCOT_PLAN_LIST_ADJOINT, SCOT_PLAN_LIST_TRAINING, SCOT_PLAN_N_LISTS };
+// What every list of a two-stream image (formats 5 and 6) may call beside its own table: the engine's fork and join edges.
+#define SCOT_PLAN_SYNC_ENTRY_POINTS(X) X(scot_event_record) X(scot_stream_wait_event)
+
+// the three tables of entry points, and which of them each of the five call lists is held to; SYNC is admitted beside a list's own table
+// in a two-stream image and nowhere else
+enum { SCOT_PLAN_LIST_FORWARD, SCOT_PLAN_LIST_ADJOINT, SCOT_PLAN_LIST_TRAINING, SCOT_PLAN_LIST_SYNC, SCOT_PLAN_N_LISTS };
+enum { SCOT_PLAN_SYNC_RECORD, SCOT_PLAN_SYNC_WAIT }; /* rows of SCOT_PLAN_LIST_SYNC */
 enum { SCOT_PLAN_CALLS_FORWARD, SCOT_PLAN_CALLS_BACKWARD, SCOT_PLAN_CALLS_STEP_FORWARD, SCOT_PLAN_CALLS_STEP_BACKWARD,
        SCOT_PLAN_CALLS_UPDATE, SCOT_PLAN_N_CALLS };
 #define SCOT_PLAN_NAME_STRING(n) #n,
 static const char* const scot_plan_entry_names[] = {SCOT_PLAN_ENTRY_POINTS(SCOT_PLAN_NAME_STRING)};
 static const char* const scot_plan_adjoint_entry_names[] = {SCOT_PLAN_ADJOINT_ENTRY_POINTS(SCOT_PLAN_NAME_STRING)};
 static const char* const scot_plan_training_entry_names[] = {SCOT_PLAN_TRAINING_ENTRY_POINTS(SCOT_PLAN_NAME_STRING)};
+static const char* const scot_plan_sync_entry_names[] = {SCOT_PLAN_SYNC_ENTRY_POINTS(SCOT_PLAN_NAME_STRING)};
 #define SCOT_PLAN_COUNT(a) ((int)(sizeof(a) / sizeof((a)[0])))
 static const struct {
   const char* const* names;
   int count;
 } scot_plan_lists[SCOT_PLAN_N_LISTS] = {{scot_plan_entry_names, SCOT_PLAN_COUNT(scot_plan_entry_names)},
                                         {scot_plan_adjoint_entry_names, SCOT_PLAN_COUNT(scot_plan_adjoint_entry_names)},
-                                        {scot_plan_training_entry_names, SCOT_PLAN_COUNT(scot_plan_training_entry_names)}};
+                                        {scot_plan_training_entry_names, SCOT_PLAN_COUNT(scot_plan_training_entry_names)},
+                                        {scot_plan_sync_entry_names, SCOT_PLAN_COUNT(scot_plan_sync_entry_names)}};
 
 // the index of `name` in one of the three tables (SCOT_PLAN_LIST_*), -1: not listed there
 static inline int scot_plan_list_index(const char* name, int list) {
@@ -157,7 +181,8 @@ typedef struct {
   uint64_t format, n_names, n_buffers, n_arrays, arrays_words, data_bytes;
   scot_plan_calls calls[SCOT_PLAN_N_CALLS]; /* SCOT_PLAN_CALLS_* */
   const uint64_t* adj;   /* format 2 (NULL otherwise): the adjoint words */
-  const uint64_t* train; /* format 4 (NULL otherwise): the training words */
+  const uint64_t* train; /* formats 4 and 6 (NULL otherwise): the training words */
+  uint64_t n_streams, n_events; /* 1 and 0 but in formats 5 and 6: what a STREAM and an EVENT pair may name */
 } scot_plan_view;
 
 // [off, off + n) inside [0, bytes), off 8-byte aligned, without overflow
@@ -184,7 +209,9 @@ static inline int scot_plan_arg_ok(const scot_plan_view* v, uint64_t tagw, uint6
     case SCOT_PLAN_ARG_NULL:
       return buf == 0;
     case SCOT_PLAN_ARG_STREAM:
-      return buf == 0 && !in_array;
+      return buf == 0 && !in_array && val < v->n_streams;
+    case SCOT_PLAN_ARG_EVENT:
+      return buf == 0 && !in_array && val < v->n_events;
     case SCOT_PLAN_ARG_PTR:
       return buf < v->n_buffers && val < v->buffers[4 * buf + 1];      /* a pointer names a byte OF the buffer */
     case SCOT_PLAN_ARG_ARRAY:
@@ -204,21 +231,54 @@ static inline uint64_t scot_plan_entry_at(const uint64_t* e, uint64_t i) {
   return w;
 }
 
-// one call list: record bounds, n_int / n_flt, every argument pair, every name in the list's OWN table
-static inline int scot_plan_entries_ok(const scot_plan_view* v, const scot_plan_calls* c) {
+// one call list: record bounds, n_int / n_flt, every argument pair, every name in the list's OWN table — or, in a two-stream image, in
+// the SYNC table: a record is exactly (EVENT, STREAM), a wait exactly (STREAM, EVENT), and no other entry carries an EVENT pair.  The
+// same pass holds the list to the closed-list rules of the header text; `recorded` (n_events bytes, the caller's) is scratch: the stream
+// + 1 of an event's latest record in THIS list.
+static inline int scot_plan_entries_ok(const scot_plan_view* v, const scot_plan_calls* c, uint8_t* recorded) {
   const uint64_t* e = c->words;
   uint64_t w = 0;
+  /* side: 0 = stream 1 not used yet, 1 = open (entries on stream 1 that stream 0 has not waited for), 2 = joined; join_event: the event
+     of the record that is the last entry on stream 1 so far (n_events: that entry is no record) */
+  int side = 0;
+  uint64_t join_event = v->n_events;
+  memset(recorded, 0, (size_t)v->n_events);
   for (uint64_t i = 0; i < c->n; ++i, w += scot_plan_entry_words(e + w)) {
     if (c->n_words - w < 4) return SCOT_PLAN_ERR_SHAPE;
     const uint64_t name = e[w], lib = e[w + 1], ni = e[w + 2], nf = e[w + 3];
     if (name >= v->n_names || lib > 1 || ni > SCOT_PLAN_MAX_INT || nf > SCOT_PLAN_MAX_FLT) return SCOT_PLAN_ERR_SHAPE;
     if (scot_plan_entry_words(e + w) > c->n_words - w) return SCOT_PLAN_ERR_SHAPE;
-    for (uint64_t k = 0; k < ni; ++k)
+    uint64_t on = 0, events = 0;      /* the stream this entry is issued on, the EVENT pairs it carries */
+    for (uint64_t k = 0; k < ni; ++k) {
       if (!scot_plan_arg_ok(v, e[w + 4 + 2 * k], e[w + 5 + 2 * k], 0)) return SCOT_PLAN_ERR_SHAPE;
+      if ((e[w + 4 + 2 * k] & 0xff) == SCOT_PLAN_ARG_STREAM) on |= e[w + 5 + 2 * k];
+      events += (e[w + 4 + 2 * k] & 0xff) == SCOT_PLAN_ARG_EVENT;
+    }
     for (uint64_t k = 0; k < nf; ++k)
       if (e[w + 4 + 2 * ni + k] >> 32) return SCOT_PLAN_ERR_SHAPE;      /* raw bits of ONE float */
-    if (scot_plan_list_index((const char*)(v->names + name * SCOT_PLAN_NAME_BYTES), c->names) < 0) return SCOT_PLAN_ERR_UNSUPPORTED;
+    const char* nm = (const char*)(v->names + name * SCOT_PLAN_NAME_BYTES);
+    const int sync = v->n_streams > 1 ? scot_plan_list_index(nm, SCOT_PLAN_LIST_SYNC) : -1;
+    if (sync < 0 && scot_plan_list_index(nm, c->names) < 0) return SCOT_PLAN_ERR_UNSUPPORTED;
+    if (sync < 0 && events) return SCOT_PLAN_ERR_SHAPE;
+    uint64_t ev = v->n_events;
+    if (sync >= 0) {
+      const int at = sync == SCOT_PLAN_SYNC_RECORD ? 0 : 1;      /* where the EVENT pair sits; the STREAM pair is the other one */
+      if (ni != 2 || nf != 0 || (e[w + 4 + 2 * at] & 0xff) != SCOT_PLAN_ARG_EVENT || (e[w + 6 - 2 * at] & 0xff) != SCOT_PLAN_ARG_STREAM)
+        return SCOT_PLAN_ERR_SHAPE;
+      ev = e[w + 5 + 2 * at];
+      if (sync == SCOT_PLAN_SYNC_WAIT && !recorded[ev]) return SCOT_PLAN_ERR_SHAPE;      /* no earlier record in this list */
+    }
+    if (on) {
+      /* the first entry on stream 1: a wait for a record on stream 0 of this list */
+      if (!side && !(sync == SCOT_PLAN_SYNC_WAIT && recorded[ev] == 1)) return SCOT_PLAN_ERR_SHAPE;
+      side = 1;
+      join_event = sync == SCOT_PLAN_SYNC_RECORD ? ev : v->n_events;
+    } else if (sync == SCOT_PLAN_SYNC_WAIT && ev == join_event && recorded[ev] == 2) {
+      side = 2;      /* stream 0 is behind everything stream 1 has been given so far */
+    }
+    if (sync == SCOT_PLAN_SYNC_RECORD) recorded[ev] = (uint8_t)(on + 1);
   }
+  if (side == 1) return SCOT_PLAN_ERR_SHAPE;      /* the list leaves stream 1 unjoined */
   return w == c->n_words ? SCOT_PLAN_OK : SCOT_PLAN_ERR_SHAPE;
 }
 
@@ -312,11 +372,14 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
   const uint8_t* b = (const uint8_t*)image;
   const uint64_t* h = (const uint64_t*)image;
   if (h[SCOT_PLAN_H_MAGIC] != SCOT_PLAN_MAGIC) return SCOT_PLAN_ERR_SHAPE;
-  if (h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT && h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT_ADJOINT &&
-      h[SCOT_PLAN_H_FORMAT] != SCOT_PLAN_FORMAT_TRAINING)
+  const uint64_t format = h[SCOT_PLAN_H_FORMAT];
+  if (format != SCOT_PLAN_FORMAT && format != SCOT_PLAN_FORMAT_ADJOINT && format != SCOT_PLAN_FORMAT_TRAINING &&
+      format != SCOT_PLAN_FORMAT_STREAMS && format != SCOT_PLAN_FORMAT_TRAINING_STREAMS)
     return SCOT_PLAN_ERR_UNSUPPORTED;
-  const int adjoint = h[SCOT_PLAN_H_FORMAT] == SCOT_PLAN_FORMAT_ADJOINT, training = h[SCOT_PLAN_H_FORMAT] == SCOT_PLAN_FORMAT_TRAINING;
-  const int enabled[SCOT_PLAN_N_LISTS] = {1, adjoint, training};      /* the tables of entry points this format may name */
+  const int streamed = format == SCOT_PLAN_FORMAT_STREAMS || format == SCOT_PLAN_FORMAT_TRAINING_STREAMS;
+  const int adjoint = format == SCOT_PLAN_FORMAT_ADJOINT;
+  const int training = format == SCOT_PLAN_FORMAT_TRAINING || format == SCOT_PLAN_FORMAT_TRAINING_STREAMS;
+  const int enabled[SCOT_PLAN_N_LISTS] = {1, adjoint, training, streamed};      /* the tables of entry points this format may name */
   if (h[SCOT_PLAN_H_ABI] != (uint64_t)abi || h[SCOT_PLAN_H_OPERAND] != (uint64_t)operand_format) return SCOT_PLAN_ERR_UNSUPPORTED;
   if (h[SCOT_PLAN_H_BYTES] != (uint64_t)bytes) return SCOT_PLAN_ERR_SHAPE;      /* a truncated (or padded) file */
   v->base = b;
@@ -328,6 +391,14 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
   v->n_arrays = h[SCOT_PLAN_H_NARRAYS];
   v->arrays_words = h[SCOT_PLAN_H_ARRAYS_WORDS];
   v->data_bytes = h[SCOT_PLAN_H_DATA_BYTES];
+  v->n_streams = 1;
+  if (streamed) {      // the streams section: exactly two streams, a bounded number of events
+    if (!scot_plan_span_ok(h[SCOT_PLAN_H_STREAMS_OFF], SCOT_PLAN_STREAMS_WORDS * 8, bytes)) return SCOT_PLAN_ERR_SHAPE;
+    const uint64_t* st = (const uint64_t*)(b + h[SCOT_PLAN_H_STREAMS_OFF]);
+    if (st[SCOT_PLAN_ST_STREAMS] != 2 || st[SCOT_PLAN_ST_EVENTS] > SCOT_PLAN_MAX_EVENTS) return SCOT_PLAN_ERR_SHAPE;
+    v->n_streams = st[SCOT_PLAN_ST_STREAMS];
+    v->n_events = st[SCOT_PLAN_ST_EVENTS];
+  }
   const uint64_t lim = (uint64_t)1 << 32;      /* counts that cannot overflow the products below */
   if (v->n_names > lim || v->n_buffers > lim || v->n_arrays > lim || v->arrays_words > lim) return SCOT_PLAN_ERR_SHAPE;
   if (!scot_plan_span_ok(h[SCOT_PLAN_H_NAMES_OFF], v->n_names * SCOT_PLAN_NAME_BYTES, bytes) ||
@@ -391,8 +462,9 @@ static inline int scot_plan_image_validate(const void* image, size_t bytes, int 
   }
   if (w != v->arrays_words) return SCOT_PLAN_ERR_SHAPE;
   // every call list against its own table, by the same rules (an absent list has no records and no words)
+  uint8_t recorded[SCOT_PLAN_MAX_EVENTS];
   for (int c = 0; c < SCOT_PLAN_N_CALLS; ++c) {
-    const int erc = scot_plan_entries_ok(v, &v->calls[c]);
+    const int erc = scot_plan_entries_ok(v, &v->calls[c], recorded);
     if (erc != SCOT_PLAN_OK) return erc;
   }
   // io: fp32 [B, Cin, H, W] in, fp32 [B, Cout, H, W] out, each whole inside a buffer of the right kind

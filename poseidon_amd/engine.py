@@ -15,6 +15,7 @@ data-flow choices described in DESIGN.md:
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import weakref
@@ -80,6 +81,13 @@ def _selected(entry: str, ok: bool):
         raise RuntimeError(f"{entry} rejected a shape the engine selected it for")
 
 
+class _StandIn:
+    """a stream or an event of a two-stream plan export recorded on the CPU emulation: a handle and nothing behind it"""
+
+    def __init__(self, handle):
+        self.cuda_stream = self.cuda_event = handle
+
+
 class _Token:
     """Lifetime marker of one taped forward call: alive while the caller (the autograd node) can still ask for its backward."""
     __slots__ = ("__weakref__",)
@@ -121,6 +129,7 @@ class ScOTEngine:
         # (one-stream) recording then adds their share of the time gradient in the side stream's row and order, so that the sum has the
         # engine's own association and the plan's d_time its bits
         self._export_side_rows = False
+        self._standin = None        # see _cur_stream: {"cur": stand-in stream, "events": stand-in events handed out}
         self._dt_side = False
         self._taped = {}
         self._pending = []
@@ -488,7 +497,7 @@ class ScOTEngine:
         if self._in_side is not None:
             # a side-stream task that produces tensors the main chain consumes later (skip blocks): allocate from the MAIN
             # stream's pool, so the block's reuse stays ordered with the main-stream kernels that read it after the join
-            with torch.cuda.stream(self._in_side):
+            with self._on_stream(self._in_side):
                 t = torch.empty(*shape, dtype=dtype, device=self.device)
             self._task_keep.append(t)      # ... and alive until the main stream has waited for the task (wait_task)
         else:
@@ -574,6 +583,8 @@ class ScOTEngine:
             out += [(f"replica_tables:{key}", td, True), (f"replica_scales:{key}", sd, True)]
         if self._small_chunks is not None and self._small_chunks[1]:
             out.append(("small_chunks", self._small_chunks[0], True))
+            # (the per-range tables of the two-stream step, which un-scales each announced range on the side stream as it becomes final)
+            out += [(f"small_chunks:{key}", ch, True) for key, (ch, n) in sorted(self._small_by_key.items()) if n]
         if self._loss_meta is not None:
             out += [("loss_groups", self._loss_meta[1]["goc"], True), ("loss_counts", self._loss_meta[1]["counts"], True)]
         out.append(("grad_arena", self.arena.grad, False))
@@ -593,11 +604,41 @@ class ScOTEngine:
         else:
             self.tdo(lambda: dst.copy_(src))
 
-    def _event(self):
-        """a torch event whose HIP handle exists (torch creates it at the first record), alive as long as the launches that name it: for
-        good inside a recorded step, until the next forward otherwise"""
+    # Where the engine reaches torch's streams and events: the current stream, "run on this stream", a new event.  On a HIP device
+    # they are the torch calls.  On the CPU emulation, and only while plan.py records a two-stream export there (`_standin`), they hand
+    # out stand-in handles: the emulated entry points ignore stream and event arguments, so the recording holds the engine's two-stream
+    # program with the stand-ins where the handles would be.
+    def _cur_stream(self):
+        if self._standin is not None:
+            return self._standin["cur"]
+        return torch.cuda.current_stream()
+
+    @contextlib.contextmanager
+    def _on_stream(self, s):
+        st = self._standin
+        if st is None:
+            with torch.cuda.stream(s):
+                yield
+            return
+        prev, prev_handle = st["cur"], ops.stream
+        st["cur"], ops.stream = s, (lambda: s.cuda_stream)      # (what the op wrappers hand every launch)
+        try:
+            yield
+        finally:
+            st["cur"], ops.stream = prev, prev_handle
+
+    def _new_event(self):
+        """an event whose HIP handle exists (torch creates it at the first record)"""
+        if self._standin is not None:
+            self._standin["events"] += 1
+            return _StandIn(self._standin["events"])
         ev = torch.cuda.Event()
         ev.record()
+        return ev
+
+    def _event(self):
+        """a new event, alive as long as the launches that name it: for good inside a recorded step, until the next forward otherwise"""
+        ev = self._new_event()
         (self._rec_keep if self._rec is not None else self._events).append(ev)
         return ev
 
@@ -802,21 +843,23 @@ class ScOTEngine:
         self._pending.append(fn)
 
     def side_stream(self):
+        if self.side is None and self._standin is not None:
+            self.side = _StandIn(1)
         if self.side is None:
             # a stream that is MEASURED to run beside the current one (streams.py: torch's pooled streams and the runtime's hardware queues
             # are both handed out round-robin, and two that share a queue serialise silently)
             from .streams import independent_stream
-            self.side = independent_stream(self.device, [torch.cuda.current_stream(self.device)])
+            self.side = independent_stream(self.device, [self._cur_stream()])
         return self.side
 
     def _run_side(self, fns):
         self.side_stream()
-        ev, cur, side = self._event(), torch.cuda.current_stream(), self.side
+        ev, cur, side = self._event(), self._cur_stream(), self.side
         self.h_record(ev, cur)
         self.h_wait(side, ev)
         prev = ops.set_workspace_slot(1)
         try:
-            with torch.cuda.stream(side):
+            with self._on_stream(side):
                 for fn in fns:
                     fn()
         finally:
@@ -830,7 +873,7 @@ class ScOTEngine:
             return fn(), None
         self.flush_side()
         box = []
-        main = torch.cuda.current_stream()
+        main = self._cur_stream()
 
         def run():
             self._in_side = main
@@ -851,7 +894,7 @@ class ScOTEngine:
 
     def wait_task(self, ev):
         if ev is not None:
-            cur = torch.cuda.current_stream()
+            cur = self._cur_stream()
             self.h_wait(cur, ev)
             self._task_keeps.pop(ev, None)
 
@@ -874,7 +917,7 @@ class ScOTEngine:
         self.finish_partials()
         self.flush_side()
         if self.use_side and self.side is not None:
-            cur, side = torch.cuda.current_stream(), self.side
+            cur, side = self._cur_stream(), self.side
             ev = self._event()
             self.h_record(ev, side)
             self.h_wait(cur, ev)
@@ -1845,7 +1888,7 @@ class ScOTEngine:
             def announce(prefix, _cb=self.on_grads_final):
                 # the callback runs with the SIDE stream current: what it enqueues (dp.py: an event the comm stream waits for) is
                 # ordered behind the range's weight gradients and un-scale without the main chain ever waiting for them
-                with torch.cuda.stream(self.side):
+                with self._on_stream(self.side):
                     _cb(prefix)
 
             def done(prefix, _cb=self.on_grads_final):

@@ -135,6 +135,11 @@ PLAN_PROTOTYPES = {
     "scot_plan_train_status": [P, P, P],
     "scot_plan_snapshot": [P, P, Z, P],
     "scot_plan_training_entry_point": [I],
+    # two-stream plans (image formats 5 and 6): the stream probe, the side stream, and the test aid that issues a list in a given order
+    "scot_stream_overlaps": [P, P, P],
+    "scot_plan_set_side_stream": [P, P],
+    "scot_plan_describe_streams": [P, P],
+    "scot_plan_issue_order": [P, I, P, I],
 }
 _VOID = {"scot_set_use_tr", "scot_gemm_wide_config", "scot_gemm_splitk_config"}
 _SIZE = {"scot_gemm_workspace_bytes", "scot_wgrad_group_workspace_bytes", "scot_cln_bwd_workspace_bytes", "scot_wgrad_mlp_workspace_bytes",

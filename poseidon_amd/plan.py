@@ -20,6 +20,12 @@ step changes: the fp32 parameters, both 16-bit copies, both moments, the step co
 `Plan.train_step` runs one step from C (scot_plan_train_step), `Plan.snapshot` reads the state back into the image, and
 `load_training_state` brings such an image's state back into a `ScOT` and its optimizer.
 
+`export_plan(..., streams=2)` (inference and training plans) records the engine's own TWO-stream program instead — the weight-gradient
+stream left on, on the CPU emulation with stand-in handles — and writes a format-5 / format-6 image: stream arguments become stream
+indices (0 the caller's, 1 the plan's side stream), the engine's fork and join edges stay in the lists as `scot_event_record` /
+`scot_stream_wait_event` entries over event indices, and every list is closed (the exporter appends the join where the engine leaves
+the side stream unjoined).  The runtime gives such a plan a side stream and its events; every call works on it unchanged.
+
 `Plan` is the ctypes wrapper of the runtime, for the tests and for a Python process that wants inference without torch (it imports
 torch only if the caller hands it tensors).
 """
@@ -36,14 +42,19 @@ MAGIC = 0x4e414c50544f4353
 FORMAT = 1
 FORMAT_ADJOINT = 2      # + a backward entries section and the adjoint words (csrc/plan_image.h)
 FORMAT_TRAINING = 4     # + the training words, which name three step lists and the state spans (3 is unassigned)
-HEADER_WORDS, NAME_BYTES, IO_WORDS, ADJ_WORDS, TRAIN_WORDS = 32, 48, 24, 24, 64
+FORMAT_STREAMS = 5      # format 1 + the streams section: lists on two streams with event entries
+FORMAT_TRAINING_STREAMS = 6      # format 4 + the streams section
+STREAMED = {FORMAT: FORMAT_STREAMS, FORMAT_TRAINING: FORMAT_TRAINING_STREAMS}      # one-stream format -> its two-stream form
+HEADER_WORDS, NAME_BYTES, IO_WORDS, ADJ_WORDS, TRAIN_WORDS, STREAMS_WORDS = 32, 48, 24, 24, 64, 2
 CONSTANT, INPUT, OUTPUT, SCRATCH, STATE = range(5)
-ARG_INT, ARG_NULL, ARG_PTR, ARG_STREAM, ARG_ARRAY = range(5)
+ARG_INT, ARG_NULL, ARG_PTR, ARG_STREAM, ARG_ARRAY, ARG_EVENT = range(6)
+MAX_EVENTS = 4096
+RECORD, WAIT = "scot_event_record", "scot_stream_wait_event"      # (EVENT, STREAM) and (STREAM, EVENT): SCOT_PLAN_SYNC_ENTRY_POINTS
 COMPUTE_CODE = {"fp32": 0, "fp16": 1, "bf16": 2, "bf16x3": 3}
 MAX_INT, MAX_FLT = 48, 8
 (H_MAGIC, H_FORMAT, H_ABI, H_OPERAND, H_COMPUTE, H_BYTES, H_NNAMES, H_NAMES_OFF, H_NBUFFERS, H_BUFFERS_OFF, H_NENTRIES, H_ENTRIES_OFF,
  H_ENTRIES_WORDS, H_NARRAYS, H_ARRAYS_OFF, H_ARRAYS_WORDS, H_IO_OFF, H_DATA_OFF, H_DATA_BYTES, H_NBACKWARD, H_BACKWARD_OFF,
- H_BACKWARD_WORDS, H_ADJ_OFF, H_TRAIN_OFF) = range(24)
+ H_BACKWARD_WORDS, H_ADJ_OFF, H_TRAIN_OFF, H_STREAMS_OFF) = range(25)
 
 
 def _slots(*words):
@@ -60,6 +71,7 @@ assert ADJ_KEPT_BYTES < ADJ_WORDS and TR_COUNTER + 3 <= TRAIN_WORDS
 ENTRY_POINT_TABLES = {"forward": ("scot_plan_entry_point", "SCOT_PLAN_ENTRY_POINTS"),
                       "adjoint": ("scot_plan_adjoint_entry_point", "SCOT_PLAN_ADJOINT_ENTRY_POINTS"),
                       "training": ("scot_plan_training_entry_point", "SCOT_PLAN_TRAINING_ENTRY_POINTS")}
+DESCRIBE_STREAMS = ("streams", "events", "overlaps", "host_stream")
 DESCRIBE_TRAINING = ("has_training", "groups", "arena_floats", "step_calls", "labels_bytes", "kept_bytes", "dynamic_scale")
 TRAIN_STATUS = ("applied", "skipped", "grad_scale", "grad_norm", "clip_coef", "nonfinite")
 # host arrays of floats among the recorded arguments: {entry point: {argument index: index of the argument that holds the count}}
@@ -104,6 +116,7 @@ class _Registry:
 
     def __init__(self):
         self.bufs = {}      # address -> dict(addr, bytes, kind, name, tensor)
+        self.streams = None      # a two-stream recording: {stream handle: index} — the current stream 0, the engine's side stream 1
 
     def add(self, t, kind, name, stored=False):
         """stored: a STATE buffer the image holds by value (a training plan's; otherwise the runtime zeroes it at load)"""
@@ -226,11 +239,14 @@ _ENGINE_SAVED = _ENGINE_SWITCHES + ("last_hidden", "last_hidden_aliased", "_rec"
 
 
 @contextlib.contextmanager
-def _recording(eng, reg, side_rows, refresh, extra_saved=(), snapshot=None):
+def _recording(eng, reg, side_rows, refresh, extra_saved=(), snapshot=None, streams=1):
     """What every export's recording run needs around it -> (recorded calls, kept tensors), both filled by the body: the engine's build
     of the library in use, the 16-bit weight copies current (`refresh`: the transposed ones too; never part of a recording), the
     engine's switches off, `ops.workspace` registering itself, the registry and the recorder installed — and all of it put back
-    afterwards.  snapshot() is called once the copies are current and returns what to call right after the recorder has been taken out."""
+    afterwards.  snapshot() is called once the copies are current and returns what to call right after the recorder has been taken out.
+    streams=2: the weight-gradient stream stays ON (and the one-stream stand-in for its rows off): the recording is the engine's own
+    two-stream program, and reg.streams classifies its stream handles afterwards.  An engine on the CPU emulation records it over
+    stand-in handles (engine._cur_stream)."""
     from . import ops
     inner_workspace = ops.workspace
 
@@ -238,7 +254,7 @@ def _recording(eng, reg, side_rows, refresh, extra_saved=(), snapshot=None):
         w = inner_workspace(need)
         reg.add(w, SCRATCH, "workspace")
         return w
-    saved = {k: getattr(eng, k) for k in _ENGINE_SAVED + tuple(extra_saved)}
+    saved = {k: getattr(eng, k) for k in _ENGINE_SAVED + tuple(extra_saved) + (("side", "_standin") if streams == 2 else ())}
     rec, keep = [], []
     prev_lib = ops.use(eng.lib_kind)
     try:
@@ -248,12 +264,22 @@ def _recording(eng, reg, side_rows, refresh, extra_saved=(), snapshot=None):
         for k in _ENGINE_SWITCHES:
             setattr(eng, k, False)
         eng._export, eng._rec, eng._rec_keep = reg, rec, keep
-        eng._export_side_rows = side_rows
+        eng._export_side_rows = side_rows and streams != 2
+        if streams == 2:
+            from .engine import _StandIn
+            eng.use_side = True
+            if eng.device.type != "cuda":
+                eng.side, eng._standin = None, dict(cur=_StandIn(ops.stream()), events=0)
+            main = _handle(ops.stream())
         prev_rec = ops.set_recorder(rec)
         try:
             yield rec, keep
         finally:
             ops.set_recorder(prev_rec)
+            if streams == 2:
+                reg.streams = {main: 0}
+                if eng.side is not None:
+                    reg.streams.setdefault(_handle(eng.side.cuda_stream), 1)
             if put_back is not None:
                 put_back()
     finally:
@@ -262,6 +288,13 @@ def _recording(eng, reg, side_rows, refresh, extra_saved=(), snapshot=None):
         for k, v in saved.items():
             setattr(eng, k, v)
         ops.use(prev_lib)
+
+
+def _handle(v):
+    """a stream or event handle among recorded arguments -> int (0: the default stream)"""
+    if v is None:
+        return 0
+    return (v.value or 0) if isinstance(v, ctypes.c_void_p) else int(v)
 
 
 def _input_copies(reg, pv, t):
@@ -273,7 +306,7 @@ def _input_copies(reg, pv, t):
     return pv_in, t_in
 
 
-def _record(model, pv, t, adjoint=()):
+def _record(model, pv, t, adjoint=(), streams=1):
     """-> (registry, recorded calls, kept tensors, prediction tensor, input copies, adjoint record or None): ONE dedicated, linear
     recording of engine._forward — with `adjoint`, of the forward a differentiable call runs (train=True without stochastic depth,
     these input gradients, no parameter gradient) followed by engine._backward from a cotangent of the prediction alone; the adjoint
@@ -287,7 +320,7 @@ def _record(model, pv, t, adjoint=()):
     if adjoint:
         cot = torch.zeros(pv.shape[0], model.config.num_out_channels, pv.shape[2], pv.shape[3], dtype=torch.float32, device=pv.device)
         reg.add(cot, INPUT, "d_prediction")
-    with _recording(eng, reg, bool(eng.use_side and not eng.stage_timing), bool(adjoint)) as (rec, keep):
+    with _recording(eng, reg, bool(eng.use_side and not eng.stage_timing), bool(adjoint), streams=streams) as (rec, keep):
         if adjoint:      # forced for the export, whatever the caller's tensors require
             eng._fwd_flags = (adjoint, False)
             _, pred, tape = eng._forward(pv_in, t_in, None, None, True)
@@ -314,11 +347,13 @@ def _training_state(model, opt):
     return ts
 
 
-def _record_training(model, opt, pv, t, labels):
+def _record_training(model, opt, pv, t, labels, streams=1):
     """-> (registry, recorded calls, kept tensors, inference prediction, input copies, training record): ONE linear recording of four
     lists on one stream — the inference forward; the step's forward through the loss; the fill of the accumulated gradients, the
     backward from d loss = 1 with the store-form weight gradients and the un-scale passes; what FusedAdamW.step issues.  The recording
-    run IS a step on the model's own tensors, so everything it changes is saved before and put back afterwards."""
+    run IS a step on the model's own tensors, so everything it changes is saved before and put back afterwards.
+    streams=2: the engine's two-stream step; the fill is the side stream's first task of the step backward, and the main stream waits for
+    it before the backward's first entry."""
     import torch
     from . import ops
     eng = model._engine
@@ -348,7 +383,7 @@ def _record_training(model, opt, pv, t, labels):
             if eng.shadow is not None:      # (put back with the master weights: current again)
                 eng._shadow_v = eng._shadow_t_v = model._weights_version()
         return put_back
-    with _recording(eng, reg, False, True, extra_saved=("grad_fill_event",), snapshot=snapshot) as (rec, keep):
+    with _recording(eng, reg, False, True, extra_saved=("grad_fill_event",), snapshot=snapshot, streams=streams) as (rec, keep):
         eng.grad_fill_event = None
         eng._fwd_flags = ((), True)
         _, pred, _ = eng._forward(pv_in, t_in, None, None, False)
@@ -357,10 +392,14 @@ def _record_training(model, opt, pv, t, labels):
         n_fwd = len(rec)
         _register(reg, eng.plan_buffers(train=opt), only_new=True)
         lazy = eng._small_chunks is not None      # ScOT.zero_grad(overlap=True): only what is accumulated into is filled
-        if lazy:
-            eng.fill_small_grads()
-        else:
-            ops.memset_async(eng.arena.grad, 0)
+
+        def fill():
+            if lazy:
+                eng.fill_small_grads()
+            else:
+                ops.memset_async(eng.arena.grad, 0)
+        _, filled = eng.fork_task(fill) if streams == 2 else (fill(), None)
+        eng.wait_task(filled)      # (both streams write gradients: the fill is in front of the first writer on either)
         eng.grads_are_zero, eng.lazy_grads = True, lazy
         eng._backward(tape, one, None)
         eng.grads_are_zero = eng.lazy_grads = False
@@ -451,16 +490,59 @@ def _float_bits(x):
     return struct.unpack("<I", struct.pack("<f", float(x)))[0]
 
 
-def _encode_calls(rec, lists, loc, own, peer, host_floats):
+def _sync_pairs(name, args, streams, events):
+    """the argument pairs of a recorded scot_event_record (EVENT, STREAM) / scot_stream_wait_event (STREAM, EVENT); events get their
+    indices in order of first appearance"""
+    ev, st = (args[0], args[1]) if name == RECORD else (args[1], args[0])
+    if _handle(st) not in streams:
+        raise PlanExportError(f"export_plan: {name} names stream 0x{_handle(st):x}, which is neither the current stream nor the engine's "
+                              "side stream: a plan has two streams")
+    pair = {"e": (ARG_EVENT, events.setdefault(_handle(ev), len(events))), "s": (ARG_STREAM, streams[_handle(st)])}
+    return [pair["e"], pair["s"]] if name == RECORD else [pair["s"], pair["e"]]
+
+
+def _side_open(entries, names):
+    """the closed-list rule of csrc/plan_image.h over encoded entries -> whether the list leaves stream 1 unjoined (the first two
+    rules — a wait pairs with an earlier record of the list, stream 1 starts behind a record of stream 0 — raise)"""
+    recorded, side, join_event = {}, 0, None
+    for name, _, ints, _ in entries:
+        on = max([v for tag, v in ints if tag == ARG_STREAM], default=0)
+        ev = next((v for tag, v in ints if tag == ARG_EVENT), None)
+        kind = names[name] if names[name] in (RECORD, WAIT) else None
+        if kind == WAIT and ev not in recorded:
+            raise PlanExportError("export_plan: a recorded stream wait pairs with no earlier event record of its own list")
+        if on:
+            if not side and not (kind == WAIT and recorded[ev] == 0):
+                raise PlanExportError("export_plan: the side stream's first entry of a list is not ordered behind the main stream")
+            side, join_event = 1, (ev if kind == RECORD else None)
+        elif kind == WAIT and ev == join_event and recorded[ev] == 1:
+            side = 2
+        if kind == RECORD:
+            recorded[ev] = on
+    return side == 1
+
+
+def _encode_calls(rec, lists, loc, own, peer, host_floats, streams=None):
     """(a) the recorded calls -> the entries of the list each falls into.  -> (names, host arrays, lr patch point or None: (entry,
-    argument, groups) of the scot_adamw_step call).  host_floats: classify HOST_FLOAT_ARRAYS (a training recording)"""
-    names, name_index, arrays, lr_point = [], {}, [], None
+    argument, groups) of the scot_adamw_step call, number of events).  host_floats: classify HOST_FLOAT_ARRAYS (a training recording).
+    streams ({handle: index}, a two-stream recording): stream arguments become their index, the record / wait entries stay in the
+    lists over event indices, and a list the engine leaves with the side stream unjoined gets the join appended"""
+    names, name_index, arrays, lr_point, events = [], {}, [], None, {}
+
+    def name_of(name):
+        if name not in name_index:
+            name_index[name] = len(names)
+            names.append(name)
+        return name_index[name]
     for pos, (fn, args) in enumerate(rec):
         lst = next(x for x in lists if pos < x.end)
         if args is None:
             label = getattr(fn, "__qualname__", None) or getattr(fn, "__name__", None) or repr(fn)
             raise PlanExportError(f"export_plan: the recorded {lst.what} holds a host-side Python step ({label}); a plan is C-ABI calls only")
         name = fn.__name__
+        if streams is not None and name in (RECORD, WAIT):
+            lst.entries.append((name_of(name), 0, _sync_pairs(name, args, streams, events), []))
+            continue
         if name not in lst.listed:
             raise PlanExportError(f"export_plan: the {lst.what} calls {name}, which the plan runtime of this library does not list "
                                   f"(csrc/plan_image.h, {lst.macro})")
@@ -490,7 +572,11 @@ def _encode_calls(rec, lists, loc, own, peer, host_floats):
                 ints.append((ARG_ARRAY, len(arrays)))
                 arrays.append((2, [(ARG_INT, _float_bits(x)) for x in values]))
             elif ty is ctypes.c_void_p and k == last:
-                ints.append((ARG_STREAM, 0))      # one stream per entry point, last: the caller's at run time
+                if streams is not None and _handle(a) not in streams:
+                    raise PlanExportError(f"export_plan: {name} was issued on stream 0x{_handle(a):x}, which is neither the current "
+                                          "stream nor the engine's side stream: a plan has two streams")
+                # one stream per entry point, last: the caller's at run time (a two-stream plan: 1 = its side stream)
+                ints.append((ARG_STREAM, 0 if streams is None else streams[_handle(a)]))
             elif isinstance(a, ctypes.Array):
                 elem = a._type_
                 if elem is ctypes.c_int:
@@ -514,11 +600,16 @@ def _encode_calls(rec, lists, loc, own, peer, host_floats):
                 raise PlanExportError(f"export_plan: {what} = {a!r} has no place in a plan image")
         if len(ints) > MAX_INT or len(flts) > MAX_FLT:
             raise PlanExportError(f"export_plan: {name} does not fit the replay's calling convention")
-        if name not in name_index:
-            name_index[name] = len(names)
-            names.append(name)
-        lst.entries.append((name_index[name], which, ints, flts))
-    return names, arrays, lr_point
+        lst.entries.append((name_of(name), which, ints, flts))
+    for lst in lists if streams is not None else ():
+        if _side_open(lst.entries, names):      # the engine joins its side stream where the NEXT list needs it: a list is closed
+            ev = len(events)
+            events[("join", lst.what)] = ev
+            lst.entries.append((name_of(RECORD), 0, [(ARG_EVENT, ev), (ARG_STREAM, 1)], []))
+            lst.entries.append((name_of(WAIT), 0, [(ARG_STREAM, 0), (ARG_EVENT, ev)], []))
+    if len(events) > MAX_EVENTS:
+        raise PlanExportError(f"export_plan: the recording holds {len(events)} events, an image at most {MAX_EVENTS}")
+    return names, arrays, lr_point, len(events)
 
 
 def _adjoint_words(eng, loc, adj, forward, backward):
@@ -579,7 +670,7 @@ def _layout(sections):
     return offs, cur + (-cur % 64)
 
 
-def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=None):
+def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=None, streams=1):
     """recorded calls + registered buffers -> the bytes of a plan image (adj: the adjoint record of _record -> a format-2 image; train:
     the training record of _record_training -> a format-4 image)"""
     eng = model._engine
@@ -593,7 +684,8 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=N
     else:
         lists = [_CallList("forward", "forward", len(rec), own)]
     forward, others = lists[0], lists[1:]
-    names, arrays, lr_point = _encode_calls(rec, lists, loc, own, peer, host_floats=train is not None)
+    names, arrays, lr_point, n_events = _encode_calls(rec, lists, loc, own, peer, host_floats=train is not None,
+                                                      streams=reg.streams if streams == 2 else None)
 
     io = [0] * IO_WORDS
     io[0:5] = [*pv_in.shape, pred.shape[1]]      # B, Cin, H, W, Cout
@@ -632,6 +724,8 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=N
         sections["adjoint"] = words(adj_words)
     if train is not None:
         sections["training"] = bytes(TRAIN_WORDS * 8)      # (names the step lists' offsets: filled in once they are known)
+    if streams == 2:
+        sections["streams"] = words([2, n_events])
     offs, data_off = _layout(sections)
 
     def named(x):      # how a header or the training words name a list: (count, offset, words)
@@ -653,6 +747,8 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=N
         for slot, x in zip((TR_FWD, TR_BWD, TR_UPD), others):
             tr_words[slot:slot + 3] = named(x)
         sections["training"] = words(tr_words)
+    if streams == 2:
+        h[H_FORMAT], h[H_STREAMS_OFF] = STREAMED[h[H_FORMAT]], offs["streams"]
     out = bytearray(words(h))
     for name, sct in sections.items():
         assert len(out) == offs[name]
@@ -664,14 +760,21 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=N
     return bytes(out)
 
 
-def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labels=None, *, adjoint=(), train=None):
+def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labels=None, *, adjoint=(), train=None, streams=1):
     """Record `model`'s inference forward for exactly these input shapes and write it as a plan image to `path` (None: only return it).
     Returns the image's bytes.  The weights are a snapshot; see the module docstring and DESIGN.md §3 for what a plan does not cover.
     adjoint: () or some of ("pixel_values", "time") — the image (format 2) then also holds the frozen-model backward from a cotangent of
     the prediction to these inputs' gradients (scot_plan_vjp), and its forward is the one a differentiable call runs.
     train: a FusedAdamW over this model, with labels — the image (format 4) then also holds one optimizer step and the training state by
-    value (scot_plan_train_step, scot_plan_snapshot); the model and the optimizer are left as they were."""
+    value (scot_plan_train_step, scot_plan_snapshot); the model and the optimizer are left as they were.
+    streams: 1, or 2 — the image (format 5, with train= format 6) then holds the engine's two-stream program, and the runtime runs the
+    bias tables, the skip blocks and the weight gradients on a side stream of its own beside the main chain.  Not with adjoint=."""
     import torch
+    if streams not in (1, 2):
+        raise PlanExportError(f"export_plan: streams={streams!r}: a plan runs on 1 stream or on 2 (the caller's and one side stream)")
+    if streams == 2 and adjoint:
+        raise PlanExportError("export_plan: adjoint= together with streams=2: an adjoint plan runs on one stream (the frozen backward has "
+                              "no weight-gradient stream to put beside the main chain)")
     _check_request(model, pixel_values, time, pixel_mask, labels, train)
     dev = pixel_values.device
     if train is not None:
@@ -691,9 +794,9 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
     bind(own)
     with torch.no_grad():
         if train is not None:
-            image = _export_training(model, train, pv, t, labels.detach().to(device=dev, dtype=torch.float32).contiguous(), own, peer)
+            image = _export_training(model, train, pv, t, labels.detach().to(device=dev, dtype=torch.float32).contiguous(), own, peer, streams)
         else:
-            image = _export_frozen(model, pv, t, adjoint, own, peer)
+            image = _export_frozen(model, pv, t, adjoint, own, peer, streams)
     if path is not None:
         with open(path, "wb") as f:
             f.write(image)
@@ -712,7 +815,7 @@ def _self_check(image, own, peer):
         plan.free()
 
 
-def _export_frozen(model, pv, t, adjoint, own, peer):
+def _export_frozen(model, pv, t, adjoint, own, peer, streams=1):
     """record, build, and check through the runtime: the model's own prediction bits and, with `adjoint`, the engine's own gradients"""
     import torch
     eng, dev = model._engine, pv.device
@@ -731,8 +834,8 @@ def _export_frozen(model, pv, t, adjoint, own, peer):
             p.grad = None
     else:
         _, ref, _ = eng.forward(pv, t, None, None, train=False, stochastic=False)      # the model's own prediction
-    reg, rec, keep, pred, pv_in, t_in, adj = _record(model, pv, t, adjoint)
-    image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj)
+    reg, rec, keep, pred, pv_in, t_in, adj = _record(model, pv, t, adjoint, streams)
+    image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj, streams=streams)
     with _self_check(image, own, peer) as plan:
         got = plan.run(pv, t)
         if dev.type == "cuda":
@@ -762,7 +865,7 @@ def _export_frozen(model, pv, t, adjoint, own, peer):
     return image
 
 
-def _export_training(model, opt, pv, t, lab, own, peer):
+def _export_training(model, opt, pv, t, lab, own, peer, streams=1):
     """record, build, and check through the runtime: scratch poisoned, one scot_plan_loss and one scot_plan_train_step on the export
     inputs — the engine's own prediction bits, a finite loss, finite parameters.  The image that is returned holds the pre-step state."""
     import torch
@@ -770,8 +873,8 @@ def _export_training(model, opt, pv, t, lab, own, peer):
     _, ref, tape = eng.forward(pv, t, lab, None, train=True, stochastic=False, param_grads=True)      # the engine's own prediction
     ref = ref.clone()
     del tape
-    reg, rec, keep, pred, pv_in, t_in, tr = _record_training(model, opt, pv, t, lab)
-    image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer, train=tr)
+    reg, rec, keep, pred, pv_in, t_in, tr = _record_training(model, opt, pv, t, lab, streams)
+    image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer, train=tr, streams=streams)
     del keep
     with _self_check(image, own, peer) as plan:
         loss, got = plan.loss(pv, t, lab)
@@ -801,7 +904,7 @@ _STATE_SPANS = (("arena", TR_ARENA, "float32"), ("exp_avg", TR_EXP_AVG, "float32
 def training_words(image):
     """the training words of a format-4 image (a tuple of TRAIN_WORDS ints)"""
     h = Plan.header(image)
-    if h[H_FORMAT] != FORMAT_TRAINING:
+    if h[H_FORMAT] not in (FORMAT_TRAINING, FORMAT_TRAINING_STREAMS):
         raise _lib.ScotLibraryError(f"not a training image: format {h[H_FORMAT]}")
     return struct.unpack_from(f"<{TRAIN_WORDS}Q", image, h[H_TRAIN_OFF])
 
@@ -909,8 +1012,9 @@ class Plan:
         return h
 
     @classmethod
-    def load(cls, source, lib=None, peer=None, stream=None):
-        """source: a path or the image's bytes.  lib: the build to load into (default: the one the image's operand format names)."""
+    def load(cls, source, lib=None, peer=None, stream=None, side_stream=None):
+        """source: a path or the image's bytes.  lib: the build to load into (default: the one the image's operand format names).
+        side_stream: a raw stream handle of the caller's for a two-stream plan, instead of the one the load picks."""
         image = source if isinstance(source, (bytes, bytearray)) else open(source, "rb").read()
         if lib is None:
             kind = {0: "bf16", 1: "f16"}.get(cls.header(image)[H_OPERAND])
@@ -926,7 +1030,24 @@ class Plan:
         rc = load_raw(lib, image, handle, stream)
         if rc != 0:
             raise _lib.ScotLibraryError(f"scot_plan_load refused the image: status {rc} ({_lib._ERR.get(rc, rc)})")
-        return cls(lib, handle)
+        plan = cls(lib, handle)
+        if side_stream is not None:
+            plan._call("scot_plan_set_side_stream", side_stream)
+        return plan
+
+    def describe_streams(self):
+        """-> {streams, events, overlaps: the side stream was measured to run beside the load's stream, host_stream: it is the caller's}"""
+        out = (ctypes.c_longlong * 4)()
+        self._call("scot_plan_describe_streams", out)
+        return dict(zip(DESCRIBE_STREAMS, [int(x) for x in out]))
+
+    def issue_order(self, which, order):
+        """test aid (scot_plan_issue_order): later calls issue call list `which` (0 forward, 2 / 3 / 4 the step lists) entry by entry in
+        `order`, both streams synchronised at every stream switch; None restores the normal replay.  Legality is the caller's."""
+        if order is None:
+            return self._call("scot_plan_issue_order", int(which), None, 0)
+        arr = (ctypes.c_int * max(1, len(order)))(*[int(x) for x in order])
+        self._call("scot_plan_issue_order", int(which), ctypes.cast(arr, ctypes.c_void_p), len(order))
 
     def _call(self, name, *args):
         """the runtime's `name`(this plan, ...), its status checked"""

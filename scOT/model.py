@@ -540,16 +540,18 @@ class ScOT(nn.Module):
         return ScOTOutput(loss=loss, output=pred, hidden_states=hs, attentions=(dec_at + enc_at) if want_attn else None,
                           reshaped_hidden_states=rhs)
 
-    def export_plan(self, pixel_values, time=None, pixel_mask=None, path=None, labels=None, *, adjoint=(), train=None):
+    def export_plan(self, pixel_values, time=None, pixel_mask=None, path=None, labels=None, *, adjoint=(), train=None, streams=1):
         """Write this model's inference forward for exactly these input shapes as a plan image: a file that `scot_plan_load` /
         `scot_plan_run` (include/scot_plan.h) run from C without Python, bit-identical to `self(...)`.  adjoint=("pixel_values", "time")
         (or one of them): the image also holds the frozen model's backward, and `scot_plan_vjp` returns these inputs' gradients for a
         cotangent of the prediction, bit-identical to `torch.autograd.grad` through `self(...)`.  train=optimizer (a `FusedAdamW` over
         this model) with labels=: a TRAINING image — it also holds one optimizer step and the training state by value, and
-        `scot_plan_train_step` fine-tunes the model from C; `poseidon_amd.plan.load_training_state` brings the result back.  See
-        poseidon_amd/plan.py."""
+        `scot_plan_train_step` fine-tunes the model from C; `poseidon_amd.plan.load_training_state` brings the result back.  streams=2
+        (not with adjoint=): a TWO-STREAM image — the engine's own two-stream program, run by the plan runtime on the caller's stream
+        and a side stream of its own.  See poseidon_amd/plan.py."""
         from poseidon_amd.plan import export_plan
-        return export_plan(self, pixel_values, time=time, pixel_mask=pixel_mask, path=path, labels=labels, adjoint=adjoint, train=train)
+        return export_plan(self, pixel_values, time=time, pixel_mask=pixel_mask, path=path, labels=labels, adjoint=adjoint, train=train,
+                           streams=streams)
 
     def _forward_resized(self, pv, t, lab, pixel_mask, in_size, want_grad):
         cfg = self.config

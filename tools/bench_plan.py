@@ -2,8 +2,11 @@
 inference forward: two streams, replayed from C behind a Python call) — Poseidon-B, fp16, batch 64 and batch 1, 20 timed calls after 5
 warm-up calls.
 
-usage: python tools/bench_plan.py [--batches 64,1] [--taped-only] [--root CHECKOUT]
+usage: python tools/bench_plan.py [--batches 64,1] [--taped-only] [--root CHECKOUT] [--streams 1,2] [--repeat N]
   --taped-only   only the taped forward (what a checkout without the plan runtime can run)
+  --streams      the plans to time: 1 = the one-stream plan (the default), 2 = the two-stream plan (`export_plan(..., streams=2)`: `plan2_ms`,
+                 with the `describe_streams` overlap flag of its side stream); "1,2" times both in one process
+  --repeat       time every case N times, the cases alternating (taped, plan, plan2, taped, ...): the values become lists
   --root         import the package from another checkout (the parent commit, built there) to time ITS taped forward in the same visit
 Prints one JSON line per batch size.  Numbers: profiles/plan/README.md."""
 import argparse
@@ -18,6 +21,8 @@ ap.add_argument("--taped-only", action="store_true")
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--calls", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=5)
+ap.add_argument("--streams", default="1")
+ap.add_argument("--repeat", type=int, default=1)
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
 
@@ -44,21 +49,34 @@ for B in [int(b) for b in args.batches.split(",")]:
     pv, t = torch.randn(B, 4, 128, 128, device="cuda"), torch.rand(B, device="cuda")
     res = dict(model="Poseidon-B", compute="fp16", batch=B, calls=args.calls, warmup=args.warmup, root=os.path.abspath(args.root))
     with torch.no_grad():
-        res["taped_ms"] = round(timed(lambda: model(pixel_values=pv, time=t)), 3)
+        plans = {}
         if not args.taped_only:
             from poseidon_amd.plan import Plan
-            t0 = time.perf_counter()
-            image = model.export_plan(pv, time=t)
-            res["export_s"] = round(time.perf_counter() - t0, 2)
-            res["image_MB"] = round(len(image) / 1e6, 1)
-            plan = Plan.load(image)
-            del image
-            out = torch.empty(B, 4, 128, 128, device="cuda")
-            stream = torch.cuda.current_stream().cuda_stream
-            res["plan_ms"] = round(timed(lambda: plan.run(pv, t, out=out, stream=stream)), 3)
-            res["plan_device_MB"] = round(plan.info["device_bytes"] / 1e6, 1)
-            res["calls_per_run"] = plan.info["calls"]
-            res["identical"] = bool(torch.equal(out, model(pixel_values=pv, time=t).output))
+            for n in [int(x) for x in args.streams.split(",")]:
+                key = "plan" if n == 1 else f"plan{n}"
+                t0 = time.perf_counter()
+                image = model.export_plan(pv, time=t, **({} if n == 1 else dict(streams=n)))
+                res[f"{key}_export_s"] = round(time.perf_counter() - t0, 2)
+                res[f"{key}_image_MB"] = round(len(image) / 1e6, 1)
+                plans[key] = Plan.load(image)
+                del image
+                if n > 1:
+                    res[f"{key}_streams"] = plans[key].describe_streams()
+        out = torch.empty(B, 4, 128, 128, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+        cases = {"taped": lambda: model(pixel_values=pv, time=t)}
+        cases.update({key: (lambda plan=plan: plan.run(pv, t, out=out, stream=stream)) for key, plan in plans.items()})
+        times = {key: [] for key in cases}
+        for _ in range(max(1, args.repeat)):
+            for key, fn in cases.items():
+                times[key].append(round(timed(fn), 3))
+        res.update({f"{key}_ms": v[0] if args.repeat <= 1 else v for key, v in times.items()})
+        ref = model(pixel_values=pv, time=t).output
+        for key, plan in plans.items():
+            plan.run(pv, t, out=out, stream=stream)
+            res.update({f"{key}_device_MB": round(plan.info["device_bytes"] / 1e6, 1), f"{key}_calls_per_run": plan.info["calls"],
+                        f"{key}_identical": bool(torch.equal(out, ref))})
             plan.free()
+        res["GPU_MAX_HW_QUEUES"] = os.environ.get("GPU_MAX_HW_QUEUES")
     model._engine.reset_tapes()
     print(json.dumps(res), flush=True)
