@@ -1,5 +1,5 @@
-/* scot_plan.h — running AND fine-tuning a trained ScOT model from C: exported inference plans, their adjoints, training plans, on one
- * stream or two (ABI 8).
+/* scot_plan.h — running, EVALUATING and fine-tuning a trained ScOT model from C: exported inference plans, their adjoints, training
+ * plans, on one stream or two, and the error sums of a prediction or a whole rollout (ABI 8).
  *
  * scot_hip.h is the kernel-level boundary: about a hundred entry points that a host program has to order itself.  This header is the
  * model-level one.  `ScOT.export_plan` (poseidon_amd/plan.py) records one inference forward for one input signature and writes it,
@@ -41,6 +41,16 @@
  * Measured on Poseidon-B fp16 with the overlap flag at 1 (profiles/plan_streams/README.md): a training step takes 19.3 ms at batch 64 and
  * 10.5 at batch 1, the Python loop's 19.3 / 10.6, against 22.6 / 11.0 on one stream; inference 6.11 against 6.15 ms at batch 64 — but
  * 3.95 against 3.62 ms at batch 1: for launch-bound inference the event edges cost more than the side stream hides, keep streams=1 there.
+ *
+ * EVALUATION (every plan; section "evaluation" below).  scot_error_sums is one kernel pair that reduces (prediction, target) to four fp64
+ * sums per sample and channel group, and scot_plan_evaluate runs a forward or a whole rollout and leaves ONLY those sums behind: no
+ * `steps`-sized prediction buffer, nothing copied to the host.  The sums are what the reference's metrics are made of (its
+ * scOT/metrics.py and the compute_metrics of scOT/inference.py): per channel group [slices[g], slices[g+1]) and sample,
+ *   S1 = sum |p - t|, N1 = sum |t|, S2 = sum (p - t)^2, N2 = sum t^2        (in this order: sums[..][0..3])
+ * and a host turns them into the reference's numbers with a few flops per sample:
+ *   lp_error (p = 1, 2)          = Sp^(1/p)
+ *   relative_lp_error            = (Sp / Np)^(1/p) * 100 (percent), with Np == 0 replaced by 1e-10
+ *   median / mean / std / min / max over the samples (and the means over groups) are the host's job.
  *
  * Status codes as in scot_hip.h: 0, -1 (malformed image / bad argument), -3 (not for this library: ABI, operand format, entry point;
  * or a host other than x86-64 System V, where the replay underneath does not exist), -4 (allocation, copy or launch failed).
@@ -179,6 +189,39 @@ int scot_plan_describe_streams(scot_plan_t plan, long long* out);
  * whenever the stream of the next entry differs from the previous one's and at the end: the device executes exactly that order.
  * order = NULL restores the normal replay.  The call does NOT judge whether the order is legal. */
 int scot_plan_issue_order(scot_plan_t plan, int list, const int* order, int n);
+
+/* ---- evaluation ---- */
+/* Bytes of workspace (device memory) scot_error_sums needs for these arguments; 0 where it would refuse them. */
+size_t scot_error_sums_workspace_bytes(int B, int C, int HW, const int* channel_slices, int groups);
+/* sums [B][groups][4] (double, device) <- { sum |p - t|, sum |t|, sum (p - t)^2, sum t^2 } over the channels [channel_slices[g],
+ * channel_slices[g+1]) and all HW pixels of sample b, of pred and target: fp32 [B, C, HW], contiguous, device memory.  channel_slices is
+ * HOST memory: groups + 1 strictly ascending ints in [0, C] (the reference's channel_slice_list), read before the call returns; NULL with
+ * groups == 1 is the one group [0, C).  Channels outside every group are not read.  Every term and every sum is fp64 (both values are
+ * converted first, then subtracted).  The result is bitwise the same from launch to launch, on any device and at any alignment of the
+ * operands: no atomics; each (sample, group) is one contiguous run of floats, cut into chunks of a compile-time constant length, one
+ * workgroup per chunk, and a second launch adds a run's partials in chunk order.  Inf and NaN go through: a non-finite input makes exactly
+ * the sums it enters non-finite.  workspace: 8-byte aligned device memory of at least the bytes the query above names; its contents on
+ * entry do not matter.  Two launches on `stream`, asynchronous.  -1: a NULL pointer, B, C or HW < 1, groups outside 1..32, slices not
+ * strictly ascending or outside [0, C], workspace too small (nothing is launched, sums is untouched); -4: a launch failed. */
+int scot_error_sums(const float* pred, const float* target, int B, int C, int HW, const int* channel_slices, int groups, double* sums,
+                    void* workspace, size_t workspace_bytes, scot_stream_t stream);
+/* A forward or a whole rollout that leaves only error sums behind.  channel_slices / groups as above, over the plan's Cout output channels.
+ *   steps == 1: exactly the forward of scot_plan_run (time as given, NULL exactly when the plan has no time input); targets [B, Cout, H, W],
+ *               sums [B][groups][4].
+ *   steps  > 1: exactly the chain of scot_plan_rollout (time / steps with that call's rounding, prediction k copied back over the first Cout
+ *               input channels); targets [steps][B, Cout, H, W], sums [steps][B][groups][4].
+ * Step k's sums are formed from the plan's own output buffer right after forward k, on `stream` (a two-stream plan: after the list has
+ * joined), before that buffer is copied back.  predictions may be NULL: then no prediction leaves the plan and the caller needs no
+ * `steps`-sized buffer; if given it receives exactly what scot_plan_rollout (steps == 1: scot_plan_run) writes.  Every image format: on a
+ * training plan it replays the inference list at the CURRENT weights (validation between training steps; no state changes); on an adjoint
+ * plan it leaves nothing to differentiate, like a rollout: a vjp right after it returns -1.  The kernel's workspace is allocated at the
+ * first evaluate call, held until the plan is freed and counted in the described device bytes (-4 if that fails).  Reads `time` on the
+ * host once when steps > 1 (waits for `stream` there); everything after that is asynchronous on `stream`.
+ * Refused before anything is copied or launched: a NULL pixel_values, targets or sums, steps < 1, groups outside 1..32, slices not strictly
+ * ascending or beyond Cout, steps > 1 with Cout > Cin, a time that is NULL where the plan takes one (or given where it takes none): -1;
+ * steps > 1 on a plan without a time input, a plan with a pixel_mask input: -3. */
+int scot_plan_evaluate(scot_plan_t plan, const float* pixel_values, const float* time, const float* targets, int steps,
+                       const int* channel_slices, int groups, double* sums, float* predictions, scot_stream_t stream);
 
 /* Refused before anything is copied or launched: scot_plan_loss / _train_step / _train_status / _snapshot on a format-1/2 plan: -3
  * (as scot_plan_vjp / scot_plan_rollout_vjp on a training plan); a NULL pixel_values, labels or lr, a NULL loss of scot_plan_loss, a NULL

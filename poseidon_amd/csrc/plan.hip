@@ -30,6 +30,10 @@
 // program's stream slots.  Every list of such an image is closed (plan_image.h), so the copies in and out stay on the caller's stream
 // and every call above works unchanged.  scot_plan_issue_order is a test aid: it issues a list entry by entry in a given order.
 //
+// EVALUATION (every image): scot_plan_evaluate is scot_plan_run's forward or scot_plan_rollout's chain with scot_error_sums
+// (error_sums.hip) behind every forward: it reads the plan's own output buffer against the caller's targets and leaves per-sample,
+// per-channel-group error sums; the predictions need not leave the plan.  Its workspace is allocated at the first such call.
+//
 // A plan is one stream's worth of state: its buffers are reused by every run, so runs of ONE plan must be ordered (same stream, or
 // the caller's own events); two plans are independent.
 #include "common.h"
@@ -45,6 +49,9 @@
 extern "C" int scot_tape_replay(const uint64_t* prog, size_t n_words, int* fail_entry);
 extern "C" int scot_abi_version();
 extern "C" int scot_operand_format();
+extern "C" size_t scot_error_sums_workspace_bytes(int B, int C, int HW, const int* channel_slices, int groups);
+extern "C" int scot_error_sums(const float* pred, const float* target, int B, int C, int HW, const int* channel_slices, int groups, double* sums,
+                               void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 // the listed entry points, by address: g_entry_address[table][index], rows in the order of scot_plan_lists[table].names (the training
 // table is the longest: it repeats the forward's)
@@ -280,6 +287,8 @@ struct Plan {
   int last_exponent = 0;                           // log2 S of the last vjp
   float* holder = nullptr;                         // scot_plan_rollout_vjp without a d_pixel_values of the caller's: the carry's [B, Cin, H, W]
   size_t holder_bytes = 0;
+  void* eval_ws = nullptr;                         // scot_plan_evaluate: the workspace of scot_error_sums, for any slices over Cout channels
+  size_t eval_ws_bytes = 0;
 };
 
 inline Plan* as_plan(void* p) {
@@ -431,6 +440,7 @@ extern "C" int scot_plan_free(void* plan) {
   if (!pl) return plan ? SCOT_ERR_SHAPE : SCOT_OK;
   if (pl->slab) dev_free(pl->slab);
   if (pl->holder) dev_free(pl->holder);
+  if (pl->eval_ws) dev_free(pl->eval_ws);
   for (dev_event_t e : pl->events) dev_event_destroy(e);
   if (pl->side_own) dev_stream_destroy(pl->side);
   pl->magic = 0;
@@ -574,7 +584,7 @@ extern "C" int scot_plan_describe(void* plan, long long* out) {
                            (long long)io[SCOT_PLAN_IO_W], (long long)io[SCOT_PLAN_IO_COUT], (long long)io[SCOT_PLAN_IO_HAS_TIME],
                            (long long)(io[SCOT_PLAN_IO_HAS_TIME] ? io[SCOT_PLAN_IO_TIME_BYTES] : 0), (long long)io[SCOT_PLAN_IO_HAS_MASK],
                            (long long)(io[SCOT_PLAN_IO_HAS_MASK] ? io[SCOT_PLAN_IO_MASK_BYTES] : 0), pl->operand_format, pl->compute,
-                           (long long)(pl->slab_bytes + pl->holder_bytes), (long long)pl->list[SCOT_PLAN_CALLS_FORWARD].calls, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
+                           (long long)(pl->slab_bytes + pl->holder_bytes + pl->eval_ws_bytes), (long long)pl->list[SCOT_PLAN_CALLS_FORWARD].calls, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
                            (long long)(hw * io[SCOT_PLAN_IO_COUT]), (long long)pl->header[SCOT_PLAN_H_FORMAT]};
   memcpy(out, d, sizeof(d));
   return SCOT_OK;
@@ -747,6 +757,58 @@ extern "C" int scot_plan_rollout(void* plan, const float* pixel_values, const fl
     rc = replay(pl, SCOT_PLAN_CALLS_FORWARD, stream);
     if (rc != SCOT_OK) return rc;
     if (!dev_copy((char*)predictions + (size_t)k * B * out_row, out, B * out_row, D2D, stream)) return SCOT_ERR_LAUNCH;
+    if (k + 1 < steps && !dev_copy2d(in, in_row, out, out_row, out_row, B, stream)) return SCOT_ERR_LAUNCH;
+  }
+  // (host_time is pageable memory: the runtime has staged it by the time the copy call returned)
+  return SCOT_OK;
+}
+
+// A forward (steps == 1: scot_plan_run's) or a whole rollout (steps > 1: scot_plan_rollout's chain) that leaves only error sums behind
+// (include/scot_plan.h): after forward k, scot_error_sums reduces the plan's own output buffer against targets[k] into sums[k] on
+// `stream` — behind the list's join on a two-stream plan, before the buffer is copied back.  predictions may be NULL: no prediction
+// leaves the plan.  Every refusal, the workspace's allocation included, comes before the first copy.
+extern "C" int scot_plan_evaluate(void* plan, const float* pixel_values, const float* time, const float* targets, int steps,
+                                  const int* channel_slices, int groups, double* sums, float* predictions, hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  const uint64_t* io = pl->io;
+  if (!pixel_values || !targets || !sums || steps < 1) return SCOT_ERR_SHAPE;
+  const int B = (int)io[SCOT_PLAN_IO_B], cout = (int)io[SCOT_PLAN_IO_COUT], HW = (int)(io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W]);
+  // (groups outside 1..32, slices not strictly ascending or beyond Cout: the kernel's own rule, asked of its workspace query)
+  if (scot_error_sums_workspace_bytes(B, cout, HW, channel_slices, groups) == 0) return SCOT_ERR_SHAPE;
+  if (io[SCOT_PLAN_IO_HAS_MASK]) return SCOT_ERR_UNSUPPORTED;
+  if (steps > 1) {
+    if (io[SCOT_PLAN_IO_COUT] > io[SCOT_PLAN_IO_CIN]) return SCOT_ERR_SHAPE;
+    if (!io[SCOT_PLAN_IO_HAS_TIME]) return SCOT_ERR_UNSUPPORTED;
+  }
+  if ((io[SCOT_PLAN_IO_HAS_TIME] != 0) != (time != nullptr)) return SCOT_ERR_SHAPE;
+  if (!pl->eval_ws) {
+    // any grouping of Cout channels: a group adds at most one chunk per sample to the one-group count (32 bytes a chunk)
+    const size_t bytes = scot_error_sums_workspace_bytes(B, cout, HW, nullptr, 1) + (size_t)B * 31 * 4 * sizeof(double);
+    pl->eval_ws = dev_alloc(bytes);
+    if (!pl->eval_ws) return SCOT_ERR_LAUNCH;
+    pl->eval_ws_bytes = bytes;
+  }
+  pl->ran = false;      // (like a rollout, an evaluation leaves nothing to differentiate)
+  const size_t out_row = (size_t)HW * 4 * (size_t)cout, in_row = (size_t)HW * 4 * (size_t)io[SCOT_PLAN_IO_CIN], per_step = (size_t)B * (size_t)groups * 4;
+  char* in = io_ptr(pl, SCOT_PLAN_IO_PV_BUF);
+  char* out = io_ptr(pl, SCOT_PLAN_IO_OUT_BUF);
+  if (steps > 1) {
+    if (!read_step_time(pl, time, steps, stream)) return SCOT_ERR_LAUNCH;
+    if (!dev_copy(io_ptr(pl, SCOT_PLAN_IO_TIME_BUF), pl->host_time.data(), (size_t)B * 4, H2D, stream)) return SCOT_ERR_LAUNCH;
+    time = nullptr;      // (the divided one, above)
+  }
+  if (!copy_inputs(pl, pixel_values, time, nullptr, stream)) return SCOT_ERR_LAUNCH;
+  for (int k = 0; k < steps; ++k) {
+    int rc = replay(pl, SCOT_PLAN_CALLS_FORWARD, stream);
+    if (rc != SCOT_OK) return rc;
+#ifdef SCOT_HIPEMU
+    ++g_emu_issued;
+#endif
+    rc = scot_error_sums((const float*)out, (const float*)((const char*)targets + (size_t)k * B * out_row), B, cout, HW, channel_slices, groups,
+                         sums + (size_t)k * per_step, pl->eval_ws, pl->eval_ws_bytes, stream);
+    if (rc != SCOT_OK) return rc;
+    if (predictions && !dev_copy((char*)predictions + (size_t)k * B * out_row, out, B * out_row, D2D, stream)) return SCOT_ERR_LAUNCH;
     if (k + 1 < steps && !dev_copy2d(in, in_row, out, out_row, out_row, B, stream)) return SCOT_ERR_LAUNCH;
   }
   // (host_time is pageable memory: the runtime has staged it by the time the copy call returned)

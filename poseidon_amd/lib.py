@@ -140,10 +140,15 @@ PLAN_PROTOTYPES = {
     "scot_plan_set_side_stream": [P, P],
     "scot_plan_describe_streams": [P, P],
     "scot_plan_issue_order": [P, I, P, I],
+    # evaluation: the error sums of (prediction, target) per sample and channel group — the kernel alone (channel_slices: a HOST array of
+    # groups + 1 ints; sums: fp64 [B][groups][4]) and behind a plan's forward or rollout
+    "scot_error_sums_workspace_bytes": [I, I, I, P, I],
+    "scot_error_sums": [P, P, I, I, I, P, I, P, P, Z, P],
+    "scot_plan_evaluate": [P, P, P, P, I, P, I, P, P, P],
 }
 _VOID = {"scot_set_use_tr", "scot_gemm_wide_config", "scot_gemm_splitk_config"}
 _SIZE = {"scot_gemm_workspace_bytes", "scot_wgrad_group_workspace_bytes", "scot_cln_bwd_workspace_bytes", "scot_wgrad_mlp_workspace_bytes",
-         "scot_cln_dtime_workspace_bytes"}      # return size_t
+         "scot_cln_dtime_workspace_bytes", "scot_error_sums_workspace_bytes"}      # return size_t
 
 
 def restype(name):

@@ -5,6 +5,7 @@ immediately (no synchronisation).  Tensors must live on the GPU and be contiguou
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -796,3 +797,38 @@ def loss_finish(sums, counts, G, normalized, loss):
 def loss_bwd(pred, labels, mask, mask_full, group_of_channel, sums, counts, G, normalized, dloss, dpred, B, Cc, HW, p):
     _lib.check(L().scot_loss_bwd(ptr(pred), ptr(labels), ptr(mask), int(mask_full), ptr(group_of_channel), ptr(sums), ptr(counts),
                                  G, int(normalized), ptr(dloss), ptr(dpred), B, Cc, HW, p, stream()), "scot_loss_bwd")
+
+
+_error_sums_typed = {}      # library handle -> itself, once its two error-sums calls are typed (a build loaded for its kernel table alone: tests)
+_slice_arrays = {}          # channel slices -> the host int array the call reads
+
+
+def _error_sums_lib():
+    l = _raw()
+    if id(l) not in _error_sums_typed:
+        for name in ("scot_error_sums_workspace_bytes", "scot_error_sums"):
+            fn = getattr(l, name)
+            fn.argtypes, fn.restype = _lib.PLAN_PROTOTYPES[name], _lib.restype(name)
+        _error_sums_typed[id(l)] = l
+    return l
+
+
+def error_sums(pred, target, channel_slices, sums):
+    """sums [B, G, 4] (float64) <- {sum |p - t|, sum |t|, sum (p - t)^2, sum t^2} per sample and channel group of pred against target
+    (float32 [B, C, ...], contiguous): scot_error_sums (include/scot_plan.h), two launches.  channel_slices: G + 1 ascending ints, or
+    None for the one group of all channels.  A model-level call: it goes to the library itself, never onto a step tape."""
+    B, C = int(pred.shape[0]), int(pred.shape[1])
+    HW = pred.numel() // max(1, B * C)
+    groups, arr = 1, None
+    if channel_slices is not None:
+        key = tuple(int(c) for c in channel_slices)
+        groups = len(key) - 1
+        arr = _slice_arrays.get(key)
+        if arr is None:
+            arr = _slice_arrays[key] = (ctypes.c_int * len(key))(*key)
+    l = _error_sums_lib()
+    need = int(l.scot_error_sums_workspace_bytes(B, C, HW, arr, groups))
+    if need == 0:
+        raise ValueError(f"error_sums: shape {tuple(pred.shape)} with channel slices {channel_slices}")
+    ws = workspace(need)
+    _lib.check(l.scot_error_sums(ptr(pred), ptr(target), B, C, HW, arr, groups, ptr(sums), ptr(ws), ws.numel(), stream()), "scot_error_sums")

@@ -995,7 +995,7 @@ def _addr(x, what):
 
 
 class Plan:
-    """A loaded plan.  `run` / `rollout` / `vjp` / `rollout_vjp` / `loss` / `train_step` take torch tensors (and return them) or raw
+    """A loaded plan.  `run` / `rollout` / `evaluate` / `vjp` / `rollout_vjp` / `loss` / `train_step` take torch tensors (and return them) or raw
     device addresses (then `out` is required)."""
 
     def __init__(self, lib, handle):
@@ -1129,6 +1129,50 @@ class Plan:
         self._call("scot_plan_rollout", _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(pixel_mask, "pixel_mask"), _addr(out, "out"),
                    int(steps), self._stream(stream, pixel_values))
         return out.transpose(0, 1).contiguous() if tensors and _is_tensor(out) else out
+
+    def evaluate(self, pixel_values, time, targets, steps=1, channel_slice_list=None, predictions=False, stream=None):
+        """-> error sums, float64 [steps, B, G, 4]: per step, sample and channel group `[channel_slice_list[g], channel_slice_list[g+1])`
+        of the Cout output channels (None: one group) the sums Σ|p−t|, Σ|t|, Σ(p−t)², Σt² of the prediction against `targets`
+        (scot_plan_evaluate; scOT.metrics' `*_from_sums` turn them into the reference's metrics).  steps == 1: one forward, as `run`,
+        targets [B, Cout, H, W]; steps > 1: the chain of `rollout`, targets [B, steps, Cout, H, W] as `rollout` returns predictions.
+        predictions=True: -> (sums, predictions [B, steps, Cout, H, W]); otherwise no prediction leaves the plan.
+        With raw addresses `targets` is in the C layout [steps][B, Cout, H, W] and `predictions` is None or the address of a buffer in
+        that layout; the sums still come back as a tensor (on the GPU where there is one)."""
+        import torch
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("steps >= 1")
+        groups = 1 if channel_slice_list is None else len(channel_slice_list) - 1
+        slices = None if channel_slice_list is None else ctypes.cast((ctypes.c_int * (groups + 1))(*[int(c) for c in channel_slice_list]),
+                                                                     ctypes.c_void_p)
+        tensors = _is_tensor(pixel_values)
+        if tensors:
+            self._require(pixel_values, "pixel_values")
+            b, c, h, w = self._shape("out_channels")
+            want = (b, c, h, w) if steps == 1 and _is_tensor(targets) and targets.dim() == 4 else (b, steps, c, h, w)
+            if not _is_tensor(targets) or tuple(targets.shape) != want:
+                raise ValueError(f"this plan's evaluation over {steps} step(s) takes targets of shape {want}")
+            device = pixel_values.device
+            targets = targets.to(device=device, dtype=torch.float32)
+            targets = (targets if targets.dim() == 4 else targets.transpose(0, 1)).contiguous()
+            time = self._time(time, counted=steps == 1)
+            if _is_tensor(time):
+                time = time.to(device)
+            # (the converted copies are temporaries of torch's CURRENT stream: held until the next call, so that a call on an explicit
+            # `stream=` never reads memory the allocator has handed on)
+            self._held = (targets, time)
+            out = self._empty(pixel_values, steps=(steps,)) if predictions else None
+        else:
+            if isinstance(predictions, bool) and predictions:
+                raise ValueError("raw addresses need `predictions` to be an address (or None)")
+            device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
+            out = predictions or None
+        sums = torch.empty(steps, self.info["batch"], groups, 4, dtype=torch.float64, device=device)
+        self._call("scot_plan_evaluate", _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(targets, "targets"), steps, slices, groups,
+                   sums.data_ptr(), _addr(out, "predictions"), self._stream(stream, pixel_values))
+        if out is None:
+            return sums
+        return sums, (out.transpose(0, 1).contiguous() if tensors and _is_tensor(out) else out)
 
     def describe_adjoint(self):
         out = (ctypes.c_longlong * 8)()

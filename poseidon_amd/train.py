@@ -644,35 +644,56 @@ class Trainer:
         self.dist.all_gather(parts, t.contiguous())
         return torch.stack(parts, 1).reshape(-1, *t.shape[1:])      # undo the rank-strided shard: sample k of rank r was index k·world + r
 
-    def _eval_loop(self, ds, prefix: str) -> PredictionOutput:
-        model = self.model
-        was_training = model.training
-        model.eval()
+    def _eval_batches(self, ds):
+        """the evaluation loop both `_eval_loop` and `evaluate_on_device` run: the model in eval mode (restored at the end, also when
+        the consumer raises), this rank's shard in order -> (prediction, labels or None) per batch; afterwards `.loss_total` holds
+        [Σ loss · b, Σ b] on the device, or None if no batch had a loss.  -> (generator, number of samples of the whole data set)"""
         n = self._num_samples(ds)
-        order = self._shard(np.arange(n))
-        preds, labs, losses, count = [], [], torch.zeros((), device=self._device()), 0
-        for batch in self._batches(ds, self.args.per_device_eval_batch_size, order, False):
-            loss, logits, labels = self.prediction_step(model, self._model_inputs(batch), prediction_loss_only=False, ignore_keys=["hidden_states", "attentions", "reshaped_hidden_states"])
-            b = (logits[0] if isinstance(logits, tuple) else logits).shape[0]
-            if loss is not None:
-                losses += loss * b
-                count += b
-            preds.append(logits[0] if isinstance(logits, tuple) else logits)
+
+        def batches():
+            model = self.model
+            was_training = model.training
+            model.eval()
+            self._eval_loss_total = None
+            losses, count = torch.zeros((), device=self._device()), 0
+            try:
+                for batch in self._batches(ds, self.args.per_device_eval_batch_size, self._shard(np.arange(n)), False):
+                    loss, logits, labels = self.prediction_step(model, self._model_inputs(batch), prediction_loss_only=False,
+                                                                ignore_keys=["hidden_states", "attentions", "reshaped_hidden_states"])
+                    pred = logits[0] if isinstance(logits, tuple) else logits
+                    if loss is not None:
+                        losses += loss * pred.shape[0]
+                        count += pred.shape[0]
+                    yield pred, labels
+                if count:
+                    self._eval_loss_total = torch.stack([losses, torch.tensor(float(count), device=losses.device)])
+            finally:
+                model.train(was_training)
+        return batches(), n
+
+    def _eval_loss(self, prefix: str) -> Dict[str, float]:
+        """{prefix_loss: the mean loss of the loop that `_eval_batches` just ran, over all ranks} (empty without a loss)"""
+        tot = self._eval_loss_total
+        if tot is None:
+            return {}
+        if self.dist is not None:
+            self.dist.all_reduce(tot)
+        return {f"{prefix}_loss": float(tot[0] / tot[1])}
+
+    def _eval_loop(self, ds, prefix: str) -> PredictionOutput:
+        batches, n = self._eval_batches(ds)
+        preds, labs = [], []
+        for pred, labels in batches:
+            preds.append(pred)
             if labels is not None:
                 labs.append(labels)
         P = self._gather(torch.cat(preds))[:n]
         Lb = self._gather(torch.cat(labs))[:n] if labs else None
-        metrics: Dict[str, float] = {}
-        if count:
-            tot = torch.stack([losses, torch.tensor(float(count), device=losses.device)])
-            if self.dist is not None:
-                self.dist.all_reduce(tot)
-            metrics[f"{prefix}_loss"] = float(tot[0] / tot[1])
+        metrics: Dict[str, float] = self._eval_loss(prefix)
         Pn, Ln = P.float().cpu().numpy(), (Lb.float().cpu().numpy() if Lb is not None else None)
         if self.compute_metrics is not None and Ln is not None:
             for k, v in self.compute_metrics(EvalPrediction(Pn, Ln)).items():
                 metrics[k if k.startswith(prefix + "_") else f"{prefix}_{k}"] = v
-        model.train(was_training)
         return PredictionOutput(Pn, Ln, metrics)
 
     def evaluate(self, eval_dataset=None, ignore_keys=None, metric_key_prefix: str = "eval") -> Dict[str, float]:
@@ -683,6 +704,33 @@ class Trainer:
         self.state["log_history"].append(dict(out.metrics, step=self.state["global_step"]))
         self._fire("on_evaluate", metrics=out.metrics)
         return out.metrics
+
+    def evaluate_on_device(self, eval_dataset=None, metric_key_prefix: str = "eval") -> Dict[str, float]:
+        """`evaluate` with the reference's per-channel-group metrics and nothing but sums kept: the same batches, sharding and `ar_steps`
+        handling as `_eval_loop`, but per batch only the loss and the [b, G, 4] error sums of the final prediction survive
+        (scOT.metrics.error_sums: on the GPU one fused kernel).  No prediction is concatenated or copied to the host; under data
+        parallelism the sums are gathered.  Groups and names are the data set's `channel_slice_list` / `printable_channel_description`
+        (one group without them).  -> {prefix}_loss and the `group_metrics_from_sums` dictionary under prefixed keys."""
+        from scOT.metrics import error_sums, group_metrics_from_sums
+        ds = eval_dataset if eval_dataset is not None else self.eval_dataset
+        if ds is None:
+            raise ValueError("Trainer: evaluation requires an eval_dataset.")
+        prefix = metric_key_prefix
+        slices, names = getattr(ds, "channel_slice_list", None), getattr(ds, "printable_channel_description", None)
+        batches, n = self._eval_batches(ds)
+        sums = []
+        for pred, labels in batches:
+            if labels is None:
+                batches.close()      # (restores the model's mode)
+                raise ValueError("Trainer.evaluate_on_device: the data set has no labels")
+            sums.append(error_sums(pred, labels, slices))
+        S = self._gather(torch.cat(sums))[:n]
+        metrics: Dict[str, float] = self._eval_loss(prefix)
+        for k, v in group_metrics_from_sums(S, names).items():
+            metrics[f"{prefix}_{k}"] = v
+        self.state["log_history"].append(dict(metrics, step=self.state["global_step"]))
+        self._fire("on_evaluate", metrics=metrics)
+        return metrics
 
     def predict(self, test_dataset, metric_key_prefix: str = "test", ignore_keys=None) -> PredictionOutput:
         out = self._eval_loop(test_dataset, metric_key_prefix)

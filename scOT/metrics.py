@@ -6,6 +6,10 @@ The reference works on numpy arrays after HF `Trainer.predict` has copied every 
 numpy arrays OR torch tensors; given GPU tensors (e.g. the `.output` of `scOT.trainer.rollout`) the reductions run on the
 device and only the per-sample error vectors / the final statistics cross PCIe.  Semantics, including
 the 1e-10 guard of an all-zero target and the percent scaling, are the reference's.
+
+`error_sums` and the `*_from_sums` functions are the same metrics in two steps: one fused reduction of (prediction, target) to four
+fp64 sums per sample and channel group — on the GPU the `scot_error_sums` kernel, which `Plan.evaluate` and
+`Trainer.evaluate_on_device` also run — and the few flops per sample that turn the sums into the reference's numbers.
 """
 from __future__ import annotations
 
@@ -109,4 +113,90 @@ def channel_group_metrics(preds, targets, channel_slice_list: Sequence[int], cha
             out[names[i] + "/" + k] = v
         if full_data:
             out[names[i] + "/full_data"] = ab[i].tolist()
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- from error sums
+SUM_ABS_ERR, SUM_ABS, SUM_SQ_ERR, SUM_SQ = range(4)      # the last axis of error sums: S1, N1, S2, N2 (include/scot_plan.h)
+
+
+def error_sums(preds, targets, channel_slice_list: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """[N, G, 4] float64: per sample and channel group `[channel_slice_list[g], channel_slice_list[g+1])` (None: one group of all
+    channels) the sums Σ|p−t|, Σ|t|, Σ(p−t)², Σt² over the group's channels and all pixels.  GPU tensors go through the
+    `scot_error_sums` kernel (one pass over both operands, no temporaries; the result stays on the device); numpy arrays and CPU
+    tensors use a plain fp64 computation.  Both convert the fp32 values to fp64 first, then subtract."""
+    pr, tg = _t(preds), _t(targets)
+    if pr.shape != tg.shape or pr.dim() < 2:
+        raise ValueError(f"error_sums: predictions {tuple(pr.shape)} against targets {tuple(tg.shape)}")
+    n, c = pr.shape[0], pr.shape[1]
+    slices = [0, c] if channel_slice_list is None else [int(s) for s in channel_slice_list]
+    if len(slices) < 2 or slices[0] < 0 or slices[-1] > c or any(b <= a for a, b in zip(slices, slices[1:])):
+        raise ValueError(f"error_sums: channel slices {slices} over {c} channels")
+    if pr.is_cuda:
+        from poseidon_amd import ops
+        pr, tg = pr.to(torch.float32).contiguous(), tg.to(device=pr.device, dtype=torch.float32).contiguous()
+        out = torch.empty(n, len(slices) - 1, 4, dtype=torch.float64, device=pr.device)
+        if n:
+            ops.error_sums(pr, tg, None if channel_slice_list is None else slices, out)
+        return out
+    pr, tg = pr.reshape(n, c, -1).to(torch.float64), tg.reshape(n, c, -1).to(torch.float64)
+    d = pr - tg
+    per_channel = torch.stack([d.abs().sum(-1), tg.abs().sum(-1), (d * d).sum(-1), (tg * tg).sum(-1)], -1)      # [N, C, 4]
+    return torch.stack([per_channel[:, a:b].sum(1) for a, b in zip(slices, slices[1:])], 1)
+
+
+def _sum_pair(sums, p):
+    if p not in (1, 2):
+        raise ValueError("error sums hold the terms of p = 1 and p = 2")
+    s = _t(sums).to(torch.float64)
+    return (s[..., SUM_ABS_ERR], s[..., SUM_ABS]) if p == 1 else (s[..., SUM_SQ_ERR], s[..., SUM_SQ])
+
+
+def lp_error_from_sums(sums, p=1):
+    """`lp_error` of every (sample, group) of `error_sums`' result: S^(1/p), shape sums.shape[:-1]."""
+    err, _ = _sum_pair(sums, p)
+    return _like(err.pow(1.0 / p), sums)
+
+
+def relative_lp_error_from_sums(sums, p=1, return_percent=True):
+    """`relative_lp_error` of every (sample, group): (S / N)^(1/p), in percent by default, N == 0 replaced by 1e-10."""
+    err, norm = _sum_pair(sums, p)
+    norm = torch.where(norm == 0, torch.full_like(norm, 1e-10), norm)
+    res = (err / norm).pow(1.0 / p)
+    if return_percent:
+        res = res * 100
+    return _like(res, sums)
+
+
+def group_metrics_from_sums(sums, channel_names: Optional[Sequence[str]] = None, full_data: bool = False) -> Dict[str, object]:
+    """The dictionary `channel_group_metrics` returns, with the same keys, from the [N, G, 4] sums of the same predictions, targets
+    and channel slices: only the order statistics over the N samples are left to do."""
+    s = _t(sums)
+    if s.dim() != 3 or s.shape[-1] != 4:
+        raise ValueError(f"group_metrics_from_sums: sums of shape [N, G, 4], not {tuple(s.shape)}")
+    groups = s.shape[1]
+    rel_all, ab_all = _t(relative_lp_error_from_sums(s, 1, True)), _t(lp_error_from_sums(s, 1))
+    rel, ab = [rel_all[:, g] for g in range(groups)], [ab_all[:, g] for g in range(groups)]
+    return _group_dictionary(rel, ab, channel_names, full_data)
+
+
+def _group_dictionary(rel, ab, channel_names, full_data):
+    """per-group relative and absolute L1 errors (one [N] tensor per group each) -> the dictionary of `channel_group_metrics`"""
+    parts = [("relative_l1_error", "relative_full_data", rel), ("l1_error", "full_data", ab)]
+    stats = {suffix: [_stats(e, suffix) for e in errs] for suffix, _, errs in parts}
+    if len(rel) == 1:
+        out: Dict[str, object] = {**stats["relative_l1_error"][0], **stats["l1_error"][0]}
+        if full_data:
+            out.update({data_key: errs[0].tolist() for _, data_key, errs in parts})
+        return out
+    names = list(channel_names) if channel_names is not None else [f"group{i}" for i in range(len(rel))]
+    out = {}
+    for suffix in ("relative_l1_error", "l1_error"):
+        out["mean_" + suffix] = float(np.mean([st["mean_" + suffix] for st in stats[suffix]]))
+        out["mean_over_median_" + suffix] = float(np.mean([st["median_" + suffix] for st in stats[suffix]]))
+    for suffix, data_key, errs in parts:
+        for i, st in enumerate(stats[suffix]):
+            out.update({names[i] + "/" + k: v for k, v in st.items()})
+            if full_data:
+                out[names[i] + "/" + data_key] = errs[i].tolist()
     return out
