@@ -7,7 +7,8 @@
  * shared library and the HIP runtime: no Python, no torch.  The prediction is bit-identical to `model(...)` in Python.
  *
  * What a plan covers: the engine's inference forward at config.image_size on ONE stream (or two: TWO-STREAM plans below) — no training, no spectral resize, no hidden
- * states or attention outputs, no labels (so no pixel_mask: the mask overwrites the prediction with label values).  The weights are a
+ * states or attention outputs, no labels (so no pixel_mask INPUT on an inference plan: the mask overwrites the prediction with label
+ * values; scot_plan_evaluate_masked takes one beside its targets, a training plan takes one with its batch).  The weights are a
  * snapshot taken at export.  A plan recorded by the binary16 build (libscot_hip_f16.so) loads into that build only; its split-MFMA
  * trunk products run in the bfloat16 build, which the runtime opens from the same directory (or from where the peer call points).
  *
@@ -26,7 +27,8 @@
  * modes (arena 1x, two moments 2x, two 16-bit copies 1x), 3x in fp32 / bf16x3, plus the small tables.  The runtime owns them after
  * load, scot_plan_run sees the current ones and scot_plan_snapshot writes them back into the image.
  * Weight decay, betas, eps, clipping and the scale schedule are fixed at export; the learning rates are an argument of every step.  Not
- * covered: gradient accumulation, data parallelism, stochastic depth, pixel_mask, partially frozen models, a trimmed image.  By
+ * covered: gradient accumulation, data parallelism, stochastic depth, partially frozen models, a trimmed image.  The reference's
+ * pixel_mask is covered: a MASKED training plan (section "pixel masks" below) takes the mask with every batch.  By
  * default it runs on ONE stream, the weight gradients in line (the Python engine puts them on a second stream: measured on
  * Poseidon-B fp16, a plan's step takes 22.7 ms against the Python loop's 19.3 at batch 64, 11.1 against 10.7 at batch 1).
  *
@@ -145,7 +147,8 @@ const char* scot_plan_adjoint_entry_point(int i);
 
 /* ---- training plans ---- */
 /* out[8]: has training, parameter groups, floats in the parameter arena, recorded calls of one step, bytes of labels, bytes kept
- * between the step's forward and its backward, whether the gradient scale is dynamic (fp16), 0.  Format-1/2 plan: all zeros, status 0. */
+ * between the step's forward and its backward, whether the gradient scale is dynamic (fp16), the kind of the batch's pixel_mask (0 none,
+ * 1 channel [B, Cout], 2 element [B, Cout, H, W]).  Format-1/2 plan: all zeros, status 0. */
 int scot_plan_describe_training(scot_plan_t plan, long long* out);
 /* loss [1] <- what `model(pixel_values, time=time, labels=labels).loss` returns at the plan's CURRENT weights, prediction [B, Cout, H, W]
  * (may be NULL) <- its output.  fp32 device buffers of the caller; labels [B, Cout, H, W].  Replays the step's forward only: no state
@@ -219,9 +222,54 @@ int scot_error_sums(const float* pred, const float* target, int B, int C, int HW
  * host once when steps > 1 (waits for `stream` there); everything after that is asynchronous on `stream`.
  * Refused before anything is copied or launched: a NULL pixel_values, targets or sums, steps < 1, groups outside 1..32, slices not strictly
  * ascending or beyond Cout, steps > 1 with Cout > Cin, a time that is NULL where the plan takes one (or given where it takes none): -1;
- * steps > 1 on a plan without a time input, a plan with a pixel_mask input: -3. */
+ * steps > 1 on a plan without a time input, an inference plan with a pixel_mask input: -3. */
 int scot_plan_evaluate(scot_plan_t plan, const float* pixel_values, const float* time, const float* targets, int steps,
                        const int* channel_slices, int groups, double* sums, float* predictions, scot_stream_t stream);
+
+/* ---- pixel masks ---- */
+/* scot_error_sums of the prediction where(mask, target, pred), in the same pass: what the reference scores after `prediction[pixel_mask]
+ * = labels[pixel_mask]` (its scOT/model.py).  mask: device bytes, any non-zero byte = masked, at ANY byte alignment; mask_full == 0: [B, C]
+ * (whole planes), mask_full != 0: [B, C, HW].  mask == NULL is exactly scot_error_sums: the same bits, pred untouched.
+ *   sums       bit for bit what scot_error_sums returns for where(mask, target, pred): same chunks, same order, no atomics, the same
+ *              workspace (scot_error_sums_workspace_bytes).  A masked element enters as if p were t: its term is (double)t - (double)t,
+ *              not a literal 0, so an Inf or NaN LABEL under the mask makes the same sums non-finite as in the overwritten tensor; a NaN
+ *              or Inf in pred under the mask reaches no sum.
+ *   overwrite  != 0: the same pass stores target over pred at the masked positions; every other float of pred keeps its bits.  It needs
+ *              groups that tile [0, C) exactly (first slice 0, last slice C), as every channel_slice_list of the reference does: otherwise
+ *              -1, nothing is launched, sums and pred are untouched.  == 0: pred is read only.  pred and target may sit at any 4-byte
+ *              alignment, as for scot_error_sums (the kernel picks vector or scalar loads per run; the bits are the same).
+ * Every other refusal as scot_error_sums. */
+int scot_error_sums_masked(float* pred, const float* target, const unsigned char* mask, int mask_full, int overwrite, int B, int C, int HW,
+                           const int* channel_slices, int groups, double* sums, void* workspace, size_t workspace_bytes,
+                           scot_stream_t stream);
+/* scot_plan_evaluate under a pixel_mask: every image format.  pixel_mask is an ARGUMENT of the call, not part of the image: device bytes,
+ * [B, Cout] (mask_full == 0) or [B, Cout, H, W] (mask_full != 0), the same mask for all steps.  After forward k, scot_error_sums_masked
+ * runs on the plan's own output buffer with overwrite = 1 against targets[k], before that buffer is copied back or out: the sums are the
+ * masked sums, the next step's input carries the label values at the masked positions, and `predictions`, if given, receives the
+ * overwritten predictions.  pixel_mask == NULL is scot_plan_evaluate, bit for bit.
+ * ONE DIFFERENCE FROM THE REFERENCE: its trainer overwrites every rollout step with the FINAL labels; this call uses that step's own
+ * target.  The two agree wherever the masked values are constant in time, which holds for every masked channel of the reference's
+ * datasets (the constant density and pressure planes, the airfoil's solid cells).
+ * Refusals as scot_plan_evaluate, and: a mask with groups that do not tile [0, Cout): -1.  A masked TRAINING plan is not refused for
+ * having a mask input (by either evaluate call): the inference list replayed here does not read it. */
+int scot_plan_evaluate_masked(scot_plan_t plan, const float* pixel_values, const float* time, const float* targets, const void* pixel_mask,
+                              int mask_full, int steps, const int* channel_slices, int groups, double* sums, float* predictions,
+                              scot_stream_t stream);
+/* MASKED TRAINING PLANS.  `export_plan(pv, time=, labels=, pixel_mask=M, train=opt[, streams=2])` records the step with the mask: bool
+ * [B, Cout] is a channel mask (B * Cout bytes), bool [B, Cout, H, W] an element mask (B * Cout * H * W bytes), bool [B, 1, H, W] is
+ * expanded over the channels into an element mask; any other shape is refused.  The image (formats 4 and 6, training flag bits 1 and 2)
+ * has the mask as one more input buffer; scot_plan_describe reports it and scot_plan_describe_training out[7] its kind (0 none, 1
+ * channel, 2 element).  The two calls below are scot_plan_loss / scot_plan_train_step with the batch's mask: device bytes of the plan's
+ * mask size.  The loss and the gradients are those of `model(..., labels=, pixel_mask=)`, and the returned prediction holds the labels at
+ * the masked positions, as `model(...).output` does.  Snapshot, status, scot_plan_run (pixel_mask NULL) at the current weights and
+ * two-stream replay work unchanged on a masked plan.
+ * Refused before anything is copied or launched: a format-1/2/5 plan: -3; scot_plan_loss / scot_plan_train_step on a masked plan (the
+ * mask is missing), a non-NULL mask on an unmasked training plan, a NULL mask on a masked plan: -1.  On an unmasked training plan with a
+ * NULL mask they ARE the unmasked calls. */
+int scot_plan_loss_masked(scot_plan_t plan, const float* pixel_values, const float* time, const float* labels, const void* pixel_mask,
+                          float* loss, float* prediction, scot_stream_t stream);
+int scot_plan_train_step_masked(scot_plan_t plan, const float* pixel_values, const float* time, const float* labels, const void* pixel_mask,
+                                const float* lr, float* loss, scot_stream_t stream);
 
 /* Refused before anything is copied or launched: scot_plan_loss / _train_step / _train_status / _snapshot on a format-1/2 plan: -3
  * (as scot_plan_vjp / scot_plan_rollout_vjp on a training plan); a NULL pixel_values, labels or lr, a NULL loss of scot_plan_loss, a NULL

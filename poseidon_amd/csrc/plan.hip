@@ -33,6 +33,12 @@
 // EVALUATION (every image): scot_plan_evaluate is scot_plan_run's forward or scot_plan_rollout's chain with scot_error_sums
 // (error_sums.hip) behind every forward: it reads the plan's own output buffer against the caller's targets and leaves per-sample,
 // per-channel-group error sums; the predictions need not leave the plan.  Its workspace is allocated at the first such call.
+// scot_plan_evaluate_masked takes a pixel_mask of the caller's beside the targets and runs scot_error_sums_masked with overwrite = 1 on
+// the output buffer instead: the sums are the masked ones, and the labels under the mask travel on into the next step's input.
+//
+// PIXEL MASKS (training images): a masked training image (training flag bits 1 and 2) has one more input buffer, the mask bytes the
+// recorded scot_head_finalize / scot_loss_bwd entries read; scot_plan_loss_masked / scot_plan_train_step_masked copy the caller's mask
+// into it, and the unmasked calls refuse such a plan (the mask is missing).
 //
 // A plan is one stream's worth of state: its buffers are reused by every run, so runs of ONE plan must be ordered (same stream, or
 // the caller's own events); two plans are independent.
@@ -52,6 +58,9 @@ extern "C" int scot_operand_format();
 extern "C" size_t scot_error_sums_workspace_bytes(int B, int C, int HW, const int* channel_slices, int groups);
 extern "C" int scot_error_sums(const float* pred, const float* target, int B, int C, int HW, const int* channel_slices, int groups, double* sums,
                                void* workspace, size_t workspace_bytes, hipStream_t stream);
+extern "C" int scot_error_sums_masked(float* pred, const float* target, const unsigned char* mask, int mask_full, int overwrite, int B, int C,
+                                      int HW, const int* channel_slices, int groups, double* sums, void* workspace, size_t workspace_bytes,
+                                      hipStream_t stream);
 
 // the listed entry points, by address: g_entry_address[table][index], rows in the order of scot_plan_lists[table].names (the training
 // table is the longest: it repeats the forward's)
@@ -602,11 +611,13 @@ extern "C" int scot_plan_poison(void* plan, int byte, hipStream_t stream) {
 }
 
 // the caller's input pointers: pixel_values and `other` (where the result goes, or a batch's labels) are required; time, and with
-// `masked` pixel_mask, have to be given exactly where the plan takes them
+// `masked` pixel_mask, have to be given exactly where the plan takes them.  (The mask input of a masked TRAINING plan belongs to its step
+// lists: the inference list does not read it, so scot_plan_run / scot_plan_rollout on such a plan take NULL as well.)
 static int check_inputs(Plan* pl, const void* pixel_values, const void* time, const void* pixel_mask, const void* other, bool masked = true) {
   if (!pixel_values || !other) return SCOT_ERR_SHAPE;
   if ((pl->io[SCOT_PLAN_IO_HAS_TIME] != 0) != (time != nullptr)) return SCOT_ERR_SHAPE;
-  if (masked && (pl->io[SCOT_PLAN_IO_HAS_MASK] != 0) != (pixel_mask != nullptr)) return SCOT_ERR_SHAPE;
+  const bool optional = pl->format == SCOT_PLAN_FORMAT_TRAINING && !pixel_mask;
+  if (masked && !optional && (pl->io[SCOT_PLAN_IO_HAS_MASK] != 0) != (pixel_mask != nullptr)) return SCOT_ERR_SHAPE;
   return SCOT_OK;
 }
 
@@ -767,8 +778,8 @@ extern "C" int scot_plan_rollout(void* plan, const float* pixel_values, const fl
 // (include/scot_plan.h): after forward k, scot_error_sums reduces the plan's own output buffer against targets[k] into sums[k] on
 // `stream` — behind the list's join on a two-stream plan, before the buffer is copied back.  predictions may be NULL: no prediction
 // leaves the plan.  Every refusal, the workspace's allocation included, comes before the first copy.
-extern "C" int scot_plan_evaluate(void* plan, const float* pixel_values, const float* time, const float* targets, int steps,
-                                  const int* channel_slices, int groups, double* sums, float* predictions, hipStream_t stream) {
+static int plan_evaluate(void* plan, const float* pixel_values, const float* time, const float* targets, const unsigned char* pixel_mask,
+                         int mask_full, int steps, const int* channel_slices, int groups, double* sums, float* predictions, hipStream_t stream) {
   Plan* pl = as_plan(plan);
   if (!pl) return SCOT_ERR_SHAPE;
   const uint64_t* io = pl->io;
@@ -776,7 +787,10 @@ extern "C" int scot_plan_evaluate(void* plan, const float* pixel_values, const f
   const int B = (int)io[SCOT_PLAN_IO_B], cout = (int)io[SCOT_PLAN_IO_COUT], HW = (int)(io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W]);
   // (groups outside 1..32, slices not strictly ascending or beyond Cout: the kernel's own rule, asked of its workspace query)
   if (scot_error_sums_workspace_bytes(B, cout, HW, channel_slices, groups) == 0) return SCOT_ERR_SHAPE;
-  if (io[SCOT_PLAN_IO_HAS_MASK]) return SCOT_ERR_UNSUPPORTED;
+  // (overwriting under the mask leaves a consistent prediction only where the groups tile [0, Cout): the kernel's rule, asked here first)
+  if (pixel_mask && channel_slices && (channel_slices[0] != 0 || channel_slices[groups] != cout)) return SCOT_ERR_SHAPE;
+  // (a mask input of a TRAINING plan belongs to its step lists: the inference list replayed here does not read it)
+  if (io[SCOT_PLAN_IO_HAS_MASK] && pl->format != SCOT_PLAN_FORMAT_TRAINING) return SCOT_ERR_UNSUPPORTED;
   if (steps > 1) {
     if (io[SCOT_PLAN_IO_COUT] > io[SCOT_PLAN_IO_CIN]) return SCOT_ERR_SHAPE;
     if (!io[SCOT_PLAN_IO_HAS_TIME]) return SCOT_ERR_UNSUPPORTED;
@@ -805,14 +819,31 @@ extern "C" int scot_plan_evaluate(void* plan, const float* pixel_values, const f
 #ifdef SCOT_HIPEMU
     ++g_emu_issued;
 #endif
-    rc = scot_error_sums((const float*)out, (const float*)((const char*)targets + (size_t)k * B * out_row), B, cout, HW, channel_slices, groups,
-                         sums + (size_t)k * per_step, pl->eval_ws, pl->eval_ws_bytes, stream);
+    // (a NULL mask is scot_error_sums itself; with one, the labels are stored over the masked positions of `out` before it is copied)
+    rc = scot_error_sums_masked((float*)out, (const float*)((const char*)targets + (size_t)k * B * out_row), pixel_mask, mask_full, 1, B, cout, HW,
+                                channel_slices, groups, sums + (size_t)k * per_step, pl->eval_ws, pl->eval_ws_bytes, stream);
     if (rc != SCOT_OK) return rc;
     if (predictions && !dev_copy((char*)predictions + (size_t)k * B * out_row, out, B * out_row, D2D, stream)) return SCOT_ERR_LAUNCH;
     if (k + 1 < steps && !dev_copy2d(in, in_row, out, out_row, out_row, B, stream)) return SCOT_ERR_LAUNCH;
   }
   // (host_time is pageable memory: the runtime has staged it by the time the copy call returned)
   return SCOT_OK;
+}
+
+extern "C" int scot_plan_evaluate(void* plan, const float* pixel_values, const float* time, const float* targets, int steps,
+                                  const int* channel_slices, int groups, double* sums, float* predictions, hipStream_t stream) {
+  return plan_evaluate(plan, pixel_values, time, targets, nullptr, 0, steps, channel_slices, groups, sums, predictions, stream);
+}
+
+// scot_plan_evaluate with the reference's pixel_mask (include/scot_plan.h): pixel_mask is the CALLER's device bytes, [B, Cout] (mask_full
+// == 0) or [B, Cout, H, W], the same for every step; after forward k the fused kernel stores targets[k] over the masked positions of the
+// plan's output buffer while it forms the sums, so the sums are the masked ones, the next step's input carries the labels there, and
+// `predictions` receives the overwritten predictions.  NULL: scot_plan_evaluate.
+extern "C" int scot_plan_evaluate_masked(void* plan, const float* pixel_values, const float* time, const float* targets, const void* pixel_mask,
+                                         int mask_full, int steps, const int* channel_slices, int groups, double* sums, float* predictions,
+                                         hipStream_t stream) {
+  return plan_evaluate(plan, pixel_values, time, targets, (const unsigned char*)pixel_mask, mask_full, steps, channel_slices, groups, sums,
+                       predictions, stream);
 }
 
 // The adjoint of that rollout with no detach between the steps (include/scot_plan.h): the gradient of sum_k <d_predictions[k],
@@ -886,7 +917,8 @@ extern "C" int scot_plan_rollout_vjp(void* plan, const float* pixel_values, cons
 
 // ------------------------------------------------------------------ training plans (image format 4)
 // out[8]: has training, parameter groups, floats in the arena, calls of one step, bytes of labels, bytes kept between the step's forward
-// and its backward, whether the gradient scale is dynamic, 0.  Format-1/2 plan: all zeros, status 0.
+// and its backward, whether the gradient scale is dynamic, the kind of the batch's pixel_mask (0 none, 1 channel [B, Cout], 2 element
+// [B, Cout, H, W]).  Format-1/2 plan: all zeros, status 0.
 extern "C" int scot_plan_describe_training(void* plan, long long* out) {
   Plan* pl = as_plan(plan);
   if (!pl || !out) return SCOT_ERR_SHAPE;
@@ -900,31 +932,34 @@ extern "C" int scot_plan_describe_training(void* plan, long long* out) {
   out[4] = (long long)t[SCOT_PLAN_TR_LABELS + 2];
   out[5] = (long long)t[SCOT_PLAN_TR_KEPT_BYTES];
   out[6] = (long long)(t[SCOT_PLAN_TR_FLAGS] & 1);
+  out[7] = (t[SCOT_PLAN_TR_FLAGS] & 2) ? ((t[SCOT_PLAN_TR_FLAGS] & 4) ? 2 : 1) : 0;      // the batch's pixel_mask: none, channel, element
   return SCOT_OK;
 }
 
-// the batch -> the plan's input copies (the caller has checked the pointers): the inputs, and the labels
-static bool copy_batch_in(Plan* pl, const float* pixel_values, const float* time, const float* labels, hipStream_t stream) {
-  return copy_inputs(pl, pixel_values, time, nullptr, stream) &&
+// the batch -> the plan's input copies (the caller has checked the pointers): the inputs, the labels, and the mask of a masked plan
+static bool copy_batch_in(Plan* pl, const float* pixel_values, const float* time, const float* labels, const void* pixel_mask, hipStream_t stream) {
+  return copy_inputs(pl, pixel_values, time, pixel_mask, stream) &&
          dev_copy(span_ptr(pl, pl->train, SCOT_PLAN_TR_LABELS), labels, (size_t)pl->train[SCOT_PLAN_TR_LABELS + 2], D2D, stream);
 }
 
-// a batch for a training plan: pixel_values, labels, and time where the plan takes it (a batch has no mask)
-static int check_batch(Plan* pl, const void* pixel_values, const void* time, const void* labels) {
+// a batch for a training plan: pixel_values, labels, time where the plan takes it, and pixel_mask exactly where the plan is a masked one
+static int check_batch(Plan* pl, const void* pixel_values, const void* time, const void* labels, const void* pixel_mask) {
   if (pl->format != SCOT_PLAN_FORMAT_TRAINING) return SCOT_ERR_UNSUPPORTED;
+  if ((pl->io[SCOT_PLAN_IO_HAS_MASK] != 0) != (pixel_mask != nullptr)) return SCOT_ERR_SHAPE;
   return check_inputs(pl, pixel_values, time, nullptr, labels, false);
 }
 
-// loss [1] <- what model(pixel_values, time, labels=labels).loss returns, prediction (may be NULL) <- its output: the step's forward
-// alone.  No state buffer is written.
-extern "C" int scot_plan_loss(void* plan, const float* pixel_values, const float* time, const float* labels, float* loss, float* prediction,
-                              hipStream_t stream) {
+// loss [1] <- what model(pixel_values, time, labels=labels, pixel_mask=pixel_mask).loss returns, prediction (may be NULL) <- its output
+// (the labels at the masked positions): the step's forward alone.  No state buffer is written.  pixel_mask: device bytes of the plan's
+// mask size on a masked plan, NULL on any other.
+extern "C" int scot_plan_loss_masked(void* plan, const float* pixel_values, const float* time, const float* labels, const void* pixel_mask,
+                                     float* loss, float* prediction, hipStream_t stream) {
   Plan* pl = as_plan(plan);
   if (!pl) return SCOT_ERR_SHAPE;
-  int rc = check_batch(pl, pixel_values, time, labels);
+  int rc = check_batch(pl, pixel_values, time, labels, pixel_mask);
   if (rc != SCOT_OK) return rc;
   if (!loss) return SCOT_ERR_SHAPE;
-  if (!copy_batch_in(pl, pixel_values, time, labels, stream)) return SCOT_ERR_LAUNCH;
+  if (!copy_batch_in(pl, pixel_values, time, labels, pixel_mask, stream)) return SCOT_ERR_LAUNCH;
   rc = replay(pl, SCOT_PLAN_CALLS_STEP_FORWARD, stream);
   if (rc != SCOT_OK) return rc;
   if (!dev_copy(loss, span_ptr(pl, pl->train, SCOT_PLAN_TR_LOSS), 4, D2D, stream)) return SCOT_ERR_LAUNCH;
@@ -932,21 +967,32 @@ extern "C" int scot_plan_loss(void* plan, const float* pixel_values, const float
   return SCOT_OK;
 }
 
+// the unmasked batch: on a masked plan the mask is missing (-1)
+extern "C" int scot_plan_loss(void* plan, const float* pixel_values, const float* time, const float* labels, float* loss, float* prediction,
+                              hipStream_t stream) {
+  return scot_plan_loss_masked(plan, pixel_values, time, labels, nullptr, loss, prediction, stream);
+}
+
 // One optimizer step on the batch: forward, loss, backward, update (include/scot_plan.h).  lr is HOST memory, read before the call
 // returns: it goes into the plan's own array, which the recorded scot_adamw_step call reads when it is issued.
-extern "C" int scot_plan_train_step(void* plan, const float* pixel_values, const float* time, const float* labels, const float* lr, float* loss,
-                                    hipStream_t stream) {
+extern "C" int scot_plan_train_step_masked(void* plan, const float* pixel_values, const float* time, const float* labels, const void* pixel_mask,
+                                           const float* lr, float* loss, hipStream_t stream) {
   Plan* pl = as_plan(plan);
   if (!pl) return SCOT_ERR_SHAPE;
-  int rc = check_batch(pl, pixel_values, time, labels);
+  int rc = check_batch(pl, pixel_values, time, labels, pixel_mask);
   if (rc != SCOT_OK) return rc;
   if (!lr || !pl->lr) return SCOT_ERR_SHAPE;
-  if (!copy_batch_in(pl, pixel_values, time, labels, stream)) return SCOT_ERR_LAUNCH;
+  if (!copy_batch_in(pl, pixel_values, time, labels, pixel_mask, stream)) return SCOT_ERR_LAUNCH;
   memcpy(pl->lr, lr, (size_t)pl->train[SCOT_PLAN_TR_GROUPS] * sizeof(float));
   for (int s = 0; s < 3; ++s)
     if ((rc = replay(pl, SCOT_PLAN_CALLS_STEP_FORWARD + s, stream)) != SCOT_OK) return rc;
   if (loss && !dev_copy(loss, span_ptr(pl, pl->train, SCOT_PLAN_TR_LOSS), 4, D2D, stream)) return SCOT_ERR_LAUNCH;
   return SCOT_OK;
+}
+
+extern "C" int scot_plan_train_step(void* plan, const float* pixel_values, const float* time, const float* labels, const float* lr, float* loss,
+                                    hipStream_t stream) {
+  return scot_plan_train_step_masked(plan, pixel_values, time, labels, nullptr, lr, loss, stream);
 }
 
 // out[6]: steps applied, steps skipped, gradient scale (1 where it is not dynamic), last gradient norm before clipping, last clip

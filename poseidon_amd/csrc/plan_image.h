@@ -93,7 +93,13 @@ enum { SCOT_PLAN_IO_B, SCOT_PLAN_IO_CIN, SCOT_PLAN_IO_H, SCOT_PLAN_IO_W, SCOT_PL
 enum { SCOT_PLAN_ADJ_FLAGS, SCOT_PLAN_ADJ_COT, SCOT_PLAN_ADJ_DPV = SCOT_PLAN_ADJ_COT + 3, SCOT_PLAN_ADJ_DTIME = SCOT_PLAN_ADJ_DPV + 3,
        SCOT_PLAN_ADJ_STATE = SCOT_PLAN_ADJ_DTIME + 3, SCOT_PLAN_ADJ_COUNTER = SCOT_PLAN_ADJ_STATE + 3,
        SCOT_PLAN_ADJ_SCALE_EXP = SCOT_PLAN_ADJ_COUNTER + 3, SCOT_PLAN_ADJ_KEPT_BYTES };
-/* the training words: FLAGS bit 0 = the gradient scale is dynamic (fp16); a span is (buffer, offset, bytes), bytes 0 = absent */
+/* the training words: FLAGS bit 0 = the gradient scale is dynamic (fp16), bit 1 = the batch has a pixel_mask (the io words name its
+   input buffer, which the recorded scot_head_finalize / scot_loss_bwd entries read), bit 2 = it is an element mask [B, Cout, H, W] and
+   not a channel mask [B, Cout] (a library from before the masks rejects FLAGS > 1: it cannot train unmasked on such an image); a span
+   is (buffer, offset, bytes), bytes 0 = absent */
+#define SCOT_PLAN_TR_FLAG_DYNAMIC 1
+#define SCOT_PLAN_TR_FLAG_MASK 2
+#define SCOT_PLAN_TR_FLAG_MASK_FULL 4
 enum { SCOT_PLAN_TR_FLAGS, SCOT_PLAN_TR_GROUPS, SCOT_PLAN_TR_ARENA_FLOATS, SCOT_PLAN_TR_FWD, SCOT_PLAN_TR_BWD = SCOT_PLAN_TR_FWD + 3,
        SCOT_PLAN_TR_UPD = SCOT_PLAN_TR_BWD + 3, SCOT_PLAN_TR_LR_ENTRY = SCOT_PLAN_TR_UPD + 3, SCOT_PLAN_TR_LR_ARG, SCOT_PLAN_TR_KEPT_BYTES,
        SCOT_PLAN_TR_LABELS, SCOT_PLAN_TR_LOSS = SCOT_PLAN_TR_LABELS + 3, SCOT_PLAN_TR_PRED = SCOT_PLAN_TR_LOSS + 3,
@@ -320,7 +326,15 @@ static inline int scot_plan_training_ok(const scot_plan_view* v) {
   const uint64_t* io = v->io;
   const scot_plan_calls* upd = &v->calls[SCOT_PLAN_CALLS_UPDATE];
   const uint64_t groups = t[SCOT_PLAN_TR_GROUPS], floats = t[SCOT_PLAN_TR_ARENA_FLOATS];
-  if (t[SCOT_PLAN_TR_FLAGS] > 1 || groups < 1 || groups > 8 || floats == 0 || floats % 8 || floats > ((uint64_t)1 << 36)) return SCOT_PLAN_ERR_SHAPE;
+  const uint64_t flags = t[SCOT_PLAN_TR_FLAGS];
+  if (flags > 7 || groups < 1 || groups > 8 || floats == 0 || floats % 8 || floats > ((uint64_t)1 << 36)) return SCOT_PLAN_ERR_SHAPE;
+  /* the batch's pixel_mask: the io words hold a mask input exactly when FLAGS says the batch has one, of the bytes its kind needs */
+  if (((flags & SCOT_PLAN_TR_FLAG_MASK) != 0) != (io[SCOT_PLAN_IO_HAS_MASK] != 0)) return SCOT_PLAN_ERR_SHAPE;
+  if ((flags & SCOT_PLAN_TR_FLAG_MASK_FULL) && !(flags & SCOT_PLAN_TR_FLAG_MASK)) return SCOT_PLAN_ERR_SHAPE;
+  if ((flags & SCOT_PLAN_TR_FLAG_MASK) &&
+      io[SCOT_PLAN_IO_MASK_BYTES] != io[SCOT_PLAN_IO_B] * io[SCOT_PLAN_IO_COUT] *
+                                         ((flags & SCOT_PLAN_TR_FLAG_MASK_FULL) ? io[SCOT_PLAN_IO_H] * io[SCOT_PLAN_IO_W] : 1))
+    return SCOT_PLAN_ERR_SHAPE;
   for (int c = SCOT_PLAN_CALLS_STEP_FORWARD; c <= SCOT_PLAN_CALLS_UPDATE; ++c)
     if (!v->calls[c].n) return SCOT_PLAN_ERR_SHAPE;
   if (t[SCOT_PLAN_TR_LR_ENTRY] >= upd->n) return SCOT_PLAN_ERR_SHAPE;

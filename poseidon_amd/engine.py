@@ -1755,8 +1755,15 @@ class ScOTEngine:
             if labels is None:
                 raise ValueError("pixel_mask needs labels")
             mask_full = pixel_mask.dim() != 2
-            mask_u8 = self.new(*((B, Cout, H, W) if mask_full else pixel_mask.shape), dtype=torch.uint8)
-            self.tdo(lambda: mask_u8.copy_(pixel_mask.expand(B, Cout, H, W) if mask_full else pixel_mask))
+            if self._export is not None and self._export.mask_u8 is not None:
+                # a masked training plan: the plan's mask INPUT is this byte tensor (the caller's bytes are copied into it before the
+                # list is replayed), so the recorded list stays C-ABI calls only
+                mask_u8 = self._export.mask_u8
+                if tuple(mask_u8.shape) != ((B, Cout, H, W) if mask_full else (B, Cout)):
+                    raise ValueError("the export's mask input does not have the pixel_mask's shape")
+            else:
+                mask_u8 = self.new(*((B, Cout, H, W) if mask_full else pixel_mask.shape), dtype=torch.uint8)
+                self.tdo(lambda: mask_u8.copy_(pixel_mask.expand(B, Cout, H, W) if mask_full else pixel_mask))
         sums = None
         if labels is not None or pv_res is not None:
             sums = self.zeros(2 * meta["G"]) if meta else None

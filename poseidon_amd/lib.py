@@ -145,6 +145,12 @@ PLAN_PROTOTYPES = {
     "scot_error_sums_workspace_bytes": [I, I, I, P, I],
     "scot_error_sums": [P, P, I, I, I, P, I, P, P, Z, P],
     "scot_plan_evaluate": [P, P, P, P, I, P, I, P, P, P],
+    # pixel masks: the error sums of where(mask, target, pred) in the same pass (mask bytes [B, C] or [B, C, HW]; overwrite stores the
+    # targets over pred there), a rollout scored that way, and the batch of a masked training plan
+    "scot_error_sums_masked": [P, P, P, I, I, I, I, I, P, I, P, P, Z, P],
+    "scot_plan_evaluate_masked": [P, P, P, P, P, I, I, P, I, P, P, P],
+    "scot_plan_loss_masked": [P, P, P, P, P, P, P, P],
+    "scot_plan_train_step_masked": [P, P, P, P, P, P, P, P],
 }
 _VOID = {"scot_set_use_tr", "scot_gemm_wide_config", "scot_gemm_splitk_config"}
 _SIZE = {"scot_gemm_workspace_bytes", "scot_wgrad_group_workspace_bytes", "scot_cln_bwd_workspace_bytes", "scot_wgrad_mlp_workspace_bytes",

@@ -806,17 +806,19 @@ _slice_arrays = {}          # channel slices -> the host int array the call read
 def _error_sums_lib():
     l = _raw()
     if id(l) not in _error_sums_typed:
-        for name in ("scot_error_sums_workspace_bytes", "scot_error_sums"):
+        for name in ("scot_error_sums_workspace_bytes", "scot_error_sums", "scot_error_sums_masked"):
             fn = getattr(l, name)
             fn.argtypes, fn.restype = _lib.PLAN_PROTOTYPES[name], _lib.restype(name)
         _error_sums_typed[id(l)] = l
     return l
 
 
-def error_sums(pred, target, channel_slices, sums):
+def error_sums(pred, target, channel_slices, sums, mask_u8=None, mask_full=False):
     """sums [B, G, 4] (float64) <- {sum |p - t|, sum |t|, sum (p - t)^2, sum t^2} per sample and channel group of pred against target
     (float32 [B, C, ...], contiguous): scot_error_sums (include/scot_plan.h), two launches.  channel_slices: G + 1 ascending ints, or
-    None for the one group of all channels.  A model-level call: it goes to the library itself, never onto a step tape."""
+    None for the one group of all channels.  A model-level call: it goes to the library itself, never onto a step tape.
+    mask_u8 (uint8 [B, C], or with mask_full [B, C, ...]): the sums of where(mask, target, pred) instead, by scot_error_sums_masked in
+    the same pass with overwrite = 0: pred is read only."""
     B, C = int(pred.shape[0]), int(pred.shape[1])
     HW = pred.numel() // max(1, B * C)
     groups, arr = 1, None
@@ -831,4 +833,8 @@ def error_sums(pred, target, channel_slices, sums):
     if need == 0:
         raise ValueError(f"error_sums: shape {tuple(pred.shape)} with channel slices {channel_slices}")
     ws = workspace(need)
+    if mask_u8 is not None:
+        _lib.check(l.scot_error_sums_masked(ptr(pred), ptr(target), ptr(mask_u8), int(bool(mask_full)), 0, B, C, HW, arr, groups, ptr(sums),
+                                            ptr(ws), ws.numel(), stream()), "scot_error_sums_masked")
+        return
     _lib.check(l.scot_error_sums(ptr(pred), ptr(target), B, C, HW, arr, groups, ptr(sums), ptr(ws), ws.numel(), stream()), "scot_error_sums")

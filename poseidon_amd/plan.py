@@ -72,7 +72,9 @@ ENTRY_POINT_TABLES = {"forward": ("scot_plan_entry_point", "SCOT_PLAN_ENTRY_POIN
                       "adjoint": ("scot_plan_adjoint_entry_point", "SCOT_PLAN_ADJOINT_ENTRY_POINTS"),
                       "training": ("scot_plan_training_entry_point", "SCOT_PLAN_TRAINING_ENTRY_POINTS")}
 DESCRIBE_STREAMS = ("streams", "events", "overlaps", "host_stream")
-DESCRIBE_TRAINING = ("has_training", "groups", "arena_floats", "step_calls", "labels_bytes", "kept_bytes", "dynamic_scale")
+DESCRIBE_TRAINING = ("has_training", "groups", "arena_floats", "step_calls", "labels_bytes", "kept_bytes", "dynamic_scale", "mask")
+TR_FLAG_DYNAMIC, TR_FLAG_MASK, TR_FLAG_MASK_FULL = 1, 2, 4      # SCOT_PLAN_TR_FLAGS: bit 1 = the batch has a mask, bit 2 = an element mask
+(IO_HAS_MASK, IO_MASK_BUF) = (11, 12)      # SCOT_PLAN_IO_HAS_MASK, then (buffer, offset, bytes)
 TRAIN_STATUS = ("applied", "skipped", "grad_scale", "grad_norm", "clip_coef", "nonfinite")
 # host arrays of floats among the recorded arguments: {entry point: {argument index: index of the argument that holds the count}}
 HOST_FLOAT_ARRAYS = {"scot_adamw_step": {6: 8, 7: 8}}
@@ -117,6 +119,7 @@ class _Registry:
     def __init__(self):
         self.bufs = {}      # address -> dict(addr, bytes, kind, name, tensor)
         self.streams = None      # a two-stream recording: {stream handle: index} — the current stream 0, the engine's side stream 1
+        self.mask_u8 = None      # a masked training recording: the mask INPUT, which the engine uses as its byte mask as it stands
 
     def add(self, t, kind, name, stored=False):
         """stored: a STATE buffer the image holds by value (a training plan's; otherwise the runtime zeroes it at load)"""
@@ -158,10 +161,7 @@ def _check_request(model, pixel_values, time, pixel_mask, labels, train=None):
     cfg = model.config
     if labels is not None and train is None:
         raise PlanExportError("export_plan: labels are not part of a plan (it covers the inference forward: no loss)")
-    if train is not None and pixel_mask is not None:
-        raise PlanExportError("export_plan: pixel_mask is not part of a training plan: the mask is one more per-batch input and the "
-                              "recorded loss has no mask argument")
-    if pixel_mask is not None:
+    if pixel_mask is not None and train is None:
         raise PlanExportError("export_plan: pixel_mask overwrites the prediction with label values (reference model.py:1411-1484) and a "
                               "plan takes no labels: apply the mask to the plan's prediction in the host program")
     if pixel_values is None or pixel_values.dim() != 4:
@@ -184,6 +184,24 @@ def _check_request(model, pixel_values, time, pixel_mask, labels, train=None):
                               "random masks on the host; call model.eval() first")
     if cfg.use_conditioning and time is None:
         raise PlanExportError("export_plan: time is required when use_conditioning=True")
+    if pixel_mask is not None:
+        _mask_bytes(pixel_mask, pixel_values.shape[0], cfg.num_out_channels, pixel_values.shape[2], pixel_values.shape[3],
+                    PlanExportError, "export_plan: ")
+
+
+def _mask_bytes(m, B, Cout, H, W, error=ValueError, prefix=""):
+    """the reference's pixel_mask in one of the forms a masked training plan takes -> (uint8 tensor: the plan's mask input, whether it
+    is an element mask).  bool (or uint8) [B, Cout]: a channel mask, B * Cout bytes; [B, Cout, H, W]: an element mask; [B, 1, H, W]:
+    expanded over the channels into an element mask.  Anything else: `error`, naming pixel_mask."""
+    import torch
+    ok = hasattr(m, "dim") and m.dtype in (torch.bool, torch.uint8)
+    shape = tuple(m.shape) if hasattr(m, "shape") else None
+    if ok and shape == (B, Cout):
+        return (m != 0).to(torch.uint8).contiguous(), False
+    if ok and shape in ((B, Cout, H, W), (B, 1, H, W)):
+        return (m != 0).to(torch.uint8).expand(B, Cout, H, W).contiguous(), True
+    raise error(f"{prefix}pixel_mask is {'a ' + str(m.dtype) + ' tensor of shape ' + str(shape) if shape is not None else repr(type(m))}: a "
+                f"training plan takes a bool mask of shape {(B, Cout)} (whole planes), {(B, Cout, H, W)} or {(B, 1, H, W)} (elements)")
 
 
 def _check_adjoint(model, adjoint):
@@ -347,13 +365,16 @@ def _training_state(model, opt):
     return ts
 
 
-def _record_training(model, opt, pv, t, labels, streams=1):
+def _record_training(model, opt, pv, t, labels, streams=1, mask=None):
     """-> (registry, recorded calls, kept tensors, inference prediction, input copies, training record): ONE linear recording of four
     lists on one stream — the inference forward; the step's forward through the loss; the fill of the accumulated gradients, the
     backward from d loss = 1 with the store-form weight gradients and the un-scale passes; what FusedAdamW.step issues.  The recording
     run IS a step on the model's own tensors, so everything it changes is saved before and put back afterwards.
     streams=2: the engine's two-stream step; the fill is the side stream's first task of the step backward, and the main stream waits for
-    it before the backward's first entry."""
+    it before the backward's first entry.
+    mask (uint8 [B, Cout] or [B, Cout, H, W]): the step is recorded with a pixel_mask.  The engine's own byte mask is a fresh tensor it
+    fills with a torch copy — no C-ABI call —, so the export hands it the plan's mask INPUT to use as that tensor (engine._forward): the
+    recorded scot_head_finalize / scot_loss_bwd name the input buffer, and the runtime copies the caller's bytes there."""
     import torch
     from . import ops
     eng = model._engine
@@ -362,6 +383,10 @@ def _record_training(model, opt, pv, t, labels, streams=1):
     pv_in, t_in = _input_copies(reg, pv, t)
     lab_in = labels.clone()
     reg.add(lab_in, INPUT, "labels")
+    mask_in = None
+    if mask is not None:
+        mask_in = reg.mask_u8 = mask.clone()
+        reg.add(mask_in, INPUT, "pixel_mask")
     one = None
     if not eng.scale_grads:      # d loss = 1 as a constant of the image (under a gradient scale the backward copies S from the state)
         one = torch.ones(1, dtype=torch.float32, device=pv.device)
@@ -388,7 +413,7 @@ def _record_training(model, opt, pv, t, labels, streams=1):
         eng._fwd_flags = ((), True)
         _, pred, _ = eng._forward(pv_in, t_in, None, None, False)
         n_inf = len(rec)
-        loss, pred_step, tape = eng._forward(pv_in, t_in, lab_in, None, True)
+        loss, pred_step, tape = eng._forward(pv_in, t_in, lab_in, mask_in, True)
         n_fwd = len(rec)
         _register(reg, eng.plan_buffers(train=opt), only_new=True)
         lazy = eng._small_chunks is not None      # ScOT.zero_grad(overlap=True): only what is accumulated into is filled
@@ -407,7 +432,7 @@ def _record_training(model, opt, pv, t, labels, streams=1):
         opt.step()
         keep.append(tape)
     _register(reg, eng.plan_buffers(train=opt), only_new=True)      # (tables the step created on first use)
-    tr = dict(n_inf=n_inf, n_fwd=n_fwd, n_bwd=n_bwd, labels=lab_in, loss=loss, pred=pred_step, opt=opt)
+    tr = dict(n_inf=n_inf, n_fwd=n_fwd, n_bwd=n_bwd, labels=lab_in, loss=loss, pred=pred_step, opt=opt, mask=mask_in)
     return reg, rec, keep, pred, pv_in, t_in, tr
 
 
@@ -651,7 +676,9 @@ def _training_words(eng, loc, train, names, lr_point, step_forward, step_backwar
                                 (TR_COUNTER, eng.grad_overflow, "the non-finite counter", STATE)):
         if t is not None:
             w[slot:slot + 3] = loc.span(t, what, kind)
-    w[TR_FLAGS] = 1 if eng.scale_grads else 0
+    w[TR_FLAGS] = TR_FLAG_DYNAMIC if eng.scale_grads else 0
+    if train.get("mask") is not None:
+        w[TR_FLAGS] |= TR_FLAG_MASK | (TR_FLAG_MASK_FULL if train["mask"].dim() == 4 else 0)
     w[TR_GROUPS], w[TR_ARENA_FLOATS] = lr_point[2], eng.arena.size
     w[TR_LR_ENTRY], w[TR_LR_ARG] = lr_point[0], lr_point[1]
     w[TR_KEPT_BYTES] = loc.kept_bytes(step_forward, step_backward)
@@ -693,6 +720,9 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=N
     if t_in is not None:
         io[7] = 1
         io[8:11] = loc.span(t_in, "the time copy", INPUT)
+    if train is not None and train.get("mask") is not None:
+        io[IO_HAS_MASK] = 1
+        io[IO_MASK_BUF:IO_MASK_BUF + 3] = loc.span(train["mask"], "the mask copy", INPUT)
     io[15:17] = loc.span(pred, "the prediction", OUTPUT)[:2]
     adj_words = _adjoint_words(eng, loc, adj, forward, *others) if adj is not None else None
     tr_words = _training_words(eng, loc, train, names, lr_point, *others) if train is not None else None
@@ -767,6 +797,9 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
     the prediction to these inputs' gradients (scot_plan_vjp), and its forward is the one a differentiable call runs.
     train: a FusedAdamW over this model, with labels — the image (format 4) then also holds one optimizer step and the training state by
     value (scot_plan_train_step, scot_plan_snapshot); the model and the optimizer are left as they were.
+    pixel_mask (with train= only): bool [B, Cout] (a channel mask), [B, Cout, H, W] or [B, 1, H, W] (an element mask) — the step is
+    recorded with the reference's mask (`prediction[pixel_mask] = labels[pixel_mask]` before the loss), the image has the mask as one
+    more input, and every batch brings its own (scot_plan_loss_masked, scot_plan_train_step_masked).
     streams: 1, or 2 — the image (format 5, with train= format 6) then holds the engine's two-stream program, and the runtime runs the
     bias tables, the skip blocks and the weight gradients on a side stream of its own beside the main chain.  Not with adjoint=."""
     import torch
@@ -794,7 +827,11 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
     bind(own)
     with torch.no_grad():
         if train is not None:
-            image = _export_training(model, train, pv, t, labels.detach().to(device=dev, dtype=torch.float32).contiguous(), own, peer, streams)
+            mask = None
+            if pixel_mask is not None:
+                mask = _mask_bytes(pixel_mask, pv.shape[0], model.config.num_out_channels, pv.shape[2], pv.shape[3])[0].to(dev)
+            image = _export_training(model, train, pv, t, labels.detach().to(device=dev, dtype=torch.float32).contiguous(), own, peer, streams,
+                                     mask)
         else:
             image = _export_frozen(model, pv, t, adjoint, own, peer, streams)
     if path is not None:
@@ -865,26 +902,27 @@ def _export_frozen(model, pv, t, adjoint, own, peer, streams=1):
     return image
 
 
-def _export_training(model, opt, pv, t, lab, own, peer, streams=1):
+def _export_training(model, opt, pv, t, lab, own, peer, streams=1, mask=None):
     """record, build, and check through the runtime: scratch poisoned, one scot_plan_loss and one scot_plan_train_step on the export
     inputs — the engine's own prediction bits, a finite loss, finite parameters.  The image that is returned holds the pre-step state."""
     import torch
     eng = model._engine
-    _, ref, tape = eng.forward(pv, t, lab, None, train=True, stochastic=False, param_grads=True)      # the engine's own prediction
+    # the engine's own prediction (under a mask: with the labels at the masked positions)
+    _, ref, tape = eng.forward(pv, t, lab, None if mask is None else mask != 0, train=True, stochastic=False, param_grads=True)
     ref = ref.clone()
     del tape
-    reg, rec, keep, pred, pv_in, t_in, tr = _record_training(model, opt, pv, t, lab, streams)
+    reg, rec, keep, pred, pv_in, t_in, tr = _record_training(model, opt, pv, t, lab, streams, mask)
     image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer, train=tr, streams=streams)
     del keep
     with _self_check(image, own, peer) as plan:
-        loss, got = plan.loss(pv, t, lab)
+        loss, got = plan.loss(pv, t, lab, pixel_mask=mask)
         if not torch.equal(got, ref):
             raise PlanExportError("export_plan: the training plan's prediction differs from the engine's own "
                                   f"(max |difference| {float((got - ref).abs().max()):.3e})")
         if not bool(torch.isfinite(loss).all()):
             raise PlanExportError("export_plan: the training plan's loss is not finite with poisoned scratch")
         plan.poison(0xFF)
-        loss = plan.train_step(pv, t, lab, [float(g["lr"]) for g in opt.param_groups])
+        loss = plan.train_step(pv, t, lab, [float(g["lr"]) for g in opt.param_groups], pixel_mask=mask)
         if not bool(torch.isfinite(loss).all()):
             raise PlanExportError("export_plan: the loss of the training plan's step is not finite with poisoned scratch")
         after = training_state(plan.snapshot(image))
@@ -1130,14 +1168,19 @@ class Plan:
                    int(steps), self._stream(stream, pixel_values))
         return out.transpose(0, 1).contiguous() if tensors and _is_tensor(out) else out
 
-    def evaluate(self, pixel_values, time, targets, steps=1, channel_slice_list=None, predictions=False, stream=None):
+    def evaluate(self, pixel_values, time, targets, steps=1, channel_slice_list=None, predictions=False, stream=None, pixel_mask=None,
+                 mask_full=None):
         """-> error sums, float64 [steps, B, G, 4]: per step, sample and channel group `[channel_slice_list[g], channel_slice_list[g+1])`
         of the Cout output channels (None: one group) the sums Σ|p−t|, Σ|t|, Σ(p−t)², Σt² of the prediction against `targets`
         (scot_plan_evaluate; scOT.metrics' `*_from_sums` turn them into the reference's metrics).  steps == 1: one forward, as `run`,
         targets [B, Cout, H, W]; steps > 1: the chain of `rollout`, targets [B, steps, Cout, H, W] as `rollout` returns predictions.
         predictions=True: -> (sums, predictions [B, steps, Cout, H, W]); otherwise no prediction leaves the plan.
         With raw addresses `targets` is in the C layout [steps][B, Cout, H, W] and `predictions` is None or the address of a buffer in
-        that layout; the sums still come back as a tensor (on the GPU where there is one)."""
+        that layout; the sums still come back as a tensor (on the GPU where there is one).
+        pixel_mask (scot_plan_evaluate_masked): bool or uint8 [B, Cout] (whole planes) or [B, Cout, H, W] / [B, 1, H, W] (elements), the
+        same for every step — or a raw address with mask_full=.  After every forward the targets of that step are stored over the
+        masked positions of the prediction, as the reference's `prediction[pixel_mask] = labels[pixel_mask]` does: the sums, the next
+        step's input and the returned predictions carry them.  The channel slices have to tile all Cout channels then."""
         import torch
         steps = int(steps)
         if steps < 1:
@@ -1168,8 +1211,13 @@ class Plan:
             device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
             out = predictions or None
         sums = torch.empty(steps, self.info["batch"], groups, 4, dtype=torch.float64, device=device)
-        self._call("scot_plan_evaluate", _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(targets, "targets"), steps, slices, groups,
-                   sums.data_ptr(), _addr(out, "predictions"), self._stream(stream, pixel_values))
+        if pixel_mask is not None:
+            mask, full = self._mask(pixel_mask, pixel_values if tensors else None, mask_full)
+            self._call("scot_plan_evaluate_masked", _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(targets, "targets"), mask,
+                       int(full), steps, slices, groups, sums.data_ptr(), _addr(out, "predictions"), self._stream(stream, pixel_values))
+        else:
+            self._call("scot_plan_evaluate", _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(targets, "targets"), steps, slices,
+                       groups, sums.data_ptr(), _addr(out, "predictions"), self._stream(stream, pixel_values))
         if out is None:
             return sums
         return sums, (out.transpose(0, 1).contiguous() if tensors and _is_tensor(out) else out)
@@ -1231,39 +1279,67 @@ class Plan:
         self._call("scot_plan_describe_training", out)
         return dict(zip(DESCRIBE_TRAINING, [int(x) for x in out]))
 
-    def _batch(self, pixel_values, time, labels):
+    def _mask(self, pixel_mask, like=None, full=None):
+        """a pixel_mask as the runtime reads it -> (address or None, whether it is an element mask): a bool / uint8 tensor [B, Cout]
+        (whole planes) or [B, Cout, H, W] / [B, 1, H, W] (elements) becomes contiguous bytes on `like`'s device, held until the next
+        call; a raw address passes through with `full`"""
+        if pixel_mask is None or isinstance(pixel_mask, int):
+            return pixel_mask, bool(full)
+        if not _is_tensor(pixel_mask):
+            raise TypeError("pixel_mask: a tensor or a raw device address")
+        m, full = _mask_bytes(pixel_mask, *self._shape("out_channels"))
+        if like is not None and _is_tensor(like):
+            m = m.to(like.device)
+        self._held_mask = m
+        return m.data_ptr(), full
+
+    def _batch(self, pixel_values, time, labels, pixel_mask=None):
         if _is_tensor(pixel_values):
             self._require(pixel_values, "pixel_values")
             self._require(labels, "labels", "out_channels")
             time = self._time(time)
-        return _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(labels, "labels")
+        mask, full = self._mask(pixel_mask, pixel_values)
+        if mask is not None and _is_tensor(pixel_mask) and self.describe_training()["mask"] not in (0, 2 if full else 1):
+            raise ValueError(f"this plan was exported with {'a channel' if full else 'an element'} mask")
+        return _addr(pixel_values, "pixel_values"), _addr(time, "time"), _addr(labels, "labels"), mask
 
-    def loss(self, pixel_values, time, labels, out=None, stream=None):
+    def loss(self, pixel_values, time, labels, out=None, stream=None, pixel_mask=None):
         """-> (loss [1], prediction) of the step's forward at the current weights (scot_plan_loss); changes no state.  out: (loss buffer,
-        prediction buffer or None), required with raw addresses."""
-        pv, t, lab = self._batch(pixel_values, time, labels)
+        prediction buffer or None), required with raw addresses.  pixel_mask: the batch's mask on a masked plan (scot_plan_loss_masked;
+        bool or uint8 [B, Cout] / [B, Cout, H, W] / [B, 1, H, W], or the address of the plan's mask bytes): the prediction then holds the
+        labels at the masked positions."""
+        pv, t, lab, mask = self._batch(pixel_values, time, labels, pixel_mask)
         if out is None:
             if not _is_tensor(pixel_values):
                 raise ValueError("raw addresses need `out`")
             import torch
             out = (torch.empty(1, dtype=torch.float32, device=pixel_values.device), self._empty(pixel_values))
-        self._call("scot_plan_loss", pv, t, lab, _addr(out[0], "loss"), _addr(out[1], "prediction"), self._stream(stream, pixel_values))
+        if pixel_mask is None:
+            self._call("scot_plan_loss", pv, t, lab, _addr(out[0], "loss"), _addr(out[1], "prediction"), self._stream(stream, pixel_values))
+        else:
+            self._call("scot_plan_loss_masked", pv, t, lab, mask, _addr(out[0], "loss"), _addr(out[1], "prediction"),
+                       self._stream(stream, pixel_values))
         return out
 
-    def train_step(self, pixel_values, time, labels, lr, out=None, stream=None):
+    def train_step(self, pixel_values, time, labels, lr, out=None, stream=None, pixel_mask=None):
         """one optimizer step on the batch (scot_plan_train_step) -> the loss before the update ([1], on the device).  lr: one float
-        per parameter group, in the export's group order (a single float: the same for all).  out: a loss buffer of the caller's."""
+        per parameter group, in the export's group order (a single float: the same for all).  out: a loss buffer of the caller's.
+        pixel_mask: the batch's mask on a masked plan, as for `loss` (scot_plan_train_step_masked)."""
         groups = self.describe_training()["groups"]
         lr = [float(lr)] * groups if isinstance(lr, (int, float)) else [float(x) for x in lr]
         if len(lr) != groups:
             raise ValueError(f"this plan has {groups} parameter groups, lr has {len(lr)} values")
-        pv, t, lab = self._batch(pixel_values, time, labels)
+        pv, t, lab, mask = self._batch(pixel_values, time, labels, pixel_mask)
         if out is None and _is_tensor(pixel_values):
             import torch
             out = torch.empty(1, dtype=torch.float32, device=pixel_values.device)
         rates = (ctypes.c_float * max(1, groups))(*lr)
-        self._call("scot_plan_train_step", pv, t, lab, ctypes.cast(rates, ctypes.c_void_p), _addr(out, "loss"),
-                   self._stream(stream, pixel_values))
+        if pixel_mask is None:
+            self._call("scot_plan_train_step", pv, t, lab, ctypes.cast(rates, ctypes.c_void_p), _addr(out, "loss"),
+                       self._stream(stream, pixel_values))
+        else:
+            self._call("scot_plan_train_step_masked", pv, t, lab, mask, ctypes.cast(rates, ctypes.c_void_p), _addr(out, "loss"),
+                       self._stream(stream, pixel_values))
         return out
 
     def train_status(self, stream=None):

@@ -120,11 +120,26 @@ def channel_group_metrics(preds, targets, channel_slice_list: Sequence[int], cha
 SUM_ABS_ERR, SUM_ABS, SUM_SQ_ERR, SUM_SQ = range(4)      # the last axis of error sums: S1, N1, S2, N2 (include/scot_plan.h)
 
 
-def error_sums(preds, targets, channel_slice_list: Optional[Sequence[int]] = None) -> torch.Tensor:
+def _mask_like(pixel_mask, pr):
+    """the reference's pixel_mask against predictions [N, C, ...] -> (bool mask [N, C] or of pr's shape, whether it is element-wise):
+    [N, C] masks whole planes; pr's own shape, or [N, 1, ...], masks elements (expanded over the channels)"""
+    m = _t(pixel_mask)
+    m = (m != 0) if m.dtype != torch.bool else m
+    if m.dim() == 2 and tuple(m.shape) == tuple(pr.shape[:2]):
+        return m, False
+    if m.dim() == pr.dim() and m.shape[0] == pr.shape[0] and m.shape[1] in (1, pr.shape[1]) and m.shape[2:] == pr.shape[2:]:
+        return m.expand(pr.shape), True
+    raise ValueError(f"error_sums: pixel_mask of shape {tuple(m.shape)} against predictions {tuple(pr.shape)}")
+
+
+def error_sums(preds, targets, channel_slice_list: Optional[Sequence[int]] = None, pixel_mask=None) -> torch.Tensor:
     """[N, G, 4] float64: per sample and channel group `[channel_slice_list[g], channel_slice_list[g+1])` (None: one group of all
     channels) the sums Σ|p−t|, Σ|t|, Σ(p−t)², Σt² over the group's channels and all pixels.  GPU tensors go through the
     `scot_error_sums` kernel (one pass over both operands, no temporaries; the result stays on the device); numpy arrays and CPU
-    tensors use a plain fp64 computation.  Both convert the fp32 values to fp64 first, then subtract."""
+    tensors use a plain fp64 computation.  Both convert the fp32 values to fp64 first, then subtract.
+    pixel_mask (bool or uint8: [N, C] whole planes, or the predictions' shape, or [N, 1, ...] expanded over the channels): the sums of
+    `where(pixel_mask, targets, preds)`, what the reference scores after `prediction[pixel_mask] = labels[pixel_mask]` — on the GPU by
+    `scot_error_sums_masked` in the same pass (the predictions are not modified)."""
     pr, tg = _t(preds), _t(targets)
     if pr.shape != tg.shape or pr.dim() < 2:
         raise ValueError(f"error_sums: predictions {tuple(pr.shape)} against targets {tuple(tg.shape)}")
@@ -132,13 +147,18 @@ def error_sums(preds, targets, channel_slice_list: Optional[Sequence[int]] = Non
     slices = [0, c] if channel_slice_list is None else [int(s) for s in channel_slice_list]
     if len(slices) < 2 or slices[0] < 0 or slices[-1] > c or any(b <= a for a, b in zip(slices, slices[1:])):
         raise ValueError(f"error_sums: channel slices {slices} over {c} channels")
+    mask, mask_full = (None, False) if pixel_mask is None else _mask_like(pixel_mask, pr)
     if pr.is_cuda:
         from poseidon_amd import ops
         pr, tg = pr.to(torch.float32).contiguous(), tg.to(device=pr.device, dtype=torch.float32).contiguous()
         out = torch.empty(n, len(slices) - 1, 4, dtype=torch.float64, device=pr.device)
         if n:
-            ops.error_sums(pr, tg, None if channel_slice_list is None else slices, out)
+            m8 = None if mask is None else mask.to(device=pr.device, dtype=torch.uint8).contiguous()
+            ops.error_sums(pr, tg, None if channel_slice_list is None else slices, out, m8, mask_full)
         return out
+    if mask is not None:
+        mask = mask.to(pr.device)
+        pr = torch.where(mask if mask_full else mask.reshape(n, c, *([1] * (pr.dim() - 2))), tg.to(pr.dtype), pr)
     pr, tg = pr.reshape(n, c, -1).to(torch.float64), tg.reshape(n, c, -1).to(torch.float64)
     d = pr - tg
     per_channel = torch.stack([d.abs().sum(-1), tg.abs().sum(-1), (d * d).sum(-1), (tg * tg).sum(-1)], -1)      # [N, C, 4]

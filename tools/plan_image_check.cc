@@ -6,7 +6,9 @@
 // everything the validator promised is in bounds: the names, every call list, the arrays, the io / adjoint / training words, and the
 // bytes of the constants and of the stored state.  Each file is read into a heap block of exactly its size, so a build with
 // -fsanitize=address,undefined turns any read past a truncated image into an error.  Exit status 0 when every image got the expected
-// answer.
+// answer.  The cases are the callers': tests/plan_support.py (check_images_stand_alone) builds this file with the host sanitizers and hands it
+// the good and the corrupt images of every format — among them masked training images (training flag bits 1 and 2) whose flag and mask
+// input, or whose mask bytes and mask kind, disagree (tests/test_plan_masked_emu_cpu.py).
 #include <stdio.h>
 #include <stdlib.h>
 
