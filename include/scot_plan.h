@@ -27,7 +27,8 @@
  * modes (arena 1x, two moments 2x, two 16-bit copies 1x), 3x in fp32 / bf16x3, plus the small tables.  The runtime owns them after
  * load, scot_plan_run sees the current ones and scot_plan_snapshot writes them back into the image.
  * Weight decay, betas, eps, clipping and the scale schedule are fixed at export; the learning rates are an argument of every step.  Not
- * covered: gradient accumulation, data parallelism, stochastic depth, partially frozen models, a trimmed image.  The reference's
+ * covered: stochastic depth, partially frozen models, a trimmed image.  Gradient accumulation is covered (section "gradient
+ * accumulation" below); data parallelism is composable through scot_plan_gradients and has never been run on more than one GPU.  The reference's
  * pixel_mask is covered: a MASKED training plan (section "pixel masks" below) takes the mask with every batch.  By
  * default it runs on ONE stream, the weight gradients in line (the Python engine puts them on a second stream: measured on
  * Poseidon-B fp16, a plan's step takes 22.7 ms against the Python loop's 19.3 at batch 64, 11.1 against 10.7 at batch 1).
@@ -270,6 +271,58 @@ int scot_plan_loss_masked(scot_plan_t plan, const float* pixel_values, const flo
                           float* loss, float* prediction, scot_stream_t stream);
 int scot_plan_train_step_masked(scot_plan_t plan, const float* pixel_values, const float* time, const float* labels, const void* pixel_mask,
                                 const float* lr, float* loss, scot_stream_t stream);
+
+/* ---- gradient accumulation ---- */
+/* The arena-wide pass behind the calls below, usable alone.  For every element i with map8[i / 8] != 255 (map8: the optimizer's group
+ * map, one byte per 8 floats of the arena, 255 = not a parameter):
+ *   acc == NULL: dst[i] = weight * grad[i]            acc != NULL: dst[i] = acc[i] + weight * grad[i]
+ * and every other float of dst keeps its bits.  The product is rounded to fp32, then the sum: two roundings, never an FMA — bit for bit
+ * what `acc + grad * weight` gives as two eager fp32 torch operations.  With acc == NULL and weight == 1 it is a masked copy that
+ * preserves every non-NaN bit pattern (-0.0, denormals, +-Inf).  Inf and NaN go through: a non-finite grad[i] makes exactly dst[i]
+ * non-finite.  dst == acc (in place) is allowed; dst must not overlap grad.  One launch on `stream`, 8 floats per lane and 16-byte
+ * accesses, no atomics: bitwise repeatable.  -1 (nothing launched, dst untouched): a NULL dst, grad or map8, n == 0 or n % 8 != 0, a
+ * dst, acc or grad that is not 16-byte aligned, a non-finite weight, dst == grad; -4: the launch failed. */
+int scot_grad_accumulate(float* dst, const float* acc, const float* grad, const unsigned char* map8, size_t n, float weight,
+                         scot_stream_t stream);
+/* Workgroups that pass launches for n floats (256 lanes each, two 8-float groups per lane and trip: one sweep of the grid covers
+ * blocks * 4096 floats, longer arenas take further trips). */
+int scot_grad_accumulate_blocks(size_t n);
+/* A training step cut between its backward and its update, for an effective batch larger than the recorded one: M micro-batches into
+ * an fp32 accumulator A, then ONE update from it.
+ *   for k in 0 .. M-1: scot_plan_accumulate(plan, pv_k, t_k, y_k, mask_k, 1.0f / M, k == 0, loss_k, stream);
+ *   scot_plan_apply(plan, lr, stream);
+ * scot_plan_accumulate is one micro-batch: it copies the batch in exactly as scot_plan_train_step_masked does (same checks and refusals;
+ * pixel_mask is NULL exactly on an unmasked plan) and replays the step's forward and backward — the gradient arena then holds this
+ * micro-batch's unscaled gradient g, its non-finite values counted as always — then runs scot_grad_accumulate on `stream` (a
+ * two-stream plan: after the list has joined): first != 0: A = weight * g, discarding whatever was open; first == 0: A = A + weight * g.
+ * loss (device [1], may be NULL) <- the micro-batch's own unweighted loss.  No state buffer changes; the gradient scale does not move
+ * during an accumulation.  A: arena_floats of fp32, allocated and zero-filled at the first such call, held until the plan is freed and
+ * counted in the described device bytes (-4 if that fails); it is 0 outside the parameter positions.  first == 0 with no accumulation
+ * open, or a non-finite weight: -1, nothing launched.
+ * scot_plan_apply is the update: it writes lr (HOST memory, as for scot_plan_train_step) into the plan's array, copies A over the
+ * gradient arena at the parameter positions (scot_grad_accumulate, weight 1), replays the recorded update unchanged and closes the
+ * accumulation.  Clipping, the skip of a non-finite norm, the step counters and the fp16 scale update stay the device's decisions, now
+ * made on the accumulated gradient: ONE update, one scale decision, however many micro-batches; scot_plan_train_status reports them as
+ * before.  Without an open accumulation, or with a NULL lr: -1, nothing launched.
+ * IDENTITY: accumulate(first = 1, weight = 1) followed by apply(lr) is scot_plan_train_step on that batch (x * 1 is exact).
+ * INTERACTIONS while an accumulation is open:
+ *   scot_plan_run, scot_plan_rollout, scot_plan_loss*, scot_plan_evaluate*   allowed (validation between micro-batches): they write neither A
+ *                                                                           nor a state buffer;
+ *   scot_plan_train_step*   -1, nothing launched: end the accumulation with scot_plan_apply, or restart it with first != 0;
+ *   scot_plan_snapshot      allowed; an open accumulation is not part of an image: after a reload the next call needs first != 0;
+ *   scot_plan_poison        also fills A and discards the open accumulation (the next first != 0 call zeroes A again).
+ * On a format-1/2/5 plan the calls of this section that take a plan return -3. */
+int scot_plan_accumulate(scot_plan_t plan, const float* pixel_values, const float* time, const float* labels, const void* pixel_mask,
+                         float weight, int first, float* loss, scot_stream_t stream);
+int scot_plan_apply(scot_plan_t plan, const float* lr, scot_stream_t stream);
+/* *ptr <- the plan's own device buffer, *floats <- its length, the arena's float count: which == 0 the gradient arena the update reads,
+ * which == 1 the accumulator A (-1 while it has never been allocated); any other which: -1.  Valid until the plan is freed.  The host may
+ * read and write them in the plan's stream order.  This is the hook for data parallelism: a host with one plan per GPU all-reduces A —
+ * with the bucket all-reduce of scot_hip.h, or its own — between the last scot_plan_accumulate and scot_plan_apply, and every rank then
+ * takes the same skip decision from the same reduced norm.  Composable, never run on more than one GPU. */
+int scot_plan_gradients(scot_plan_t plan, int which, float** ptr, size_t* floats);
+/* out[2]: micro-batches in the open accumulation (0: none is open), bytes of the accumulator (0 before it is allocated). */
+int scot_plan_accumulation_status(scot_plan_t plan, long long* out);
 
 /* Refused before anything is copied or launched: scot_plan_loss / _train_step / _train_status / _snapshot on a format-1/2 plan: -3
  * (as scot_plan_vjp / scot_plan_rollout_vjp on a training plan); a NULL pixel_values, labels or lr, a NULL loss of scot_plan_loss, a NULL

@@ -155,6 +155,55 @@ extern "C" int scot_optim_finish(int* step_state, const float* clip, float* scal
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
+// Gradient accumulation (include/scot_plan.h: scot_grad_accumulate): dst = weight·grad, or acc + weight·grad, at the parameter
+// positions of the arena (map8 as above); every other float of dst keeps its bits.  One streaming pass, 8 or 12 bytes per parameter.
+// The product is rounded to fp32 and then the sum is: two roundings, never an FMA, so that the result is bit for bit what
+// `acc + grad * weight` gives as two eager torch operations.  A lane takes two 8-float groups per trip, a grid's width apart: their
+// eight (first form: four) 16-byte loads are issued before the first value is used.  No atomics, no LDS: bitwise repeatable.
+constexpr int ACC_PER_TRIP = 2, ACC_MAX_BLOCKS = 2048;
+template <bool ADD>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* dst, const float* acc, const float* __restrict__ g,
+                                                              const uint8_t* __restrict__ map8, size_t n8, float weight) {
+#pragma clang fp contract(off)
+  const size_t width = (size_t)gridDim.x * 256;
+  for (size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x; i0 < n8; i0 += ACC_PER_TRIP * width) {
+    const size_t i1 = i0 + width;
+    const bool on0 = map8[i0] != 255, on1 = i1 < n8 && map8[i1] != 255;
+    float g0[8], g1[8], a0[8], a1[8];
+    if (on0) { ld8(g, SCOT_F32, i0 * 8, g0); if (ADD) ld8(acc, SCOT_F32, i0 * 8, a0); }
+    if (on1) { ld8(g, SCOT_F32, i1 * 8, g1); if (ADD) ld8(acc, SCOT_F32, i1 * 8, a1); }
+    if (on0) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const float p = g0[j] * weight; g0[j] = ADD ? a0[j] + p : p; }
+      st8(dst, SCOT_F32, i0 * 8, g0);
+    }
+    if (on1) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const float p = g1[j] * weight; g1[j] = ADD ? a1[j] + p : p; }
+      st8(dst, SCOT_F32, i1 * 8, g1);
+    }
+  }
+}
+
+static int acc_blocks(size_t n8) {
+  const size_t b = (n8 + 256 * ACC_PER_TRIP - 1) / (256 * ACC_PER_TRIP);
+  return (int)(b > ACC_MAX_BLOCKS ? ACC_MAX_BLOCKS : (b < 1 ? 1 : b));
+}
+
+// workgroups scot_grad_accumulate launches for n floats; one sweep of that grid covers blocks · 256 · 2 · 8 floats
+extern "C" int scot_grad_accumulate_blocks(size_t n) { return acc_blocks(n / 8); }
+
+extern "C" int scot_grad_accumulate(float* dst, const float* acc, const float* grad, const unsigned char* map8, size_t n, float weight,
+                                    hipStream_t stream) {
+  if (!dst || !grad || !map8 || n == 0 || n % 8 || dst == grad || !(fabsf(weight) <= 3.4028234e38f)) return SCOT_ERR_SHAPE;
+  if ((((uintptr_t)dst) | ((uintptr_t)acc) | ((uintptr_t)grad)) & 15) return SCOT_ERR_SHAPE;
+  const dim3 grid(acc_blocks(n / 8)), block(256);
+  if (acc) hipLaunchKernelGGL(grad_accumulate_kernel<true>, grid, block, 0, stream, dst, acc, grad, map8, n / 8, weight);
+  else hipLaunchKernelGGL(grad_accumulate_kernel<false>, grid, block, 0, stream, dst, (const float*)nullptr, grad, map8, n / 8, weight);
+  return scot_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
 // Data-parallel wire format (poseidon_amd/dp.py): the fp32 gradient arena goes over xGMI as bfloat16 (half the bytes; the
 // reference's DDP sends fp32 — reference scOT/train.py via HF Trainer/accelerate).  One pass each way, the mean's 1/N folded in
 // (the first version used two torch elementwise kernels per chunk plus a div).  ALWAYS bfloat16 (gradient range), whatever

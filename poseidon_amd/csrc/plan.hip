@@ -40,6 +40,11 @@
 // recorded scot_head_finalize / scot_loss_bwd entries read; scot_plan_loss_masked / scot_plan_train_step_masked copy the caller's mask
 // into it, and the unmasked calls refuse such a plan (the mask is missing).
 //
+// GRADIENT ACCUMULATION (training images): the step cut between its backward and its update.  scot_plan_accumulate replays the step's
+// forward and backward and folds the gradient arena into an fp32 accumulator with scot_grad_accumulate (optim.hip); scot_plan_apply copies
+// the accumulator back over the gradient arena with the same kernel and replays the update.  The arena and the group map are arguments
+// of the recorded scot_adamw_step entry, resolved at load beside the lr patch point; the accumulator is allocated at the first call.
+//
 // A plan is one stream's worth of state: its buffers are reused by every run, so runs of ONE plan must be ordered (same stream, or
 // the caller's own events); two plans are independent.
 #include "common.h"
@@ -61,6 +66,8 @@ extern "C" int scot_error_sums(const float* pred, const float* target, int B, in
 extern "C" int scot_error_sums_masked(float* pred, const float* target, const unsigned char* mask, int mask_full, int overwrite, int B, int C,
                                       int HW, const int* channel_slices, int groups, double* sums, void* workspace, size_t workspace_bytes,
                                       hipStream_t stream);
+extern "C" int scot_grad_accumulate(float* dst, const float* acc, const float* grad, const unsigned char* map8, size_t n, float weight,
+                                    hipStream_t stream);
 
 // the listed entry points, by address: g_entry_address[table][index], rows in the order of scot_plan_lists[table].names (the training
 // table is the longest: it repeats the forward's)
@@ -256,6 +263,8 @@ inline bool dev_cotangent(float* cot, const float* d_pred, const float* hold, si
 #endif
 
 const uint64_t PLAN_HANDLE_MAGIC = 0x50414c5053434f54ull;
+// scot_adamw_step(params, GRADS, exp_avg, exp_avg_sq, MAP8, n, lr, ...): what the accumulation calls take from the recorded entry
+const uint64_t SCOT_PLAN_ADAMW_GRAD_ARG = 1, SCOT_PLAN_ADAMW_MAP_ARG = 4;
 const size_t SLAB_ALIGN = 256, SLAB_TAIL = 64 << 10;
 
 struct Plan {
@@ -298,6 +307,15 @@ struct Plan {
   size_t holder_bytes = 0;
   void* eval_ws = nullptr;                         // scot_plan_evaluate: the workspace of scot_error_sums, for any slices over Cout channels
   size_t eval_ws_bytes = 0;
+  // gradient accumulation: what the recorded scot_adamw_step reads as its gradients and its group map (resolved at load; NULL where the
+  // entry does not hold them as spans of the plan's buffers), the fp32 accumulator A of arena_floats (allocated at the first
+  // scot_plan_accumulate), the micro-batches of the open accumulation (0: none is open), and whether scot_plan_poison has filled A
+  float* grad_arena = nullptr;
+  const unsigned char* group_map = nullptr;
+  float* accum = nullptr;
+  size_t accum_bytes = 0;
+  long long accum_open = 0;
+  bool accum_poisoned = false;
 };
 
 inline Plan* as_plan(void* p) {
@@ -450,6 +468,7 @@ extern "C" int scot_plan_free(void* plan) {
   if (pl->slab) dev_free(pl->slab);
   if (pl->holder) dev_free(pl->holder);
   if (pl->eval_ws) dev_free(pl->eval_ws);
+  if (pl->accum) dev_free(pl->accum);
   for (dev_event_t e : pl->events) dev_event_destroy(e);
   if (pl->side_own) dev_stream_destroy(pl->side);
   pl->magic = 0;
@@ -566,6 +585,16 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
       const uint64_t* upd = v.calls[SCOT_PLAN_CALLS_UPDATE].words;
       const uint64_t* e = upd + scot_plan_entry_at(upd, v.train[SCOT_PLAN_TR_LR_ENTRY]);
       pl->lr = (float*)(uintptr_t)array_address[e[5 + 2 * v.train[SCOT_PLAN_TR_LR_ARG]]];
+      // the same entry's gradients (argument 1) and group map (argument 4), for scot_plan_accumulate / _apply: spans of the plan's own
+      // buffers that hold the whole arena, or the accumulation calls refuse
+      const uint64_t floats = v.train[SCOT_PLAN_TR_ARENA_FLOATS];
+      const uint64_t gt = e[4 + 2 * SCOT_PLAN_ADAMW_GRAD_ARG], go = e[5 + 2 * SCOT_PLAN_ADAMW_GRAD_ARG];
+      const uint64_t mt = e[4 + 2 * SCOT_PLAN_ADAMW_MAP_ARG], mo = e[5 + 2 * SCOT_PLAN_ADAMW_MAP_ARG];
+      if (e[2] > SCOT_PLAN_ADAMW_MAP_ARG && (gt & 0xff) == SCOT_PLAN_ARG_PTR && (mt & 0xff) == SCOT_PLAN_ARG_PTR && floats && floats % 8 == 0 &&
+          go % 16 == 0 && go + floats * 4 <= pl->buf_bytes[gt >> 8] && mo + floats / 8 <= pl->buf_bytes[mt >> 8]) {
+        pl->grad_arena = (float*)(pl->buf[gt >> 8] + go);
+        pl->group_map = (const unsigned char*)(pl->buf[mt >> 8] + mo);
+      }
     }
     // the image may be released when this returns: the uploads read it
     if (status == SCOT_OK && !dev_sync(stream)) status = SCOT_ERR_LAUNCH;
@@ -593,13 +622,13 @@ extern "C" int scot_plan_describe(void* plan, long long* out) {
                            (long long)io[SCOT_PLAN_IO_W], (long long)io[SCOT_PLAN_IO_COUT], (long long)io[SCOT_PLAN_IO_HAS_TIME],
                            (long long)(io[SCOT_PLAN_IO_HAS_TIME] ? io[SCOT_PLAN_IO_TIME_BYTES] : 0), (long long)io[SCOT_PLAN_IO_HAS_MASK],
                            (long long)(io[SCOT_PLAN_IO_HAS_MASK] ? io[SCOT_PLAN_IO_MASK_BYTES] : 0), pl->operand_format, pl->compute,
-                           (long long)(pl->slab_bytes + pl->holder_bytes + pl->eval_ws_bytes), (long long)pl->list[SCOT_PLAN_CALLS_FORWARD].calls, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
+                           (long long)(pl->slab_bytes + pl->holder_bytes + pl->eval_ws_bytes + pl->accum_bytes), (long long)pl->list[SCOT_PLAN_CALLS_FORWARD].calls, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
                            (long long)(hw * io[SCOT_PLAN_IO_COUT]), (long long)pl->header[SCOT_PLAN_H_FORMAT]};
   memcpy(out, d, sizeof(d));
   return SCOT_OK;
 }
 
-// every scratch buffer and the prediction's buffer <- byte (a test aid: with 0xff a run that reads what it did not write yields NaN)
+// every scratch buffer, the prediction's buffer and the gradient accumulator <- byte (a test aid: with 0xff a run that reads what it did not write yields NaN)
 extern "C" int scot_plan_poison(void* plan, int byte, hipStream_t stream) {
   Plan* pl = as_plan(plan);
   if (!pl) return SCOT_ERR_SHAPE;
@@ -607,6 +636,11 @@ extern "C" int scot_plan_poison(void* plan, int byte, hipStream_t stream) {
   for (size_t i = 0; i < pl->buf.size(); ++i)
     if (pl->buf_kind[i] == SCOT_PLAN_BUF_SCRATCH || pl->buf_kind[i] == SCOT_PLAN_BUF_OUTPUT)
       if (!dev_fill(pl->buf[i], byte, (size_t)((pl->buf_bytes[i] + SLAB_ALIGN - 1) / SLAB_ALIGN * SLAB_ALIGN), stream)) return SCOT_ERR_LAUNCH;
+  pl->accum_open = 0;      // (an open accumulation is discarded, and the accumulator filled: the next first micro-batch zeroes it again)
+  if (pl->accum) {
+    pl->accum_poisoned = true;
+    if (!dev_fill(pl->accum, byte, pl->accum_bytes, stream)) return SCOT_ERR_LAUNCH;
+  }
   return SCOT_OK;
 }
 
@@ -981,7 +1015,7 @@ extern "C" int scot_plan_train_step_masked(void* plan, const float* pixel_values
   if (!pl) return SCOT_ERR_SHAPE;
   int rc = check_batch(pl, pixel_values, time, labels, pixel_mask);
   if (rc != SCOT_OK) return rc;
-  if (!lr || !pl->lr) return SCOT_ERR_SHAPE;
+  if (!lr || !pl->lr || pl->accum_open) return SCOT_ERR_SHAPE;      // (an open accumulation ends with scot_plan_apply)
   if (!copy_batch_in(pl, pixel_values, time, labels, pixel_mask, stream)) return SCOT_ERR_LAUNCH;
   memcpy(pl->lr, lr, (size_t)pl->train[SCOT_PLAN_TR_GROUPS] * sizeof(float));
   for (int s = 0; s < 3; ++s)
@@ -993,6 +1027,80 @@ extern "C" int scot_plan_train_step_masked(void* plan, const float* pixel_values
 extern "C" int scot_plan_train_step(void* plan, const float* pixel_values, const float* time, const float* labels, const float* lr, float* loss,
                                     hipStream_t stream) {
   return scot_plan_train_step_masked(plan, pixel_values, time, labels, nullptr, lr, loss, stream);
+}
+
+// ---- gradient accumulation: the step cut between its backward and its update (include/scot_plan.h)
+// scot_grad_accumulate on the plan's gradient arena (counted in the emulation's launch log)
+static int accumulate_pass(Plan* pl, float* dst, const float* acc, const float* grad, float weight, hipStream_t stream) {
+#ifdef SCOT_HIPEMU
+  ++g_emu_issued;
+#endif
+  return scot_grad_accumulate(dst, acc, grad, pl->group_map, (size_t)pl->train[SCOT_PLAN_TR_ARENA_FLOATS], weight, stream);
+}
+
+// One micro-batch: forward and backward as scot_plan_train_step_masked runs them, then A = weight * g (first) or A += weight * g.
+extern "C" int scot_plan_accumulate(void* plan, const float* pixel_values, const float* time, const float* labels, const void* pixel_mask,
+                                    float weight, int first, float* loss, hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  int rc = check_batch(pl, pixel_values, time, labels, pixel_mask);
+  if (rc != SCOT_OK) return rc;
+  if (!pl->grad_arena || !(fabsf(weight) <= 3.4028234e38f) || (!first && !pl->accum_open)) return SCOT_ERR_SHAPE;
+  if (!pl->accum) {
+    const size_t bytes = (size_t)pl->train[SCOT_PLAN_TR_ARENA_FLOATS] * sizeof(float);
+    pl->accum = (float*)dev_alloc(bytes);
+    if (!pl->accum) return SCOT_ERR_LAUNCH;
+    pl->accum_bytes = bytes;
+    pl->accum_poisoned = true;      // (whoever held the memory before: zeroed below)
+  }
+  if (pl->accum_poisoned) {
+    if (!dev_fill(pl->accum, 0, pl->accum_bytes, stream)) return SCOT_ERR_LAUNCH;
+    pl->accum_poisoned = false;
+  }
+  if (first) pl->accum_open = 0;
+  if (!copy_batch_in(pl, pixel_values, time, labels, pixel_mask, stream)) return SCOT_ERR_LAUNCH;
+  for (int s = 0; s < 2; ++s)
+    if ((rc = replay(pl, SCOT_PLAN_CALLS_STEP_FORWARD + s, stream)) != SCOT_OK) return rc;
+  if ((rc = accumulate_pass(pl, pl->accum, first ? nullptr : pl->accum, pl->grad_arena, weight, stream)) != SCOT_OK) return rc;
+  ++pl->accum_open;
+  if (loss && !dev_copy(loss, span_ptr(pl, pl->train, SCOT_PLAN_TR_LOSS), 4, D2D, stream)) return SCOT_ERR_LAUNCH;
+  return SCOT_OK;
+}
+
+// The update from the accumulator: gradient arena <- A at the parameter positions, then the recorded update list, unchanged.
+extern "C" int scot_plan_apply(void* plan, const float* lr, hipStream_t stream) {
+  Plan* pl = as_plan(plan);
+  if (!pl) return SCOT_ERR_SHAPE;
+  if (pl->format != SCOT_PLAN_FORMAT_TRAINING) return SCOT_ERR_UNSUPPORTED;
+  if (!lr || !pl->lr || !pl->accum_open) return SCOT_ERR_SHAPE;
+  memcpy(pl->lr, lr, (size_t)pl->train[SCOT_PLAN_TR_GROUPS] * sizeof(float));
+  int rc = accumulate_pass(pl, pl->grad_arena, nullptr, pl->accum, 1.0f, stream);
+  if (rc != SCOT_OK) return rc;
+  pl->accum_open = 0;      // (the gradient arena holds the sum: whatever the update does, this accumulation is over)
+  return replay(pl, SCOT_PLAN_CALLS_UPDATE, stream);
+}
+
+// which = 0: the gradient arena the update reads; 1: the accumulator (-1 until the first scot_plan_accumulate has allocated it)
+extern "C" int scot_plan_gradients(void* plan, int which, float** ptr, size_t* floats) {
+  Plan* pl = as_plan(plan);
+  if (!pl || !ptr || !floats) return SCOT_ERR_SHAPE;
+  if (pl->format != SCOT_PLAN_FORMAT_TRAINING) return SCOT_ERR_UNSUPPORTED;
+  float* p = which == 0 ? pl->grad_arena : (which == 1 ? pl->accum : nullptr);
+  if (!p) return SCOT_ERR_SHAPE;
+  *ptr = p;
+  *floats = (size_t)pl->train[SCOT_PLAN_TR_ARENA_FLOATS];
+  return SCOT_OK;
+}
+
+// out[2]: micro-batches in the open accumulation (0: none is open), bytes of the accumulator (0 before it is allocated)
+extern "C" int scot_plan_accumulation_status(void* plan, long long* out) {
+  Plan* pl = as_plan(plan);
+  if (!pl || !out) return SCOT_ERR_SHAPE;
+  out[0] = out[1] = 0;
+  if (pl->format != SCOT_PLAN_FORMAT_TRAINING) return SCOT_ERR_UNSUPPORTED;
+  out[0] = pl->accum_open;
+  out[1] = (long long)pl->accum_bytes;
+  return SCOT_OK;
 }
 
 // out[6]: steps applied, steps skipped, gradient scale (1 where it is not dynamic), last gradient norm before clipping, last clip

@@ -151,6 +151,14 @@ PLAN_PROTOTYPES = {
     "scot_plan_evaluate_masked": [P, P, P, P, P, I, I, P, I, P, P, P],
     "scot_plan_loss_masked": [P, P, P, P, P, P, P, P],
     "scot_plan_train_step_masked": [P, P, P, P, P, P, P, P],
+    # gradient accumulation: the arena-wide pass dst = [acc +] weight * grad at the parameter positions (and the grid it launches), a
+    # micro-batch into the plan's accumulator, the update from it, the two gradient buffers (ptr: float**, floats: size_t*), the status
+    "scot_grad_accumulate": [P, P, P, P, Z, F, P],
+    "scot_grad_accumulate_blocks": [Z],
+    "scot_plan_accumulate": [P, P, P, P, P, F, I, P, P],
+    "scot_plan_apply": [P, P, P],
+    "scot_plan_gradients": [P, I, P, P],
+    "scot_plan_accumulation_status": [P, P],
 }
 _VOID = {"scot_set_use_tr", "scot_gemm_wide_config", "scot_gemm_splitk_config"}
 _SIZE = {"scot_gemm_workspace_bytes", "scot_wgrad_group_workspace_bytes", "scot_cln_bwd_workspace_bytes", "scot_wgrad_mlp_workspace_bytes",

@@ -813,6 +813,28 @@ def _error_sums_lib():
     return l
 
 
+_grad_accumulate_typed = {}      # as _error_sums_typed, for the gradient-accumulation pass
+
+
+def _grad_accumulate_lib():
+    l = _raw()
+    if id(l) not in _grad_accumulate_typed:
+        for name in ("scot_grad_accumulate", "scot_grad_accumulate_blocks"):
+            fn = getattr(l, name)
+            fn.argtypes, fn.restype = _lib.PLAN_PROTOTYPES[name], _lib.restype(name)
+        _grad_accumulate_typed[id(l)] = l
+    return l
+
+
+def grad_accumulate(dst, acc, grad, map8, weight):
+    """dst = weight * grad (acc None) or acc + weight * grad at the parameter positions of the arena (map8: the optimizer's group map, one
+    byte per 8 floats, 255 = not a parameter); every other float of dst keeps its bits: scot_grad_accumulate (include/scot_plan.h), one
+    launch.  float32, 16-byte aligned; dst may be acc, never grad.  Product and sum are rounded separately: `acc + grad * weight` in
+    torch, bit for bit.  A model-level call: it goes to the library itself, never onto a step tape."""
+    _lib.check(_grad_accumulate_lib().scot_grad_accumulate(ptr(dst), ptr(acc), ptr(grad), ptr(map8), dst.numel(), float(weight), stream()),
+               "scot_grad_accumulate")
+
+
 def error_sums(pred, target, channel_slices, sums, mask_u8=None, mask_full=False):
     """sums [B, G, 4] (float64) <- {sum |p - t|, sum |t|, sum (p - t)^2, sum t^2} per sample and channel group of pred against target
     (float32 [B, C, ...], contiguous): scot_error_sums (include/scot_plan.h), two launches.  channel_slices: G + 1 ascending ints, or

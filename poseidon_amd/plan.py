@@ -1033,7 +1033,7 @@ def _addr(x, what):
 
 
 class Plan:
-    """A loaded plan.  `run` / `rollout` / `evaluate` / `vjp` / `rollout_vjp` / `loss` / `train_step` take torch tensors (and return them) or raw
+    """A loaded plan.  `run` / `rollout` / `evaluate` / `vjp` / `rollout_vjp` / `loss` / `train_step` / `accumulate` take torch tensors (and return them) or raw
     device addresses (then `out` is required)."""
 
     def __init__(self, lib, handle):
@@ -1325,15 +1325,11 @@ class Plan:
         """one optimizer step on the batch (scot_plan_train_step) -> the loss before the update ([1], on the device).  lr: one float
         per parameter group, in the export's group order (a single float: the same for all).  out: a loss buffer of the caller's.
         pixel_mask: the batch's mask on a masked plan, as for `loss` (scot_plan_train_step_masked)."""
-        groups = self.describe_training()["groups"]
-        lr = [float(lr)] * groups if isinstance(lr, (int, float)) else [float(x) for x in lr]
-        if len(lr) != groups:
-            raise ValueError(f"this plan has {groups} parameter groups, lr has {len(lr)} values")
+        rates = self._rates(lr)
         pv, t, lab, mask = self._batch(pixel_values, time, labels, pixel_mask)
         if out is None and _is_tensor(pixel_values):
             import torch
             out = torch.empty(1, dtype=torch.float32, device=pixel_values.device)
-        rates = (ctypes.c_float * max(1, groups))(*lr)
         if pixel_mask is None:
             self._call("scot_plan_train_step", pv, t, lab, ctypes.cast(rates, ctypes.c_void_p), _addr(out, "loss"),
                        self._stream(stream, pixel_values))
@@ -1341,6 +1337,53 @@ class Plan:
             self._call("scot_plan_train_step_masked", pv, t, lab, mask, ctypes.cast(rates, ctypes.c_void_p), _addr(out, "loss"),
                        self._stream(stream, pixel_values))
         return out
+
+    def _rates(self, lr):
+        """lr -> the host array a step or an apply reads: one float per parameter group (a single float: the same for all)"""
+        groups = self.describe_training()["groups"]
+        lr = [float(lr)] * groups if isinstance(lr, (int, float)) else [float(x) for x in lr]
+        if len(lr) != groups:
+            raise ValueError(f"this plan has {groups} parameter groups, lr has {len(lr)} values")
+        return (ctypes.c_float * max(1, groups))(*lr)
+
+    def accumulate(self, pixel_values, time, labels, weight, first, out=None, stream=None, pixel_mask=None):
+        """one micro-batch into the plan's gradient accumulator (scot_plan_accumulate): forward and backward as `train_step` runs them,
+        then A = weight * g (first) or A += weight * g; no state changes -> the micro-batch's own unweighted loss ([1], on the device).
+        `apply` ends the accumulation with the update.  out: a loss buffer of the caller's.  pixel_mask: as for `train_step`."""
+        pv, t, lab, mask = self._batch(pixel_values, time, labels, pixel_mask)
+        if out is None and _is_tensor(pixel_values):
+            import torch
+            out = torch.empty(1, dtype=torch.float32, device=pixel_values.device)
+        self._call("scot_plan_accumulate", pv, t, lab, mask, float(weight), int(bool(first)), _addr(out, "loss"),
+                   self._stream(stream, pixel_values))
+        return out
+
+    def apply(self, lr, stream=None):
+        """the optimizer update from the accumulated gradient (scot_plan_apply); lr as for `train_step`.  Clipping, the skip of a
+        non-finite norm, the counters and the fp16 scale are the device's decisions on the accumulated gradient (`train_status`)."""
+        rates = self._rates(lr)
+        self._call("scot_plan_apply", ctypes.cast(rates, ctypes.c_void_p), self._stream(stream, None))
+
+    def gradients(self, which):
+        """-> a float32 [arena_floats] VIEW (no copy) of the plan's own memory: which = 0 the gradient arena the update reads, 1 the
+        accumulator (scot_plan_gradients).  Valid until the plan is freed; read and write it in the plan's stream order — an
+        all-reduce of the accumulator goes between the last `accumulate` and `apply`.  On the GPU a CUDA tensor on the current device,
+        on the CPU emulation a tensor over the host buffer."""
+        import torch
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._call("scot_plan_gradients", int(which), ctypes.byref(p), ctypes.byref(n))
+        if hasattr(self._lib, "scot_plan_emu_issued"):      # the emulation: the buffer is host memory
+            return torch.frombuffer((ctypes.c_float * n.value).from_address(p.value), dtype=torch.float32)
+
+        class _Device:      # (the owner torch keeps alive with the view is this object, not the plan)
+            __cuda_array_interface__ = {"shape": (n.value,), "typestr": "<f4", "data": (p.value, False), "version": 2, "strides": None}
+        return torch.as_tensor(_Device(), device="cuda")
+
+    def accumulation_status(self):
+        """-> {micro_batches: in the open accumulation (0: none is open), bytes: of the accumulator (0 before the first accumulate)}"""
+        out = (ctypes.c_longlong * 2)()
+        self._call("scot_plan_accumulation_status", out)
+        return {"micro_batches": int(out[0]), "bytes": int(out[1])}
 
     def train_status(self, stream=None):
         """-> {applied, skipped, grad_scale, grad_norm, clip_coef, nonfinite} (scot_plan_train_status: waits for the stream)"""
