@@ -81,6 +81,14 @@ int scot_mask_tokens_bwd(float* g, const void* mask_u8, float* d_token, int rows
  * U = X [Pr; Pi]^T is a scot_gemm (NT, compute 0); this entry does Y[b] = Pr·U[b,:,:t] - Pi·U[b,:,t:] per image.
  * U [nimg, s, 2t], Pr / Pi [t, s], Y [nimg, t, t], all fp32; s <= 512. */
 int scot_spectral_apply(const float* U, const float* Pr, const float* Pi, float* Y, int nimg, int s, int t, scot_stream_t stream);
+/* The WHOLE spectral resize in one launch: Y[b] = Pr X[b] Pr^T - Pi X[b] Pi^T for any Pr, Pi (not only resize operators), on the
+ * exact fp32 MFMA with fp32 accumulation; the intermediate [32, s] panel of a workgroup stays in LDS (csrc/spectral_resize.hip).
+ * X [nimg, s, s], Pr / Pi [t, s] row-major, Y [nimg, t, t], all fp32; any s, t in 1..512 (s % 4 != 0 takes scalar loads).  Every
+ * output element is one accumulation chain in a fixed order: the bits repeat from run to run, are the same in both builds of the
+ * library and do not depend on nimg.  Refused with nothing launched and Y untouched: -1 for a NULL pointer, nimg < 1, s or t < 1, a
+ * base pointer that is not 16-byte aligned, or Y == X; -3 for s or t > 512.  Its adjoint is the same call with Pr^T, Pi^T (s and t
+ * exchanged).  An exported plan at a foreign resolution records it in front of and behind the engine (include/scot_plan.h). */
+int scot_spectral_resize(const float* X, const float* Pr, const float* Pi, float* Y, int nimg, int s, int t, scot_stream_t stream);
 /* Data-parallel wire format of the gradient arena (the exchange itself is torch.distributed's RCCL all-reduce / reduce-scatter on
  * the buffers below; reference: DDP's fp32 bucket all-reduce via HF Trainer/accelerate, scOT/train.py):
  *   scot_dp_pack:   wire[i] = bfloat16(scale * src[i])     (scale = 1/world: the mean is taken before the 16-bit sum)

@@ -6,7 +6,8 @@
  * with the weights, as a relocatable plan image; the calls below load such a file and run it.  A host needs nothing but the
  * shared library and the HIP runtime: no Python, no torch.  The prediction is bit-identical to `model(...)` in Python.
  *
- * What a plan covers: the engine's inference forward at config.image_size on ONE stream (or two: TWO-STREAM plans below) — no training, no spectral resize, no hidden
+ * What a plan covers: the engine's inference forward on ONE stream (or two: TWO-STREAM plans below), at config.image_size or — a
+ * RESIZED plan, below — at any square resolution the export was given — no training, no hidden
  * states or attention outputs, no labels (so no pixel_mask INPUT on an inference plan: the mask overwrites the prediction with label
  * values; scot_plan_evaluate_masked takes one beside its targets, a training plan takes one with its batch).  The weights are a
  * snapshot taken at export.  A plan recorded by the binary16 build (libscot_hip_f16.so) loads into that build only; its split-MFMA
@@ -45,6 +46,17 @@
  * 10.5 at batch 1, the Python loop's 19.3 / 10.6, against 22.6 / 11.0 on one stream; inference 6.11 against 6.15 ms at batch 64 — but
  * 3.95 against 3.62 ms at batch 1: for launch-bound inference the event edges cost more than the side stream hides, keep streams=1 there.
  *
+ * A RESIZED plan (`export_plan(..., resize=True)` with square inputs of size r != config.image_size; image formats 1, 2 and 5, no new
+ * format and no new header word) runs a model at the host's resolution, as the reference's forward does for any input size: its
+ * forward list is one scot_spectral_resize call (declared in scot_hip.h) from the input [B, Cin, r, r] to the model's size, the engine's forward, and one
+ * scot_spectral_resize from the engine's prediction to [B, Cout, r, r]; the four operator matrices are constants of the image.  An
+ * adjoint plan's backward list is the mirror image: the cotangent through the second resize's adjoint, the engine's backward, d_pixel_values
+ * through the first one's; d_time is untouched.  H = W = r in scot_plan_describe, and every call below — run, rollout (which resamples
+ * at every step, as the reference's rollout does), evaluate, evaluate_masked with element masks at r, vjp, rollout_vjp, poison — works at
+ * r unchanged.  Bit-identical to the Python model with `fused_resize = True`.  Not covered: training plans at a foreign resolution
+ * (the loss there is not a kernel yet), non-square inputs.  A library from before scot_spectral_resize refuses such an image by the
+ * entry point's name (-3).  Measured: profiles/plan_resize/README.md.
+ *
  * EVALUATION (every plan; section "evaluation" below).  scot_error_sums is one kernel pair that reduces (prediction, target) to four fp64
  * sums per sample and channel group, and scot_plan_evaluate runs a forward or a whole rollout and leaves ONLY those sums behind: no
  * `steps`-sized prediction buffer, nothing copied to the host.  The sums are what the reference's metrics are made of (its
@@ -80,6 +92,9 @@ int scot_plan_load(const void* image, size_t bytes, scot_plan_t* plan, scot_stre
  * bytes, operand format (0 bfloat16, 1 binary16), compute mode (0 fp32, 1 fp16, 2 bf16, 3 bf16x3), bytes of device memory held,
  * recorded calls, bytes of pixel_values, bytes of the prediction, image format version. */
 int scot_plan_describe(scot_plan_t plan, long long* out);
+/* out[4]: whether the plan resamples (1: a RESIZED plan), the size the model runs at (config.image_size), the size of the host's
+ * tensors (H = W above), the number of scot_spectral_resize entries in all its call lists.  Read from the forward list at load. */
+int scot_plan_describe_resize(scot_plan_t plan, long long* out);
 /* prediction [B, Cout, H, W] <- model(pixel_values [B, Cin, H, W], time [B]); fp32 device buffers of the caller.  time / pixel_mask
  * are NULL exactly when the plan has no such input.  Copies in, replays the recorded calls with every stream slot = `stream` (a
  * two-stream plan: the slots of stream 1 = its side stream), copies out; everything is asynchronous on `stream`. */

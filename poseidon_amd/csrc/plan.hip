@@ -300,6 +300,7 @@ struct Plan {
   uint64_t io[SCOT_PLAN_IO_WORDS] = {};
   uint64_t adj[SCOT_PLAN_ADJ_WORDS] = {};
   int operand_format = 0, compute = 0, format = SCOT_PLAN_FORMAT;      // format: the ONE-stream format (1, 2, 4) the image extends
+  long long resize[4] = {0, 0, 0, 0};              // scot_plan_describe_resize: read from the forward list at load (read_resize)
   bool ran = false;                                // a completed scot_plan_run whose saved activations no vjp / poison / rollout has used up
   float host_scale[4] = {1.0f, 1.0f, 0.0f, 0.0f};  // {S, 1/S, 0, 0} on its way to the state buffer
   int last_exponent = 0;                           // log2 S of the last vjp
@@ -438,6 +439,25 @@ bool build_program(Plan* pl, const scot_plan_calls& c, const std::vector<void*>&
   return true;
 }
 
+// A plan at a foreign resolution (export_plan(..., resize=True)) has no header word of its own: its forward list starts with a
+// scot_spectral_resize(X, Pr, Pi, Y, nimg, s, t, stream) entry from the host's resolution s to the model's t.  -> {resized, native size,
+// host size, resize entries in all lists}; an image without such a first entry runs at its native size H.
+void read_resize(const scot_plan_view& v, long long out[4]) {
+  const long long H = (long long)v.io[SCOT_PLAN_IO_H];
+  out[0] = 0; out[1] = H; out[2] = H; out[3] = 0;
+  for (int c = 0; c < SCOT_PLAN_N_CALLS; ++c) {
+    const uint64_t* e = v.calls[c].words;
+    for (uint64_t i = 0; i < v.calls[c].n; ++i, e += scot_plan_entry_words(e)) {
+      if (strcmp((const char*)(v.names + e[0] * SCOT_PLAN_NAME_BYTES), "scot_spectral_resize") != 0) continue;
+      ++out[3];
+      if (c == SCOT_PLAN_CALLS_FORWARD && i == 0 && e[2] >= 7 && (e[4 + 2 * 6] & 0xff) == SCOT_PLAN_ARG_INT) {
+        out[0] = 1;
+        out[1] = (long long)e[5 + 2 * 6];      // t of the first entry: what the engine runs at
+      }
+    }
+  }
+}
+
 // the address of a (buffer, offset, bytes) span of the adjoint or training words (pl->adj, pl->train)
 char* span_ptr(Plan* pl, const uint64_t* words, int slot) { return pl->buf[words[slot]] + words[slot + 1]; }
 
@@ -491,6 +511,7 @@ extern "C" int scot_plan_load(const void* image, size_t bytes, void** plan, hipS
   int status = SCOT_OK;
   try {
     memcpy(pl->io, v.io, sizeof(pl->io));
+    read_resize(v, pl->resize);
     pl->format = v.format == SCOT_PLAN_FORMAT_STREAMS ? SCOT_PLAN_FORMAT : (v.format == SCOT_PLAN_FORMAT_TRAINING_STREAMS ? SCOT_PLAN_FORMAT_TRAINING : (int)v.format);
     pl->n_streams = v.n_streams;
     pl->load_stream = stream;
@@ -625,6 +646,15 @@ extern "C" int scot_plan_describe(void* plan, long long* out) {
                            (long long)(pl->slab_bytes + pl->holder_bytes + pl->eval_ws_bytes + pl->accum_bytes), (long long)pl->list[SCOT_PLAN_CALLS_FORWARD].calls, (long long)(hw * io[SCOT_PLAN_IO_CIN]),
                            (long long)(hw * io[SCOT_PLAN_IO_COUT]), (long long)pl->header[SCOT_PLAN_H_FORMAT]};
   memcpy(out, d, sizeof(d));
+  return SCOT_OK;
+}
+
+// out[4]: the plan resamples its input and its prediction (0 / 1), the size the model runs at, the size the host's tensors have (H = W of
+// scot_plan_describe), scot_spectral_resize entries in all call lists
+extern "C" int scot_plan_describe_resize(void* plan, long long* out) {
+  Plan* pl = as_plan(plan);
+  if (!pl || !out) return SCOT_ERR_SHAPE;
+  memcpy(out, pl->resize, sizeof(pl->resize));
   return SCOT_OK;
 }
 

@@ -33,6 +33,11 @@
 // runtime's copies in and out, the next list, the caller's own work — is ordered with all of it, and the caller's contract stays "runs
 // of one plan are ordered on the one stream you pass".  A library from before these formats refuses them by the format word (-3).
 //
+// RESIZED images (`export_plan(..., resize=True)` at a resolution r other than the model's) have no format, no section and no header word
+// of their own: the forward list of a format-1, -2 or -5 image starts and ends with a scot_spectral_resize entry (a format-2 backward
+// list likewise), the operator matrices are CONSTANT buffers, and the io words carry H = W = r.  A library from before that entry point
+// refuses them by its name (-3).
+//
 // The five lists (SCOT_PLAN_CALLS_*), each held to ONE table of entry points (SCOT_PLAN_LIST_*): what can run is what is listed.
 //
 //   FORWARD        every format, table FORWARD: the inference forward.  In a format-2 image (an ADJOINT plan, `export_plan(...,
@@ -113,7 +118,8 @@ enum { SCOT_PLAN_TR_FLAGS, SCOT_PLAN_TR_GROUPS, SCOT_PLAN_TR_ARENA_FLOATS, SCOT_
 #define SCOT_PLAN_ENTRY_POINTS(X)                                                                                                     \
   X(scot_gemm) X(scot_cpb_fwd_batched) X(scot_cln_fwd) X(scot_window_attn_fwd) X(scot_mlp_block_fwd) X(scot_block_tail_fwd)          \
   X(scot_proj_cln_fwd) X(scot_add) X(scot_copy2d) X(scot_space_to_depth) X(scot_depth_to_space) X(scot_patchify) X(scot_unpatchify) \
-  X(scot_scale_residual) X(scot_dwconv7) X(scot_conv5) X(scot_head_finalize) X(scot_memset_async) X(scot_memcpy_async)
+  X(scot_scale_residual) X(scot_dwconv7) X(scot_conv5) X(scot_head_finalize) X(scot_memset_async) X(scot_memcpy_async)              \
+  X(scot_spectral_resize)
 
 // What the backward of an adjoint plan may call: the data-gradient chain of the frozen model and nothing else — no weight-gradient
 // kernel, no column sum into a parameter gradient, no optimizer step is listed in either table.
@@ -121,7 +127,7 @@ enum { SCOT_PLAN_TR_FLAGS, SCOT_PLAN_TR_GROUPS, SCOT_PLAN_TR_ARENA_FLOATS, SCOT_
   X(scot_gemm) X(scot_cln_bwd) X(scot_cln_dtime) X(scot_window_attn_bwd_rep) X(scot_block_tail_bwd) X(scot_proj_cln_bwd) X(scot_add)  \
   X(scot_add_channels) X(scot_copy2d) X(scot_space_to_depth) X(scot_depth_to_space) X(scot_patchify) X(scot_unpatchify)              \
   X(scot_scale_residual) X(scot_dwconv7) X(scot_conv5) X(scot_scale_inplace_dev) X(scot_pow2_rescale) X(scot_colscale_dev)           \
-  X(scot_axpy_dev) X(scot_memset_async) X(scot_memcpy_async)
+  X(scot_axpy_dev) X(scot_memset_async) X(scot_memcpy_async) X(scot_spectral_resize)
 
 // What the three step lists of a training plan may call: the differentiable forward with the loss, the whole backward — data AND
 // weight gradients —, the gradient arena's fill and un-scale, and the optimizer update.  A table of its own: none of the weight-gradient

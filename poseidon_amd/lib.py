@@ -97,6 +97,7 @@ PROTOTYPES = {
     "scot_zero_masked": [P, P, I, I, I, I, P],
     "scot_add_channels": [P, I, P, I, I, I, P],
     "scot_spectral_apply": [P, P, P, P, I, I, I, P],
+    "scot_spectral_resize": [P, P, P, P, I, I, I, P],
     "scot_dp_pack": [P, P, Z, F, P],
     "scot_dp_unpack": [P, P, Z, F, P],
     "scot_dp_unique_id": [P],
@@ -116,6 +117,7 @@ PROTOTYPES = {
 PLAN_PROTOTYPES = {
     "scot_plan_load": [P, Z, P, P],
     "scot_plan_describe": [P, P],
+    "scot_plan_describe_resize": [P, P],      # resized 0/1, native size, host size, resize entries in all lists
     "scot_plan_run": [P, P, P, P, P, P],
     "scot_plan_rollout": [P, P, P, P, P, I, P],
     "scot_plan_free": [P],

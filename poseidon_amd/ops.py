@@ -690,6 +690,11 @@ def spectral_apply(U, Pr, Pi, Y, nimg: int, s: int, t: int):
     _lib.check(L().scot_spectral_apply(ptr(U), ptr(Pr), ptr(Pi), ptr(Y), nimg, s, t, stream()), "scot_spectral_apply")
 
 
+def spectral_resize(X, Pr, Pi, Y, nimg: int, s: int, t: int):
+    """Y[b] = Pr · X[b] · Pr^T - Pi · X[b] · Pi^T in one launch  (X: [nimg, s, s], Pr/Pi: [t, s], Y: [nimg, t, t]; all fp32, s, t <= 512)."""
+    _lib.check(L().scot_spectral_resize(ptr(X), ptr(Pr), ptr(Pi), ptr(Y), nimg, s, t, stream()), "scot_spectral_resize")
+
+
 def dp_pack(src, wire, scale: float):
     """wire (bfloat16) <- scale * src (fp32): the gradient arena's wire format for the data-parallel exchange, one pass."""
     if src.dtype != torch.float32 or wire.dtype != torch.bfloat16 or wire.numel() < src.numel():

@@ -156,7 +156,7 @@ def _address(fn):
     return ctypes.cast(fn, ctypes.c_void_p).value
 
 
-def _check_request(model, pixel_values, time, pixel_mask, labels, train=None):
+def _check_request(model, pixel_values, time, pixel_mask, labels, train=None, resize=False):
     from . import ops
     cfg = model.config
     if labels is not None and train is None:
@@ -172,8 +172,18 @@ def _check_request(model, pixel_values, time, pixel_mask, labels, train=None):
         raise PlanExportError("export_plan: a CPU model cannot be exported — the forward that is recorded runs on the GPU "
                               f"(move the model and the example inputs there first): {e}") from None
     if pixel_values.shape[2] != cfg.image_size or pixel_values.shape[3] != cfg.image_size:
-        raise PlanExportError(f"export_plan: input size {tuple(pixel_values.shape[2:])} differs from config.image_size = {cfg.image_size}; the "
-                              "spectral resize lives outside the engine and a plan covers the engine forward only")
+        if not resize:
+            raise PlanExportError(f"export_plan: input size {tuple(pixel_values.shape[2:])} differs from config.image_size = {cfg.image_size}; the "
+                                  "spectral resize lives outside the engine and a plan covers the engine forward only (pass resize=True "
+                                  "for a plan that resamples a square input to config.image_size and the prediction back)")
+        if pixel_values.shape[2] != pixel_values.shape[3]:
+            raise PlanExportError(f"export_plan: resize=True with a non-square input {tuple(pixel_values.shape[2:])}: the spectral resize "
+                                  "assumes square images (as the reference does)")
+        if pixel_values.shape[2] > 512 or cfg.image_size > 512:
+            raise PlanExportError("export_plan: resize=True covers sizes up to 512 (scot_spectral_resize)")
+        if train is not None:
+            raise PlanExportError(f"export_plan: resize=True together with train=: a training plan runs at image_size = {cfg.image_size} "
+                                  "only (the loss at another resolution is not a kernel yet)")
     if pixel_values.shape[1] != cfg.num_channels:
         raise PlanExportError(f"export_plan: pixel_values has {pixel_values.shape[1]} channels, the model takes {cfg.num_channels}")
     if train is not None and float(getattr(cfg, "drop_path_rate", 0.0) or 0.0) > 0.0:
@@ -324,34 +334,92 @@ def _input_copies(reg, pv, t):
     return pv_in, t_in
 
 
-def _record(model, pv, t, adjoint=(), streams=1):
+class _Resize:
+    """The two resamplings around the engine of a plan at a foreign resolution r (export_plan(..., resize=True)), each ONE
+    scot_spectral_resize call through `ops` — so a recording sees it: `into` r -> image_size in front of the forward, `back` image_size
+    -> r behind it, and their adjoints (the same call with the transposed operators) around the backward.  What ScOT.forward runs with
+    `fused_resize = True`, call for call."""
+
+    def __init__(self, model, r, device):
+        from scOT.model import _resize_mats
+        self.r, self.S = int(r), int(model.config.image_size)
+        self.m_in, self.m_out = _resize_mats(self.r, self.S, device), _resize_mats(self.S, self.r, device)
+
+    def constants(self, adjoint):
+        """[(name, operator matrix)] a plan's lists name"""
+        keys = ("pr", "pi") + (("prT", "piT") if adjoint else ())
+        return [(f"resize_{side}_{k}", m[k]) for side, m in (("in", self.m_in), ("out", self.m_out)) for k in keys]
+
+    @staticmethod
+    def _apply(x, pr, pi, s, t, out=None):
+        import torch
+        from . import ops
+        if out is None:
+            out = torch.empty(*x.shape[:-2], t, t, dtype=torch.float32, device=x.device)
+        ops.spectral_resize(x, pr, pi, out, x.numel() // (s * s), s, t)
+        return out
+
+    def into(self, x, out=None):
+        return self._apply(x, self.m_in["pr"], self.m_in["pi"], self.r, self.S, out)
+
+    def back(self, y, out=None):
+        return self._apply(y, self.m_out["pr"], self.m_out["pi"], self.S, self.r, out)
+
+    def back_adjoint(self, g, out=None):      # a cotangent at r -> at image_size
+        return self._apply(g, self.m_out["prT"], self.m_out["piT"], self.r, self.S, out)
+
+    def into_adjoint(self, g, out=None):      # d_pixel_values at image_size -> at r
+        return self._apply(g, self.m_in["prT"], self.m_in["piT"], self.S, self.r, out)
+
+
+def _record(model, pv, t, adjoint=(), streams=1, rs=None):
     """-> (registry, recorded calls, kept tensors, prediction tensor, input copies, adjoint record or None): ONE dedicated, linear
     recording of engine._forward — with `adjoint`, of the forward a differentiable call runs (train=True without stochastic depth,
     these input gradients, no parameter gradient) followed by engine._backward from a cotangent of the prediction alone; the adjoint
-    record holds where the second list starts and the cotangent / gradient tensors"""
+    record holds where the second list starts and the cotangent / gradient tensors.
+    rs (a _Resize; pv is at its r): the forward list is resize, engine forward, resize; the backward list resize adjoint, engine
+    backward, resize adjoint.  The resampled tensors are scratch of the plan, the operator matrices constants."""
     import torch
     eng = model._engine
     reg = _Registry()
     _register(reg, eng.plan_buffers(adjoint=bool(adjoint)))
     pv_in, t_in = _input_copies(reg, pv, t)
+    B, S, dev = pv.shape[0], model.config.image_size, pv.device
+    Cin, Cout = pv.shape[1], model.config.num_out_channels
+
+    def room(name, *shape):
+        x = torch.empty(*shape, dtype=torch.float32, device=dev)
+        reg.add(x, SCRATCH, name)
+        return x
+    if rs is not None:
+        for name, m in rs.constants(bool(adjoint)):
+            reg.add(m, CONSTANT, name)
+        pv_s, pred_r = room("resized input", B, Cin, S, S), room("resized prediction", B, Cout, rs.r, rs.r)
     adj = None
     if adjoint:
-        cot = torch.zeros(pv.shape[0], model.config.num_out_channels, pv.shape[2], pv.shape[3], dtype=torch.float32, device=pv.device)
+        cot = torch.zeros(B, Cout, pv.shape[2], pv.shape[3], dtype=torch.float32, device=dev)
         reg.add(cot, INPUT, "d_prediction")
     with _recording(eng, reg, bool(eng.use_side and not eng.stage_timing), bool(adjoint), streams=streams) as (rec, keep):
+        x = pv_in if rs is None else rs.into(pv_in, pv_s)
         if adjoint:      # forced for the export, whatever the caller's tensors require
             eng._fwd_flags = (adjoint, False)
-            _, pred, tape = eng._forward(pv_in, t_in, None, None, True)
+            _, pred, tape = eng._forward(x, t_in, None, None, True)
+            if rs is not None:
+                pred = rs.back(pred, pred_r)
             n_fwd = len(rec)
             cot.copy_(pred / float(pred.numel()))      # (a value for the recording run; a vjp copies the caller's in)
             counted = None if eng.grad_overflow is None else eng.grad_overflow.clone()
-            d_pv, d_t = eng._backward(tape, None, cot)
+            d_pv, d_t = eng._backward(tape, None, cot if rs is None else rs.back_adjoint(cot, room("resized cotangent", B, Cout, S, S)))
+            if rs is not None and d_pv is not None:
+                d_pv = rs.into_adjoint(d_pv, room("resized d_pixel_values", B, Cin, rs.r, rs.r))
             if counted is not None:      # (the recording run is not a step of the model's: its un-scale passes do not count)
                 eng.grad_overflow.copy_(counted)
             keep.append(tape)
             adj = dict(n_fwd=n_fwd, cot=cot, d_pv=d_pv, d_t=d_t)
         else:
-            _, pred, _ = eng._forward(pv_in, t_in, None, None, False)
+            _, pred, _ = eng._forward(x, t_in, None, None, False)
+            if rs is not None:
+                pred = rs.back(pred, pred_r)
     _register(reg, eng.plan_buffers(adjoint=bool(adjoint)), only_new=True)      # (tables the forward created on first use)
     return reg, rec, keep, pred, pv_in, t_in, adj
 
@@ -790,7 +858,7 @@ def build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj=None, train=N
     return bytes(out)
 
 
-def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labels=None, *, adjoint=(), train=None, streams=1):
+def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labels=None, *, adjoint=(), train=None, streams=1, resize=False):
     """Record `model`'s inference forward for exactly these input shapes and write it as a plan image to `path` (None: only return it).
     Returns the image's bytes.  The weights are a snapshot; see the module docstring and DESIGN.md §3 for what a plan does not cover.
     adjoint: () or some of ("pixel_values", "time") — the image (format 2) then also holds the frozen-model backward from a cotangent of
@@ -801,14 +869,19 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
     recorded with the reference's mask (`prediction[pixel_mask] = labels[pixel_mask]` before the loss), the image has the mask as one
     more input, and every batch brings its own (scot_plan_loss_masked, scot_plan_train_step_masked).
     streams: 1, or 2 — the image (format 5, with train= format 6) then holds the engine's two-stream program, and the runtime runs the
-    bias tables, the skip blocks and the weight gradients on a side stream of its own beside the main chain.  Not with adjoint=."""
+    bias tables, the skip blocks and the weight gradients on a side stream of its own beside the main chain.  Not with adjoint=.
+    resize: True — square inputs of a size r other than config.image_size are accepted (inference, adjoint and two-stream plans, not
+    train=): the forward list becomes one scot_spectral_resize from the input [B, Cin, r, r] to image_size, the engine's forward, and
+    one scot_spectral_resize of its prediction to [B, Cout, r, r]; an adjoint plan's backward list gets the two adjoints around the
+    engine's backward.  The plan then takes and returns tensors at r, bit-identical to the model with `fused_resize = True`.  At
+    r == image_size the image is the one resize=False gives."""
     import torch
     if streams not in (1, 2):
         raise PlanExportError(f"export_plan: streams={streams!r}: a plan runs on 1 stream or on 2 (the caller's and one side stream)")
     if streams == 2 and adjoint:
         raise PlanExportError("export_plan: adjoint= together with streams=2: an adjoint plan runs on one stream (the frozen backward has "
                               "no weight-gradient stream to put beside the main chain)")
-    _check_request(model, pixel_values, time, pixel_mask, labels, train)
+    _check_request(model, pixel_values, time, pixel_mask, labels, train, resize)
     dev = pixel_values.device
     if train is not None:
         model._ensure_arena(dev)
@@ -833,7 +906,7 @@ def export_plan(model, pixel_values, time=None, pixel_mask=None, path=None, labe
             image = _export_training(model, train, pv, t, labels.detach().to(device=dev, dtype=torch.float32).contiguous(), own, peer, streams,
                                      mask)
         else:
-            image = _export_frozen(model, pv, t, adjoint, own, peer, streams)
+            image = _export_frozen(model, pv, t, adjoint, own, peer, streams, resize)
     if path is not None:
         with open(path, "wb") as f:
             f.write(image)
@@ -852,26 +925,34 @@ def _self_check(image, own, peer):
         plan.free()
 
 
-def _export_frozen(model, pv, t, adjoint, own, peer, streams=1):
-    """record, build, and check through the runtime: the model's own prediction bits and, with `adjoint`, the engine's own gradients"""
+def _export_frozen(model, pv, t, adjoint, own, peer, streams=1, resize=False):
+    """record, build, and check through the runtime: the model's own prediction bits and, with `adjoint`, the engine's own gradients.
+    resize (pv at another size than config.image_size): the reference is resize(engine(resize(pv))) on the one-launch kernel, and for
+    the gradients its adjoints around the engine's backward — what ScOT.forward computes with `fused_resize = True`."""
     import torch
     eng, dev = model._engine, pv.device
     ref_g = None
+    rs = _Resize(model, pv.shape[2], dev) if resize and pv.shape[2] != model.config.image_size else None
+    x = pv if rs is None else rs.into(pv)      # what the engine sees
     if adjoint:      # the engine's own bits of the differentiable call: its prediction, and a vjp
-        _, ref, tape = eng.forward(pv, t, None, None, train=True, stochastic=False, input_grads=adjoint, param_grads=False)
-        ref = ref.clone()
+        _, ref, tape = eng.forward(x, t, None, None, train=True, stochastic=False, input_grads=adjoint, param_grads=False)
+        ref = ref.clone() if rs is None else rs.back(ref)
         # (the cotangent of the self-check: the prediction brought to at most 1 / its element count — the magnitude a mean loss
         # hands back and the fp16 gradient scale is chosen for)
         cot = ref / (float(ref.numel()) * max(1.0, float(ref.abs().max())))
         counted = 0 if eng.grad_overflow is None else int(eng.grad_overflow)
-        ref_g = eng.backward(tape, None, cot.clone())
+        ref_g = eng.backward(tape, None, cot.clone() if rs is None else rs.back_adjoint(cot))
+        if rs is not None and ref_g[0] is not None:
+            ref_g = (rs.into_adjoint(ref_g[0]), ref_g[1])
         counted = 0 if eng.grad_overflow is None else int(eng.grad_overflow) - counted
         del tape
         for p in model._params:      # (as after any frozen backward: by-products of the fused tails may sit in the gradient arena)
             p.grad = None
     else:
-        _, ref, _ = eng.forward(pv, t, None, None, train=False, stochastic=False)      # the model's own prediction
-    reg, rec, keep, pred, pv_in, t_in, adj = _record(model, pv, t, adjoint, streams)
+        _, ref, _ = eng.forward(x, t, None, None, train=False, stochastic=False)      # the model's own prediction
+        if rs is not None:
+            ref = rs.back(ref)
+    reg, rec, keep, pred, pv_in, t_in, adj = _record(model, pv, t, adjoint, streams, rs)
     image = build_image(model, reg, rec, pred, pv_in, t_in, own, peer, adj, streams=streams)
     with _self_check(image, own, peer) as plan:
         got = plan.run(pv, t)
@@ -1095,6 +1176,12 @@ class Plan:
         out = (ctypes.c_longlong * 16)()
         self._call("scot_plan_describe", out)
         return dict(zip(DESCRIBE, [int(x) for x in out]))
+
+    def describe_resize(self):
+        """-> (resized 0 / 1, the size the model runs at, the size of the host's tensors, scot_spectral_resize entries in all lists)"""
+        out = (ctypes.c_longlong * 4)()
+        self._call("scot_plan_describe_resize", out)
+        return tuple(int(x) for x in out)
 
     def poison(self, byte=0xFF, stream=None):
         self._call("scot_plan_poison", int(byte), self._stream(stream, None))

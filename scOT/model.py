@@ -246,6 +246,9 @@ class ScOT(nn.Module):
 
         self._init_weights()
         self.use_mask_token = bool(use_mask_token)
+        # True: an input at another resolution than config.image_size is resampled by the one-launch kernel (scot_spectral_resize) —
+        # the Python model an exported plan with resize=True is bit-identical to.  False: the GEMM + scot_spectral_apply pair
+        self.fused_resize = False
         self._shapes = param_shapes(cfg, use_mask_token=self.use_mask_token)
         got = OrderedDict((k, tuple(v.shape)) for k, v in self.named_parameters())
         if list(got.items()) != list(self._shapes.items()):  # schema self-check
@@ -491,7 +494,7 @@ class ScOT(nn.Module):
         in_size = pv.shape[2]
         resized = in_size != cfg.image_size
         if resized:
-            pv = self._upsample(pv, cfg.image_size) if in_size < cfg.image_size else self._downsample(pv, cfg.image_size)
+            pv = spectral_resize(pv, cfg.image_size, fused=self.fused_resize)
         self._param_grads_now = any(p.requires_grad for p in self._params)
         want_grad = torch.is_grad_enabled() and (self._param_grads_now or pv.requires_grad or (t is not None and t.requires_grad))
         bmp = None
@@ -507,12 +510,14 @@ class ScOT(nn.Module):
             loss, pred = _ScOTFunction.apply(self._anchor, self, pv, t, lab, pixel_mask, bmp)
             if lab is None:
                 loss = None
+            if resized:      # (reference model.py:1416-1420: the prediction always goes back to the input resolution)
+                pred = spectral_resize(pred, in_size, fused=self.fused_resize)
         else:
             loss, pred, _ = self._engine.forward(pv, t, lab, pixel_mask, train=False, stochastic=self.training, bool_masked_pos=bmp)
             if loss is not None:
                 loss = loss.view(())
             if resized:
-                pred = self._upsample(pred, in_size) if in_size > cfg.image_size else self._downsample(pred, in_size)
+                pred = spectral_resize(pred, in_size, fused=self.fused_resize)
         self._engine.collect_attn = False
         hs = rhs = None
         want_hs = bool(output_hidden_states or (output_hidden_states is None and cfg.output_hidden_states))
@@ -540,7 +545,8 @@ class ScOT(nn.Module):
         return ScOTOutput(loss=loss, output=pred, hidden_states=hs, attentions=(dec_at + enc_at) if want_attn else None,
                           reshaped_hidden_states=rhs)
 
-    def export_plan(self, pixel_values, time=None, pixel_mask=None, path=None, labels=None, *, adjoint=(), train=None, streams=1):
+    def export_plan(self, pixel_values, time=None, pixel_mask=None, path=None, labels=None, *, adjoint=(), train=None, streams=1,
+                    resize=False):
         """Write this model's inference forward for exactly these input shapes as a plan image: a file that `scot_plan_load` /
         `scot_plan_run` (include/scot_plan.h) run from C without Python, bit-identical to `self(...)`.  adjoint=("pixel_values", "time")
         (or one of them): the image also holds the frozen model's backward, and `scot_plan_vjp` returns these inputs' gradients for a
@@ -548,10 +554,12 @@ class ScOT(nn.Module):
         this model) with labels=: a TRAINING image — it also holds one optimizer step and the training state by value, and
         `scot_plan_train_step` fine-tunes the model from C; `poseidon_amd.plan.load_training_state` brings the result back.  streams=2
         (not with adjoint=): a TWO-STREAM image — the engine's own two-stream program, run by the plan runtime on the caller's stream
-        and a side stream of its own.  See poseidon_amd/plan.py."""
+        and a side stream of its own.  resize=True (not with train=): square inputs of another size than config.image_size are
+        accepted — the plan resamples them to image_size and the prediction back (scot_spectral_resize), bit-identical to `self(...)`
+        with `self.fused_resize = True`.  See poseidon_amd/plan.py."""
         from poseidon_amd.plan import export_plan
         return export_plan(self, pixel_values, time=time, pixel_mask=pixel_mask, path=path, labels=labels, adjoint=adjoint, train=train,
-                           streams=streams)
+                           streams=streams, resize=resize)
 
     def _forward_resized(self, pv, t, lab, pixel_mask, in_size, want_grad):
         cfg = self.config
@@ -559,7 +567,7 @@ class ScOT(nn.Module):
             _, pred = _ScOTFunction.apply(self._anchor, self, pv, t, None, None)
         else:
             _, pred, _ = self._engine.forward(pv, t, None, None, train=False, stochastic=self.training)
-        pred = self._upsample(pred, in_size) if in_size > cfg.image_size else self._downsample(pred, in_size)
+        pred = spectral_resize(pred, in_size, fused=self.fused_resize)
         if pixel_mask is not None:
             m = pixel_mask.view(pixel_mask.shape[0], pixel_mask.shape[1], 1, 1).expand_as(pred) if pixel_mask.dim() == 2 else pixel_mask
             pred = torch.where(m, lab, pred)
@@ -649,14 +657,45 @@ class _SpectralResize(torch.autograd.Function):
         return dx.view(*g.shape[:-2], s, s), None
 
 
-def spectral_resize(image: torch.Tensor, target_size: int) -> torch.Tensor:
+def _resize_fused(x, pr, pi, s, t):
+    from poseidon_amd import ops
+    nimg = x.numel() // (s * s)
+    Y = torch.empty(nimg, t, t, dtype=torch.float32, device=x.device)
+    ops.spectral_resize(x, pr, pi, Y, nimg, s, t)
+    return Y
+
+
+class _SpectralResizeFused(torch.autograd.Function):
+    """the resize as ONE launch (scot_spectral_resize); its backward is the same kernel with the cached transposed operator"""
+
+    @staticmethod
+    def forward(ctx, image, target):
+        s = image.shape[-1]
+        if image.shape[-2] != s:
+            raise ValueError("spectral resize assumes square images (as the reference does)")
+        m = _resize_mats(s, target, image.device)
+        ctx.m, ctx.s, ctx.t = m, s, target
+        x = image.to(torch.float32).contiguous()
+        return _resize_fused(x, m["pr"], m["pi"], s, target).view(*image.shape[:-2], target, target)
+
+    @staticmethod
+    def backward(ctx, g):
+        m, s, t = ctx.m, ctx.s, ctx.t
+        dx = _resize_fused(g.to(torch.float32).contiguous(), m["prT"], m["piT"], t, s)
+        return dx.view(*g.shape[:-2], s, s), None
+
+
+def spectral_resize(image: torch.Tensor, target_size: int, fused: bool = False) -> torch.Tensor:
     """reference ScOT._downsample / _upsample (model.py:1293-1316) as two launches of the native library: an NT GEMM on the exact
-    fp32 MFMA and scot_spectral_apply; differentiable (the adjoint is the same pair with the transposed operator)."""
-    if not image.is_cuda:
-        raise ScotLibraryError("spectral_resize needs CUDA(HIP) tensors: no CPU path exists in the product")
+    fp32 MFMA and scot_spectral_apply; differentiable (the adjoint is the same pair with the transposed operator).
+    fused=True: one launch of scot_spectral_resize instead (and one in the backward), the intermediate never in HBM."""
+    try:
+        _require_hip(image)      # (the one check the CPU emulation of the tests replaces)
+    except ScotLibraryError:
+        raise ScotLibraryError("spectral_resize needs CUDA(HIP) tensors: no CPU path exists in the product") from None
     if image.shape[-1] == target_size:
         return image
-    return _SpectralResize.apply(image, int(target_size))
+    return (_SpectralResizeFused if fused else _SpectralResize).apply(image, int(target_size))
 
 
 def _torch_loss(pred, labels, p, groups):
